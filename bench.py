@@ -2,6 +2,8 @@
 """bench.py - BASELINE.json metric on the MI355X-native rasterizer path.
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                               (the extras below as well)
+    python bench.py ... --dump-outputs DIR                   (what the last timed step computed, as DIR/<name>.npy)
 
 Workload (N=1 and N>1): BASELINE.json configs[2] - the configuration the metric is quoted on
 ("@1080p, 1M Gaussians"): 1,000,000 synthetic Gaussians, SH degree 3, 1920x1080, 100 synthetic views
@@ -10,8 +12,10 @@ reference train.py:96-137,170-179: render() forward -> (1-l)L1 + l(1-SSIM) loss 
 ranks every rank renders a different view and the 59 floats/Gaussian of gradients are all-reduced (RCCL) before
 Adam.  `value` = view-iterations per second over the whole job (N*K / max-over-ranks time): weak scaling.
 
-Extra keys on the same JSON line: `roofline` (dominant kernel, algorithmic bytes / measured HIP-event time),
-`cpu_baseline` (the CPU oracle timed on a bounded sample on rank 0 at N=1), `fwd_mpix_per_s`, `kernels`.
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the same line also carries what takes runs
+of its own after the timed steps: `fwd_mpix_per_s` / `fwd_ms` (forward-only renders), `kernels`, `roofline` and `rooflines`
+(per-kernel HIP-event times of extra profiled steps, algorithmic bytes / FLOP model; unless --no-kernel-profile) and
+`cpu_baseline` (the CPU oracle timed on a bounded sample on rank 0 at N=1; unless --no-cpu-baseline).
 """
 import argparse
 import json
@@ -289,10 +293,48 @@ def pair_count(model, cam, bg, cfg, dgr):
                                 rotations=ro, raw_activations=True)
 
 
+DUMP_IMAGE_MAX = 8 << 20       # floats: the whole 1080p image (6.2 M); larger ones a sample of their elements
+DUMP_RADII_MAX = 1 << 20       # Gaussians with all their radii; beyond that the rows of the parameter sample
+DUMP_ROWS = 1 << 16            # parameter rows: 59 floats each at SH degree 3 -> 15.5 MB
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, model, seed=20240611):
+    """--dump-outputs: what the last timed step returned to its caller (Trainer.step: loss, image, radii) and the parameters it
+    left behind, as float32 DIR/<name>.npy.  Arrays above their share of the 64 MB budget are a sample whose indices depend
+    only on the array's size and a fixed seed, so two builds run with the same arguments write the same elements."""
+    import numpy as np
+    gen = torch.Generator().manual_seed(seed)
+
+    def pick(n, k):
+        return None if n <= k else torch.randperm(n, generator=gen)[:k].sort().values
+
+    last = trainer.last
+    P = int(model.get_xyz.shape[0])
+    rows = pick(P, DUMP_ROWS)
+    image = last["image"].detach().float().reshape(-1)
+    sel = pick(image.numel(), DUMP_IMAGE_MAX)
+    radii = last["radii"].detach()
+    out = {"loss": last["loss"].detach().float().reshape(1),
+           "image": last["image"].detach().float() if sel is None else image[sel.to(image.device)],
+           "radii": (radii if P <= DUMP_RADII_MAX else radii[rows.to(radii.device)]).float()}
+    for name, p in (("xyz", model._xyz), ("features_dc", model._features_dc), ("features_rest", model._features_rest),
+                    ("opacity", model._opacity), ("scaling", model._scaling), ("rotation", model._rotation)):
+        p = p.detach()
+        out[name] = (p if rows is None else p[rows.to(p.device)]).float()
+    arrays = {k: v.cpu().numpy().astype(np.float32, copy=False) for k, v in out.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"outputs of the last timed step: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; --config 5: 2500)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--gaussians", type=int, default=None)
@@ -347,8 +389,14 @@ def main():
                     help="tile lists truncated by depth (Trainer.enable_tile_cull; implies --forward-mode async unless one is given): "
                          "every view remembers the depth its tiles saturated at, its next render emits only what lies in front; a frame "
                          "whose truncation was too tight is a no-op on the device and is run again - same parameters bit for bit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: forward-only throughput, the "
+                         "per-kernel table and rooflines, the CPU oracle baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="--full without the per-kernel table and rooflines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): the loss, image "
+                         "and radii Trainer.step returned and the parameters it left (a fixed, seeded sample of rows)")
     ap.add_argument("--forward-mode", default=None, choices=["exact", "async", "sync"],
                     help="rasterizer forward: exact (default: the frame is enqueued whole for a capacity estimate, its count is "
                          "verified before the call returns and phase 2 repeated if the estimate did not hold - every frame "
@@ -366,8 +414,12 @@ def main():
             args.densify_grad_threshold = 0.00002
         if args.densify_max is None:
             args.densify_max = 500000
-        if "--steps" not in sys.argv:
+        if args.steps is None:
             args.steps = 2500
+    if args.steps is None:
+        args.steps = 50
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (torch.distributed.run, one process per
     # GPU) BEFORE anything in this process touches the GPU, relay the child's stdout / exit code.
@@ -548,9 +600,32 @@ def main():
                                  and args.optimizer in ("hip", "hip_fused") and k == 1 else "")},
     }
 
-    # ---- untimed extras (rank 0 reports) ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, model)
+    if args.full:
+        full_extras(args, result, trainer, model, cams, gts, pipe, bg, cfg, render, view_at, device, rank, world)
+
+    if rank == 0:
+        # ONE line on the real stdout (everything else that writes to descriptor 1 - RCCL prints a version banner there - was sent
+        # to stderr at start-up), written and flushed before the process group is touched again: a teardown that aborts would
+        # otherwise take a block-buffered line with it
+        _emit_json_line(json.dumps(result))
+    if world > 1 or single_rank_group:
+        try:
+            dist.barrier()
+            dist.destroy_process_group()
+        except Exception as e:      # the number is out; a failing teardown must not turn the run into an error
+            log(f"process-group teardown: {e!r}")
+
+
+def full_extras(args, result, trainer, model, cams, gts, pipe, bg, cfg, render, view_at, device, rank, world):
+    """--full: untimed extras after the timed steps, added to `result` (rank 0 reports)."""
+    import diff_gaussian_rasterization as dgr
     from diff_gaussian_rasterization import _C
     lib = _C.lib()
+    P = cfg["P"]
+    M = (cfg["deg"] + 1) ** 2
+    W, H = cfg["W"], cfg["H"]
     # forward-only throughput (reference render.py:37-49 path: no_grad)
     with torch.no_grad():
         for _ in range(3):
@@ -636,18 +711,6 @@ def main():
             result["cpu_baseline"] = cpu_baseline(args, model, cams[v0], gts[v0], bg, cfg, gpu_img)
         except Exception as e:  # the baseline is a reported extra; never lose the headline number to it
             result["cpu_baseline"] = {"value": None, "error": repr(e)}
-
-    if rank == 0:
-        # ONE line on the real stdout (everything else that writes to descriptor 1 - RCCL prints a version banner there - was sent
-        # to stderr at start-up), written and flushed before the process group is touched again: a teardown that aborts would
-        # otherwise take a block-buffered line with it
-        _emit_json_line(json.dumps(result))
-    if world > 1 or single_rank_group:
-        try:
-            dist.barrier()
-            dist.destroy_process_group()
-        except Exception as e:      # the number is out; a failing teardown must not turn the run into an error
-            log(f"process-group teardown: {e!r}")
 
 
 if __name__ == "__main__":
