@@ -22,7 +22,9 @@ void gsr_launch_shade(const gsr_settings*, const gsr_gaussians*, char*, const Gs
 void gsr_launch_adam_culled_rows(int, int, const char*, const GsrGeomLayout&, const GsrAdamArgs&, uint32_t, hipStream_t);
 int gsr_launch_preprocess_bwd(const gsr_settings*, const gsr_gaussians*, const int32_t*, const char*,
                               const GsrGeomLayout&, const float4*, uint32_t, const gsr_grads*, const GsrAdamArgs*, int,
-                              hipStream_t);
+                              float*, hipStream_t);
+size_t gsr_cam_scratch_floats(int);
+void gsr_launch_cam_reduce(int, float*, float*, float*, float*, hipStream_t);
 void gsr_launch_mark_visible(int, const float*, const float*, uint8_t*, hipStream_t);
 void gsr_launch_emit(int, int, int, char*, const GsrGeomLayout&, char*, const GsrBinLayout&, uint32_t, bool, unsigned long long*,
                      int, const uint32_t*, hipStream_t);
@@ -270,6 +272,7 @@ size_t gsr_backward_scratch_bytes(int32_t P, int64_t R) {
   const size_t cap = (size_t)(R < 1 ? 1 : R);
   return gsr_igrad_bytes(cap) + gsr_align(cap + 16); // records + one validity byte per emission slot (gsr_common.h; + the reader's over-read)
 }
+size_t gsr_camera_grad_scratch_bytes(int32_t P) { return gsr_align(gsr_cam_scratch_floats(P) * sizeof(float)); }
 
 // Colour pass (SH -> RGB, the HBM-heavy half of the projection) on a library-owned side stream, concurrent with the depth sort /
 // scan / emission / tile sort, which are latency-bound and leave most of the machine idle.  Used by gsr_forward_async from
@@ -775,9 +778,15 @@ extern "C" int gsr_adam_set_dynamic(const gsr_fused_adam* opt, float* dynamic_de
 static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
                          const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
-                         const gsr_fused_adam* opt, void* stream) {
+                         const gsr_fused_adam* opt, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
+                         void* stream) {
   int rc = validate(s, g);
   if (rc) return rc;
+  if (cam && !cam->dL_dviewmatrix && !cam->dL_dprojmatrix && !cam->dL_dcampos) cam = nullptr;   // nothing asked for: plain
+  if (cam && (!cam_scratch || cam_scratch_bytes < gsr_camera_grad_scratch_bytes(g->P))) {
+    gsr_set_error("backward_camera: camera scratch too small (gsr_camera_grad_scratch_bytes)");
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
   if (!grads || !grads->dL_dmeans2D || !dL_dcolor || (!opt && (!grads->dL_dmeans3D || !grads->dL_dopacities))) {
     gsr_set_error("backward: missing mandatory gradient buffers");
     return GSR_ERR_INVALID_ARGUMENT;
@@ -787,8 +796,12 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
     gsr_set_error("backward: densification statistics need all three arrays (or none)");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (g->P == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (g->P == 0) {
+    if (!cam) return 0;
+    gsr_launch_cam_reduce(0, (float*)cam_scratch, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, st);   // zeros
+    return gsr_launch_status("backward camera");
+  }
   const int W = s->image_width, H = s->image_height;
   const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
   const int tiles = gx * gy;
@@ -817,12 +830,19 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   if (opt && (rc = adam_args(g, opt, A))) return rc;
   // rows: 0 every row (dense) / 1 rows with radii > 0, no bias correction (sparse) / 2 dense, rows with instances only
   const int mode = !opt ? 0 : (opt->sparse == 1 ? 2 : (opt->sparse == 2 ? 3 : 1));
-  if (gsr_launch_preprocess_bwd(s, g, radii, geom, GL, igrad, (uint32_t)R, grads, opt ? &A : nullptr, mode, st)) {
+  float* cam_rows = cam ? (float*)cam_scratch : nullptr;
+  const int groups = gsr_launch_preprocess_bwd(s, g, radii, geom, GL, igrad, (uint32_t)R, grads, opt ? &A : nullptr, mode,
+                                               cam_rows, st);
+  if (groups < 0) {
     gsr_set_error("backward_adam needs the raw-parameter call form with dc / shs passed separately (raw_activations = 1, "
                   "dc != NULL, no colors_precomp / cov3D_precomp, every stored SH coefficient active)");
     return GSR_ERR_INVALID_ARGUMENT;
   }
   if ((rc = debug_sync(s, st, "preprocess backward"))) return rc;
+  if (cam) {
+    gsr_launch_cam_reduce(groups, cam_rows, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, st);
+    if ((rc = debug_sync(s, st, "camera gradient reduce"))) return rc;
+  }
   return gsr_launch_status("backward");
 }
 
@@ -831,7 +851,15 @@ int gsr_backward(const gsr_settings* s, const gsr_gaussians* g, const int32_t* r
                  const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                  void* stream) {
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, nullptr, stream);
+                       scratch, scratch_bytes, grads, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                        const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                        const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                        const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream) {
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream);
 }
 
 int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
@@ -840,7 +868,7 @@ int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32
                       const gsr_fused_adam* opt, void* stream) {
   if (!opt) { gsr_set_error("backward_adam: null optimizer arguments"); return GSR_ERR_INVALID_ARGUMENT; }
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, opt, stream);
+                       scratch, scratch_bytes, grads, opt, nullptr, nullptr, 0, stream);
 }
 
 int gsr_adam_step_culled_rows(const gsr_gaussians* g, const void* geometry_state, int64_t num_rendered,

@@ -370,6 +370,24 @@ __device__ __forceinline__ void gsr_st_stream4(float4* p, const float4& v) {
   __builtin_nontemporal_store(gsr_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<gsr_f4*>(p));
 }
 
+// Cross-lane primitives of the recursive-halving wave sums (render.hip wave_sum*_halving, preprocess.hip wave_sum32_halving).
+typedef unsigned gsr_u2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float swap32_add(float x, float y) {
+  const gsr_u2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+  return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+__device__ __forceinline__ float swap16_add(float x, float y) {
+  const gsr_u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+  return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float dpp_get(float v) {
+  // old = 0 + bound_ctrl: lanes without a source (and rows masked off) read 0.0, so `x + dpp_get(x)` folds into ONE
+  // v_add_f32_dpp
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
+}
+
 // Exact tile culling shared by preprocess (count) and emit (write).  Pixels that can blend a Gaussian satisfy
 // Q(d) = A dx^2 + 2B dx dy + C dy^2 <= q (q = -2 pmin, i.e. power >= pmin).  The part of that ellipse inside the horizontal
 // band of tile row ty (pixel centres 16ty .. 16ty+15) is convex, so the tile columns it reaches form ONE interval: its

@@ -591,6 +591,64 @@ __device__ __forceinline__ void adam_row(const GsrAdamArgs& A, const int grp, co
   for (int j = 0; j < N; j++) { P[j] = p[j]; M[j] = m[j]; V[j] = v[j]; }
 }
 
+// ---- camera gradients (gsr_backward_camera): 27 per-Gaussian terms summed over the frame, without float atomics ----
+// Slots of a partial row (GSR_CAM_SLOTS floats): 0..11 dL/dviewmatrix[4r + i] (r = 0..3, i = 0..2; column 3 is zero),
+// 12..23 dL/dprojmatrix[4r + {0, 1, 3}] (column 2 is zero), 24..26 dL/dcampos, 27..31 zero padding.
+#define GSR_CAM_SLOTS 32
+#define GSR_CAM_TERMS 27
+#define GSR_CAM_RED_ROWS 128   // partial rows summed by one workgroup of k_cam_reduce
+
+// 32 full-wave sums by recursive halving (the tree of render.hip wave_sum10_halving, carried two stages further):
+//   A  lanes l <-> l^32  v_permlane32_swap   32 -> 16 registers        D  lanes l <-> l^7  DPP row_half_mirror   4 -> 2
+//   B  rows  r <-> r^1   v_permlane16_swap   16 -> 8                   E  lanes l <-> l^2  DPP quad_perm xor 2   2 -> 1
+//   C  lanes l <-> l^8   DPP row_ror:8        8 -> 4                   F  lanes l <-> l^1  DPP quad_perm xor 1   (last add)
+// At stages C-E a lane keeps the value its lane bit selects and sends the other one to its partner, whose bit is the opposite.
+// Result: lane l holds the total of value bitrev5(l >> 1) (both lanes of a pair hold it).  Fixed tree -> deterministic.
+__device__ __forceinline__ float wave_sum32_halving(const float* v /*32*/) {
+  const int lane = (int)(threadIdx.x & 63);
+  float r[16], s[8], c[4], d[2];
+#pragma unroll
+  for (int i = 0; i < 16; i++) r[i] = swap32_add(v[2 * i], v[2 * i + 1]);    // lanes < 32: v[2i], >= 32: v[2i+1]
+#pragma unroll
+  for (int i = 0; i < 8; i++) s[i] = swap16_add(r[2 * i], r[2 * i + 1]);     // row q: v[4i + (q >> 1) + 2 (q & 1)]
+  const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0, b1 = (lane & 2) != 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) c[i] = (b3 ? s[2 * i + 1] : s[2 * i]) + dpp_get<0x128>(b3 ? s[2 * i] : s[2 * i + 1]);   // row_ror:8
+#pragma unroll
+  for (int i = 0; i < 2; i++) d[i] = (b2 ? c[2 * i + 1] : c[2 * i]) + dpp_get<0x141>(b2 ? c[2 * i] : c[2 * i + 1]);   // row_half_mirror
+  float e = (b1 ? d[1] : d[0]) + dpp_get<0x4E>(b1 ? d[0] : d[1]);            // quad_perm:[2,3,0,1]
+  e += dpp_get<0xB1>(e);                                                     // quad_perm:[1,0,3,2]
+  return e;
+}
+__device__ __forceinline__ int gsr_bitrev5(int x) {
+  return ((x & 1) << 4) | ((x & 2) << 2) | (x & 4) | ((x & 8) >> 2) | ((x & 16) >> 4);
+}
+
+// The workgroup's totals of the GSR_CAM_TERMS terms -> row blockIdx.x of `rows` (every slot written).  Called by every thread of
+// the workgroup (full waves: the tree is cross-lane).
+template <int BT>
+__device__ __forceinline__ void cam_block_partial(const float* cg, float* __restrict__ rows) {
+  float v[GSR_CAM_SLOTS];
+#pragma unroll
+  for (int i = 0; i < GSR_CAM_SLOTS; i++) v[i] = i < GSR_CAM_TERMS ? cg[i] : 0.f;
+  const float t = wave_sum32_halving(v);
+  const int lane = (int)(threadIdx.x & 63), slot = gsr_bitrev5(lane >> 1);
+  float* row = rows + (size_t)blockIdx.x * GSR_CAM_SLOTS;
+  if (BT == 64) {
+    if ((lane & 1) == 0) row[slot] = t;
+  } else {
+    __shared__ float wave_tot[BT / 64][GSR_CAM_SLOTS];
+    if ((lane & 1) == 0) wave_tot[threadIdx.x >> 6][slot] = t;
+    __syncthreads();
+    if (threadIdx.x < GSR_CAM_SLOTS) {
+      float s = wave_tot[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < BT / 64; w++) s += wave_tot[w][threadIdx.x];     // waves in order
+      row[threadIdx.x] = s;
+    }
+  }
+}
+
 #ifndef GSR_SHADE_BT
 #define GSR_SHADE_BT 64
 #endif
@@ -606,7 +664,9 @@ __device__ __forceinline__ void adam_row(const GsrAdamArgs& A, const int grp, co
 // BT = Gaussians (threads) per workgroup.  The folded-optimizer instantiations stage 64 floats per row in LDS: 256-row workgroups
 // fit two per CU, one-wave workgroups of 64 rows eight or nine - the same waves, but four times as many independent phases
 // (gather / arithmetic / streaming) in flight, and the barriers become free.
-template <bool STAGE, int ADAM, int BT>
+// CAM (instantiated with ADAM = 0 only): also the camera-gradient terms of every visible Gaussian, summed per workgroup into row
+// blockIdx.x of `cam_rows` (gsr_backward_camera; k_cam_reduce adds the rows).  The per-Gaussian gradients are unchanged.
+template <bool STAGE, int ADAM, int BT, bool CAM = false>
 __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     int P, int deg, int sh_stride, const float* __restrict__ means3D, const float* __restrict__ dc,
     const float* __restrict__ shs, const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -619,7 +679,7 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     float* __restrict__ dL_ddc, float* __restrict__ dL_dshs, float* __restrict__ dL_dcolors,
     float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales, float* __restrict__ dL_drotations,
     float* __restrict__ dL_dcov3D, float* __restrict__ st_accum, float* __restrict__ st_denom,
-    float* __restrict__ st_max_radii, const GsrAdamArgs A_in, uint32_t flags_min_r) {
+    float* __restrict__ st_max_radii, const GsrAdamArgs A_in, uint32_t flags_min_r, float* __restrict__ cam_rows) {
   extern __shared__ __attribute__((aligned(16))) float sh_lds[];
   const GsrAdamArgs A = ADAM ? gsr_adam_resolve(A_in) : A_in;
   __shared__ int32_t need_sh[BT];
@@ -673,6 +733,12 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
   float g_rot[4] = {0.f, 0.f, 0.f, 0.f};
   float bs[16];
   bool have_sh = false;
+  // camera terms (slots of GSR_CAM_SLOTS).  `if constexpr` throughout: the other instantiations compile to the code they had
+  float cg[CAM ? GSR_CAM_TERMS : 1];
+  if constexpr (CAM) {
+#pragma unroll
+    for (int i = 0; i < GSR_CAM_TERMS; i++) cg[i] = 0.f;
+  }
 
   if (visible) {
     // ---- deterministic gather-sum over this Gaussian's instances (slot order) ----
@@ -795,6 +861,11 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
         g_mean[0] += (gdx - x * dot) * inv;
         g_mean[1] += (gdy - y * dot) * inv;
         g_mean[2] += (gdz - z * dot) * inv;
+        if constexpr (CAM) {      // dir = (p - campos) / |p - campos|: the camera centre takes the opposite of the mean's term
+          cg[24] = -((gdx - x * dot) * inv);
+          cg[25] = -((gdy - y * dot) * inv);
+          cg[26] = -((gdz - z * dot) * inv);
+        }
       }
       g_col[0] = g_rgb[0]; g_col[1] = g_rgb[1]; g_col[2] = g_rgb[2];  // masked dL/drgb, used for dL/dsh below
     }
@@ -891,6 +962,24 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     // t = V p
 #pragma unroll
     for (int j = 0; j < 3; j++) g_mean[j] += v.V[4 * j + 0] * g_t[0] + v.V[4 * j + 1] * g_t[1] + v.V[4 * j + 2] * g_t[2];
+    if constexpr (CAM) {
+      // t = V^T p^ (p^ = (p, 1)): dL/dV[4r + i] = p^[r] g_t[i]; and M = J W with W[k][j] = V[4j + k] (J as the forward formed it,
+      // from the clamped tx / ty): dL/dV[4j + k] += (J^T dL/dM)[k][j]
+      const float ph[4] = {p[0], p[1], p[2], 1.0f};
+      const float j00 = fx / e.tz, j02 = -(fx * e.tx) / (e.tz * e.tz);
+      const float j11 = fy / e.tz, j12 = -(fy * e.ty) / (e.tz * e.tz);
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) cg[3 * r + i] = ph[r] * g_t[i];
+      }
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        cg[3 * j + 0] += j00 * gm0[j];
+        cg[3 * j + 1] += j11 * gm1[j];
+        cg[3 * j + 2] += j02 * gm0[j] + j12 * gm1[j];
+      }
+    }
 
     // ---- mean2D (NDC) -> mean3D (A.7 iii) ----
     {
@@ -903,6 +992,16 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
       for (int j = 0; j < 3; j++) {
         g_mean[j] += (v.PV[4 * j + 0] * pw - v.PV[4 * j + 3] * mul1) * g_m2d[0] +
                      (v.PV[4 * j + 1] * pw - v.PV[4 * j + 3] * mul2) * g_m2d[1];
+      }
+      if constexpr (CAM) {
+        // hom = PV^T p^, ndc = hom.xy / (hom.w + eps): dL/dhom = (pw g0, pw g1, 0, -(mul1 g0 + mul2 g1)), dL/dPV[4r + i] = p^[r] dL/dhom[i]
+        const float gh[3] = {pw * g_m2d[0], pw * g_m2d[1], -(mul1 * g_m2d[0] + mul2 * g_m2d[1])};
+        const float ph[4] = {p[0], p[1], p[2], 1.0f};
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+#pragma unroll
+          for (int i = 0; i < 3; i++) cg[12 + 3 * r + i] = ph[r] * gh[i];
+        }
       }
     }
 
@@ -942,6 +1041,13 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
       }
     }
     if (raw_act) g_opac *= opac * (1.0f - opac);     // through sigmoid
+  }
+  if constexpr (CAM) {
+    if (!active) {       // (an idle tail thread mirrors the last Gaussian: its terms must not count twice)
+#pragma unroll
+      for (int i = 0; i < GSR_CAM_TERMS; i++) cg[i] = 0.f;
+    }
+    cam_block_partial<BT>(cg, cam_rows);
   }
 
   // ---- write every output (zeros for culled Gaussians: no memset pass needed) ----
@@ -1300,11 +1406,13 @@ void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, in
 #undef GSR_PRE_FWD_ARGS
 }
 
-// adam: nullptr (plain backward) or the folded optimizer step; adam_mode 1 dense / 2 sparse.  Returns 0, or -1 when the
+// adam: nullptr (plain backward) or the folded optimizer step; adam_mode 1 dense / 2 sparse.  cam_rows: nullptr, or (plain
+// backward only) the camera form, one partial row per workgroup.  Returns the number of workgroups launched, or -1 when the
 // folded form does not apply to these inputs (the caller reports the error).
 int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
                               const char* geom, const GsrGeomLayout& L, const float4* igrad, uint32_t cap,
-                              const gsr_grads* gr, const GsrAdamArgs* adam, int adam_mode, hipStream_t st) {
+                              const gsr_grads* gr, const GsrAdamArgs* adam, int adam_mode, float* cam_rows,
+                              hipStream_t st) {
   const int P = g->P;
   size_t lds = 0;
   GsrAdamArgs A;
@@ -1329,16 +1437,23 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
       (const uint32_t*)(geom + L.tiles_touched), (const uint32_t*)(geom + L.slot_start), igrad,                       \
       (const uint32_t*)(geom + L.meta) + 2, cap, gr->dL_dmeans3D,                                                      \
       gr->dL_dmeans2D, gr->dL_ddc, gr->dL_dshs, gr->dL_dcolors, gr->dL_dopacities, gr->dL_dscales, gr->dL_drotations, \
-      gr->dL_dcov3D, gr->xyz_gradient_accum, gr->denom, gr->max_radii2D, A, g_gsr_flags_min_r
-#define GSR_PRE_BWD(ST, AD, BT_)                                                                                       \
+      gr->dL_dcov3D, gr->xyz_gradient_accum, gr->denom, gr->max_radii2D, A, g_gsr_flags_min_r, cam_rows
+#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME)                                                                         \
   do {                                                                                                                 \
     if (lds > 48 * 1024)                                                                                               \
-      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_>,                                            \
+      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_>,                                      \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    GSR_LAUNCH(AD ? "preprocess_bwd_adam" : "preprocess_bwd", (k_preprocess_bwd<ST, AD, BT_>),                         \
+    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_>),                                                            \
                dim3((P + BT_ - 1) / BT_), dim3(BT_), ST ? lds : 0, st, GSR_PRE_BWD_ARGS);                              \
+    groups = (P + BT_ - 1) / BT_;                                                                                      \
   } while (0)
-  if (!adam) {
+  int groups = 0;
+#define GSR_PRE_BWD(ST, AD, BT_) GSR_PRE_BWD_K(ST, AD, BT_, false, AD ? "preprocess_bwd_adam" : "preprocess_bwd")
+  if (cam_rows) {
+    if (adam) return -1;
+    if (stage) GSR_PRE_BWD_K(true, 0, GSR_BWD_PLAIN_BT, true, "preprocess_bwd_cam");
+    else GSR_PRE_BWD_K(false, 0, 256, true, "preprocess_bwd_cam");
+  } else if (!adam) {
     if (stage) GSR_PRE_BWD(true, 0, GSR_BWD_PLAIN_BT); else GSR_PRE_BWD(false, 0, 256);
   } else if (adam_mode == 2) {
     if (stage) GSR_PRE_BWD(true, 2, GSR_BWD_ADAM_BT); else GSR_PRE_BWD(false, 2, 256);
@@ -1348,8 +1463,68 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
     if (stage) GSR_PRE_BWD(true, 1, GSR_BWD_ADAM_BT); else GSR_PRE_BWD(false, 1, 256);
   }
 #undef GSR_PRE_BWD
+#undef GSR_PRE_BWD_K
 #undef GSR_PRE_BWD_ARGS
-  return 0;
+  return groups;
+}
+
+// Fixed-order sum of the camera partial rows: workgroup b adds rows [b R, b R + R) (R = GSR_CAM_RED_ROWS; thread (q, c) the rows
+// q, q + 8, ... of column c, then the eight groups in order).  More than one workgroup: one row per workgroup to `out`; one
+// workgroup: the totals go to the three outputs, in full (zeros in the always-zero entries, n = 0: all zeros).
+__global__ __launch_bounds__(256) void k_cam_reduce(int n, const float* __restrict__ in, float* __restrict__ out,
+                                                    float* __restrict__ dV, float* __restrict__ dPV, float* __restrict__ dcam) {
+  __shared__ float grp_sum[8][GSR_CAM_SLOTS];
+  const int c = threadIdx.x & (GSR_CAM_SLOTS - 1), q = threadIdx.x / GSR_CAM_SLOTS;
+  const int r0 = blockIdx.x * GSR_CAM_RED_ROWS, r1 = min(n, r0 + GSR_CAM_RED_ROWS);
+  float s = 0.f;
+  for (int r = r0 + q; r < r1; r += 8) s += in[(size_t)r * GSR_CAM_SLOTS + c];
+  grp_sum[q][c] = s;
+  __syncthreads();
+  if (threadIdx.x >= GSR_CAM_SLOTS) return;
+  float t = grp_sum[0][c];
+#pragma unroll
+  for (int k = 1; k < 8; k++) t += grp_sum[k][c];
+  if (gridDim.x > 1) {
+    out[(size_t)blockIdx.x * GSR_CAM_SLOTS + c] = t;
+    return;
+  }
+  if (c < 12) {
+    if (dV) dV[4 * (c / 3) + c % 3] = t;
+  } else if (c < 24) {
+    const int k = c - 12, col = k % 3;
+    if (dPV) dPV[4 * (k / 3) + (col == 2 ? 3 : col)] = t;
+  } else if (c < GSR_CAM_TERMS) {
+    if (dcam) dcam[c - 24] = t;
+  }
+  if (c < 4) {
+    if (dV) dV[4 * c + 3] = 0.f;
+    if (dPV) dPV[4 * c + 2] = 0.f;
+  }
+}
+
+// floats of the camera scratch: the partial rows of the backward (one per workgroup of <= 64 Gaussians) and those of every
+// reduction level but the last
+size_t gsr_cam_scratch_floats(int P) {
+  size_t n = (size_t)(P < 1 ? 1 : (P + 63) / 64), tot = n;
+  while (n > GSR_CAM_RED_ROWS) {
+    n = (n + GSR_CAM_RED_ROWS - 1) / GSR_CAM_RED_ROWS;
+    tot += n;
+  }
+  return tot * GSR_CAM_SLOTS;
+}
+
+// rows: the partial rows of the backward that just ran with `cam_rows` = rows (n of them; 0 = nothing ran: zeros)
+void gsr_launch_cam_reduce(int n, float* rows, float* dV, float* dPV, float* dcam, hipStream_t st) {
+  float* in = rows;
+  float* out = rows + (size_t)n * GSR_CAM_SLOTS;
+  while (n > GSR_CAM_RED_ROWS) {
+    const int nb = (n + GSR_CAM_RED_ROWS - 1) / GSR_CAM_RED_ROWS;
+    GSR_LAUNCH("cam_reduce", k_cam_reduce, dim3(nb), dim3(256), 0, st, n, (const float*)in, out, dV, dPV, dcam);
+    in = out;
+    out += (size_t)nb * GSR_CAM_SLOTS;
+    n = nb;
+  }
+  GSR_LAUNCH("cam_reduce", k_cam_reduce, dim3(1), dim3(256), 0, st, n, (const float*)in, out, dV, dPV, dcam);
 }
 
 void gsr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present,

@@ -41,22 +41,7 @@ __device__ __forceinline__ float gsr_power2(const float4& r0, const float4& r1, 
 // 27 VALU instead of 60.  Result: u0 in octet o = lane>>3 holds the total of value OCTET_VALUE[o] = {0,4,2,6,1,5,3,7}[o];
 // u1 holds the total of v8 in lanes 0..15 and of v9 in lanes 32..47.  The summation tree is fixed -> deterministic.
 // ---------------------------------------------------------------------------------------------------------------
-typedef unsigned gsr_u2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float swap32_add(float x, float y) {
-  const gsr_u2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ float swap16_add(float x, float y) {
-  const gsr_u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_get(float v) {
-  // old = 0 + bound_ctrl: lanes without a source (and rows masked off) read 0.0, so `x + dpp_get(x)` folds into ONE
-  // v_add_f32_dpp
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
+// (swap32_add / swap16_add / dpp_get: gsr_common.h)
 
 __device__ __forceinline__ void wave_sum10_halving(float v0, float v1, float v2, float v3, float v4, float v5, float v6,
                                                    float v7, float v8, float v9, bool lane_bit3, float& u0, float& u1) {

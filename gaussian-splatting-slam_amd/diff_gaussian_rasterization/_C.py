@@ -46,6 +46,10 @@ class gsr_grads(C.Structure):
     ]
 
 
+class gsr_camera_grads(C.Structure):
+    _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p)]
+
+
 class gsr_fused_adam(C.Structure):
     _fields_ = [
         ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("lr", C.c_float * 6), ("step", C.c_int64 * 6),
@@ -87,6 +91,11 @@ EXPORTS = {
     "gsr_backward": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.POINTER(gsr_grads), C.c_void_p]),
+    "gsr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_backward_camera": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
     "gsr_backward_adam": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p]),

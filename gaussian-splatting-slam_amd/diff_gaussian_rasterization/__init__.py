@@ -284,13 +284,15 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                 raster_settings, raw_activations=False, for_backward=True, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True):
+                tile_cull=None, tile_cull_apply=True, viewmatrix=None, projmatrix=None, campos=None):
         """fold: a BackwardFold for THIS call's backward (kept on ctx).  sh_ready_event: a recorded torch.cuda.Event after which
         `dc` / `shs` hold this step's values (the view-sharded trainer's SH all-reduce + Adam update, in flight on another
         stream): the geometry stages run first, the stream waits for the event and only then evaluates the colours
         (gsr_forward_prepare_geometry / gsr_forward_shade).  forward_mode: "exact" | "async" | "sync" for this call (default:
         the process-wide mode, GSR_FORWARD_MODE / set_forward_mode).  tile_cull: this VIEW's per-tile depth cut-offs
-        (`new_tile_cull`), updated by every speculative forward and applied by unverified ones (gsr_forward_async_culled)."""
+        (`new_tile_cull`), updated by every speculative forward and applied by unverified ones (gsr_forward_async_culled).
+        viewmatrix / projmatrix / campos: raster_settings' own tensors, passed (by rasterize_gaussians) only when one of them
+        requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera)."""
         lib = _C.lib()
         raw_activations = bool(raw_activations) and cov3D_precomp is None
         if not means3D.is_cuda:
@@ -427,6 +429,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                           cov3D_precomp)
                 raise
         ctx.raster_settings = rs
+        ctx.camera = viewmatrix is not None or projmatrix is not None or campos is not None
         ctx.raw_activations = raw_activations
         ctx.fold = fold if needs_grad else None
         ctx.num_rendered = R                 # what the binning state was laid out for (the count itself, or the capacity)
@@ -470,8 +473,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                                         for t in stats)):
                 raise _C.GsrError("fold_densification_stats: statistics tensors do not match this forward's Gaussians")
             fused, split, opt = None, False, (fold.optimizer if fold is not None else None)
+            # (the camera form is not folded: gsr_backward_adam returns no camera gradient - the gradients go to `.grad`)
             if P > 0 and opt is not None and not fold.optimizer_taken and ctx.raw_activations and dc is not None \
-                    and colors_precomp is None:
+                    and colors_precomp is None and not ctx.camera:
                 split = fold.split_rows and not isinstance(opt, SparseGaussianAdam)
                 # factors kept in device memory (enable_dynamic_hyperparameters): an eager backward stores this step's values
                 # in front of its kernels; under graph capture nothing is counted or stored - whoever replays the graph does
@@ -504,6 +508,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d_cov = like(cov3D_precomp, P, 6)
             else:       # the optimizer step rides in the backward: no gradient but the screen-space one is materialised
                 d_means3D = d_opac = d_dc = d_sh = d_col = d_scales = d_rot = d_cov = None
+            cam_grads = (None, None, None)
+            if ctx.camera:
+                if torch.cuda.is_current_stream_capturing():
+                    raise _C.GsrError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) are not "
+                                      "supported under HIP-graph capture: run this backward eagerly")
+                want = ctx.needs_input_grad[-3:]
+                cam_flat = torch.zeros(16 + 16 + 3, dtype=torch.float32, device=dev)   # (P = 0: stays zero)
+                cam_parts = (cam_flat[:16], cam_flat[16:32], cam_flat[32:])
+                cam_struct = _C.gsr_camera_grads(*[t.data_ptr() if w else None for t, w in zip(cam_parts, want)])
             if P > 0:
                 cur = _C.raw_stream()
                 if ws.stream is not None and ws.stream != cur:
@@ -535,6 +548,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                        C.byref(fused[0]), _stream()))
                         if split:
                             torch.cuda.current_stream().wait_stream(side)   # what follows here sees both halves of the update
+                    elif ctx.camera:
+                        cam_scratch = torch.empty(lib.gsr_camera_grad_scratch_bytes(P), dtype=torch.uint8, device=dev)
+                        _C.check(lib.gsr_backward_camera(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
+                                                         _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
+                                                         _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(), C.byref(gr),
+                                                         C.byref(cam_struct), _C.ptr(cam_scratch), cam_scratch.numel(),
+                                                         _stream()))
                     else:
                         _C.check(lib.gsr_backward(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom), _C.ptr(binning),
                                                   _C.ptr(img), R, _C.ptr(grad_color), _C.ptr(grad_invdepth),
@@ -548,8 +568,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             if fold is not None:
                 fold.stats_taken = fold.stats_taken or stats is not None      # (P == 0: no rows, nothing to add)
                 fold.sh_rest_skipped = bool(skip_rest)
+            if ctx.camera:
+                # each gradient with its input's shape, dtype and device
+                cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
+                                  for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
         return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None, None, None, None, None, None,
-                None)
+                None) + (cam_grads if ctx.camera else ())
 
 
 def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -558,10 +582,16 @@ def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, sca
     # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
     # what only a backward would need
     tensors = (means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-    for_backward = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+    rs = raster_settings
+    # camera form: the settings' viewmatrix / projmatrix / campos take part in autograd when one of them requires grad (pose
+    # refinement / tracking, also with every Gaussian tensor frozen); they then travel as trailing inputs of the Function
+    camera = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
+                                             for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+    for_backward = camera or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors))
+    extra = (rs.viewmatrix, rs.projmatrix, rs.campos) if camera else ()
     return _RasterizeGaussians.apply(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, raw_activations, for_backward, fold, sh_ready_event,
-                                     forward_mode, tile_cull, tile_cull_apply)
+                                     forward_mode, tile_cull, tile_cull_apply, *extra)
 
 
 def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

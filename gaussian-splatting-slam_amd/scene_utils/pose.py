@@ -1,0 +1,133 @@
+"""Camera pose as a differentiable SE(3) correction, and photometric pose refinement against a frozen model.
+
+The rasterizer returns gradients for the camera's `viewmatrix` / `projmatrix` / `campos` when one of them requires grad
+(diff_gaussian_rasterization, gsr_backward_camera).  `PoseCamera` derives all three from a base world-to-camera matrix and a leaf
+twist `tau` with torch ops, so those gradients reach `tau`; `refine_pose` optimises `tau` against an image (tracking: the map
+stays frozen).  Conventions: the matrices are the reference's row-major transposed 4x4 tensors (world_view_transform = W2C^T,
+full_proj_transform = (P W2C)^T), and the correction is applied on the left, W2C' = exp(tau) W2C, tau = (rho, theta): rho
+a translation and theta a rotation vector, both in the camera frame."""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .cameras import projection_matrix
+
+
+def _hat(w):
+    """[..., 3] -> [..., 3, 3] skew-symmetric matrices (w x v = hat(w) v)."""
+    z = torch.zeros_like(w[..., 0])
+    return torch.stack([z, -w[..., 2], w[..., 1],
+                        w[..., 2], z, -w[..., 0],
+                        -w[..., 1], w[..., 0], z], dim=-1).reshape(*w.shape[:-1], 3, 3)
+
+
+def se3_exp(tau):
+    """tau [6] = (rho, theta) -> 4x4 exp of the twist [[hat(theta), rho], [0, 0]] = [[R, V rho], [0, 1]], with
+    R = I + A K + B K^2, V = I + B K + C K^2 (K = hat(theta), A = sin t / t, B = (1 - cos t) / t^2, C = (t - sin t) / t^3,
+    t = |theta|).  Differentiable, float32 or float64; below a small angle A, B, C come from their Taylor series (no 0 / 0, and
+    finite gradients at theta = 0)."""
+    rho, theta = tau[:3], tau[3:]
+    dt = tau.dtype
+    t2 = (theta * theta).sum()
+    small = t2 < (1e-6 if dt == torch.float64 else 1e-4)
+    t2s = torch.where(small, torch.ones_like(t2), t2)         # (the unused branch of torch.where must stay finite)
+    t = torch.sqrt(t2s)
+    s, h = torch.sin(t), torch.sin(0.5 * t)
+    A = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, s / t)
+    B = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 2.0 * h * h / t2s)     # (1 - cos t) = 2 sin^2(t / 2): no cancellation
+    C = torch.where(small, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0, (t - s) / (t2s * t))
+    K = _hat(theta)
+    K2 = K @ K
+    eye = torch.eye(3, dtype=dt, device=tau.device)
+    R = eye + A * K + B * K2
+    V = eye + B * K + C * K2
+    top = torch.cat([R, (V @ rho).unsqueeze(1)], dim=1)
+    bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=dt, device=tau.device)
+    return torch.cat([top, bottom], dim=0)
+
+
+class PoseCamera:
+    """A camera with the attribute surface `render()` reads (scene_utils.MiniCam, reference scene/cameras.py:74-85) whose
+    `world_view_transform`, `full_proj_transform` and `camera_center` are torch functions of a base W2C and the leaf twist
+    `tau` (W2C' = exp(tau) W2C): the rasterizer's camera gradients flow into `tau.grad`.  Built from any camera with that
+    surface; `dtype` / `device` choose where it lives (float64 on the CPU drives the oracle with the same object)."""
+
+    def __init__(self, cam, dtype=None, device=None, requires_grad=True):
+        wv = cam.world_view_transform
+        dtype = dtype or wv.dtype
+        device = torch.device(device) if device is not None else wv.device
+        self.image_width, self.image_height = int(cam.image_width), int(cam.image_height)
+        self.FoVx, self.FoVy = float(cam.FoVx), float(cam.FoVy)
+        self.znear, self.zfar = cam.znear, cam.zfar
+        self.image_name = getattr(cam, "image_name", "")
+        self.base_w2c = wv.detach().to(dtype=dtype, device=device).transpose(0, 1).contiguous()
+        self.proj_T = projection_matrix(self.znear, self.zfar, self.FoVx, self.FoVy).transpose(0, 1).to(dtype=dtype,
+                                                                                                        device=device)
+        self.tau = torch.zeros(6, dtype=dtype, device=device, requires_grad=requires_grad)
+
+    def w2c(self):
+        """The corrected world-to-camera matrix exp(tau) W2C (4x4, column-vector convention)."""
+        return se3_exp(self.tau) @ self.base_w2c
+
+    @property
+    def world_view_transform(self):
+        return self.w2c().transpose(0, 1).contiguous()
+
+    @property
+    def full_proj_transform(self):
+        return (self.w2c().transpose(0, 1) @ self.proj_T).contiguous()
+
+    @property
+    def camera_center(self):
+        T = self.w2c()
+        return -(T[:3, :3].transpose(0, 1) @ T[:3, 3])          # -R^T t (rigid: no general inverse)
+
+    def commit(self):
+        """Folds tau into the base pose and zeroes it (the pose is unchanged; an optimizer over `tau` keeps the same leaf)."""
+        with torch.no_grad():
+            self.base_w2c = (se3_exp(self.tau) @ self.base_w2c).contiguous()
+            self.tau.zero_()
+        return self
+
+
+def pose_error(w2c_a, w2c_b):
+    """(rotation angle in radians, camera-centre distance) between two 4x4 world-to-camera matrices."""
+    Ra, Rb = w2c_a[:3, :3].double(), w2c_b[:3, :3].double()
+    ca = -(Ra.transpose(0, 1) @ w2c_a[:3, 3].double())
+    cb = -(Rb.transpose(0, 1) @ w2c_b[:3, 3].double())
+    cos = ((Ra @ Rb.transpose(0, 1)).trace() - 1.0) * 0.5
+    return float(torch.arccos(cos.clamp(-1.0, 1.0))), float((ca - cb).norm())
+
+
+def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda_dssim=0.0, bg=None, pipe=None,
+                separate_sh=False, callback=None):
+    """Photometric pose refinement of one camera against a frozen `model` (tracking): Adam over the twist of a `PoseCamera`,
+    loss = L1(render, gt_image) (lambda_dssim > 0: the fused L1 + D-SSIM training loss), learning rate decaying
+    exponentially from `lr` to `lr_final`.  `cam`: a PoseCamera (refined in place) or any camera (wrapped in a float64 PoseCamera
+    on the host: the pose arithmetic is a few dozen 4x4 operations, cheaper there than as many device launches; the rasterizer
+    moves the three matrices to the device and returns their gradients where they came from).  The model's tensors are read,
+    never written; whether they require grad does not matter.  Returns (the PoseCamera with tau committed, the loss of every
+    iteration)."""
+    from gaussian_renderer import render, PipelineParams
+    from .losses import l1_loss, training_loss_fused
+    pc = cam if isinstance(cam, PoseCamera) else PoseCamera(cam, dtype=torch.float64, device="cpu")
+    pipe = pipe or PipelineParams()
+    if bg is None:
+        bg = torch.zeros(3, dtype=torch.float32, device=gt_image.device)
+    opt = torch.optim.Adam([pc.tau], lr=lr)
+    gamma = math.exp(math.log(lr_final / lr) / max(1, iters - 1)) if iters > 1 else 1.0
+    history = []
+    for it in range(iters):
+        opt.zero_grad(set_to_none=True)
+        image = render(pc, model, pipe, bg, separate_sh=separate_sh)["render"]
+        loss = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+        loss.backward()
+        opt.step()
+        for g in opt.param_groups:
+            g["lr"] *= gamma
+        history.append(float(loss.detach()))
+        if callback is not None:
+            callback(it, pc)
+    return pc.commit(), history

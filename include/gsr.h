@@ -34,6 +34,7 @@ extern "C" {
 /* 7: gsr_debug_mx_reduce (the compositing backward's sums on the matrix pipe: opt-in form GSR_BWD_REDUCE=mfma, measured slower);
  *    the image state carries the frame's walk classes (gsr_image_state_bytes grew; gsr_debug_walk_views); the backward's scratch
  *    carries validity flags of the gradient records (gsr_backward_scratch_bytes grew; gsr_debug_set_flags_min_r);
+ *    later, additive: gsr_camera_grads, gsr_camera_grad_scratch_bytes, gsr_backward_camera (gradients of the camera);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -225,6 +226,25 @@ int gsr_backward(const gsr_settings* s, const gsr_gaussians* g, const int32_t* r
                  const void* geometry_state, const void* binning_state, const void* image_state,
                  int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth,
                  void* scratch, size_t scratch_bytes, const gsr_grads* grads, void* stream);
+
+/* gsr_backward that also returns the gradients of the CAMERA: dL/d(viewmatrix), dL/d(projmatrix) (the settings' row-major
+ * transposed 4x4 matrices, [16] each) and dL/d(campos) [3] - what a photometric pose refinement (tracking) differentiates through.
+ * Everything gsr_backward writes is written too, bit for bit the same.  Each non-NULL pointer of `cam` is a DEVICE array written in
+ * full: column 3 of dL/dviewmatrix and column 2 of dL/dprojmatrix are always zero, dL/dcampos is zero for colors_precomp and SH
+ * degree 0, and all are zero for P = 0, a frame without visible Gaussians and an overflowed unverified frame.  The per-Gaussian
+ * terms are summed per workgroup by cross-lane trees, then in a fixed order over the workgroups: no float atomics, the result is
+ * bitwise reproducible.  cam_scratch: gsr_camera_grad_scratch_bytes(P) bytes of device memory.  `grads` as for gsr_backward. */
+typedef struct gsr_camera_grads {
+  float* dL_dviewmatrix; /* [16] or NULL */
+  float* dL_dprojmatrix; /* [16] or NULL */
+  float* dL_dcampos;     /* [3]  or NULL */
+} gsr_camera_grads;
+size_t gsr_camera_grad_scratch_bytes(int32_t P);
+int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                        const void* geometry_state, const void* binning_state, const void* image_state,
+                        int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth,
+                        void* scratch, size_t scratch_bytes, const gsr_grads* grads, const gsr_camera_grads* cam,
+                        void* cam_scratch, size_t cam_scratch_bytes, void* stream);
 
 /* gsr_backward with the optimizer step folded in (single-GPU training step: reference train.py:139 loss.backward() followed
  * by :170-179 optimizer.step(), when nothing sits between the two - no gradient exchange, no accumulation over views, no
