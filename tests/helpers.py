@@ -162,3 +162,49 @@ def lowlevel_forward(raw, cam, deg, bg, antialiasing=False, device="cuda"):
     out["walk_list"] = _view(img, pw[1].value, classes * tiles, torch.int32).numpy().view(np.uint32).reshape(classes, tiles)
     out["walk_of_tile"] = _view(img, pw[2].value, tiles, torch.int32).numpy().view(np.uint32)
     return out
+
+
+# ---- camera gradients: numpy restatement of the fixed-order reduction of gsr_backward_camera (csrc/preprocess.hip) ----
+CAM_SLOTS, CAM_TERMS, CAM_RED_ROWS = 32, 27, 128
+
+
+def cam_reduce_block(block):
+    """One workgroup of k_cam_reduce on `block` [m <= 128, 32] float32: thread (q, c) adds rows q, q + 8, ... of column c in
+    float32 from 0.0, then the eight group sums are added in order q = 0 .. 7.  -> [32] float32"""
+    block = np.asarray(block, dtype=np.float32)
+    m = block.shape[0]
+    assert m <= CAM_RED_ROWS and block.shape[1] == CAM_SLOTS
+    grp = np.zeros((8, CAM_SLOTS), dtype=np.float32)
+    for q in range(8):
+        s = np.zeros(CAM_SLOTS, dtype=np.float32)
+        for r in range(q, m, 8):
+            s = s + block[r]
+        grp[q] = s
+    t = grp[0].copy()
+    for k in range(1, 8):
+        t = t + grp[k]
+    return t
+
+
+def cam_reduce_levels(rows):
+    """k_cam_reduce's levels on the partial rows [n, 32] (gsr_launch_cam_reduce): while more than 128 rows remain, workgroup b
+    sums rows [128 b, 128 b + 128) into row b of the next level.  -> (intermediate levels [[nb, 32] ...], final totals [32])"""
+    cur = np.asarray(rows, dtype=np.float32).reshape(-1, CAM_SLOTS)
+    levels = []
+    while cur.shape[0] > CAM_RED_ROWS:
+        nb = (cur.shape[0] + CAM_RED_ROWS - 1) // CAM_RED_ROWS
+        cur = np.stack([cam_reduce_block(cur[b * CAM_RED_ROWS:(b + 1) * CAM_RED_ROWS]) for b in range(nb)])
+        levels.append(cur)
+    return levels, cam_reduce_block(cur)
+
+
+def cam_slots_to_grads(t):
+    """The totals' slot map -> (dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3]) float32: slots 0..11 ->
+    dV[4 r + i] (i < 3), slots 12..23 -> dPV[4 r + {0, 1, 3}], slots 24..26 -> dcampos; column 3 of dV and column 2 of dPV zero."""
+    t = np.asarray(t, dtype=np.float32)
+    dV, dPV = np.zeros(16, dtype=np.float32), np.zeros(16, dtype=np.float32)
+    for c in range(12):
+        dV[4 * (c // 3) + c % 3] = t[c]
+    for k in range(12):
+        dPV[4 * (k // 3) + (0, 1, 3)[k % 3]] = t[12 + k]
+    return dV, dPV, t[24:CAM_TERMS].copy()
