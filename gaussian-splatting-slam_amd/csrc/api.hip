@@ -17,12 +17,12 @@
 
 // launchers defined in the kernel files
 void gsr_launch_preprocess_fwd(const gsr_settings*, const gsr_gaussians*, int32_t*, char*, const GsrGeomLayout&, bool, bool, uint32_t*, int,
-                               const uint32_t*, uint32_t*, uint32_t, hipStream_t);
+                               const uint32_t*, uint32_t*, uint32_t, bool, hipStream_t);
 void gsr_launch_shade(const gsr_settings*, const gsr_gaussians*, char*, const GsrGeomLayout&, bool, hipStream_t);
 void gsr_launch_adam_culled_rows(int, int, const char*, const GsrGeomLayout&, const GsrAdamArgs&, uint32_t, hipStream_t);
 int gsr_launch_preprocess_bwd(const gsr_settings*, const gsr_gaussians*, const int32_t*, const char*,
                               const GsrGeomLayout&, const float4*, uint32_t, const gsr_grads*, const GsrAdamArgs*, int,
-                              float*, hipStream_t);
+                              float*, bool, hipStream_t);
 size_t gsr_cam_scratch_floats(int);
 void gsr_launch_cam_reduce(int, float*, float*, float*, float*, hipStream_t);
 void gsr_launch_mark_visible(int, const float*, const float*, uint8_t*, hipStream_t);
@@ -34,12 +34,13 @@ void gsr_launch_finalize(uint32_t, const uint32_t*, const uint32_t*, char*, cons
 void gsr_launch_sum_tiles(int, const char*, const GsrGeomLayout&, uint32_t*, hipStream_t);
 void gsr_launch_render_fwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, float*,
                            float*, float*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
-                           uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, hipStream_t);
+                           uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, float*, hipStream_t);
 void gsr_launch_count_pairs(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, uint32_t*,
                             hipStream_t);
 void gsr_launch_render_bwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*,
                            const float*, const uint32_t*, const float*, const float*, const uint32_t*, float4*,
-                           const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, hipStream_t);
+                           const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const float*,
+                           hipStream_t);
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -310,7 +311,8 @@ static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void*
                             unsigned long long** early_word = nullptr,
                             uint32_t* tile_sort_head = nullptr /* tile-local form: cleared by the projection kernel */,
                             const uint32_t* tile_cutoff = nullptr /* lists truncated by depth (gsr_forward_async_culled) */,
-                            uint32_t* culled_any = nullptr, uint32_t frame_tag = 0) {
+                            uint32_t* culled_any = nullptr, uint32_t frame_tag = 0,
+                            bool depth_z = false /* gsr_render_extras.depth_kind = GSR_DEPTH_Z */) {
   const int P = g->P;
   const GsrGeomLayout L = gsr_geom_layout(P);
   if (!geometry_state || geometry_bytes < L.total) {
@@ -327,7 +329,7 @@ static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void*
   if (!tile_local && (rc = gsr_check(hipMemsetAsync(meta, 0, 256 + GSR_RADIX_HEAD_WORDS * 4, st), "memset meta"))) return rc;
 
   gsr_launch_preprocess_fwd(s, g, radii, geom, L, defer_color, /*block_sums=*/tile_local, tile_local ? tile_sort_head : nullptr,
-                            GSR_RADIX_HEAD_WORDS, tile_cutoff, culled_any, frame_tag, st);
+                            GSR_RADIX_HEAD_WORDS, tile_cutoff, culled_any, frame_tag, depth_z, st);
   if ((rc = debug_sync(s, st, "preprocess"))) return rc;
   // (tile-local binning form: the colour pass is forked behind the emission instead - forward_render_impl - because the
   // two are both HBM-bound and slowed each other down (emission 36 -> 55 us); the tile sort and the per-tile ordering that
@@ -436,10 +438,24 @@ static int64_t wait_for_count(uint32_t* host, hipEvent_t ev, bool early_word) {
   return (int64_t)total;
 }
 
+// gsr_render_extras: NULL = the inverse-depth channel and no opacity plane (every entry point without `_ex`)
+static int check_extras(const gsr_render_extras* ex) {
+  if (ex && ex->depth_kind != GSR_DEPTH_INVERSE && ex->depth_kind != GSR_DEPTH_Z) {
+    gsr_set_error("gsr_render_extras.depth_kind %d: expected GSR_DEPTH_INVERSE (0) or GSR_DEPTH_Z (1)", (int)ex->depth_kind);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  return 0;
+}
+static bool ex_depth_z(const gsr_render_extras* ex) { return ex && ex->depth_kind == GSR_DEPTH_Z; }
+static float* ex_alpha(const gsr_render_extras* ex) { return ex ? ex->out_alpha : nullptr; }
+static const float* ex_dalpha(const gsr_render_extras* ex) { return ex ? ex->dL_dalpha : nullptr; }
+
 static int64_t forward_prepare_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
-                                    size_t geometry_bytes, int32_t* radii, void* stream, bool defer_color) {
+                                    size_t geometry_bytes, int32_t* radii, void* stream, bool defer_color,
+                                    const gsr_render_extras* ex = nullptr) {
   int rc = validate(s, g);
   if (rc) return rc;
+  if ((rc = check_extras(ex))) return rc;
   if (g->P == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   uint32_t* host = pinned_slot();
@@ -447,7 +463,8 @@ static int64_t forward_prepare_impl(const gsr_settings* s, const gsr_gaussians* 
   if (!host || !ev) { gsr_set_error("hipHostMalloc / hipEventCreate failed"); return GSR_ERR_HIP; }
   // the host waits on an event recorded right behind the 16-byte copy, i.e. while the depth sort and the offset scan are still
   // queued: the GPU has ~0.1 ms of work left when the host goes on to size the binning state and enqueue the rest
-  if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, st, defer_color, host, ev, nullptr, false, nullptr)))
+  if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, st, defer_color, host, ev, nullptr, false, nullptr,
+                             nullptr, nullptr, nullptr, 0, ex_depth_z(ex))))
     return rc;
   return wait_for_count(host, ev, false);
 }
@@ -460,6 +477,16 @@ int64_t gsr_forward_prepare(const gsr_settings* s, const gsr_gaussians* g, void*
 int64_t gsr_forward_prepare_geometry(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
                                      size_t geometry_bytes, int32_t* radii, void* stream) {
   return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, true);
+}
+
+int64_t gsr_forward_prepare_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                               int32_t* radii, void* stream, const gsr_render_extras* extras) {
+  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, false, extras);
+}
+
+int64_t gsr_forward_prepare_geometry_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
+                                        size_t geometry_bytes, int32_t* radii, void* stream, const gsr_render_extras* extras) {
+  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, true, extras);
 }
 
 int gsr_forward_shade(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* stream) {
@@ -483,7 +510,7 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
                                bool sort_head_clean = false /* this call's projection kernel cleared the tile sort's head */,
                                uint32_t* tile_cutoff = nullptr /* per-tile depth cut-off: updated by the compositing kernel */,
                                bool cull_applied = false /* ... and the projection counted with it: emit with it too */,
-                               uint32_t frame_tag = 0) {
+                               uint32_t frame_tag = 0, float* out_alpha = nullptr /* gsr_render_extras.out_alpha */) {
   int rc = validate(s, g);
   if (rc) return rc;
   if (num_rendered < 0 || num_rendered > 0x3FFFFFFFll) {   // the tile sort counts keys in 30-bit fields (sort_scan.hip)
@@ -605,7 +632,7 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
                         (g->P > 0 && R > 0) ? tile_cutoff : nullptr, (const uint32_t*)(geom + GL.depth_key),
                         cull_applied ? (const uint32_t*)(bin + BL.culled_any) : nullptr, frame_tag, (uint32_t*)(geom + GL.meta),
                         walk_cnt, walk_cnt ? (uint32_t*)(img + IL.walk_list) : nullptr,
-                        walk_cnt ? (uint32_t*)(img + IL.walk_of_tile) : nullptr, st);
+                        walk_cnt ? (uint32_t*)(img + IL.walk_of_tile) : nullptr, out_alpha, st);
   if ((rc = debug_sync(s, st, "render forward"))) return rc;
   return gsr_launch_status("forward");
 }
@@ -625,13 +652,37 @@ int gsr_forward_render_shade(const gsr_settings* s, const gsr_gaussians* g, void
                              out_color, out_invdepth, for_backward != 0, true, (hipEvent_t)sh_ready_event, stream);
 }
 
+// (the depth kind was applied by the gsr_forward_prepare*_ex call that filled the geometry state: phase 2 takes the opacity plane)
+int gsr_forward_render_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                          size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes, float* out_color,
+                          float* out_invdepth, int32_t for_backward, void* stream, const gsr_render_extras* extras) {
+  int rc = check_extras(extras);
+  if (rc) return rc;
+  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
+                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr,
+                             nullptr, false, nullptr, false, 0, ex_alpha(extras));
+}
+
+int gsr_forward_render_shade_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                                size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
+                                float* out_color, float* out_invdepth, int32_t for_backward, void* sh_ready_event,
+                                void* stream, const gsr_render_extras* extras) {
+  int rc = check_extras(extras);
+  if (rc) return rc;
+  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
+                             out_color, out_invdepth, for_backward != 0, true, (hipEvent_t)sh_ready_event, stream, false, nullptr,
+                             nullptr, nullptr, nullptr, false, nullptr, false, 0, ex_alpha(extras));
+}
+
 static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
                       int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
                       size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
                       int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
-                      void* stream, int64_t* num_rendered_out, uint32_t* tile_cutoff, bool cull_apply) {
+                      void* stream, int64_t* num_rendered_out, uint32_t* tile_cutoff, bool cull_apply,
+                      const gsr_render_extras* ex = nullptr) {
   int rc = validate(s, g);
   if (rc) return rc;
+  if ((rc = check_extras(ex))) return rc;
   const bool tlo = tile_local_sort != 0;
   if (num_rendered_out) *num_rendered_out = 0;
   if (g->P > 0) {
@@ -672,13 +723,13 @@ static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, voi
     if (!culled_any) cull = false;
     if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, (hipStream_t)stream, late || aside != nullptr,
                                host, ev, aside, tlo, &early, sort_head, cull ? tile_cutoff : nullptr, cull ? culled_any : nullptr,
-                               frame_tag)))
+                               frame_tag, ex_depth_z(ex))))
       return rc;
     // (the caller's status words - flags, num_rendered and, in the tile-local form, the longest tile list meta[4] - leave at the END)
     rc = forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
                              out_color, out_invdepth, for_backward != 0, aside ? false : late,
                              aside ? aside->join : (hipEvent_t)sh_ready_event, stream, tlo, host_status, early, tlo ? host : nullptr,
-                             ev, /*sort_head_clean=*/sort_head != nullptr, tile_cutoff, cull, frame_tag);
+                             ev, /*sort_head_clean=*/sort_head != nullptr, tile_cutoff, cull, frame_tag, ex_alpha(ex));
     if (rc) return rc;
     if (num_rendered_out) {
       const int64_t n = wait_for_count(host, ev, early != nullptr);
@@ -688,7 +739,8 @@ static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, voi
     return 0;
   }
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, 0, image_state, image_bytes, out_color,
-                             out_invdepth, for_backward != 0, false, nullptr, stream);
+                             out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr, nullptr,
+                             false, nullptr, false, 0, ex_alpha(ex));
 }
 
 int gsr_forward_async(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -709,6 +761,38 @@ int gsr_forward_async_culled(const gsr_settings* s, const gsr_gaussians* g, void
   return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
                             image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
                             tile_local_sort, stream, num_rendered_out, tile_depth_cutoff, apply != 0);
+}
+
+int gsr_forward_async_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                         int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
+                         size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
+                         int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
+                         void* stream, int64_t* num_rendered_out, const gsr_render_extras* extras) {
+  return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
+                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
+                            tile_local_sort, stream, num_rendered_out, nullptr, false, extras);
+}
+
+int gsr_forward_async_culled_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                                int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
+                                size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
+                                int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
+                                void* stream, int64_t* num_rendered_out, uint32_t* tile_depth_cutoff, int32_t apply,
+                                const gsr_render_extras* extras) {
+  return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
+                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
+                            tile_local_sort, stream, num_rendered_out, tile_depth_cutoff, apply != 0, extras);
+}
+
+int gsr_forward_rerender_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                            size_t binning_bytes, int64_t capacity, void* image_state, size_t image_bytes, float* out_color,
+                            float* out_invdepth, int32_t for_backward, int32_t tile_local_sort, uint32_t* host_status,
+                            void* stream, const gsr_render_extras* extras) {
+  int rc = check_extras(extras);
+  if (rc) return rc;
+  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
+                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream, tile_local_sort != 0,
+                             host_status, nullptr, nullptr, nullptr, false, nullptr, false, 0, ex_alpha(extras));
 }
 
 int gsr_forward_rerender(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
@@ -779,9 +863,10 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
                          const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                          const gsr_fused_adam* opt, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
-                         void* stream) {
+                         void* stream, const gsr_render_extras* ex = nullptr) {
   int rc = validate(s, g);
   if (rc) return rc;
+  if ((rc = check_extras(ex))) return rc;
   if (cam && !cam->dL_dviewmatrix && !cam->dL_dprojmatrix && !cam->dL_dcampos) cam = nullptr;   // nothing asked for: plain
   if (cam && (!cam_scratch || cam_scratch_bytes < gsr_camera_grad_scratch_bytes(g->P))) {
     gsr_set_error("backward_camera: camera scratch too small (gsr_camera_grad_scratch_bytes)");
@@ -823,7 +908,7 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
                           (const uint32_t*)(img + IL.n_contrib), dL_dcolor, dL_dinvdepth,
                           (const uint32_t*)(bin + (tile_sort_result_buffer(tiles) ? BL.val_b : BL.val_a)), igrad,
                           (const uint32_t*)(geom + GL.meta) + 2, (uint32_t)R, (const uint32_t*)(img + IL.walk_cnt),
-                          (const uint32_t*)(img + IL.walk_list), (const uint32_t*)(img + IL.walk_of_tile), st);
+                          (const uint32_t*)(img + IL.walk_list), (const uint32_t*)(img + IL.walk_of_tile), ex_dalpha(ex), st);
     if ((rc = debug_sync(s, st, "render backward"))) return rc;
   }
   GsrAdamArgs A;
@@ -832,7 +917,7 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   const int mode = !opt ? 0 : (opt->sparse == 1 ? 2 : (opt->sparse == 2 ? 3 : 1));
   float* cam_rows = cam ? (float*)cam_scratch : nullptr;
   const int groups = gsr_launch_preprocess_bwd(s, g, radii, geom, GL, igrad, (uint32_t)R, grads, opt ? &A : nullptr, mode,
-                                               cam_rows, st);
+                                               cam_rows, ex_depth_z(ex), st);
   if (groups < 0) {
     gsr_set_error("backward_adam needs the raw-parameter call form with dc / shs passed separately (raw_activations = 1, "
                   "dc != NULL, no colors_precomp / cov3D_precomp, every stored SH coefficient active)");
@@ -869,6 +954,32 @@ int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32
   if (!opt) { gsr_set_error("backward_adam: null optimizer arguments"); return GSR_ERR_INVALID_ARGUMENT; }
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
                        scratch, scratch_bytes, grads, opt, nullptr, nullptr, 0, stream);
+}
+
+int gsr_backward_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                    const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                    const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads, void* stream,
+                    const gsr_render_extras* extras) {
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, grads, nullptr, nullptr, nullptr, 0, stream, extras);
+}
+
+int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                           const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                           const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                           const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream,
+                           const gsr_render_extras* extras) {
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, extras);
+}
+
+int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                         const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                         const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                         const gsr_fused_adam* opt, void* stream, const gsr_render_extras* extras) {
+  if (!opt) { gsr_set_error("backward_adam: null optimizer arguments"); return GSR_ERR_INVALID_ARGUMENT; }
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, grads, opt, nullptr, nullptr, 0, stream, extras);
 }
 
 int gsr_adam_step_culled_rows(const gsr_gaussians* g, const void* geometry_state, int64_t num_rendered,

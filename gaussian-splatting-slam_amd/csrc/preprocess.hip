@@ -264,7 +264,8 @@ __global__ __launch_bounds__(256) void k_preprocess_fwd(
     uint8_t* __restrict__ clamped, uint32_t* __restrict__ meta, uint32_t* __restrict__ block_sums,
     uint32_t* __restrict__ zero_words, int n_zero_words,
     const uint32_t* __restrict__ tile_cutoff /* nullptr, or per tile the depth bits beyond which nothing is emitted */,
-    uint32_t* __restrict__ culled_any /* [tiles]: set to frame_tag where an instance is dropped */, uint32_t frame_tag) {
+    uint32_t* __restrict__ culled_any /* [tiles]: set to frame_tag where an instance is dropped */, uint32_t frame_tag,
+    int depth_z /* GSR_DEPTH_Z: the composited depth channel (record slot 10) holds z itself instead of 1/z */) {
   extern __shared__ __attribute__((aligned(16))) float sh_lds[];
   // (round 4) the head of the tile sort's scratch - histogram replicas + pass tickets - is cleared HERE, one kernel ahead of
   // k_emit_instances, whose workgroups all add their digit counts to it (binning.hip)
@@ -451,7 +452,7 @@ __global__ __launch_bounds__(256) void k_preprocess_fwd(
     }
     rec[3 * (size_t)idx + 0] = make_float4(px, py, sA, sB);
     rec[3 * (size_t)idx + 1] = make_float4(sC, op, spmin, rgb[0]);
-    rec[3 * (size_t)idx + 2] = make_float4(rgb[1], rgb[2], 1.0f / depth, depth);
+    rec[3 * (size_t)idx + 2] = make_float4(rgb[1], rgb[2], depth_z ? depth : 1.0f / depth, depth);
     rect[idx] = make_ushort4((unsigned short)cx0, (unsigned short)cy0, (unsigned short)cx1, (unsigned short)cy1);
     // the emit pass walks the Gaussians in DEPTH order: one 32-B gather per Gaussian instead of three (record, rect, count)
     bin_rec[2 * (size_t)idx + 0] = make_float4(px, py, sA, sB);
@@ -666,7 +667,9 @@ __device__ __forceinline__ void cam_block_partial(const float* cg, float* __rest
 // (gather / arithmetic / streaming) in flight, and the barriers become free.
 // CAM (instantiated with ADAM = 0 only): also the camera-gradient terms of every visible Gaussian, summed per workgroup into row
 // blockIdx.x of `cam_rows` (gsr_backward_camera; k_cam_reduce adds the rows).  The per-Gaussian gradients are unchanged.
-template <bool STAGE, int ADAM, int BT, bool CAM = false>
+// ZD: the forward composited z instead of 1/z (gsr_render_extras.depth_kind = GSR_DEPTH_Z): the depth channel's gradient enters
+// dL/dt.z as it is instead of through d(1/z)/dz = -1/z^2 (the camera form reads g_t after it: dL/dviewmatrix follows)
+template <bool STAGE, int ADAM, int BT, bool CAM = false, bool ZD = false>
 __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     int P, int deg, int sh_stride, const float* __restrict__ means3D, const float* __restrict__ dc,
     const float* __restrict__ shs, const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -957,8 +960,12 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     g_t[0] = e.in_x ? (-fx * tz2 * gJ02) : 0.f;
     g_t[1] = e.in_y ? (-fy * tz2 * gJ12) : 0.f;
     g_t[2] = -fx * tz2 * gJ00 - fy * tz2 * gJ11 + 2.f * fx * e.tx * tz3 * gJ02 + 2.f * fy * e.ty * tz3 * gJ12;
-    // inverse depth output: invd = 1/t.z
-    g_t[2] += -g_invd * tz2;
+    if constexpr (ZD) {
+      g_t[2] += g_invd;           // z-depth output: the channel is t.z itself
+    } else {
+      // inverse depth output: invd = 1/t.z
+      g_t[2] += -g_invd * tz2;
+    }
     // t = V p
 #pragma unroll
     for (int j = 0; j < 3; j++) g_mean[j] += v.V[4 * j + 0] * g_t[0] + v.V[4 * j + 1] * g_t[1] + v.V[4 * j + 2] * g_t[2];
@@ -1386,7 +1393,7 @@ void gsr_launch_shade(const gsr_settings* s, const gsr_gaussians* g, char* geom,
 void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, int32_t* radii, char* geom,
                                const GsrGeomLayout& L, bool defer_color, bool block_sums, uint32_t* zero_words,
                                int n_zero_words, const uint32_t* tile_cutoff, uint32_t* culled_any, uint32_t frame_tag,
-                               hipStream_t st) {
+                               bool depth_z, hipStream_t st) {
   const int P = g->P;
   size_t lds = 0;
   const bool stage = !defer_color && can_stage_sh(s, g, &lds);
@@ -1398,7 +1405,7 @@ void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, in
       (uint32_t*)(geom + L.depth_key), (uint32_t*)(geom + L.order), (uint32_t*)(geom + L.tiles_touched),              \
       (ushort4*)(geom + L.rect), (float4*)(geom + L.bin_rec), (uint8_t*)(geom + L.clamped), (uint32_t*)(geom + L.meta), \
       block_sums ? (uint32_t*)(geom + L.offsets) : (uint32_t*)nullptr, zero_words, n_zero_words, tile_cutoff,       \
-      culled_any, frame_tag
+      culled_any, frame_tag, (int)depth_z
   if (stage)
     GSR_LAUNCH("preprocess_fwd", k_preprocess_fwd<true>, dim3((P + 255) / 256), dim3(256), lds, st, GSR_PRE_FWD_ARGS);
   else
@@ -1412,7 +1419,7 @@ void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, in
 int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
                               const char* geom, const GsrGeomLayout& L, const float4* igrad, uint32_t cap,
                               const gsr_grads* gr, const GsrAdamArgs* adam, int adam_mode, float* cam_rows,
-                              hipStream_t st) {
+                              bool depth_z, hipStream_t st) {
   const int P = g->P;
   size_t lds = 0;
   GsrAdamArgs A;
@@ -1438,14 +1445,19 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
       (const uint32_t*)(geom + L.meta) + 2, cap, gr->dL_dmeans3D,                                                      \
       gr->dL_dmeans2D, gr->dL_ddc, gr->dL_dshs, gr->dL_dcolors, gr->dL_dopacities, gr->dL_dscales, gr->dL_drotations, \
       gr->dL_dcov3D, gr->xyz_gradient_accum, gr->denom, gr->max_radii2D, A, g_gsr_flags_min_r, cam_rows
-#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME)                                                                         \
+#define GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, ZD_, NAME)                                                                   \
   do {                                                                                                                 \
     if (lds > 48 * 1024)                                                                                               \
-      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_>,                                      \
+      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_>,                                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_>),                                                            \
+    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_>),                                                       \
                dim3((P + BT_ - 1) / BT_), dim3(BT_), ST ? lds : 0, st, GSR_PRE_BWD_ARGS);                              \
     groups = (P + BT_ - 1) / BT_;                                                                                      \
+  } while (0)
+  // (z-depth: the ZD instantiations; without it every launch below is the one it was)
+#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME)                                                                         \
+  do {                                                                                                                 \
+    if (depth_z) GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, true, NAME); else GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, false, NAME);   \
   } while (0)
   int groups = 0;
 #define GSR_PRE_BWD(ST, AD, BT_) GSR_PRE_BWD_K(ST, AD, BT_, false, AD ? "preprocess_bwd_adam" : "preprocess_bwd")
@@ -1464,6 +1476,7 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
   }
 #undef GSR_PRE_BWD
 #undef GSR_PRE_BWD_K
+#undef GSR_PRE_BWD_KZ
 #undef GSR_PRE_BWD_ARGS
   return groups;
 }

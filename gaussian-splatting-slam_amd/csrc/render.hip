@@ -255,7 +255,9 @@ __device__ __forceinline__ uint32_t gsr_subblock_mask(const float4& r0, const fl
 // wave takes the bit of ITS quadrant of all 256 staged entries with four ballots and walks only the entries whose bit is set -
 // an entry out of reach costs a scalar bit scan instead of 8 VALU + a ballot + a branch.  Entries that ARE walked take the exact
 // published test, in the published order: images, final_T and n_contrib are bit-identical.
-template <bool COUNT, bool MASKED>
+// ALPHA: also writes the accumulated opacity 1 - T_final of every pixel to `out_alpha` (gsr_render_extras); the other
+// instantiations compile to the code they had.
+template <bool COUNT, bool MASKED, bool ALPHA = false>
 __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                                                     const uint32_t* __restrict__ point_list,
                                                     const float4* __restrict__ rec, const float* __restrict__ bg,
@@ -269,7 +271,8 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
                                                     const uint32_t* __restrict__ culled_any /* nullptr: lists not truncated */,
                                                     uint32_t frame_tag, uint32_t* __restrict__ meta, uint32_t margin_q8,
                                                     uint32_t margin_add, uint32_t* __restrict__ walk_cnt,
-                                                    uint32_t* __restrict__ walk_list, uint32_t* __restrict__ walk_of_tile) {
+                                                    uint32_t* __restrict__ walk_list, uint32_t* __restrict__ walk_of_tile,
+                                                    float* __restrict__ out_alpha) {
   __shared__ float4 s0[FWD_BATCH + 6], s1[FWD_BATCH + 6], s2[FWD_BATCH];  // +6: the prefetch may touch [n+5]
   __shared__ uint32_t s_need;
   __shared__ uint32_t s_wave_last[4];
@@ -462,6 +465,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
     out_color[N + pix] = C1 + T * bg[1];
     out_color[2 * N + pix] = C2 + T * bg[2];
     out_invdepth[pix] = D;
+    if constexpr (ALPHA) out_alpha[pix] = 1.0f - T;
   }
 }
 
@@ -470,8 +474,10 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
 #endif
 
 // DEPTH = false: no gradient arrives on the inverse-depth image (the usual training step): its recurrence and its
-// reduction are compiled out.
-template <bool DEPTH>
+// reduction are compiled out.  ALPHA: a gradient arrives on the accumulated opacity A = 1 - T_final (gsr_render_extras); the
+// per-pixel background constant takes it (dA/dalpha_i = T_final / (1 - alpha_i), the background's own factor) - nothing in
+// the entry loop changes, and the other instantiations compile to the code they had.
+template <bool DEPTH, bool ALPHA = false>
 __global__ __launch_bounds__(256) void k_render_bwd(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                                                     const uint32_t* __restrict__ point_list,
                                                     const float4* __restrict__ rec, const float* __restrict__ bg,
@@ -483,7 +489,8 @@ __global__ __launch_bounds__(256) void k_render_bwd(int W, int H, int grid_x, co
                                                     float4* __restrict__ igrad, const uint32_t* __restrict__ n_dev,
                                                     uint32_t cap, const uint32_t* __restrict__ walk_cnt,
                                                     const uint32_t* __restrict__ walk_list,
-                                                    const uint32_t* __restrict__ walk_of_tile, uint32_t flags_min_r) {
+                                                    const uint32_t* __restrict__ walk_of_tile, uint32_t flags_min_r,
+                                                    const float* __restrict__ dL_dalpha) {
   __shared__ float4 s0[BWD_BATCH + 6], s1[BWD_BATCH + 6], s2[BWD_BATCH];  // +6: the prefetch may touch [n+5]
   if (gsr_overflowed(n_dev, cap)) return;   // grid-uniform: a truncated frame teaches nothing (gsr_common.h)
   unsigned char* const iflags = gsr_igrad_flags(igrad, cap);
@@ -546,7 +553,13 @@ __global__ __launch_bounds__(256) void k_render_bwd(int W, int H, int grid_x, co
     gp2 = dL_dpix[2 * N + pix];
     if (DEPTH) gd = dL_dinvdepth[pix];
   }
-  const float neg_Tf_bg = -T_final * (bg[0] * gp0 + bg[1] * gp1 + bg[2] * gp2);
+  float neg_Tf_bg;
+  if constexpr (ALPHA) {
+    const float gA = inside ? dL_dalpha[pix] : 0.f;
+    neg_Tf_bg = -T_final * ((bg[0] * gp0 + bg[1] * gp1 + bg[2] * gp2) - gA);
+  } else {
+    neg_Tf_bg = -T_final * (bg[0] * gp0 + bg[1] * gp1 + bg[2] * gp2);
+  }
 
   // entries beyond the deepest contributor of any pixel are never visited
   if (tid == 0) s_max = 0;
@@ -708,7 +721,7 @@ __global__ __launch_bounds__(256) void k_render_bwd(int W, int H, int grid_x, co
 #ifndef BWD_TILE_WAVES
 #define BWD_TILE_WAVES 5   // waves per SIMD the register allocation must admit (<= 96 VGPRs; measured: 4, 5 and 6 within 2 %, 6 needs spills)
 #endif
-template <bool DEPTH, bool MASK>
+template <bool DEPTH, bool MASK, bool ALPHA = false>   // (ALPHA: as in k_render_bwd)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_TILE_WAVES, 8))) void k_render_bwd_tile(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                                                         const uint32_t* __restrict__ point_list,
                                                         const float4* __restrict__ rec, const float* __restrict__ bg,
@@ -721,7 +734,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_TILE_WAV
                                                         uint32_t cap, int prio1, int prio2, int prio3,
                                                         const uint32_t* __restrict__ walk_cnt,
                                                         const uint32_t* __restrict__ walk_list,
-                                                        const uint32_t* __restrict__ walk_of_tile, uint32_t flags_min_r) {
+                                                        const uint32_t* __restrict__ walk_of_tile, uint32_t flags_min_r,
+                                                        const float* __restrict__ dL_dalpha) {
   // (one object: the three arrays sit at fixed distances, so an entry's reads share ONE address register and differ in the
   // instruction's immediate offset - two v_add_u32 per walked entry less than three separate __shared__ arrays cost)
   __shared__ struct { float4 s0[BWD1_BATCH + 2], s1[BWD1_BATCH + 2], s2[BWD1_BATCH]; } stg;   // +2: the prefetch may touch [n+1]
@@ -801,7 +815,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_TILE_WAV
     gp1[s] = inside ? dL_dpix[N + pix] : 0.f;
     gp2[s] = inside ? dL_dpix[2 * N + pix] : 0.f;
     gd[s] = (DEPTH && inside) ? dL_dinvdepth[pix] : 0.f;
-    nTb[s] = -T[s] * (bg0 * gp0[s] + bg1 * gp1[s] + bg2 * gp2[s]);
+    if constexpr (ALPHA) {
+      const float gA = inside ? dL_dalpha[pix] : 0.f;
+      nTb[s] = -T[s] * ((bg0 * gp0[s] + bg1 * gp1[s] + bg2 * gp2[s]) - gA);
+    } else {
+      nTb[s] = -T[s] * (bg0 * gp0[s] + bg1 * gp1[s] + bg2 * gp2[s]);
+    }
     S[s] = 0.f;
     int m = last[s];
 #pragma unroll
@@ -1247,13 +1266,13 @@ extern "C" int gsr_debug_mx_reduce(const float* in514, float* out10, void* strea
 #ifndef BWD_MX_WAVES
 #define BWD_MX_WAVES 4
 #endif
-template <bool DEPTH>
+template <bool DEPTH, bool ALPHA = false>   // (ALPHA: as in k_render_bwd)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES, 8))) void k_render_bwd_tile_mx(
     int W, int H, int grid_x, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float4* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, const float* __restrict__ dL_dinvdepth,
     const uint32_t* __restrict__ slot_of_pos, float4* __restrict__ igrad, const uint32_t* __restrict__ n_dev, uint32_t cap,
-    int prio1, int prio2, int prio3, uint32_t flags_min_r) {
+    int prio1, int prio2, int prio3, uint32_t flags_min_r, const float* __restrict__ dL_dalpha) {
   __shared__ float4 s0[BWD1_BATCH + 2], s1[BWD1_BATCH + 2], s2[BWD1_BATCH];
   if (gsr_overflowed(n_dev, cap)) return;
   unsigned char* const iflags = gsr_igrad_flags(igrad, cap);
@@ -1284,7 +1303,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
     gp01[s] = gsr_f2{g0, g1};
     gp2[s] = inside ? dL_dpix[2 * N + pix] : 0.f;
     gd[s] = (DEPTH && inside) ? dL_dinvdepth[pix] : 0.f;
-    nTb[s] = -T[s] * (bg0 * g0 + bg1 * g1 + bg2 * gp2[s]);
+    if constexpr (ALPHA) {
+      const float gA = inside ? dL_dalpha[pix] : 0.f;
+      nTb[s] = -T[s] * ((bg0 * g0 + bg1 * g1 + bg2 * gp2[s]) - gA);
+    } else {
+      nTb[s] = -T[s] * (bg0 * g0 + bg1 * g1 + bg2 * gp2[s]);
+    }
     S[s] = 0.f;
     int m = last[s];
 #pragma unroll
@@ -1433,21 +1457,26 @@ void gsr_launch_render_fwd(const gsr_settings* s, int tiles, int grid_x, const u
                            const uint32_t* point_list, const float4* rec, float* out_color, float* out_invdepth,
                            float* final_T, uint32_t* n_contrib, const uint32_t* status_src, uint32_t* status_dst,
                            uint32_t* tile_cutoff, const uint32_t* depth_key, const uint32_t* culled_any, uint32_t frame_tag,
-                           uint32_t* meta, uint32_t* walk_cnt, uint32_t* walk_list, uint32_t* walk_of_tile, hipStream_t st) {
+                           uint32_t* meta, uint32_t* walk_cnt, uint32_t* walk_list, uint32_t* walk_of_tile, float* out_alpha,
+                           hipStream_t st) {
   // cut-off margin of the depth-truncated lists: 1.75 x the entries a tile needed + 48 (measured, profiles/r04_tile_cull.txt: 1.25 x + 16
   // flags 54 % of the frames of a run that trains from scratch, 1.5 x + 32 1 %, 1.75 x + 48 none; C3 and the 2 x splats scene)
   unsigned mq8 = 448, madd = 48;
   if (const char* mg = getenv("GSR_CULL_MARGIN")) sscanf(mg, "%u,%u", &mq8, &madd);
   // GSR_FWD_MASK=1 selects the masked walk (measured: 0.208 against 0.179 ms at C3, profiles/r04_fwd_mask_ab.txt - not the default)
   const char* mk = getenv("GSR_FWD_MASK");          // (read per call: the tests switch inside one process)
-  if (!(mk && !strcmp(mk, "1")))
-    GSR_LAUNCH("render_fwd", (k_render_fwd<false, false>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x,
-               ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,
-               status_dst, tile_cutoff, depth_key, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile);
-  else
-    GSR_LAUNCH("render_fwd", (k_render_fwd<false, true>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x,
-               ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,
-               status_dst, tile_cutoff, depth_key, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile);
+  const bool masked = mk && !strcmp(mk, "1");
+#define GSR_FWD_LAUNCH(M, A)                                                                                                  \
+  GSR_LAUNCH("render_fwd", (k_render_fwd<false, M, A>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
+             ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,        \
+             status_dst, tile_cutoff, depth_key, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile,       \
+             out_alpha)
+  if (out_alpha) {
+    if (masked) GSR_FWD_LAUNCH(true, true); else GSR_FWD_LAUNCH(false, true);
+  } else {
+    if (masked) GSR_FWD_LAUNCH(true, false); else GSR_FWD_LAUNCH(false, false);
+  }
+#undef GSR_FWD_LAUNCH
 }
 
 void gsr_launch_count_pairs(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges, const uint32_t* point_list,
@@ -1457,14 +1486,16 @@ void gsr_launch_count_pairs(const gsr_settings* s, int tiles, int grid_x, const 
   hipLaunchKernelGGL((k_render_fwd<true, false>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, ranges,
                      point_list, rec, s->bg, (float*)nullptr, (float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, pairs,
                      (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                     (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+                     (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                     (float*)nullptr);
 }
 
 void gsr_launch_render_bwd(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges,
                            const uint32_t* point_list, const float4* rec, const float* final_T,
                            const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dinvdepth,
                            const uint32_t* slot_of_pos, float4* igrad, const uint32_t* n_dev, uint32_t cap,
-                           const uint32_t* walk_cnt, const uint32_t* walk_list, const uint32_t* walk_of_tile, hipStream_t st) {
+                           const uint32_t* walk_cnt, const uint32_t* walk_list, const uint32_t* walk_of_tile,
+                           const float* dL_dalpha, hipStream_t st) {
   // GSR_BWD_LPT=0: tiles in index order (the A/B of the walk classes, profiles/r04_bwd_lpt_ab.txt)
   if (const char* lp = getenv("GSR_BWD_LPT")) {
     if (lp[0] == '0') walk_cnt = nullptr;
@@ -1492,34 +1523,35 @@ void gsr_launch_render_bwd(const gsr_settings* s, int tiles, int grid_x, const u
   // v_mfma_f32_16x16x4_f32 (k_render_bwd_tile_mx); the default is the v_permlane / DPP halving tree
   const char* red = getenv("GSR_BWD_REDUCE");
   const bool mx = mask && red && !strcmp(red, "mfma");
+  // dL_dalpha (gsr_render_extras): the ALPHA instantiations; without it every launch below is the one it was
+#define GSR_BWD_BY_DA(LAUNCH, ...) do { if (dL_dalpha) LAUNCH(__VA_ARGS__, true); else LAUNCH(__VA_ARGS__, false); } while (0)
   if ((!quad || (form && !strcmp(form, "tile"))) && mx) {
-    if (dL_dinvdepth)
-      GSR_LAUNCH("render_bwd", (k_render_bwd_tile_mx<true>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x,
-                 ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, g_gsr_flags_min_r);
-    else
-      GSR_LAUNCH("render_bwd", (k_render_bwd_tile_mx<false>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x,
-                 ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, g_gsr_flags_min_r);
+#define GSR_BWD_MX_LAUNCH(D, A)                                                                                                   \
+  GSR_LAUNCH("render_bwd", (k_render_bwd_tile_mx<D, A>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x, \
+             ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, \
+             g_gsr_flags_min_r, dL_dalpha)
+    if (dL_dinvdepth) GSR_BWD_BY_DA(GSR_BWD_MX_LAUNCH, true); else GSR_BWD_BY_DA(GSR_BWD_MX_LAUNCH, false);
+#undef GSR_BWD_MX_LAUNCH
     return;
   }
   if (!quad || (form && !strcmp(form, "tile"))) {
-#define GSR_BWD_TILE_LAUNCH(D, M)                                                                                          \
-  GSR_LAUNCH("render_bwd", (k_render_bwd_tile<D, M>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x, \
+#define GSR_BWD_TILE_LAUNCH(D, M, A)                                                                                       \
+  GSR_LAUNCH("render_bwd", (k_render_bwd_tile<D, M, A>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x, \
              ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, \
-             walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r)
+             walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r, dL_dalpha)
     if (dL_dinvdepth) {
-      if (mask) GSR_BWD_TILE_LAUNCH(true, true); else GSR_BWD_TILE_LAUNCH(true, false);
+      if (mask) GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, true, true); else GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, true, false);
     } else {
-      if (mask) GSR_BWD_TILE_LAUNCH(false, true); else GSR_BWD_TILE_LAUNCH(false, false);
+      if (mask) GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, false, true); else GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, false, false);
     }
 #undef GSR_BWD_TILE_LAUNCH
     return;
   }
-  if (dL_dinvdepth)
-    GSR_LAUNCH("render_bwd", k_render_bwd<true>, dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height,
-               grid_x, ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,
-               walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r);
-  else
-    GSR_LAUNCH("render_bwd", k_render_bwd<false>, dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height,
-               grid_x, ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,
-               walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r);
+#define GSR_BWD_QUAD_LAUNCH(D, A)                                                                                    \
+  GSR_LAUNCH("render_bwd", (k_render_bwd<D, A>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
+             ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,    \
+             walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r, dL_dalpha)
+  if (dL_dinvdepth) GSR_BWD_BY_DA(GSR_BWD_QUAD_LAUNCH, true); else GSR_BWD_BY_DA(GSR_BWD_QUAD_LAUNCH, false);
+#undef GSR_BWD_QUAD_LAUNCH
+#undef GSR_BWD_BY_DA
 }

@@ -50,6 +50,13 @@ class gsr_camera_grads(C.Structure):
     _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p)]
 
 
+class gsr_render_extras(C.Structure):
+    _fields_ = [("depth_kind", C.c_int32), ("out_alpha", C.c_void_p), ("dL_dalpha", C.c_void_p)]
+
+
+DEPTH_KINDS = {"inverse": 0, "z": 1}     # gsr_render_extras.depth_kind: GSR_DEPTH_INVERSE, GSR_DEPTH_Z
+
+
 class gsr_fused_adam(C.Structure):
     _fields_ = [
         ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("lr", C.c_float * 6), ("step", C.c_int64 * 6),
@@ -99,6 +106,40 @@ EXPORTS = {
     "gsr_backward_adam": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p]),
+    # the *_ex forms: the same arguments plus a gsr_render_extras* (NULL = the form without _ex)
+    "gsr_forward_prepare_ex": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_forward_prepare_geometry_ex": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p,
+                                                    C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_forward_render_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_forward_render_shade_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_forward_async_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.POINTER(C.c_int64), C.POINTER(gsr_render_extras)]),
+    "gsr_forward_async_culled_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32,
+                                              C.POINTER(gsr_render_extras)]),
+    "gsr_forward_rerender_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_backward_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.POINTER(gsr_grads), C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_backward_camera_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_backward_adam_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p,
+                                       C.POINTER(gsr_render_extras)]),
     "gsr_adam_step_culled_rows": (C.c_int, [C.POINTER(gsr_gaussians), C.c_void_p, C.c_int64, C.POINTER(gsr_fused_adam),
                                             C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

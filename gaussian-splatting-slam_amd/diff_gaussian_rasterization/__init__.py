@@ -284,7 +284,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                 raster_settings, raw_activations=False, for_backward=True, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True, viewmatrix=None, projmatrix=None, campos=None):
+                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, viewmatrix=None, projmatrix=None,
+                campos=None):
         """fold: a BackwardFold for THIS call's backward (kept on ctx).  sh_ready_event: a recorded torch.cuda.Event after which
         `dc` / `shs` hold this step's values (the view-sharded trainer's SH all-reduce + Adam update, in flight on another
         stream): the geometry stages run first, the stream waits for the event and only then evaluates the colours
@@ -292,8 +293,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         the process-wide mode, GSR_FORWARD_MODE / set_forward_mode).  tile_cull: this VIEW's per-tile depth cut-offs
         (`new_tile_cull`), updated by every speculative forward and applied by unverified ones (gsr_forward_async_culled).
         viewmatrix / projmatrix / campos: raster_settings' own tensors, passed (by rasterize_gaussians) only when one of them
-        requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera)."""
+        requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera).  depth / alpha: the
+        depth kind of the third output and whether a fourth, the accumulated opacity, is returned (gsr_render_extras)."""
         lib = _C.lib()
+        depth_kind = _depth_kind(depth)
         raw_activations = bool(raw_activations) and cov3D_precomp is None
         if not means3D.is_cuda:
             raise _C.GsrError("GaussianRasterizer needs tensors on the HIP device (no CPU path)")
@@ -326,6 +329,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
             invdepth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
             radii = torch.empty(P, dtype=torch.int32, device=dev)     # every entry is written by the projection kernel
+            alpha_img = torch.empty(1, H, W, dtype=torch.float32, device=dev) if alpha else None
+            # (no extras: NULL, the entry points without _ex exactly)
+            extras = _C.gsr_render_extras(depth_kind, _C.ptr(alpha_img) if alpha else None, None) \
+                if (depth_kind or alpha) else None
+            ex = C.byref(extras) if extras is not None else None
             s, keep = _settings_struct(rs, dev)
             g = _gauss_struct(P, means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                               raw_activations)
@@ -343,6 +351,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 if mode not in _ws._MODES:
                     raise ValueError(f"forward_mode={mode!r}: expected one of {_ws._MODES}")
                 if capturing:
+                    if extras is not None:
+                        raise _C.GsrError("depth='z' / alpha=True are not supported under HIP-graph capture: render eagerly")
                     if rs.debug or rs.prefiltered or key not in pool.capacity or not pool.status_free:
                         raise _C.GsrError("gsr: a forward under graph capture needs an eager warm-up of the same shape first "
                                           "(and neither debug nor prefiltered)")
@@ -370,12 +380,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                                               "(diff_gaussian_rasterization.new_tile_cull)")
                     # lists truncated by depth only where a frame may flag itself afterwards: unverified, not under capture
                     cull_apply = tile_cull is not None and bool(tile_cull_apply) and not verify and not capturing and tlo == 1
-                    _C.check(lib.gsr_forward_async_culled(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii),
-                                                          _C.ptr(binning), binning.numel(), R, _C.ptr(img), img.numel(),
-                                                          _C.ptr(color), _C.ptr(invdepth), 1 if needs_grad else 0,
-                                                          1 if split else 0, evh, C.c_void_p(status.data_ptr()), tlo, stream,
-                                                          C.byref(count) if verify else None, _C.ptr(tile_cull),
-                                                          1 if cull_apply else 0))
+                    _C.check(lib.gsr_forward_async_culled_ex(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(),
+                                                             _C.ptr(radii), _C.ptr(binning), binning.numel(), R, _C.ptr(img),
+                                                             img.numel(), _C.ptr(color), _C.ptr(invdepth),
+                                                             1 if needs_grad else 0, 1 if split else 0, evh,
+                                                             C.c_void_p(status.data_ptr()), tlo, stream,
+                                                             C.byref(count) if verify else None, _C.ptr(tile_cull),
+                                                             1 if cull_apply else 0, ex))
                     if cull_apply:
                         pool.stats["culled_frames"] = pool.stats.get("culled_frames", 0) + 1
                     pool.ticket += 1
@@ -389,10 +400,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                             rerendered = True
                             R = _ws._capacity_for(n)
                             binning = ws.ensure_binning(lib, P, W, H, R)
-                            _C.check(lib.gsr_forward_rerender(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                              binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                              _C.ptr(invdepth), 1 if needs_grad else 0, tlo,
-                                                              C.c_void_p(status.data_ptr()), stream))
+                            _C.check(lib.gsr_forward_rerender_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
+                                                                 binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
+                                                                 _C.ptr(invdepth), 1 if needs_grad else 0, tlo,
+                                                                 C.c_void_p(status.data_ptr()), stream, ex))
                         pool.note(key, n)
                     pool.stats["exact_frames" if mode == "exact" else "async_frames"] += 1
                     # a verified frame's status (only its longest tile list is still of interest) is recognised by the
@@ -409,20 +420,20 @@ class _RasterizeGaussians(torch.autograd.Function):
                 else:
                     # blocking read-back of num_rendered (the published rasterizer's one host synchronisation): debug mode,
                     # prefiltered=True (its "culled point" error is raised by this very call), or GSR_FORWARD_MODE=sync
-                    prepare = lib.gsr_forward_prepare_geometry if split else lib.gsr_forward_prepare
-                    R = _C.check(prepare(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii), stream))
+                    prepare = lib.gsr_forward_prepare_geometry_ex if split else lib.gsr_forward_prepare_ex
+                    R = _C.check(prepare(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii), stream, ex))
                     pool.note(key, R)
                     pool.stats["sync_frames"] += 1
                     binning = ws.ensure_binning(lib, P, W, H, max(R, pool.capacity[key]))
                     if split:
                         # split forward: geometry stages, emission + tile sort, THEN wait for the SH update, shade, composite
-                        _C.check(lib.gsr_forward_render_shade(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                              binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                              _C.ptr(invdepth), 1 if needs_grad else 0, evh, stream))
+                        _C.check(lib.gsr_forward_render_shade_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
+                                                                 binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
+                                                                 _C.ptr(invdepth), 1 if needs_grad else 0, evh, stream, ex))
                     else:
-                        _C.check(lib.gsr_forward_render(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                        binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                        _C.ptr(invdepth), 1 if needs_grad else 0, stream))
+                        _C.check(lib.gsr_forward_render_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
+                                                           binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
+                                                           _C.ptr(invdepth), 1 if needs_grad else 0, stream, ex))
             except _C.GsrError:
                 if rs.debug:   # reference README.md:168-169: with --debug a failing rasterizer call dumps its inputs
                     _dump("snapshot_fw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
@@ -431,6 +442,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.camera = viewmatrix is not None or projmatrix is not None or campos is not None
         ctx.raw_activations = raw_activations
+        ctx.depth_kind, ctx.alpha = depth_kind, bool(alpha)
         ctx.fold = fold if needs_grad else None
         ctx.num_rendered = R                 # what the binning state was laid out for (the count itself, or the capacity)
         ctx.has = (dc is not None, sh is not None, colors_precomp is not None, scales is not None,
@@ -442,10 +454,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)     # an unused inverse-depth output reaches backward as None, not as zeros
+        if alpha:
+            return color, radii, invdepth, alpha_img
         return color, radii, invdepth
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_invdepth):
+    def backward(ctx, grad_color, grad_radii, grad_invdepth, grad_alpha=None):
         lib = _C.lib()
         (means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii) = ctx.saved_tensors
         ws = ctx.lease.ws
@@ -461,6 +475,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_color is None:
             grad_color = torch.zeros(3, H, W, device=dev)
         grad_invdepth = _f32c(grad_invdepth)
+        grad_alpha = _f32c(grad_alpha) if ctx.alpha else None     # (None: no gradient reached the opacity plane - zero)
+        extras = _C.gsr_render_extras(ctx.depth_kind, None, _C.ptr(grad_alpha) if grad_alpha is not None else None) \
+            if (ctx.depth_kind or grad_alpha is not None) else None
+        ex = C.byref(extras) if extras is not None else None
 
         def like(t, *shape):
             return torch.empty(*shape, dtype=torch.float32, device=dev) if t is not None else None
@@ -542,23 +560,23 @@ class _RasterizeGaussians(torch.autograd.Function):
                             with torch.cuda.stream(side):
                                 _C.check(lib.gsr_adam_step_culled_rows(C.byref(g), _C.ptr(geom), R, C.byref(fused[0]),
                                                                        _stream()))
-                        _C.check(lib.gsr_backward_adam(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
-                                                       _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
-                                                       _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(), C.byref(gr),
-                                                       C.byref(fused[0]), _stream()))
+                        _C.check(lib.gsr_backward_adam_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
+                                                          _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
+                                                          _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(), C.byref(gr),
+                                                          C.byref(fused[0]), _stream(), ex))
                         if split:
                             torch.cuda.current_stream().wait_stream(side)   # what follows here sees both halves of the update
                     elif ctx.camera:
                         cam_scratch = torch.empty(lib.gsr_camera_grad_scratch_bytes(P), dtype=torch.uint8, device=dev)
-                        _C.check(lib.gsr_backward_camera(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
-                                                         _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
-                                                         _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(), C.byref(gr),
-                                                         C.byref(cam_struct), _C.ptr(cam_scratch), cam_scratch.numel(),
-                                                         _stream()))
+                        _C.check(lib.gsr_backward_camera_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
+                                                            _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
+                                                            _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(),
+                                                            C.byref(gr), C.byref(cam_struct), _C.ptr(cam_scratch),
+                                                            cam_scratch.numel(), _stream(), ex))
                     else:
-                        _C.check(lib.gsr_backward(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom), _C.ptr(binning),
-                                                  _C.ptr(img), R, _C.ptr(grad_color), _C.ptr(grad_invdepth),
-                                                  _C.ptr(scratch), scratch.numel(), C.byref(gr), _stream()))
+                        _C.check(lib.gsr_backward_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom), _C.ptr(binning),
+                                                     _C.ptr(img), R, _C.ptr(grad_color), _C.ptr(grad_invdepth),
+                                                     _C.ptr(scratch), scratch.numel(), C.byref(gr), _stream(), ex))
                 except _C.GsrError:
                     if rs.debug:
                         _dump("snapshot_bw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
@@ -573,14 +591,25 @@ class _RasterizeGaussians(torch.autograd.Function):
                 cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
                                   for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
         return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None, None, None, None, None, None,
-                None) + (cam_grads if ctx.camera else ())
+                None, None, None) + (cam_grads if ctx.camera else ())
+
+
+def _depth_kind(depth):
+    """gsr_render_extras.depth_kind of a `depth=` argument; raises for anything but "inverse" / "z"."""
+    kind = _C.DEPTH_KINDS.get(depth) if isinstance(depth, str) else None
+    if kind is None:
+        raise ValueError(f"depth={depth!r}: expected 'inverse' (sum w / z, the default) or 'z' (sum w z)")
+    return kind
 
 
 def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, raw_activations=False, fold=None, sh_ready_event=None, forward_mode=None,
-                        tile_cull=None, tile_cull_apply=True):
+                        tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False):
     # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
     # what only a backward would need
+    _depth_kind(depth)                   # (validated before any device work)
+    if not isinstance(alpha, bool):
+        raise TypeError(f"alpha={alpha!r}: expected a bool")
     tensors = (means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
     rs = raster_settings
     # camera form: the settings' viewmatrix / projmatrix / campos take part in autograd when one of them requires grad (pose
@@ -591,7 +620,7 @@ def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, sca
     extra = (rs.viewmatrix, rs.projmatrix, rs.campos) if camera else ()
     return _RasterizeGaussians.apply(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, raw_activations, for_backward, fold, sh_ready_event,
-                                     forward_mode, tile_cull, tile_cull_apply, *extra)
+                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, *extra)
 
 
 def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -650,7 +679,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, raw_activations=False, *, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True):
+                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False):
         """Arguments of the reference's call (gaussian_renderer/__init__.py:90-109).  Extensions, all optional and all PER CALL
         (nothing is armed process-wide): `raw_activations=True`: `opacities`, `scales`, `rotations` are the model's RAW
         parameters; sigmoid / exp / normalize are applied inside the projection kernel and the returned gradients are w.r.t. the
@@ -658,7 +687,14 @@ class GaussianRasterizer(nn.Module):
         backward).  `sh_ready_event`: colours wait for this event.  `forward_mode`: "exact" | "async" | "sync" for this call.
         `tile_cull`: `new_tile_cull(...)` tensor of the VIEW being rendered (one per camera of a training set): tile lists
         truncated by the depth each tile saturated at when the view was last rendered (include/gsr.h gsr_forward_async_culled);
-        `tile_cull_apply=False`: only keep the cut-offs up to date in this call."""
+        `tile_cull_apply=False`: only keep the cut-offs up to date in this call.  `depth`: what the third output holds -
+        "inverse" (sum_i w_i / z_i, the reference's inverse depth) or "z" (sum_i w_i z_i, view-space z-depth), w_i = alpha_i T_i
+        the compositing weight.  `alpha=True`: a fourth output, the accumulated opacity A = 1 - T_final [1,H,W] (tracking mask /
+        silhouette).  Both come from the same single rasterization and are differentiable (include/gsr.h gsr_render_extras);
+        with neither the call is exactly the reference's.  Not under HIP-graph capture."""
+        _depth_kind(depth)
+        if not isinstance(alpha, bool):
+            raise TypeError(f"alpha={alpha!r}: expected a bool")
         def none_if_empty(t):
             return None if (t is None or t.numel() == 0) else t
         shs, colors_precomp, dc = none_if_empty(shs), none_if_empty(colors_precomp), none_if_empty(dc)
@@ -673,7 +709,7 @@ class GaussianRasterizer(nn.Module):
                 raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings, raw_activations, fold, sh_ready_event, forward_mode,
-                                   tile_cull, tile_cull_apply)
+                                   tile_cull, tile_cull_apply, depth, alpha)
 
 
 from .sparse_adam import SparseGaussianAdam, FusedAdam  # noqa: E402,F401   (reference train.py:37-41)

@@ -63,9 +63,17 @@ def _screenspace_zeros(like):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, separate_sh=False,
-           override_color=None, use_trained_exp=False, **rasterizer_kw):
+           override_color=None, use_trained_exp=False, depth="inverse", alpha=False, **rasterizer_kw):
     """`rasterizer_kw`: per-call extensions of this rasterizer, forwarded to `GaussianRasterizer.forward` (`fold`, `sh_ready_event`,
-    `forward_mode`); none given = the reference's call forms, unchanged."""
+    `forward_mode`); none given = the reference's call forms, unchanged.  `depth="z"`: the `"depth"` key holds the view-space
+    z-depth sum_i w_i z_i instead of the inverse depth; `alpha=True`: the package gains `"alpha"`, the accumulated opacity
+    1 - T_final [1,H,W] - both from the same single rasterization, both differentiable."""
+    if depth not in ("inverse", "z"):         # (before any device work)
+        raise ValueError(f"depth={depth!r}: expected 'inverse' or 'z'")
+    if not isinstance(alpha, bool):
+        raise TypeError(f"alpha={alpha!r}: expected a bool")
+    if depth != "inverse" or alpha:
+        rasterizer_kw = dict(rasterizer_kw, depth=depth, alpha=alpha)
     # zero tensor that receives the screen-space (NDC) gradient of the 2-D means (reference :26-30)
     # (a leaf here: its .grad is what the callers read; the reference's `+ 0` / retain_grad() pair gives the same .grad at
     # the price of one more launch per step)
@@ -125,22 +133,26 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         colors_precomp = override_color
 
     if separate_sh:
-        rendered_image, radii, depth_image = rasterizer(
+        out = rasterizer(
             means3D=means3D, means2D=means2D, dc=dc, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
             scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **({"raw_activations": True} if use_raw else {}),
             **rasterizer_kw)
     else:
-        rendered_image, radii, depth_image = rasterizer(
+        out = rasterizer(
             means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
             scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **({"raw_activations": True} if use_raw else {}),
             **rasterizer_kw)
+    rendered_image, radii, depth_image = out[:3]
 
     if use_trained_exp:
         exposure = pc.get_exposure_from_name(viewpoint_camera.image_name)
         rendered_image = torch.matmul(rendered_image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + \
             exposure[:3, 3, None, None]
 
-    return RenderPackage({"render": rendered_image,
-                          "viewspace_points": screenspace_points,
-                          "radii": radii,
-                          "depth": depth_image})
+    pkg = RenderPackage({"render": rendered_image,
+                         "viewspace_points": screenspace_points,
+                         "radii": radii,
+                         "depth": depth_image})
+    if alpha:
+        dict.__setitem__(pkg, "alpha", out[3])
+    return pkg

@@ -102,16 +102,28 @@ def pose_error(w2c_a, w2c_b):
 
 
 def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda_dssim=0.0, bg=None, pipe=None,
-                separate_sh=False, callback=None):
-    """Photometric pose refinement of one camera against a frozen `model` (tracking): Adam over the twist of a `PoseCamera`,
+                separate_sh=False, callback=None, gt_depth=None, depth_weight=0.5, alpha_min=0.5):
+    """Photometric (or RGB-D) pose refinement of one camera against a frozen `model` (tracking): Adam over the twist of a `PoseCamera`,
     loss = L1(render, gt_image) (lambda_dssim > 0: the fused L1 + D-SSIM training loss), learning rate decaying
     exponentially from `lr` to `lr_final`.  `cam`: a PoseCamera (refined in place) or any camera (wrapped in a float64 PoseCamera
     on the host: the pose arithmetic is a few dozen 4x4 operations, cheaper there than as many device launches; the rasterizer
     moves the three matrices to the device and returns their gradients where they came from).  The model's tensors are read,
     never written; whether they require grad does not matter.  Returns (the PoseCamera with tau committed, the loss of every
-    iteration)."""
+    iteration).
+
+    RGB-D tracking: `gt_depth` [1,H,W] or [H,W], the sensor's view-space z-depth (0 = no reading).  Every iteration then renders
+    ONCE with depth="z", alpha=True and minimises (1 - depth_weight) L_rgb + depth_weight mean|(D_z - gt_depth) valid|, the mean
+    over all pixels (the form of the reference's Ll1depth, train.py:130; no count is read back), valid = (gt_depth > 0) &
+    (A > alpha_min): pixels with a reading that the map covers (the mask is not differentiated).  gt_depth=None: the photometric
+    loss alone, exactly as before."""
     from gaussian_renderer import render, PipelineParams
     from .losses import l1_loss, training_loss_fused
+    if gt_depth is not None:
+        from fused_ssim import l1_mean_loss
+        if not 0.0 <= float(depth_weight) <= 1.0:
+            raise ValueError(f"depth_weight={depth_weight}: expected a value in [0, 1]")
+        gt_depth = gt_depth.detach().float().reshape(1, *gt_image.shape[-2:]).contiguous()
+        has_reading = gt_depth > 0
     pc = cam if isinstance(cam, PoseCamera) else PoseCamera(cam, dtype=torch.float64, device="cpu")
     pipe = pipe or PipelineParams()
     if bg is None:
@@ -121,8 +133,17 @@ def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambd
     history = []
     for it in range(iters):
         opt.zero_grad(set_to_none=True)
-        image = render(pc, model, pipe, bg, separate_sh=separate_sh)["render"]
-        loss = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+        if gt_depth is None:
+            image = render(pc, model, pipe, bg, separate_sh=separate_sh)["render"]
+            loss = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+        else:
+            pkg = render(pc, model, pipe, bg, separate_sh=separate_sh, depth="z", alpha=True)
+            valid = (has_reading & (pkg["alpha"].detach() > alpha_min)).float()
+            loss = l1_mean_loss(pkg["depth"], gt_depth, float(depth_weight), valid)
+            if depth_weight < 1.0:
+                image = pkg["render"]
+                rgb = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+                loss = loss + (1.0 - float(depth_weight)) * rgb
         loss.backward()
         opt.step()
         for g in opt.param_groups:

@@ -35,6 +35,7 @@ extern "C" {
  *    the image state carries the frame's walk classes (gsr_image_state_bytes grew; gsr_debug_walk_views); the backward's scratch
  *    carries validity flags of the gradient records (gsr_backward_scratch_bytes grew; gsr_debug_set_flags_min_r);
  *    later, additive: gsr_camera_grads, gsr_camera_grad_scratch_bytes, gsr_backward_camera (gradients of the camera);
+ *    gsr_render_extras and the *_ex entry points (z-depth channel, accumulated-opacity plane and their gradients);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -286,6 +287,66 @@ int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32
                       const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                       const gsr_fused_adam* opt, void* stream);
 
+/* Depth and opacity images for RGB-D tracking.  Every `_ex` entry point below takes the
+ * arguments of the entry point of the same name without `_ex`, plus `extras` LAST; extras == NULL is exactly that entry point.
+ *   depth_kind: what the depth plane (`out_invdepth` of the forward, `dL_dinvdepth` of the backward) holds -
+ *               GSR_DEPTH_INVERSE: sum_i w_i / z_i (the reference's inverse depth, the default);
+ *               GSR_DEPTH_Z:       sum_i w_i z_i (view-space z-depth), w_i = alpha_i T_i the compositing weight.
+ *               It takes effect in the projection (gsr_forward_prepare*_ex / gsr_forward_async*_ex: the state buffers then hold it)
+ *               and must be given again, with the same value, to the backward of that frame.  Colour, radii, final_T and
+ *               n_contrib do not depend on it.
+ *   out_alpha:  forward: NULL, or a DEVICE [H,W] plane that receives the accumulated opacity A = 1 - T_final of every pixel
+ *               (bit for bit 1 - the final_T of gsr_debug_image_views).
+ *   dL_dalpha:  backward: NULL (zero), or the DEVICE [H,W] gradient of that plane.  It reaches opacities, means, covariances
+ *               and the camera through the compositing backward's per-pixel background term (dA/dalpha_i = T_final / (1 -
+ *               alpha_i)): no extra work per composited entry, no float atomics; a zero plane gives the gradients of NULL bit
+ *               for bit.  An overflowed unverified frame gives zero gradients through it, as through everything else. */
+enum { GSR_DEPTH_INVERSE = 0, GSR_DEPTH_Z = 1 };
+typedef struct gsr_render_extras {
+  int32_t depth_kind;      /* GSR_DEPTH_INVERSE | GSR_DEPTH_Z; anything else: GSR_ERR_INVALID_ARGUMENT */
+  float* out_alpha;        /* [H,W] or NULL (forward) */
+  const float* dL_dalpha;  /* [H,W] or NULL (backward) */
+} gsr_render_extras;
+int64_t gsr_forward_prepare_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                               int32_t* radii, void* stream, const gsr_render_extras* extras);
+int64_t gsr_forward_prepare_geometry_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
+                                        size_t geometry_bytes, int32_t* radii, void* stream, const gsr_render_extras* extras);
+int gsr_forward_render_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                          size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes, float* out_color,
+                          float* out_invdepth, int32_t for_backward, void* stream, const gsr_render_extras* extras);
+int gsr_forward_render_shade_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                                size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
+                                float* out_color, float* out_invdepth, int32_t for_backward, void* sh_ready_event,
+                                void* stream, const gsr_render_extras* extras);
+int gsr_forward_async_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                         int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
+                         size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
+                         int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
+                         void* stream, int64_t* num_rendered_out, const gsr_render_extras* extras);
+int gsr_forward_async_culled_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
+                                int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
+                                size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
+                                int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
+                                void* stream, int64_t* num_rendered_out, uint32_t* tile_depth_cutoff, int32_t apply,
+                                const gsr_render_extras* extras);
+int gsr_forward_rerender_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                            size_t binning_bytes, int64_t capacity, void* image_state, size_t image_bytes, float* out_color,
+                            float* out_invdepth, int32_t for_backward, int32_t tile_local_sort, uint32_t* host_status,
+                            void* stream, const gsr_render_extras* extras);
+int gsr_backward_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                    const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                    const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads, void* stream,
+                    const gsr_render_extras* extras);
+int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                           const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                           const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                           const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream,
+                           const gsr_render_extras* extras);
+int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                         const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                         const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                         const gsr_fused_adam* opt, void* stream, const gsr_render_extras* extras);
+
 /* Dense Adam update (zero gradient: moments decay, the parameter follows its momentum) of the rows that reached no tile in the
  * forward whose geometry state is given; companion of gsr_backward_adam(opt->sparse = 2).  May be enqueued on any stream once
  * the forward call that filled `geometry_state` has been enqueued and that stream waits for it; the caller orders it before the
@@ -298,7 +359,7 @@ int gsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, u
 
 /* Introspection for tests / bench: DEVICE pointers into the opaque state buffers (valid while the buffer lives). */
 /* rec48: the packed 48-B splat records, 12 floats per Gaussian = (mean2D.xy, conic A' B') (conic C', opacity, cut-off, r)
- * (g, b, 1/depth, depth); clamped: one byte per Gaussian, bit c set = colour channel c was clamped at 0 (any out pointer may
+ * (g, b, 1/depth - or depth with GSR_DEPTH_Z -, depth); clamped: one byte per Gaussian, bit c set = colour channel c was clamped at 0 (any out pointer may
  * be NULL) */
 int gsr_debug_geometry_views(const void* geometry_state, int32_t P, const float** rec48, const uint32_t** depth_keys_sorted,
                              const uint32_t** order, const uint32_t** tiles_touched, const uint16_t** rect,

@@ -2,9 +2,15 @@
 """Cost of the camera gradients at BASELINE configs[3] (1 M Gaussians, 1080p), one view, map frozen:
    (a) tracking iteration: forward + L1 loss + backward with ONLY the camera twist as a leaf (gsr_backward_camera) + Adam on it;
    (b) the same iteration with the plain backward of a call whose Gaussians require grad (no camera gradient), for comparison.
+With --rgbd, three RGB-D tracking iterations (loss 0.5 L1(colour) + 0.5 mean|(D_z - gt_depth) valid|, valid = gt_depth > 0 and
+A > 0.5, as scene_utils.refine_pose forms it):
+   (c) photometric only (= (a));
+   (d) RGB-D in ONE pass: render(depth="z", alpha=True);
+   (e) RGB-D through the two-render workaround: the colour render, then a second full rasterization with colors_precomp =
+       (z, 0, 0) and bg = (0, 1, 0) - channel 0 is D_z, channel 1 is T_final - z formed with torch from the pose's viewmatrix.
 Prints one JSON line (ms per iteration, medians of timed repetitions).  Per-kernel times: run under
 `rocprofv3 --kernel-trace --stats -- python tools/camera_grad_bench.py` and read preprocess_bwd vs its camera form and cam_reduce.
-    python tools/camera_grad_bench.py [--iters N]            (GPU box, repo root)"""
+    python tools/camera_grad_bench.py [--iters N] [--rgbd]   (GPU box, repo root)"""
 import argparse
 import json
 import os
@@ -19,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rgbd", action="store_true", help="also time the RGB-D tracking iterations (c) - (e)")
     a = ap.parse_args()
     from scene_utils import make_config, GaussianModel, PoseCamera, l1_loss
     from gaussian_renderer import render, PipelineParams
@@ -43,8 +50,36 @@ def main():
             p.grad = None
         l1_loss(render(cam, trained, pipe, bg)["render"], gt).backward()
 
+    fns = [("tracking_iter_ms", tracking), ("plain_train_bwd_iter_ms", plain)]
+    if a.rgbd:
+        from fused_ssim import l1_mean_loss
+        with torch.no_grad():
+            gt_depth = render(cams[1].to(dev), frozen, pipe, bg, depth="z")["depth"].clone()
+        has = gt_depth > 0
+        aux_bg = torch.tensor([0.0, 1.0, 0.0], device=dev)
+
+        def rgbd_one_pass():
+            opt.zero_grad(set_to_none=True)
+            pkg = render(pc, frozen, pipe, bg, depth="z", alpha=True)
+            valid = (has & (pkg["alpha"].detach() > 0.5)).float()
+            (0.5 * l1_loss(pkg["render"], gt) + l1_mean_loss(pkg["depth"], gt_depth, 0.5, valid)).backward()
+            opt.step()
+
+        def rgbd_two_render():
+            opt.zero_grad(set_to_none=True)
+            image = render(pc, frozen, pipe, bg)["render"]
+            V = pc.world_view_transform.to(dev, torch.float32)
+            z = frozen.get_xyz @ V[:3, 2] + V[3, 2]
+            aux_col = torch.stack([z, torch.zeros_like(z), torch.zeros_like(z)], dim=1)
+            aux = render(pc, frozen, pipe, aux_bg, override_color=aux_col)["render"]
+            D, A = aux[0:1], 1.0 - aux[1:2]
+            valid = (has & (A.detach() > 0.5)).float()
+            (0.5 * l1_loss(image, gt) + l1_mean_loss(D.contiguous(), gt_depth, 0.5, valid)).backward()
+            opt.step()
+
+        fns += [("rgbd_one_pass_iter_ms", rgbd_one_pass), ("rgbd_two_render_iter_ms", rgbd_two_render)]
     out = {"config": 3, "P": cfg["P"], "W": cfg["W"], "H": cfg["H"]}
-    for name, fn in (("tracking_iter_ms", tracking), ("plain_train_bwd_iter_ms", plain)):
+    for name, fn in fns:
         for _ in range(a.warmup):
             fn()
         torch.cuda.synchronize()
