@@ -1,0 +1,442 @@
+// knn.hip - the mapping half's two native calls: exact 3-nearest-neighbour distances (what the reference takes from
+// `simple_knn._C.distCUDA2`, scene/gaussian_model.py:20,:140) and the back-projection of an RGB-D keyframe into new points.
+//
+// gsr_knn_dist2: mean squared distance of every point to its three nearest OTHER points, exact.
+//   1. bounding box of the finite coordinates: per-workgroup min / max over a fixed slice, then one workgroup over the partials
+//      (min / max are order-independent: deterministic without any ordering argument, and no float atomics);
+//   2. 30-bit Morton code per point (10 bits per axis of the box), sorted with the library's stable radix sort (value = index);
+//   3. the points gathered in sorted order as float4 (xyz, original index), cut into BOXES of GSR_KNN_BOX = 64 consecutive
+//      points (one wave builds one box: its AABB by cross-lane min / max) and SUPER-BOXES of GSR_KNN_SUPER = 64 consecutive
+//      boxes (4096 points);
+//   4. one thread per query, queries in Morton order so that the lanes of a wave accept the same boxes: an upper bound of the
+//      third-nearest distance from the six neighbours in Morton order, then a sweep over ALL super-boxes (their AABBs staged
+//      through LDS, 256 at a time), descending into the boxes of a super-box and the points of a box only where the AABB
+//      distance does not exceed min(bound, current third best).
+//   The structure only prunes.  A box is skipped when its AABB distance is GREATER than the threshold, and that distance is formed
+//   with the same rounding sequence as a point distance (differences, then fma(dz,dz, fma(dy,dy, dx*dx))): rounding is monotone,
+//   so the fp32 AABB distance never exceeds the fp32 distance of a point inside - no neighbour can be lost to rounding.  The answer
+//   of a query is the three smallest values of a multiset that does not depend on the traversal: two runs, and runs with a
+//   different first_query, give the same bits.
+//   Box size: 64 = one wave builds a box, and a leaf visit is 64 distance evaluations against a box test of about the same cost
+//   as two of them; with 64 x 64 the sweep at 5 M points is 1.2 k super-box tests per query (a single level of 64-point boxes
+//   would be 78 k).  Distances are (a-b).(a-b) from differences: scenes sit far from the origin.
+//   Fewer than four points: the mean runs over the min(3, P-1) neighbours that exist, P == 1 gives 0.  (The upstream module is
+//   recalled to leave FLT_MAX-derived values there; nothing in the reference pins either behaviour.)
+//   Non-finite coordinates never enter the bounding box, get Morton code 0 where the quantisation is undefined, and fail every
+//   `<` comparison: no hang, no out-of-bounds access, unspecified values for those rows.
+//
+// gsr_unproject_rgbd: strided pixels of a depth image -> world-space points + colours, selected by validity and (optionally) by
+//   what the map's render of the same view does not explain, compacted in row-major pixel order by a prefix sum.
+#include "gsr_common.h"
+
+#define GSR_KNN_BOX 64
+#define GSR_KNN_SUPER 64
+#define GSR_KNN_BBOX_BLOCKS 1024
+
+struct GsrKnnLayout {
+  size_t bbox_part;   // float[GSR_KNN_BBOX_BLOCKS][6]
+  size_t bbox;        // float[8]: min xyz, max xyz
+  size_t key_a, key_b, val_a, val_b;   // u32[P] each: Morton codes / point indices, ping-pong
+  size_t pts;         // float4[P]: sorted points (x, y, z, bits of the original index)
+  size_t box_lo, box_hi;   // float4[nbox]
+  size_t sup_lo, sup_hi;   // float4[nsuper]
+  size_t qflag, qpos, qlist;   // u32[P] each: first_query > 0 only - query flags in sorted order, their scan, the compacted list
+  size_t scan_tmp;
+  size_t radix_tmp;
+  size_t total;
+};
+
+static inline size_t knn_nbox(size_t P) { return (P + GSR_KNN_BOX - 1) / GSR_KNN_BOX; }
+static inline size_t knn_nsuper(size_t P) { return (knn_nbox(P) + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER; }
+
+static inline GsrKnnLayout knn_layout(size_t P) {
+  GsrKnnLayout L;
+  size_t o = 0;
+  if (P == 0) P = 1;
+  L.bbox_part = o; o += gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4);
+  L.bbox = o;      o += 256;
+  L.key_a = o;     o += gsr_align(P * 4);
+  L.key_b = o;     o += gsr_align(P * 4);
+  L.val_a = o;     o += gsr_align(P * 4);
+  L.val_b = o;     o += gsr_align(P * 4);
+  L.pts = o;       o += gsr_align(P * 16);
+  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.qflag = o;     o += gsr_align(P * 4);
+  L.qpos = o;      o += gsr_align(P * 4);
+  L.qlist = o;     o += gsr_align(P * 4);
+  L.scan_tmp = o;  o += gsr_align(gsr_scan_tmp_elems(P) * 4);
+  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
+  L.total = o;
+  return L;
+}
+
+#define KNN_INF __builtin_huge_valf()
+
+__device__ __forceinline__ bool knn_finite(float x) { return fabsf(x) < KNN_INF; }   // false for NaN and +-inf
+
+__device__ __forceinline__ float knn_wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float knn_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// min / max of six per-thread values over a 256-thread workgroup -> out[6] (thread 0 writes)
+__device__ __forceinline__ void knn_block_minmax(float lo[3], float hi[3], float* __restrict__ out) {
+  __shared__ float s[4][6];
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    lo[a] = knn_wave_min(lo[a]);
+    hi[a] = knn_wave_max(hi[a]);
+  }
+  if (gsr_lane() == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      s[w][a] = lo[a];
+      s[w][3 + a] = hi[a];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int a = threadIdx.x;
+    float v = s[0][a];
+    for (int k = 1; k < 4; k++) v = a < 3 ? fminf(v, s[k][a]) : fmaxf(v, s[k][a]);
+    out[a] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_knn_bbox_partial(uint32_t P, const float* __restrict__ pts, float* __restrict__ part) {
+  float lo[3] = {KNN_INF, KNN_INF, KNN_INF}, hi[3] = {-KNN_INF, -KNN_INF, -KNN_INF};
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < P; i += gridDim.x * 256u) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const float v = pts[3 * (size_t)i + a];
+      if (knn_finite(v)) {
+        lo[a] = fminf(lo[a], v);
+        hi[a] = fmaxf(hi[a], v);
+      }
+    }
+  }
+  knn_block_minmax(lo, hi, part + 6 * (size_t)blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_knn_bbox_final(uint32_t nblk, const float* __restrict__ part, float* __restrict__ bbox) {
+  float lo[3] = {KNN_INF, KNN_INF, KNN_INF}, hi[3] = {-KNN_INF, -KNN_INF, -KNN_INF};
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      lo[a] = fminf(lo[a], part[6 * (size_t)b + a]);
+      hi[a] = fmaxf(hi[a], part[6 * (size_t)b + 3 + a]);
+    }
+  }
+  knn_block_minmax(lo, hi, bbox);
+}
+
+__device__ __forceinline__ uint32_t knn_spread10(uint32_t x) {      // 10 bits -> every third bit of 30
+  x = (x | (x << 16)) & 0x030000FFu;
+  x = (x | (x << 8)) & 0x0300F00Fu;
+  x = (x | (x << 4)) & 0x030C30C3u;
+  x = (x | (x << 2)) & 0x09249249u;
+  return x;
+}
+// (v - lo) / (hi - lo) on a 1024-cell axis; NaN (a flat axis: 0 / 0, a non-finite coordinate) and negatives give cell 0
+__device__ __forceinline__ uint32_t knn_cell(float v, float lo, float hi) {
+  const float t = (v - lo) / (hi - lo) * 1023.0f;
+  return t >= 0.f ? (uint32_t)fminf(t, 1023.0f) : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_knn_morton(uint32_t P, const float* __restrict__ pts, const float* __restrict__ bbox,
+                                                    uint32_t* __restrict__ codes) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P) return;
+  const uint32_t cx = knn_cell(pts[3 * (size_t)i], bbox[0], bbox[3]);
+  const uint32_t cy = knn_cell(pts[3 * (size_t)i + 1], bbox[1], bbox[4]);
+  const uint32_t cz = knn_cell(pts[3 * (size_t)i + 2], bbox[2], bbox[5]);
+  codes[i] = knn_spread10(cx) | (knn_spread10(cy) << 1) | (knn_spread10(cz) << 2);
+}
+
+// one wave per box: gathers its 64 points into sorted order and reduces their AABB
+__global__ __launch_bounds__(256) void k_knn_boxes(uint32_t P, const float* __restrict__ pts, const uint32_t* __restrict__ order,
+                                                   float4* __restrict__ sorted, float4* __restrict__ box_lo,
+                                                   float4* __restrict__ box_hi, uint32_t first_query,
+                                                   uint32_t* __restrict__ qflag) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;      // sorted position; box = j / 64 = one wave
+  float lo[3] = {KNN_INF, KNN_INF, KNN_INF}, hi[3] = {-KNN_INF, -KNN_INF, -KNN_INF};
+  if (j < P) {
+    const uint32_t i = order[j];
+    const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    sorted[j] = make_float4(x, y, z, __uint_as_float(i));
+    if (qflag) qflag[j] = i >= first_query ? 1u : 0u;
+    lo[0] = hi[0] = x;      // (fminf / fmaxf drop a NaN operand: a box of NaN points keeps +inf / -inf and is never entered)
+    lo[1] = hi[1] = y;
+    lo[2] = hi[2] = z;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    lo[a] = knn_wave_min(lo[a]);
+    hi[a] = knn_wave_max(hi[a]);
+  }
+  const uint32_t b = j >> 6;
+  if (gsr_lane() == 0 && (size_t)b * GSR_KNN_BOX < P) {
+    box_lo[b] = make_float4(lo[0], lo[1], lo[2], 0.f);
+    box_hi[b] = make_float4(hi[0], hi[1], hi[2], 0.f);
+  }
+}
+
+// one wave per super-box: lane l holds box l of it
+__global__ __launch_bounds__(256) void k_knn_supers(uint32_t nbox, const float4* __restrict__ box_lo,
+                                                    const float4* __restrict__ box_hi, float4* __restrict__ sup_lo,
+                                                    float4* __restrict__ sup_hi) {
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  float4 lo = make_float4(KNN_INF, KNN_INF, KNN_INF, 0.f), hi = make_float4(-KNN_INF, -KNN_INF, -KNN_INF, 0.f);
+  if (b < nbox) {
+    lo = box_lo[b];
+    hi = box_hi[b];
+  }
+  lo.x = knn_wave_min(lo.x); lo.y = knn_wave_min(lo.y); lo.z = knn_wave_min(lo.z);
+  hi.x = knn_wave_max(hi.x); hi.y = knn_wave_max(hi.y); hi.z = knn_wave_max(hi.z);
+  const uint32_t s = b >> 6;
+  if (gsr_lane() == 0 && s * (uint32_t)GSR_KNN_SUPER < nbox) {
+    sup_lo[s] = lo;
+    sup_hi[s] = hi;
+  }
+}
+
+// first_query > 0: the sorted positions that hold a query, in sorted order
+__global__ __launch_bounds__(256) void k_knn_compact(uint32_t P, const uint32_t* __restrict__ qflag,
+                                                     const uint32_t* __restrict__ qpos, uint32_t* __restrict__ qlist) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j < P && qflag[j]) qlist[qpos[j]] = j;
+}
+
+// the one rounding sequence of every squared distance, point or box (see the header: the pruning relies on it)
+__device__ __forceinline__ float knn_sq(float dx, float dy, float dz) {
+  return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
+}
+__device__ __forceinline__ float knn_point_d2(const float4 q, const float4 p) {
+  return knn_sq(__fsub_rn(q.x, p.x), __fsub_rn(q.y, p.y), __fsub_rn(q.z, p.z));
+}
+__device__ __forceinline__ float knn_box_d2(const float4 q, const float4 lo, const float4 hi) {
+  // per axis max(q - hi, lo - q, 0) = |q - nearest point of the interval|; for a point p of the box |q - p| is at least that,
+  // and stays so after rounding
+  const float dx = fmaxf(0.f, fmaxf(__fsub_rn(q.x, hi.x), __fsub_rn(lo.x, q.x)));
+  const float dy = fmaxf(0.f, fmaxf(__fsub_rn(q.y, hi.y), __fsub_rn(lo.y, q.y)));
+  const float dz = fmaxf(0.f, fmaxf(__fsub_rn(q.z, hi.z), __fsub_rn(lo.z, q.z)));
+  return knn_sq(dx, dy, dz);
+}
+__device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float& b2) {
+  if (d < b2) {      // (false for NaN: it never enters the min / max network below)
+    const float t0 = fmaxf(b0, d);
+    b0 = fminf(b0, d);
+    const float t1 = fmaxf(b1, t0);
+    b1 = fminf(b1, t0);
+    b2 = fminf(b2, t1);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, const uint32_t* __restrict__ qlist,
+                                                   const float4* __restrict__ pts, const float4* __restrict__ box_lo,
+                                                   const float4* __restrict__ box_hi, uint32_t nbox,
+                                                   const float4* __restrict__ sup_lo, const float4* __restrict__ sup_hi,
+                                                   uint32_t nsuper, uint32_t first_query, float* __restrict__ out) {
+  __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  const bool active = q < nq;
+  const uint32_t pos = active ? (qlist ? qlist[q] : q) : 0u;
+  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  float b0 = KNN_INF, b1 = KNN_INF, b2 = KNN_INF;
+  if (active) {
+    const uint32_t j0 = pos >= 3u ? pos - 3u : 0u, j1 = min(P - 1u, pos + 3u);
+    for (uint32_t j = j0; j <= j1; j++)
+      if (j != pos) knn_insert(knn_point_d2(me, pts[j]), b0, b1, b2);
+  }
+  // an upper bound of the third-nearest distance (inf with fewer than three candidates); the sweep starts from an empty
+  // list again, so no candidate is counted twice
+  const float bound = b2;
+  b0 = b1 = b2 = KNN_INF;
+  for (uint32_t base = 0; base < nsuper; base += 256u) {
+    __syncthreads();
+    if (base + threadIdx.x < nsuper) {
+      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
+      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
+    }
+    __syncthreads();
+    if (!active) continue;
+    const uint32_t n = min(256u, nsuper - base);
+    for (uint32_t s = 0; s < n; s++) {
+      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b2, bound))) continue;
+      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
+      for (uint32_t b = bb; b < be; b++) {
+        if (!(knn_box_d2(me, box_lo[b], box_hi[b]) <= fminf(b2, bound))) continue;
+        const uint32_t jb = b * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
+        for (uint32_t j = jb; j < je; j++)
+          if (j != pos) knn_insert(knn_point_d2(me, pts[j]), b0, b1, b2);
+      }
+    }
+  }
+  if (active) {
+    float r;
+    if (P >= 4u) r = __fdiv_rn(__fadd_rn(__fadd_rn(b0, b1), b2), 3.0f);
+    else if (P == 3u) r = __fmul_rn(__fadd_rn(b0, b1), 0.5f);
+    else if (P == 2u) r = b0;
+    else r = 0.f;
+    out[__float_as_uint(me.w) - first_query] = r;
+  }
+}
+
+// ---- RGB-D keyframe -> points -------------------------------------------------------------------------------------------------
+struct GsrUnprojectArgs {
+  int H, W, Hs, Ws, stride;
+  float tanfovx, tanfovy, min_depth, max_depth, alpha_below, front_margin;
+};
+
+__device__ __forceinline__ bool unproject_selected(const GsrUnprojectArgs& a, size_t pix, const float* __restrict__ depth,
+                                                   const float* __restrict__ alpha, const float* __restrict__ rendered_z,
+                                                   float& d) {
+  d = depth[pix];
+  if (!(knn_finite(d) && d > a.min_depth && d <= a.max_depth)) return false;
+  if (!alpha) return true;
+  const float A = alpha[pix];
+  if (A < a.alpha_below) return true;
+  if (!rendered_z) return false;
+  // in front of the surface the map renders there (sum w z / A), by more than front_margin x the reading
+  const float surface = __fdiv_rn(rendered_z[pix], A);
+  return d < __fsub_rn(surface, __fmul_rn(a.front_margin, d));
+}
+
+__global__ __launch_bounds__(256) void k_unproject_flag(GsrUnprojectArgs a, const float* __restrict__ depth,
+                                                        const float* __restrict__ alpha, const float* __restrict__ rendered_z,
+                                                        uint32_t* __restrict__ flags) {
+  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+  if (c >= (uint32_t)(a.Ws * a.Hs)) return;
+  const int sy = (int)(c / (uint32_t)a.Ws), sx = (int)(c % (uint32_t)a.Ws);
+  float d;
+  flags[c] = unproject_selected(a, (size_t)(sy * a.stride) * a.W + (size_t)(sx * a.stride), depth, alpha, rendered_z, d) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_unproject_write(GsrUnprojectArgs a, const float* __restrict__ depth,
+                                                         const float* __restrict__ color, const float* __restrict__ view,
+                                                         const uint32_t* __restrict__ flags, const uint32_t* __restrict__ offs,
+                                                         float* __restrict__ xyz, float* __restrict__ rgb, uint32_t capacity,
+                                                         int64_t* __restrict__ count) {
+  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t n = (uint32_t)(a.Ws * a.Hs);
+  if (c >= n) return;
+  const uint32_t f = flags[c], o = offs[c];
+  if (c == n - 1u) *count = (int64_t)o + (int64_t)f;
+  if (!f || o >= capacity) return;
+  const int py = (int)(c / (uint32_t)a.Ws) * a.stride, px = (int)(c % (uint32_t)a.Ws) * a.stride;
+  const size_t pix = (size_t)py * a.W + px;
+  const float d = depth[pix];
+  // pixel centres at integer coordinates: ndc = (2 p + 1) / S - 1
+  const float nx = __fsub_rn(__fdiv_rn((float)(2 * px + 1), (float)a.W), 1.0f);
+  const float ny = __fsub_rn(__fdiv_rn((float)(2 * py + 1), (float)a.H), 1.0f);
+  // view = W2C^T row-major: view-space v_i = sum_j w_j view[4 j + i] + view[12 + i]; rigid inverse w_j = sum_i view[4 j + i] (v_i - t_i)
+  const float v0 = __fsub_rn(__fmul_rn(__fmul_rn(nx, a.tanfovx), d), view[12]);
+  const float v1 = __fsub_rn(__fmul_rn(__fmul_rn(ny, a.tanfovy), d), view[13]);
+  const float v2 = __fsub_rn(d, view[14]);
+#pragma unroll
+  for (int j = 0; j < 3; j++)
+    xyz[3 * (size_t)o + j] = __builtin_fmaf(view[4 * j + 2], v2, __builtin_fmaf(view[4 * j + 1], v1, __fmul_rn(view[4 * j], v0)));
+  const size_t plane = (size_t)a.H * a.W;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) rgb[3 * (size_t)o + ch] = color[ch * plane + pix];
+}
+
+extern "C" {
+
+size_t gsr_knn_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1 : P)).total; }
+
+int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* mean_dist2, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (P <= 0 || P > 0x3FFFFFFF || !points || !mean_dist2 || !workspace || first_query < 0 || first_query >= P) {
+    gsr_set_error("knn_dist2: bad arguments (P = %lld, first_query = %lld)", (long long)P, (long long)first_query);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrKnnLayout L = knn_layout((size_t)P);
+  if (workspace_bytes < L.total) {
+    gsr_set_error("knn_dist2: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
+  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
+  float* part = (float*)(ws + L.bbox_part);
+  float* bbox = (float*)(ws + L.bbox);
+  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
+  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
+  float4* pts = (float4*)(ws + L.pts);
+  float4 *box_lo = (float4*)(ws + L.box_lo), *box_hi = (float4*)(ws + L.box_hi);
+  float4 *sup_lo = (float4*)(ws + L.sup_lo), *sup_hi = (float4*)(ws + L.sup_hi);
+  uint32_t *qflag = (uint32_t*)(ws + L.qflag), *qpos = (uint32_t*)(ws + L.qpos), *qlist = (uint32_t*)(ws + L.qlist);
+  const bool subset = first_query > 0;
+
+  const uint32_t bblk = nblk < (uint32_t)GSR_KNN_BBOX_BLOCKS ? nblk : (uint32_t)GSR_KNN_BBOX_BLOCKS;
+  GSR_LAUNCH("knn_bbox_partial", k_knn_bbox_partial, dim3(bblk), dim3(256), 0, st, n, points, part);
+  GSR_LAUNCH("knn_bbox_final", k_knn_bbox_final, dim3(1), dim3(256), 0, st, bblk, (const float*)part, bbox);
+  GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, key[0]);
+  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
+  GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)val[where], pts, box_lo, box_hi,
+             (uint32_t)first_query, subset ? qflag : (uint32_t*)nullptr);
+  GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)box_lo,
+             (const float4*)box_hi, sup_lo, sup_hi);
+  const uint32_t nq = (uint32_t)(P - first_query);
+  if (subset) {
+    gsr_scan_u32(qflag, nullptr, qpos, (size_t)n, 0, (uint32_t*)(ws + L.scan_tmp), st);
+    GSR_LAUNCH("knn_compact", k_knn_compact, dim3(nblk), dim3(256), 0, st, n, (const uint32_t*)qflag, (const uint32_t*)qpos, qlist);
+  }
+  GSR_LAUNCH("knn_query", k_knn_query, dim3((nq + 255u) / 256u), dim3(256), 0, st, n, nq,
+             subset ? (const uint32_t*)qlist : (const uint32_t*)nullptr, (const float4*)pts, (const float4*)box_lo,
+             (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, (uint32_t)first_query, mean_dist2);
+  return gsr_launch_status("knn_dist2 launch");
+}
+
+size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) {
+  const size_t n = (size_t)(W < 1 ? 1 : W) * (size_t)(H < 1 ? 1 : H);
+  return 2 * gsr_align(n * 4) + gsr_align(gsr_scan_tmp_elems(n) * 4);
+}
+
+int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth, const float* color, const float* alpha,
+                       const float* rendered_z, float* xyz, float* rgb, int64_t capacity, int64_t* count_dev, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (!p || !depth || !color || !count_dev || !workspace || capacity < 0 || (capacity > 0 && (!xyz || !rgb)) ||
+      p->image_width < 1 || p->image_height < 1 || (int64_t)p->image_width * p->image_height > 0x3FFFFFFF || p->stride < 1 ||
+      !p->viewmatrix || !(p->tanfovx > 0.f) || !(p->tanfovy > 0.f)) {
+    gsr_set_error("unproject_rgbd: bad arguments");
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  if (workspace_bytes < gsr_unproject_workspace_bytes(p->image_width, p->image_height)) {
+    gsr_set_error("unproject_rgbd: workspace of %zu bytes, %zu needed", workspace_bytes,
+                  gsr_unproject_workspace_bytes(p->image_width, p->image_height));
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  GsrUnprojectArgs a;
+  a.H = p->image_height; a.W = p->image_width; a.stride = p->stride;
+  a.Hs = (a.H + a.stride - 1) / a.stride; a.Ws = (a.W + a.stride - 1) / a.stride;
+  a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.min_depth = p->min_depth; a.max_depth = p->max_depth;
+  a.alpha_below = p->alpha_below; a.front_margin = p->front_margin;
+  const size_t full = (size_t)a.W * a.H, n = (size_t)a.Ws * a.Hs;
+  char* ws = (char*)workspace;
+  uint32_t* flags = (uint32_t*)ws;
+  uint32_t* offs = (uint32_t*)(ws + gsr_align(full * 4));
+  uint32_t* scan_tmp = (uint32_t*)(ws + 2 * gsr_align(full * 4));
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  GSR_LAUNCH("unproject_flag", k_unproject_flag, dim3(grid), dim3(256), 0, st, a, depth, alpha, rendered_z, flags);
+  gsr_scan_u32(flags, nullptr, offs, n, 0, scan_tmp, st);
+  const uint32_t cap = (uint32_t)(capacity > 0x7FFFFFFF ? 0x7FFFFFFF : capacity);
+  GSR_LAUNCH("unproject_write", k_unproject_write, dim3(grid), dim3(256), 0, st, a, depth, color, p->viewmatrix,
+             (const uint32_t*)flags, (const uint32_t*)offs, xyz, rgb, cap, count_dev);
+  return gsr_launch_status("unproject_rgbd launch");
+}
+
+}  // extern "C"

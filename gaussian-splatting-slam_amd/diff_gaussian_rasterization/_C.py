@@ -57,6 +57,14 @@ class gsr_render_extras(C.Structure):
 DEPTH_KINDS = {"inverse": 0, "z": 1}     # gsr_render_extras.depth_kind: GSR_DEPTH_INVERSE, GSR_DEPTH_Z
 
 
+class gsr_unproject_params(C.Structure):
+    _fields_ = [
+        ("image_height", C.c_int32), ("image_width", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float),
+        ("viewmatrix", C.c_void_p), ("stride", C.c_int32), ("min_depth", C.c_float), ("max_depth", C.c_float),
+        ("alpha_below", C.c_float), ("front_margin", C.c_float),
+    ]
+
+
 class gsr_fused_adam(C.Structure):
     _fields_ = [
         ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("lr", C.c_float * 6), ("step", C.c_int64 * 6),
@@ -186,6 +194,11 @@ EXPORTS = {
                                       C.c_void_p, C.c_void_p]),
     "gsr_sh_rank1_adam": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                     C.c_void_p, C.POINTER(gsr_fused_adam), C.c_void_p]),
+    "gsr_knn_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_knn_dist2": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                                                                           C.c_size_t, C.c_void_p]),
     "gsr_profile_enable": (None, [C.c_int32]),
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

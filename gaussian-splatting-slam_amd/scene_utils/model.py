@@ -30,6 +30,7 @@ class GaussianModel:
         self._scaling = self._rotation = self._opacity = None
         self._exposure = None
         self.exposure_mapping = {}
+        self._resize_hooks = []      # called with "before" / "after" around a row insertion from outside a training step (mapping.add_from_rgbd)
 
     @classmethod
     def from_raw(cls, raw: RawGaussians, requires_grad: bool = True, active_sh_degree=None):

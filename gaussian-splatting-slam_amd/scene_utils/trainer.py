@@ -100,6 +100,31 @@ class Trainer:
         self.graph_replay = False        # enable_graph_replay(): the single-view step as ONE HIP graph launch
         self._graph = None
         self.rerun_views = 0             # ... and how many truncated frames were run again
+        hooks = getattr(model, "_resize_hooks", None)
+        if hooks is not None:            # rows inserted between steps (GaussianModel.add_from_rgbd) replace every parameter too
+            import weakref
+            ref = weakref.WeakMethod(self._on_model_resize)
+            hooks.append(lambda stage: ref() is not None and ref()(stage))
+
+    def _on_model_resize(self, stage):
+        """Around a row insertion made outside step() (mapping.add_from_rgbd).  "before": everything still in flight that reads
+        or re-runs the old rows is settled - an SH update on the side stream, a replayed graph, unverified frames.  "after": what
+        _maybe_densify does when a densification replaced the parameters - a new gradient bucket, no captured graph, every
+        view's tile cut-offs relearnt.  (Workspace pools and capacity estimates are keyed by the model size and the folded
+        optimizer's pointers are taken from the optimizer's groups at every step: nothing to do for those.)"""
+        if self.sharded is not None:
+            raise RuntimeError("exchange='sharded' keeps the Adam moments per row shard: rows cannot be inserted into it")
+        if stage == "before":
+            if self.model.get_xyz.is_cuda:
+                self.finish()
+            return
+        if self.bucket is not None:
+            self.bucket = GradBucket(self._arena_order_params())
+        if self.graph_replay:
+            self._drop_graph()
+        if self.tile_cull:
+            for t in self.tile_cull.values():
+                t.fill_(-1)
 
     def _arena_order_params(self):
         """The six leaves in the order the rasterizer's backward lays their gradients out (geometry first): GradBucket's span over

@@ -36,6 +36,8 @@ extern "C" {
  *    carries validity flags of the gradient records (gsr_backward_scratch_bytes grew; gsr_debug_set_flags_min_r);
  *    later, additive: gsr_camera_grads, gsr_camera_grad_scratch_bytes, gsr_backward_camera (gradients of the camera);
  *    gsr_render_extras and the *_ex entry points (z-depth channel, accumulated-opacity plane and their gradients);
+ *    gsr_knn_dist2 / gsr_knn_workspace_bytes (exact 3-nearest-neighbour distances) and gsr_unproject_rgbd /
+ *    gsr_unproject_workspace_bytes (RGB-D keyframe -> points): the mapping half;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -495,6 +497,49 @@ int gsr_sh_rank1_expand(int32_t P, int32_t n_ranks, int32_t sh_degree, int32_t s
  * lr, 1-based step AFTER this update; sparse must be 0).  Bit-identical to gsr_sh_rank1_expand + gsr_adam_step on those tensors. */
 int gsr_sh_rank1_adam(int32_t P, int32_t n_ranks, int32_t sh_degree, int32_t sh_coeffs_rest, const float* means3D,
                       const float* gathered, float scale, float* f_dc, float* f_rest, const gsr_fused_adam* opt, void* stream);
+
+/* ---- mapping: seeding Gaussians from point clouds and RGB-D keyframes ---- */
+
+/* What the reference takes from `simple_knn._C.distCUDA2` (scene/gaussian_model.py:20,:140; the fourth native module it imports):
+ * mean_dist2[i - first_query] = mean of the three smallest squared Euclidean distances from point i to the OTHER points of the
+ * whole set (other = a different index: a duplicate at distance 0 counts), for first_query <= i < P.  first_query = 0 is distCUDA2;
+ * first_query > 0 is the keyframe case - neighbours are searched in map + new points, answers only for the new ones - and gives
+ * the tail of the first_query = 0 result bit for bit.  EXACT nearest neighbours (Morton order + two levels of boxes that only
+ * prune, csrc/knn.hip); distances are formed from differences, never as |a|^2 + |b|^2 - 2 a.b.  No float atomics, nothing depends on
+ * scheduling: two runs give identical bits.  No device allocation: everything lives in `workspace` (gsr_knn_workspace_bytes(P)).
+ * Fewer than four points: the mean runs over the min(3, P - 1) neighbours that exist, P == 1 gives 0.  (The upstream module is
+ * recalled to leave FLT_MAX-derived values there; nothing in the reference pins either behaviour.)  Non-finite coordinates: no hang
+ * and no out-of-bounds access; the values of those rows (and of rows whose neighbours they would be) are unspecified.
+ * Errors, all before anything is launched: P <= 0 or > 2^30 - 1, NULL pointers, first_query outside [0, P):
+ * GSR_ERR_INVALID_ARGUMENT; workspace_bytes too small: GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_knn_workspace_bytes(int64_t P);
+int gsr_knn_dist2(int64_t P, const float* points /*[P,3]*/, int64_t first_query, float* mean_dist2 /*[P - first_query]*/,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
+ * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
+ * the view matrix (R^T, -R^T t).  A strided pixel is selected iff its reading is valid and
+ *   alpha == NULL: always (first keyframe; `rendered_z` is then ignored);
+ *   else: A < alpha_below (the map does not cover it), or - with `rendered_z`, what a render with GSR_DEPTH_Z returns, sum w_i z_i,
+ *         not normalised, hence the division by A - d < rendered_z / A - front_margin * d (the reading lies in front of the map).
+ * The selected pixels are compacted in ROW-MAJOR pixel order (prefix sum): deterministic.  *count_dev (device int64) receives the
+ * number selected; rows beyond `capacity` are dropped, never written.  capacity = ceil(W / stride) ceil(H / stride) cannot overflow.
+ * Errors before any launch: NULL p / depth / color / count_dev / workspace / viewmatrix, xyz or rgb NULL with capacity > 0,
+ * capacity < 0, sides < 1, stride < 1, tanfov <= 0: GSR_ERR_INVALID_ARGUMENT; workspace too small: GSR_ERR_STATE_TOO_SMALL. */
+typedef struct gsr_unproject_params {
+  int32_t image_height, image_width;
+  float tanfovx, tanfovy;
+  const float* viewmatrix;      /* [16] device, the settings' row-major W2C^T */
+  int32_t stride;               /* >= 1: pixels with x % stride == 0 && y % stride == 0 */
+  float min_depth, max_depth;   /* a reading d is valid iff finite and min_depth < d <= max_depth */
+  float alpha_below;
+  float front_margin;
+} gsr_unproject_params;
+size_t gsr_unproject_workspace_bytes(int32_t image_width, int32_t image_height);
+int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth /*[H,W] view-space z*/, const float* color /*[3,H,W]*/,
+                       const float* alpha /*[H,W] or NULL*/, const float* rendered_z /*[H,W] or NULL*/, float* xyz /*[capacity,3]*/,
+                       float* rgb /*[capacity,3]*/, int64_t capacity, int64_t* count_dev, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py's roofline block).  A measurement aid, process-
  * global and meant for ONE host thread driving the library at a time: enabling it while several host threads launch
