@@ -34,7 +34,7 @@ void gsr_launch_finalize(uint32_t, const uint32_t*, const uint32_t*, char*, cons
 void gsr_launch_sum_tiles(int, const char*, const GsrGeomLayout&, uint32_t*, hipStream_t);
 void gsr_launch_render_fwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, float*,
                            float*, float*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
-                           uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, float*, hipStream_t);
+                           uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, float*, uint32_t*, float, uint32_t, hipStream_t);
 void gsr_launch_count_pairs(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, uint32_t*,
                             hipStream_t);
 void gsr_launch_render_bwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*,
@@ -444,6 +444,11 @@ static int check_extras(const gsr_render_extras* ex) {
     gsr_set_error("gsr_render_extras.depth_kind %d: expected GSR_DEPTH_INVERSE (0) or GSR_DEPTH_Z (1)", (int)ex->depth_kind);
     return GSR_ERR_INVALID_ARGUMENT;
   }
+  // (written so that a NaN fails it too)
+  if (ex && ex->n_touched && !(ex->touched_T_min >= 0.0f && ex->touched_T_min < 1.0f)) {
+    gsr_set_error("gsr_render_extras.touched_T_min %g: expected a transmittance threshold in [0, 1)", (double)ex->touched_T_min);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
   return 0;
 }
 static bool ex_depth_z(const gsr_render_extras* ex) { return ex && ex->depth_kind == GSR_DEPTH_Z; }
@@ -510,7 +515,9 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
                                bool sort_head_clean = false /* this call's projection kernel cleared the tile sort's head */,
                                uint32_t* tile_cutoff = nullptr /* per-tile depth cut-off: updated by the compositing kernel */,
                                bool cull_applied = false /* ... and the projection counted with it: emit with it too */,
-                               uint32_t frame_tag = 0, float* out_alpha = nullptr /* gsr_render_extras.out_alpha */) {
+                               uint32_t frame_tag = 0, const gsr_render_extras* ex = nullptr /* out_alpha, n_touched */) {
+  float* out_alpha = ex_alpha(ex);
+  uint32_t* n_touched = (ex && g && g->P > 0) ? ex->n_touched : nullptr;
   int rc = validate(s, g);
   if (rc) return rc;
   if (num_rendered < 0 || num_rendered > 0x3FFFFFFFll) {   // the tile sort counts keys in 30-bit fields (sort_scan.hip)
@@ -626,13 +633,18 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
     gsr_launch_shade(s, g, geom, GL, false, st);
     if ((rc = debug_sync(s, st, "shade"))) return rc;
   }
+  // n_touched: the library owns the zeroing, and it happens HERE, in front of every compositing launch - phase 2 is the one stage
+  // all forward paths share, so a frame whose phase 2 is repeated (capacity did not hold, culled frame flagged, re-render) starts
+  // from zero again and nothing is counted twice
+  if (n_touched && (rc = gsr_check(hipMemsetAsync(n_touched, 0, (size_t)g->P * 4, st), "memset n_touched"))) return rc;
   gsr_launch_render_fwd(s, tiles, gx, (const uint2*)(bin + BL.ranges), (const uint32_t*)(bin + point_list_offset(BL, tiles)),
                         (const float4*)(geom + GL.rec), out_color, out_invdepth, (float*)(img + IL.final_T),
                         (uint32_t*)(img + IL.n_contrib), status_dev ? (const uint32_t*)(geom + GL.meta) : nullptr, status_dev,
                         (g->P > 0 && R > 0) ? tile_cutoff : nullptr, (const uint32_t*)(geom + GL.depth_key),
                         cull_applied ? (const uint32_t*)(bin + BL.culled_any) : nullptr, frame_tag, (uint32_t*)(geom + GL.meta),
                         walk_cnt, walk_cnt ? (uint32_t*)(img + IL.walk_list) : nullptr,
-                        walk_cnt ? (uint32_t*)(img + IL.walk_of_tile) : nullptr, out_alpha, st);
+                        walk_cnt ? (uint32_t*)(img + IL.walk_of_tile) : nullptr, out_alpha, n_touched,
+                        n_touched ? ex->touched_T_min : 0.f, (uint32_t)R, st);
   if ((rc = debug_sync(s, st, "render forward"))) return rc;
   return gsr_launch_status("forward");
 }
@@ -660,7 +672,7 @@ int gsr_forward_render_ex(const gsr_settings* s, const gsr_gaussians* g, void* g
   if (rc) return rc;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
                              out_color, out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr,
-                             nullptr, false, nullptr, false, 0, ex_alpha(extras));
+                             nullptr, false, nullptr, false, 0, extras);
 }
 
 int gsr_forward_render_shade_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
@@ -671,7 +683,7 @@ int gsr_forward_render_shade_ex(const gsr_settings* s, const gsr_gaussians* g, v
   if (rc) return rc;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
                              out_color, out_invdepth, for_backward != 0, true, (hipEvent_t)sh_ready_event, stream, false, nullptr,
-                             nullptr, nullptr, nullptr, false, nullptr, false, 0, ex_alpha(extras));
+                             nullptr, nullptr, nullptr, false, nullptr, false, 0, extras);
 }
 
 static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -729,7 +741,7 @@ static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, voi
     rc = forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
                              out_color, out_invdepth, for_backward != 0, aside ? false : late,
                              aside ? aside->join : (hipEvent_t)sh_ready_event, stream, tlo, host_status, early, tlo ? host : nullptr,
-                             ev, /*sort_head_clean=*/sort_head != nullptr, tile_cutoff, cull, frame_tag, ex_alpha(ex));
+                             ev, /*sort_head_clean=*/sort_head != nullptr, tile_cutoff, cull, frame_tag, ex);
     if (rc) return rc;
     if (num_rendered_out) {
       const int64_t n = wait_for_count(host, ev, early != nullptr);
@@ -740,7 +752,7 @@ static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, voi
   }
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, 0, image_state, image_bytes, out_color,
                              out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr, nullptr,
-                             false, nullptr, false, 0, ex_alpha(ex));
+                             false, nullptr, false, 0, ex);
 }
 
 int gsr_forward_async(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -792,7 +804,7 @@ int gsr_forward_rerender_ex(const gsr_settings* s, const gsr_gaussians* g, void*
   if (rc) return rc;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
                              out_color, out_invdepth, for_backward != 0, false, nullptr, stream, tile_local_sort != 0,
-                             host_status, nullptr, nullptr, nullptr, false, nullptr, false, 0, ex_alpha(extras));
+                             host_status, nullptr, nullptr, nullptr, false, nullptr, false, 0, extras);
 }
 
 int gsr_forward_rerender(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,

@@ -257,7 +257,11 @@ __device__ __forceinline__ uint32_t gsr_subblock_mask(const float4& r0, const fl
 // published test, in the published order: images, final_T and n_contrib are bit-identical.
 // ALPHA: also writes the accumulated opacity 1 - T_final of every pixel to `out_alpha` (gsr_render_extras); the other
 // instantiations compile to the code they had.
-template <bool COUNT, bool MASKED, bool ALPHA = false>
+// TOUCH: per-Gaussian visibility counts (gsr_render_extras.n_touched): n_touched[id] += the number of
+// pixels that BLEND the entry while their transmittance before it is > touch_T_min.  Integer adds only, summed on chip: one lane
+// per wave adds the popcount of the wave's ballot to the staged slot's LDS counter, and at the end of the round the thread that
+// staged a slot issues at most one global atomicAdd for it.  A frame beyond its capacity (truncated lists) counts nothing.
+template <bool COUNT, bool MASKED, bool ALPHA = false, bool TOUCH = false>
 __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, const uint2* __restrict__ ranges,
                                                     const uint32_t* __restrict__ point_list,
                                                     const float4* __restrict__ rec, const float* __restrict__ bg,
@@ -272,7 +276,9 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
                                                     uint32_t frame_tag, uint32_t* __restrict__ meta, uint32_t margin_q8,
                                                     uint32_t margin_add, uint32_t* __restrict__ walk_cnt,
                                                     uint32_t* __restrict__ walk_list, uint32_t* __restrict__ walk_of_tile,
-                                                    float* __restrict__ out_alpha) {
+                                                    float* __restrict__ out_alpha,
+                                                    uint32_t* __restrict__ n_touched, float touch_T_min, uint32_t touch_cap) {
+  __shared__ uint32_t s_touch[TOUCH ? FWD_BATCH : 1];                     // (TOUCH) pixels that counted each staged entry
   __shared__ float4 s0[FWD_BATCH + 6], s1[FWD_BATCH + 6], s2[FWD_BATCH];  // +6: the prefetch may touch [n+5]
   __shared__ uint32_t s_need;
   __shared__ uint32_t s_wave_last[4];
@@ -311,13 +317,19 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
   int vzero;   // keeps the LDS base in a VGPR (see k_render_bwd)
   asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
   const float4 *s0v = s0 + vzero, *s1v = s1 + vzero, *s2v = s2 + vzero;
+  // (TOUCH) grid-uniform: the lists of a frame beyond its capacity are truncated - its counts stay zero, like its gradients
+  bool touch_on = false;
+  if constexpr (TOUCH) touch_on = !(meta[3] != 0u || meta[2] > touch_cap);
 
   for (int r = 0; r < rounds; r++, toDo -= FWD_BATCH) {
     if (__syncthreads_count(pxe > 1.0e14f) == 256) break;
     const uint32_t progress = range.x + (uint32_t)(r * FWD_BATCH + tid);
     uint32_t mymask = 0u;
+    uint32_t myid = 0xFFFFFFFFu;   // (TOUCH) the Gaussian this thread staged; padding slots and slots beyond the list: none
+    if constexpr (TOUCH) s_touch[tid] = 0u;
     if (progress < range.y) {
       const uint32_t id32 = point_list[progress];
+      if constexpr (TOUCH) myid = id32;
       if (id32 != 0xFFFFFFFFu) {
         const size_t id = id32;
         const float4 r0 = rec[3 * id + 0], r1 = rec[3 * id + 1];
@@ -334,6 +346,15 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
     if (MASKED) smask[tid] = mymask;
     __syncthreads();
     const int n = toDo < FWD_BATCH ? toDo : FWD_BATCH;
+    // (TOUCH) end of a round: all four waves have left the walk (whichever way: list end, live == 0), then every thread hands
+    // the count of the slot it staged - and cleared - to the Gaussian's row.  Its next access to the slot is its own clear.
+    auto flush_touch = [&]() __attribute__((always_inline)) {
+      if constexpr (TOUCH) {
+        __syncthreads();
+        const uint32_t c = s_touch[tid];
+        if (touch_on && c != 0u && myid != 0xFFFFFFFFu) atomicAdd(&n_touched[myid], c);
+      }
+    };
     // one list entry against this wave's 64 pixels
     auto step = [&](const float4& a, const float4& b, const int j) __attribute__((always_inline)) {
       const float dx = a.x - pxe, dy = a.y - pyf;
@@ -349,6 +370,10 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
         const bool blend = ok && !stop;
         const float wgt = blend ? alpha * T : 0.f;
         if (COUNT) blended += blend ? 1u : 0u;
+        if constexpr (TOUCH) {   // T is still the transmittance BEFORE this entry
+          const uint64_t seen = BALLOT(blend && T > touch_T_min);
+          if (seen != 0ull && lane == 0) atomicAdd(&s_touch[j], (uint32_t)__builtin_popcountll(seen));
+        }
         C0 += b.w * wgt;
         C1 += c.x * wgt;
         C2 += c.y * wgt;
@@ -381,6 +406,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
           a = an; b = bn; j = jn;
         }
       }
+      flush_touch();
       continue;
     }
     // four entries per trip, records prefetched two entries ahead into rotating register sets
@@ -397,6 +423,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
       b1 = s1v[j + 5];
       if (j + 3 < n && live != 0ull) step(a3, b3, j + 3);
     }
+    flush_touch();
   }
   if (COUNT) {   // pairs[0 .. N) = entries evaluated per pixel, pairs[N .. 2N) = entries blended per pixel
     if (inside) {
@@ -1458,7 +1485,7 @@ void gsr_launch_render_fwd(const gsr_settings* s, int tiles, int grid_x, const u
                            float* final_T, uint32_t* n_contrib, const uint32_t* status_src, uint32_t* status_dst,
                            uint32_t* tile_cutoff, const uint32_t* depth_key, const uint32_t* culled_any, uint32_t frame_tag,
                            uint32_t* meta, uint32_t* walk_cnt, uint32_t* walk_list, uint32_t* walk_of_tile, float* out_alpha,
-                           hipStream_t st) {
+                           uint32_t* n_touched, float touch_T_min, uint32_t touch_cap, hipStream_t st) {
   // cut-off margin of the depth-truncated lists: 1.75 x the entries a tile needed + 48 (measured, profiles/r04_tile_cull.txt: 1.25 x + 16
   // flags 54 % of the frames of a run that trains from scratch, 1.5 x + 32 1 %, 1.75 x + 48 none; C3 and the 2 x splats scene)
   unsigned mq8 = 448, madd = 48;
@@ -1466,16 +1493,20 @@ void gsr_launch_render_fwd(const gsr_settings* s, int tiles, int grid_x, const u
   // GSR_FWD_MASK=1 selects the masked walk (measured: 0.208 against 0.179 ms at C3, profiles/r04_fwd_mask_ab.txt - not the default)
   const char* mk = getenv("GSR_FWD_MASK");          // (read per call: the tests switch inside one process)
   const bool masked = mk && !strcmp(mk, "1");
-#define GSR_FWD_LAUNCH(M, A)                                                                                                  \
-  GSR_LAUNCH("render_fwd", (k_render_fwd<false, M, A>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
+#define GSR_FWD_LAUNCH(M, A, C)                                                                                               \
+  GSR_LAUNCH("render_fwd", (k_render_fwd<false, M, A, C>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
              ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,        \
              status_dst, tile_cutoff, depth_key, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile,       \
-             out_alpha)
-  if (out_alpha) {
-    if (masked) GSR_FWD_LAUNCH(true, true); else GSR_FWD_LAUNCH(false, true);
+             out_alpha, n_touched, touch_T_min, touch_cap)
+#define GSR_FWD_LAUNCH_A(M, C)                                                         \
+  do { if (out_alpha) GSR_FWD_LAUNCH(M, true, C); else GSR_FWD_LAUNCH(M, false, C); } while (0)
+  // n_touched (gsr_render_extras): the TOUCH instantiations; without it every launch below is the one it was
+  if (n_touched) {
+    if (masked) GSR_FWD_LAUNCH_A(true, true); else GSR_FWD_LAUNCH_A(false, true);
   } else {
-    if (masked) GSR_FWD_LAUNCH(true, false); else GSR_FWD_LAUNCH(false, false);
+    if (masked) GSR_FWD_LAUNCH_A(true, false); else GSR_FWD_LAUNCH_A(false, false);
   }
+#undef GSR_FWD_LAUNCH_A
 #undef GSR_FWD_LAUNCH
 }
 
@@ -1487,7 +1518,7 @@ void gsr_launch_count_pairs(const gsr_settings* s, int tiles, int grid_x, const 
                      point_list, rec, s->bg, (float*)nullptr, (float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, pairs,
                      (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
                      (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                     (float*)nullptr);
+                     (float*)nullptr, (uint32_t*)nullptr, 0.f, 0u);
 }
 
 void gsr_launch_render_bwd(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges,

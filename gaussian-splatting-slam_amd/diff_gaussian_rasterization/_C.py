@@ -51,7 +51,9 @@ class gsr_camera_grads(C.Structure):
 
 
 class gsr_render_extras(C.Structure):
-    _fields_ = [("depth_kind", C.c_int32), ("out_alpha", C.c_void_p), ("dL_dalpha", C.c_void_p)]
+    # (ctypes zero-fills fields that are not given: three positional values leave n_touched NULL and touched_T_min 0)
+    _fields_ = [("depth_kind", C.c_int32), ("out_alpha", C.c_void_p), ("dL_dalpha", C.c_void_p),
+                ("n_touched", C.c_void_p), ("touched_T_min", C.c_float)]
 
 
 DEPTH_KINDS = {"inverse": 0, "z": 1}     # gsr_render_extras.depth_kind: GSR_DEPTH_INVERSE, GSR_DEPTH_Z

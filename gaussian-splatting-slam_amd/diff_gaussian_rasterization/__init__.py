@@ -284,8 +284,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                 raster_settings, raw_activations=False, for_backward=True, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, viewmatrix=None, projmatrix=None,
-                campos=None):
+                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
+                viewmatrix=None, projmatrix=None, campos=None):
         """fold: a BackwardFold for THIS call's backward (kept on ctx).  sh_ready_event: a recorded torch.cuda.Event after which
         `dc` / `shs` hold this step's values (the view-sharded trainer's SH all-reduce + Adam update, in flight on another
         stream): the geometry stages run first, the stream waits for the event and only then evaluates the colours
@@ -294,7 +294,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         (`new_tile_cull`), updated by every speculative forward and applied by unverified ones (gsr_forward_async_culled).
         viewmatrix / projmatrix / campos: raster_settings' own tensors, passed (by rasterize_gaussians) only when one of them
         requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera).  depth / alpha: the
-        depth kind of the third output and whether a fourth, the accumulated opacity, is returned (gsr_render_extras)."""
+        depth kind of the third output and whether a fourth, the accumulated opacity, is returned (gsr_render_extras).
+        n_touched / touched_T_min: one more output, LAST, the int32 [P] visibility counts (gsr_render_extras.n_touched)."""
         lib = _C.lib()
         depth_kind = _depth_kind(depth)
         raw_activations = bool(raw_activations) and cov3D_precomp is None
@@ -331,8 +332,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             radii = torch.empty(P, dtype=torch.int32, device=dev)     # every entry is written by the projection kernel
             alpha_img = torch.empty(1, H, W, dtype=torch.float32, device=dev) if alpha else None
             # (no extras: NULL, the entry points without _ex exactly)
-            extras = _C.gsr_render_extras(depth_kind, _C.ptr(alpha_img) if alpha else None, None) \
-                if (depth_kind or alpha) else None
+            # (uninitialised on purpose: the library zeroes the counts in front of every compositing launch)
+            touched = torch.empty(P, dtype=torch.int32, device=dev) if n_touched else None
+            extras = _C.gsr_render_extras(depth_kind, _C.ptr(alpha_img) if alpha else None, None,
+                                          _C.ptr(touched) if n_touched and P > 0 else None, float(touched_T_min)) \
+                if (depth_kind or alpha or n_touched) else None
             ex = C.byref(extras) if extras is not None else None
             s, keep = _settings_struct(rs, dev)
             g = _gauss_struct(P, means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
@@ -352,7 +356,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                     raise ValueError(f"forward_mode={mode!r}: expected one of {_ws._MODES}")
                 if capturing:
                     if extras is not None:
-                        raise _C.GsrError("depth='z' / alpha=True are not supported under HIP-graph capture: render eagerly")
+                        raise _C.GsrError("depth='z' / alpha=True / n_touched=True are not supported under HIP-graph capture: "
+                                          "render eagerly")
                     if rs.debug or rs.prefiltered or key not in pool.capacity or not pool.status_free:
                         raise _C.GsrError("gsr: a forward under graph capture needs an eager warm-up of the same shape first "
                                           "(and neither debug nor prefiltered)")
@@ -442,7 +447,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.camera = viewmatrix is not None or projmatrix is not None or campos is not None
         ctx.raw_activations = raw_activations
-        ctx.depth_kind, ctx.alpha = depth_kind, bool(alpha)
+        ctx.depth_kind, ctx.alpha = depth_kind, bool(alpha)      # (the counts are forward only: the backward's extras never carry them)
         ctx.fold = fold if needs_grad else None
         ctx.num_rendered = R                 # what the binning state was laid out for (the count itself, or the capacity)
         ctx.has = (dc is not None, sh is not None, colors_precomp is not None, scales is not None,
@@ -452,14 +457,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             lease.release()                  # forward-only: later work on this stream may reuse them at once
         ctx.save_for_backward(means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii)
-        ctx.mark_non_differentiable(radii)
+        ctx.mark_non_differentiable(*((radii, touched) if n_touched else (radii,)))
         ctx.set_materialize_grads(False)     # an unused inverse-depth output reaches backward as None, not as zeros
-        if alpha:
-            return color, radii, invdepth, alpha_img
-        return color, radii, invdepth
+        outs = (color, radii, invdepth) + ((alpha_img,) if alpha else ())
+        return outs + ((touched,) if n_touched else ())
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_invdepth, grad_alpha=None):
+    def backward(ctx, grad_color, grad_radii, grad_invdepth, *grad_more):
+        # (grad_more: the opacity plane's gradient if the forward returned one, then None for the non-differentiable counts)
+        grad_alpha = grad_more[0] if ctx.alpha and grad_more else None
         lib = _C.lib()
         (means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii) = ctx.saved_tensors
         ws = ctx.lease.ws
@@ -591,7 +597,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
                                   for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
         return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None, None, None, None, None, None,
-                None, None, None) + (cam_grads if ctx.camera else ())
+                None, None, None, None, None) + (cam_grads if ctx.camera else ())
 
 
 def _depth_kind(depth):
@@ -602,14 +608,26 @@ def _depth_kind(depth):
     return kind
 
 
+def _check_touched(n_touched, touched_T_min):
+    """Validates the `n_touched=` / `touched_T_min=` arguments (before any device work)."""
+    if not isinstance(n_touched, bool):
+        raise TypeError(f"n_touched={n_touched!r}: expected a bool")
+    if isinstance(touched_T_min, bool) or not isinstance(touched_T_min, (int, float)):
+        raise TypeError(f"touched_T_min={touched_T_min!r}: expected a real number in [0, 1)")
+    if not 0.0 <= float(touched_T_min) < 1.0:     # (a NaN fails it too)
+        raise ValueError(f"touched_T_min={touched_T_min!r}: expected a transmittance threshold in [0, 1)")
+
+
 def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, raw_activations=False, fold=None, sh_ready_event=None, forward_mode=None,
-                        tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False):
+                        tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False,
+                        touched_T_min=0.5):
     # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
     # what only a backward would need
     _depth_kind(depth)                   # (validated before any device work)
     if not isinstance(alpha, bool):
         raise TypeError(f"alpha={alpha!r}: expected a bool")
+    _check_touched(n_touched, touched_T_min)
     tensors = (means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
     rs = raster_settings
     # camera form: the settings' viewmatrix / projmatrix / campos take part in autograd when one of them requires grad (pose
@@ -620,7 +638,7 @@ def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, sca
     extra = (rs.viewmatrix, rs.projmatrix, rs.campos) if camera else ()
     return _RasterizeGaussians.apply(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, raw_activations, for_backward, fold, sh_ready_event,
-                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, *extra)
+                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min, *extra)
 
 
 def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -679,7 +697,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, raw_activations=False, *, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False):
+                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5):
         """Arguments of the reference's call (gaussian_renderer/__init__.py:90-109).  Extensions, all optional and all PER CALL
         (nothing is armed process-wide): `raw_activations=True`: `opacities`, `scales`, `rotations` are the model's RAW
         parameters; sigmoid / exp / normalize are applied inside the projection kernel and the returned gradients are w.r.t. the
@@ -691,7 +709,12 @@ class GaussianRasterizer(nn.Module):
         "inverse" (sum_i w_i / z_i, the reference's inverse depth) or "z" (sum_i w_i z_i, view-space z-depth), w_i = alpha_i T_i
         the compositing weight.  `alpha=True`: a fourth output, the accumulated opacity A = 1 - T_final [1,H,W] (tracking mask /
         silhouette).  Both come from the same single rasterization and are differentiable (include/gsr.h gsr_render_extras);
-        with neither the call is exactly the reference's.  Not under HIP-graph capture."""
+        with neither the call is exactly the reference's.  `n_touched=True`: one more output, LAST (behind the opacity if that
+        is asked for too): int32 [P], for every Gaussian the number of pixels that blend it while their transmittance before it is
+        still > `touched_T_min` (in [0, 1); 0 counts every blended pair, the default 0.5 means "seen through less than half
+        occlusion") - what a SLAM back end's keyframe and pruning decisions need and `radii > 0` cannot say (occlusion).  Counted
+        by the same compositing pass with integer adds (bit-identical run to run and across forward modes), not differentiable,
+        works with or without a backward to follow.  None of the three under HIP-graph capture."""
         _depth_kind(depth)
         if not isinstance(alpha, bool):
             raise TypeError(f"alpha={alpha!r}: expected a bool")
@@ -709,7 +732,7 @@ class GaussianRasterizer(nn.Module):
                 raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings, raw_activations, fold, sh_ready_event, forward_mode,
-                                   tile_cull, tile_cull_apply, depth, alpha)
+                                   tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min)
 
 
 from .sparse_adam import SparseGaussianAdam, FusedAdam  # noqa: E402,F401   (reference train.py:37-41)

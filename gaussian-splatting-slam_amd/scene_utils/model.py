@@ -30,7 +30,7 @@ class GaussianModel:
         self._scaling = self._rotation = self._opacity = None
         self._exposure = None
         self.exposure_mapping = {}
-        self._resize_hooks = []      # called with "before" / "after" around a row insertion from outside a training step (mapping.add_from_rgbd)
+        self._resize_hooks = []      # called with "before" / "after" around a row insertion / removal from outside a training step (mapping.add_from_rgbd, prune_points)
 
     @classmethod
     def from_raw(cls, raw: RawGaussians, requires_grad: bool = True, active_sh_degree=None):
@@ -257,7 +257,49 @@ def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, radi
     return (nk, nc, ns, src) if return_source else (nk, nc, ns)
 
 
+def prune_points(self, mask):
+    """reference scene/gaussian_model.py prune_points: removes the rows where `mask` (bool [P]) is True and returns how many.
+    The surviving rows keep their six parameters, their Adam moments (bit for bit), xyz_gradient_accum, denom and max_radii2D.
+    Made for use BETWEEN training steps, like mapping.add_from_rgbd: the model's resize hooks are called ("before" / "after"),
+    so a Trainer in flight settles its work first and rebuilds what depends on the rows afterwards (under exchange="sharded"
+    its hook raises: the moments live per row shard).  An all-False mask changes nothing and calls no hook.  Works where the
+    tensors live (plain boolean indexing: this is not a per-frame path; one read-back, the count)."""
+    with torch.no_grad():
+        P = int(self._xyz.shape[0])
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != (P,):
+            raise ValueError(f"prune_points: expected a bool mask of shape ({P},), got "
+                             f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}"
+                             f"{' ' + str(mask.dtype) if isinstance(mask, torch.Tensor) else ''}")
+        mask = mask.to(self._xyz.device)
+        n = int(mask.sum().item())
+        if n == 0:
+            return 0
+        for hook in getattr(self, "_resize_hooks", ()):
+            hook("before")
+        keep = ~mask
+        opt = getattr(self, "optimizer", None)
+        tensors, moments = [], []
+        for attr in _PARAM_ATTRS:
+            old = getattr(self, attr)
+            tensors.append(old.detach()[keep].contiguous())
+            st = opt.state.get(old, None) if opt is not None else None
+            if st and "exp_avg" in st:
+                moments.append((st["exp_avg"][keep].contiguous(), st["exp_avg_sq"][keep].contiguous()))
+            else:
+                moments.append(None)
+        _replace_params(self, tensors, moments)
+        if getattr(self, "xyz_gradient_accum", None) is not None:
+            self.xyz_gradient_accum = self.xyz_gradient_accum[keep]
+            self.denom = self.denom[keep]
+        if getattr(self, "max_radii2D", None) is not None:
+            self.max_radii2D = self.max_radii2D[keep]
+        for hook in getattr(self, "_resize_hooks", ()):
+            hook("after")
+    return n
+
+
 GaussianModel.training_setup = training_setup
+GaussianModel.prune_points = prune_points
 GaussianModel.add_densification_stats = add_densification_stats
 GaussianModel.reset_opacity = reset_opacity
 GaussianModel.densify_and_prune = densify_and_prune

@@ -107,13 +107,13 @@ class Trainer:
             hooks.append(lambda stage: ref() is not None and ref()(stage))
 
     def _on_model_resize(self, stage):
-        """Around a row insertion made outside step() (mapping.add_from_rgbd).  "before": everything still in flight that reads
+        """Around a row insertion or removal made outside step() (mapping.add_from_rgbd, GaussianModel.prune_points).  "before": everything still in flight that reads
         or re-runs the old rows is settled - an SH update on the side stream, a replayed graph, unverified frames.  "after": what
         _maybe_densify does when a densification replaced the parameters - a new gradient bucket, no captured graph, every
         view's tile cut-offs relearnt.  (Workspace pools and capacity estimates are keyed by the model size and the folded
         optimizer's pointers are taken from the optimizer's groups at every step: nothing to do for those.)"""
         if self.sharded is not None:
-            raise RuntimeError("exchange='sharded' keeps the Adam moments per row shard: rows cannot be inserted into it")
+            raise RuntimeError("exchange='sharded' keeps the Adam moments per row shard: rows cannot be inserted into it or pruned from it")
         if stage == "before":
             if self.model.get_xyz.is_cuda:
                 self.finish()

@@ -38,6 +38,7 @@ extern "C" {
  *    gsr_render_extras and the *_ex entry points (z-depth channel, accumulated-opacity plane and their gradients);
  *    gsr_knn_dist2 / gsr_knn_workspace_bytes (exact 3-nearest-neighbour distances) and gsr_unproject_rgbd /
  *    gsr_unproject_workspace_bytes (RGB-D keyframe -> points): the mapping half;
+ *    gsr_render_extras.n_touched / touched_T_min (trailing fields; zero = as before): per-Gaussian visibility counts;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -302,12 +303,26 @@ int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32
  *   dL_dalpha:  backward: NULL (zero), or the DEVICE [H,W] gradient of that plane.  It reaches opacities, means, covariances
  *               and the camera through the compositing backward's per-pixel background term (dA/dalpha_i = T_final / (1 -
  *               alpha_i)): no extra work per composited entry, no float atomics; a zero plane gives the gradients of NULL bit
- *               for bit.  An overflowed unverified frame gives zero gradients through it, as through everything else. */
+ *               for bit.  An overflowed unverified frame gives zero gradients through it, as through everything else.
+ * Per-Gaussian visibility counts for keyframe selection and pruning, two TRAILING fields: a
+ * zero-initialised tail is the struct as it was.
+ *   n_touched:  forward: NULL (off), or a DEVICE [P] array; n_touched[i] receives the number of pixels in which Gaussian i is
+ *               BLENDED (power <= 0, alpha >= 1/255, pixel not finished, not the entry that stops the pixel) while the pixel's
+ *               transmittance BEFORE blending it is > touched_T_min.  The memory may be uninitialised: every forward call that
+ *               composites (phase 2, gsr_forward_async*_ex, gsr_forward_rerender_ex) zeroes it first, so the counts always belong
+ *               to the frame that call returns and a repeated phase 2 counts nothing twice.  Rows that reach no tile get 0; an
+ *               unverified frame truncated by its capacity gets all zeros, like its gradients.  Integer adds only: bit-identical
+ *               from run to run and across forward modes, binning forms and walk orders.  gsr_forward_prepare*_ex and the
+ *               backward ignore it.
+ *   touched_T_min: in [0, 1); 0 counts every blended (Gaussian, pixel) pair, 0.5 "seen through less than half occlusion".
+ *               Outside [0, 1), or NaN, with n_touched != NULL: GSR_ERR_INVALID_ARGUMENT before any device work. */
 enum { GSR_DEPTH_INVERSE = 0, GSR_DEPTH_Z = 1 };
 typedef struct gsr_render_extras {
   int32_t depth_kind;      /* GSR_DEPTH_INVERSE | GSR_DEPTH_Z; anything else: GSR_ERR_INVALID_ARGUMENT */
   float* out_alpha;        /* [H,W] or NULL (forward) */
   const float* dL_dalpha;  /* [H,W] or NULL (backward) */
+  uint32_t* n_touched;     /* [P] or NULL (forward) */
+  float touched_T_min;     /* [0, 1); read only when n_touched != NULL */
 } gsr_render_extras;
 int64_t gsr_forward_prepare_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
                                int32_t* radii, void* stream, const gsr_render_extras* extras);
