@@ -22,7 +22,7 @@ void gsr_launch_shade(const gsr_settings*, const gsr_gaussians*, char*, const Gs
 void gsr_launch_adam_culled_rows(int, int, const char*, const GsrGeomLayout&, const GsrAdamArgs&, uint32_t, hipStream_t);
 int gsr_launch_preprocess_bwd(const gsr_settings*, const gsr_gaussians*, const int32_t*, const char*,
                               const GsrGeomLayout&, const float4*, uint32_t, const gsr_grads*, const GsrAdamArgs*, int,
-                              float*, bool, hipStream_t);
+                              float*, bool, bool, hipStream_t);
 size_t gsr_cam_scratch_floats(int);
 void gsr_launch_cam_reduce(int, float*, float*, float*, float*, hipStream_t);
 void gsr_launch_mark_visible(int, const float*, const float*, uint8_t*, hipStream_t);
@@ -875,16 +875,26 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
                          const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                          const gsr_fused_adam* opt, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
-                         void* stream, const gsr_render_extras* ex = nullptr) {
+                         void* stream, const gsr_render_extras* ex = nullptr, bool cam_only = false) {
   int rc = validate(s, g);
   if (rc) return rc;
   if ((rc = check_extras(ex))) return rc;
   if (cam && !cam->dL_dviewmatrix && !cam->dL_dprojmatrix && !cam->dL_dcampos) cam = nullptr;   // nothing asked for: plain
+  // camera-only form (gsr_backward_camera_only): no per-Gaussian output at all - `grads` is not looked at
+  static const gsr_grads no_grads = {};
+  if (cam_only) {
+    if (!cam || !dL_dcolor) {
+      gsr_set_error("backward_camera_only: no camera gradient asked for (or dL_dcolor missing)");
+      return GSR_ERR_INVALID_ARGUMENT;
+    }
+    grads = &no_grads;
+  }
   if (cam && (!cam_scratch || cam_scratch_bytes < gsr_camera_grad_scratch_bytes(g->P))) {
     gsr_set_error("backward_camera: camera scratch too small (gsr_camera_grad_scratch_bytes)");
     return GSR_ERR_STATE_TOO_SMALL;
   }
-  if (!grads || !grads->dL_dmeans2D || !dL_dcolor || (!opt && (!grads->dL_dmeans3D || !grads->dL_dopacities))) {
+  if (!cam_only &&
+      (!grads || !grads->dL_dmeans2D || !dL_dcolor || (!opt && (!grads->dL_dmeans3D || !grads->dL_dopacities)))) {
     gsr_set_error("backward: missing mandatory gradient buffers");
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -929,7 +939,7 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   const int mode = !opt ? 0 : (opt->sparse == 1 ? 2 : (opt->sparse == 2 ? 3 : 1));
   float* cam_rows = cam ? (float*)cam_scratch : nullptr;
   const int groups = gsr_launch_preprocess_bwd(s, g, radii, geom, GL, igrad, (uint32_t)R, grads, opt ? &A : nullptr, mode,
-                                               cam_rows, ex_depth_z(ex), st);
+                                               cam_rows, ex_depth_z(ex), cam_only, st);
   if (groups < 0) {
     gsr_set_error("backward_adam needs the raw-parameter call form with dc / shs passed separately (raw_activations = 1, "
                   "dc != NULL, no colors_precomp / cov3D_precomp, every stored SH coefficient active)");
@@ -959,6 +969,15 @@ int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int
                        scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream);
 }
 
+int gsr_backward_camera_only(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                             const void* geometry_state, const void* binning_state, const void* image_state,
+                             int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
+                             size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
+                             void* stream) {
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, nullptr, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, nullptr, true);
+}
+
 int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
                       const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                       const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
@@ -983,6 +1002,15 @@ int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const 
                            const gsr_render_extras* extras) {
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
                        scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, extras);
+}
+
+int gsr_backward_camera_only_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                                const void* geometry_state, const void* binning_state, const void* image_state,
+                                int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
+                                size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch,
+                                size_t cam_scratch_bytes, void* stream, const gsr_render_extras* extras) {
+  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                       scratch, scratch_bytes, nullptr, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, extras, true);
 }
 
 int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,

@@ -669,7 +669,10 @@ __device__ __forceinline__ void cam_block_partial(const float* cg, float* __rest
 // blockIdx.x of `cam_rows` (gsr_backward_camera; k_cam_reduce adds the rows).  The per-Gaussian gradients are unchanged.
 // ZD: the forward composited z instead of 1/z (gsr_render_extras.depth_kind = GSR_DEPTH_Z): the depth channel's gradient enters
 // dL/dt.z as it is instead of through d(1/z)/dz = -1/z^2 (the camera form reads g_t after it: dL/dviewmatrix follows)
-template <bool STAGE, int ADAM, int BT, bool CAM = false, bool ZD = false>
+// CAMONLY (with CAM, ADAM = 0; gsr_backward_camera_only): no per-Gaussian store at all - the gradient pointers are NULL and not
+// looked at; what only those stores read (the scale / rotation chain, the SH gradient rows) is left to dead-code elimination,
+// the camera terms and their sums are the CAM form's operation for operation (no contraction in this file): identical bits
+template <bool STAGE, int ADAM, int BT, bool CAM = false, bool ZD = false, bool CAMONLY = false>
 __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     int P, int deg, int sh_stride, const float* __restrict__ means3D, const float* __restrict__ dc,
     const float* __restrict__ shs, const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -1057,6 +1060,7 @@ __global__ __launch_bounds__(BT) void k_preprocess_bwd(
     cam_block_partial<BT>(cg, cam_rows);
   }
 
+  if constexpr (CAMONLY) return;     // (the workgroup's camera row is written: nothing else leaves this form)
   // ---- write every output (zeros for culled Gaussians: no memset pass needed) ----
   if (active) {
     dL_dmeans2D[3 * (size_t)idx + 0] = g_m2d[0];
@@ -1419,7 +1423,7 @@ void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, in
 int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
                               const char* geom, const GsrGeomLayout& L, const float4* igrad, uint32_t cap,
                               const gsr_grads* gr, const GsrAdamArgs* adam, int adam_mode, float* cam_rows,
-                              bool depth_z, hipStream_t st) {
+                              bool depth_z, bool cam_only, hipStream_t st) {
   const int P = g->P;
   size_t lds = 0;
   GsrAdamArgs A;
@@ -1434,7 +1438,10 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
     if (stage) lds = (lds / 256) * GSR_BWD_ADAM_BT + (size_t)GSR_BWD_ADAM_BT * 19 * sizeof(float);   // rows of this kernel's workgroup
     A = *adam;
   } else {
-    stage = can_stage_sh(s, g, &lds) && (gr->dL_dshs ? (((uintptr_t)gr->dL_dshs & 15) == 0) : gr->dL_ddc != nullptr);
+    // (camera-only: nothing is staged out, so only the input rows decide - the choice gsr_backward_camera makes for an aligned
+    // dL_dshs, and with it the same workgroup size and the same order of the camera sums)
+    stage = can_stage_sh(s, g, &lds) &&
+            (cam_only || (gr->dL_dshs ? (((uintptr_t)gr->dL_dshs & 15) == 0) : gr->dL_ddc != nullptr));
     if (stage) lds = (lds / 256) * GSR_BWD_PLAIN_BT;
   }
 #define GSR_PRE_BWD_ARGS                                                                                              \
@@ -1445,23 +1452,29 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
       (const uint32_t*)(geom + L.meta) + 2, cap, gr->dL_dmeans3D,                                                      \
       gr->dL_dmeans2D, gr->dL_ddc, gr->dL_dshs, gr->dL_dcolors, gr->dL_dopacities, gr->dL_dscales, gr->dL_drotations, \
       gr->dL_dcov3D, gr->xyz_gradient_accum, gr->denom, gr->max_radii2D, A, g_gsr_flags_min_r, cam_rows
-#define GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, ZD_, NAME)                                                                   \
+#define GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, ZD_, CO_, NAME)                                                              \
   do {                                                                                                                 \
     if (lds > 48 * 1024)                                                                                               \
-      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_>,                                 \
+      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_, CO_>,                            \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_>),                                                       \
+    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_, CO_>),                                                  \
                dim3((P + BT_ - 1) / BT_), dim3(BT_), ST ? lds : 0, st, GSR_PRE_BWD_ARGS);                              \
     groups = (P + BT_ - 1) / BT_;                                                                                      \
   } while (0)
   // (z-depth: the ZD instantiations; without it every launch below is the one it was)
-#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME)                                                                         \
+#define GSR_PRE_BWD_KC(ST, AD, BT_, CAM_, CO_, NAME)                                                                   \
   do {                                                                                                                 \
-    if (depth_z) GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, true, NAME); else GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, false, NAME);   \
+    if (depth_z) GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, true, CO_, NAME);                                                   \
+    else GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, false, CO_, NAME);                                                          \
   } while (0)
+#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME) GSR_PRE_BWD_KC(ST, AD, BT_, CAM_, false, NAME)
   int groups = 0;
 #define GSR_PRE_BWD(ST, AD, BT_) GSR_PRE_BWD_K(ST, AD, BT_, false, AD ? "preprocess_bwd_adam" : "preprocess_bwd")
-  if (cam_rows) {
+  if (cam_only) {
+    if (adam || !cam_rows) return -1;
+    if (stage) GSR_PRE_BWD_KC(true, 0, GSR_BWD_PLAIN_BT, true, true, "preprocess_bwd_cam_only");
+    else GSR_PRE_BWD_KC(false, 0, 256, true, true, "preprocess_bwd_cam_only");
+  } else if (cam_rows) {
     if (adam) return -1;
     if (stage) GSR_PRE_BWD_K(true, 0, GSR_BWD_PLAIN_BT, true, "preprocess_bwd_cam");
     else GSR_PRE_BWD_K(false, 0, 256, true, "preprocess_bwd_cam");
@@ -1476,6 +1489,7 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
   }
 #undef GSR_PRE_BWD
 #undef GSR_PRE_BWD_K
+#undef GSR_PRE_BWD_KC
 #undef GSR_PRE_BWD_KZ
 #undef GSR_PRE_BWD_ARGS
   return groups;

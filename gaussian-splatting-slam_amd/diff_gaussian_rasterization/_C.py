@@ -50,6 +50,17 @@ class gsr_camera_grads(C.Structure):
     _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p)]
 
 
+class gsr_pose_adam(C.Structure):
+    # lives in DEVICE memory: eighteen 8-byte words (POSE_ADAM_WORDS; scene_utils.pose keeps it as a float64 tensor whose last word,
+    # `step`, is read through an int64 view)
+    _fields_ = [("exp_avg", C.c_double * 6), ("exp_avg_sq", C.c_double * 6), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("lr_decay", C.c_double), ("step", C.c_int64)]
+
+
+POSE_ADAM_WORDS = 18
+POSE_ADAM_LR, POSE_ADAM_BETA1, POSE_ADAM_BETA2, POSE_ADAM_EPS, POSE_ADAM_LR_DECAY, POSE_ADAM_STEP = 12, 13, 14, 15, 16, 17
+
+
 class gsr_render_extras(C.Structure):
     # (ctypes zero-fills fields that are not given: three positional values leave n_touched NULL and touched_T_min 0)
     _fields_ = [("depth_kind", C.c_int32), ("out_alpha", C.c_void_p), ("dL_dalpha", C.c_void_p),
@@ -113,6 +124,9 @@ EXPORTS = {
                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    "gsr_backward_camera_only": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gsr_backward_adam": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p]),
@@ -146,6 +160,10 @@ EXPORTS = {
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.POINTER(gsr_render_extras)]),
+    "gsr_backward_camera_only_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.POINTER(gsr_render_extras)]),
     "gsr_backward_adam_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p,
@@ -201,6 +219,8 @@ EXPORTS = {
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),
+    "gsr_pose_forward": (C.c_int, [C.c_void_p] * 7),
+    "gsr_pose_backward": (C.c_int, [C.c_void_p] * 9),
     "gsr_profile_enable": (None, [C.c_int32]),
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

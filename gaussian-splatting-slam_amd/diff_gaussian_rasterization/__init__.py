@@ -285,7 +285,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                 raster_settings, raw_activations=False, for_backward=True, fold=None, sh_ready_event=None, forward_mode=None,
                 tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
-                viewmatrix=None, projmatrix=None, campos=None):
+                camera_only=False, viewmatrix=None, projmatrix=None, campos=None):
         """fold: a BackwardFold for THIS call's backward (kept on ctx).  sh_ready_event: a recorded torch.cuda.Event after which
         `dc` / `shs` hold this step's values (the view-sharded trainer's SH all-reduce + Adam update, in flight on another
         stream): the geometry stages run first, the stream waits for the event and only then evaluates the colours
@@ -295,7 +295,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         viewmatrix / projmatrix / campos: raster_settings' own tensors, passed (by rasterize_gaussians) only when one of them
         requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera).  depth / alpha: the
         depth kind of the third output and whether a fourth, the accumulated opacity, is returned (gsr_render_extras).
-        n_touched / touched_T_min: one more output, LAST, the int32 [P] visibility counts (gsr_render_extras.n_touched)."""
+        n_touched / touched_T_min: one more output, LAST, the int32 [P] visibility counts (gsr_render_extras.n_touched).
+        camera_only: (camera form) the backward returns the three camera gradients and None for every Gaussian input
+        (gsr_backward_camera_only: no per-Gaussian gradient is formed or stored, no gradient arena is allocated)."""
         lib = _C.lib()
         depth_kind = _depth_kind(depth)
         raw_activations = bool(raw_activations) and cov3D_precomp is None
@@ -320,6 +322,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             # (allocated from the graph's pool, never handed to eager calls) and its status slot is left to the graph's owner
             # (`graph_status_slot`): a replay rewrites it, and a count beyond the capacity means what it means in mode "async".
             capturing = torch.cuda.is_current_stream_capturing()
+            if capturing and camera_only:
+                raise _C.GsrError("camera_only=True (camera gradients) is not supported under HIP-graph capture: run this "
+                                  "iteration eagerly")
             if not capturing:
                 pool.poll()                  # instance counts of earlier frames that have arrived meanwhile
                 ws = pool.acquire()          # state buffers of this forward (-> backward): grow-only, recycled
@@ -446,6 +451,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise
         ctx.raster_settings = rs
         ctx.camera = viewmatrix is not None or projmatrix is not None or campos is not None
+        ctx.camera_only = bool(camera_only)
         ctx.raw_activations = raw_activations
         ctx.depth_kind, ctx.alpha = depth_kind, bool(alpha)      # (the counts are forward only: the backward's extras never carry them)
         ctx.fold = fold if needs_grad else None
@@ -489,6 +495,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         def like(t, *shape):
             return torch.empty(*shape, dtype=torch.float32, device=dev) if t is not None else None
 
+        if ctx.camera_only:
+            return _RasterizeGaussians._backward_camera_only(ctx, grad_color, grad_invdepth, ex)
         fold = ctx.fold
         with _C.on_device(dev):
             stats = fold.stats if (fold is not None and not fold.stats_taken) else None    # (once per request)
@@ -597,7 +605,52 @@ class _RasterizeGaussians(torch.autograd.Function):
                 cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
                                   for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
         return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None, None, None, None, None, None,
-                None, None, None, None, None) + (cam_grads if ctx.camera else ())
+                None, None, None, None, None, None) + (cam_grads if ctx.camera else ())
+
+    @staticmethod
+    def _backward_camera_only(ctx, grad_color, grad_invdepth, ex):
+        """backward() of a camera_only=True call: the compositing backward, then gsr_backward_camera_only - the projection backward
+        without a single per-Gaussian store - and the fixed-order reduction.  Returns None for every Gaussian input, `means2D`
+        included; allocates the 35 floats of the camera gradients and the reduction's scratch, nothing of size P x anything."""
+        lib = _C.lib()
+        (means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii) = ctx.saved_tensors
+        ws = ctx.lease.ws
+        rs = ctx.raster_settings
+        R = ctx.num_rendered
+        dev = means3D.device
+        P = int(means3D.shape[0])
+        with _C.on_device(dev):
+            if torch.cuda.is_current_stream_capturing():
+                raise _C.GsrError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) are not "
+                                  "supported under HIP-graph capture: run this backward eagerly")
+            want = ctx.needs_input_grad[-3:]
+            cam_flat = torch.zeros(16 + 16 + 3, dtype=torch.float32, device=dev)   # (P = 0: stays zero)
+            cam_parts = (cam_flat[:16], cam_flat[16:32], cam_flat[32:])
+            cam_struct = _C.gsr_camera_grads(*[t.data_ptr() if w else None for t, w in zip(cam_parts, want)])
+            if P > 0:
+                cur = _C.raw_stream()
+                if ws.stream is not None and ws.stream != cur:
+                    torch.cuda.current_stream().wait_stream(torch.cuda.ExternalStream(ws.stream))
+                s, keep = _settings_struct(rs, dev)
+                g = _gauss_struct(P, means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                  ctx.raw_activations)
+                scratch = ws.ensure_scratch(lib, P, R)
+                cam_scratch = torch.empty(lib.gsr_camera_grad_scratch_bytes(P), dtype=torch.uint8, device=dev)
+                try:
+                    _C.check(lib.gsr_backward_camera_only_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(ws.geom),
+                                                             _C.ptr(ws.binning), _C.ptr(ws.img), R, _C.ptr(grad_color),
+                                                             _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(),
+                                                             C.byref(cam_struct), _C.ptr(cam_scratch), cam_scratch.numel(),
+                                                             _stream(), ex))
+                except _C.GsrError:
+                    if rs.debug:
+                        _dump("snapshot_bw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
+                              cov3D_precomp, grad_color, grad_invdepth, radii)
+                    raise
+                ws.stream = cur
+            cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
+                              for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
+        return (None,) * 22 + cam_grads
 
 
 def _depth_kind(depth):
@@ -621,7 +674,7 @@ def _check_touched(n_touched, touched_T_min):
 def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, raw_activations=False, fold=None, sh_ready_event=None, forward_mode=None,
                         tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False,
-                        touched_T_min=0.5):
+                        touched_T_min=0.5, camera_only=False):
     # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
     # what only a backward would need
     _depth_kind(depth)                   # (validated before any device work)
@@ -634,11 +687,22 @@ def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, sca
     # refinement / tracking, also with every Gaussian tensor frozen); they then travel as trailing inputs of the Function
     camera = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
                                              for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+    if not isinstance(camera_only, bool):
+        raise TypeError(f"camera_only={camera_only!r}: expected a bool")
+    if camera_only:
+        # asked for, never inferred: render() always passes a means2D that requires grad.  Before any launch:
+        if not camera:
+            raise _C.GsrError("camera_only=True needs the camera form: none of the settings' viewmatrix / projmatrix / campos "
+                              "requires grad (or grad mode is off)")
+        if fold is not None:
+            raise _C.GsrError("camera_only=True returns no per-Gaussian gradient: a BackwardFold (optimizer step / "
+                              "densification statistics in the backward) cannot be combined with it")
     for_backward = camera or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors))
     extra = (rs.viewmatrix, rs.projmatrix, rs.campos) if camera else ()
     return _RasterizeGaussians.apply(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, raw_activations, for_backward, fold, sh_ready_event,
-                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min, *extra)
+                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min,
+                                     camera_only, *extra)
 
 
 def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -697,7 +761,8 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, raw_activations=False, *, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5):
+                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
+                camera_only=False):
         """Arguments of the reference's call (gaussian_renderer/__init__.py:90-109).  Extensions, all optional and all PER CALL
         (nothing is armed process-wide): `raw_activations=True`: `opacities`, `scales`, `rotations` are the model's RAW
         parameters; sigmoid / exp / normalize are applied inside the projection kernel and the returned gradients are w.r.t. the
@@ -714,7 +779,11 @@ class GaussianRasterizer(nn.Module):
         still > `touched_T_min` (in [0, 1); 0 counts every blended pair, the default 0.5 means "seen through less than half
         occlusion") - what a SLAM back end's keyframe and pruning decisions need and `radii > 0` cannot say (occlusion).  Counted
         by the same compositing pass with integer adds (bit-identical run to run and across forward modes), not differentiable,
-        works with or without a backward to follow.  None of the three under HIP-graph capture."""
+        works with or without a backward to follow.  None of the three under HIP-graph capture.  `camera_only=True` (tracking:
+        the map is frozen, only the pose is refined): the call must be in the camera form - one of the settings' viewmatrix /
+        projmatrix / campos requires grad, GsrError otherwise - and its backward returns those gradients alone, bit for bit the
+        ones of the full camera form: every Gaussian input, `means2D` included, gets None, no per-Gaussian gradient is formed
+        or stored (gsr_backward_camera_only) and no gradient arena is allocated.  Not with `fold`, not under capture."""
         _depth_kind(depth)
         if not isinstance(alpha, bool):
             raise TypeError(f"alpha={alpha!r}: expected a bool")
@@ -732,7 +801,7 @@ class GaussianRasterizer(nn.Module):
                 raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, self.raster_settings, raw_activations, fold, sh_ready_event, forward_mode,
-                                   tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min)
+                                   tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min, camera_only)
 
 
 from .sparse_adam import SparseGaussianAdam, FusedAdam  # noqa: E402,F401   (reference train.py:37-41)

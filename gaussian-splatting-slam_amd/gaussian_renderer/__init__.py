@@ -66,7 +66,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
            override_color=None, use_trained_exp=False, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
            **rasterizer_kw):
     """`rasterizer_kw`: per-call extensions of this rasterizer, forwarded to `GaussianRasterizer.forward` (`fold`, `sh_ready_event`,
-    `forward_mode`); none given = the reference's call forms, unchanged.  `depth="z"`: the `"depth"` key holds the view-space
+    `forward_mode`, `camera_only` - tracking against a frozen map: the backward returns the camera's gradients alone);
+    none given = the reference's call forms, unchanged.  `depth="z"`: the `"depth"` key holds the view-space
     z-depth sum_i w_i z_i instead of the inverse depth; `alpha=True`: the package gains `"alpha"`, the accumulated opacity
     1 - T_final [1,H,W] - both from the same single rasterization, both differentiable.  `n_touched=True`: the package gains
     `"n_touched"`, int32 [P]: for every Gaussian the number of pixels that blend it while their transmittance before it is

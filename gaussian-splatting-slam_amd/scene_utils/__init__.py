@@ -9,6 +9,6 @@ from .parallel import init_from_env, shard_views, GradBucket, ShardedStep, reduc
     rank1_sh_exchange, exchange_bytes_per_gaussian
 from .trainer import Trainer
 from .io import save_ply, load_ply, read_ply_vertices, capture, restore
-from .pose import se3_exp, PoseCamera, refine_pose, pose_error
+from .pose import se3_exp, PoseCamera, refine_pose, pose_error, DevicePoseCamera, track_pose
 from .mapping import unproject_rgbd, create_from_pcd, add_from_rgbd
 from .keyframes import covisibility, KeyframeWindow, prune_unobserved

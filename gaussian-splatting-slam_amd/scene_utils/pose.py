@@ -5,9 +5,13 @@ The rasterizer returns gradients for the camera's `viewmatrix` / `projmatrix` / 
 twist `tau` with torch ops, so those gradients reach `tau`; `refine_pose` optimises `tau` against an image (tracking: the map
 stays frozen).  Conventions: the matrices are the reference's row-major transposed 4x4 tensors (world_view_transform = W2C^T,
 full_proj_transform = (P W2C)^T), and the correction is applied on the left, W2C' = exp(tau) W2C, tau = (rho, theta): rho
-a translation and theta a rotation vector, both in the camera frame."""
+a translation and theta a rotation vector, both in the camera frame.
+
+`DevicePoseCamera` / `track_pose` are the same camera and the same optimisation with the pose arithmetic and the optimizer step in
+two HIP kernels (csrc/pose.hip) and the state in device memory: a tracking iteration then never crosses to the host."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import torch
@@ -152,3 +156,171 @@ def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambd
         if callback is not None:
             callback(it, pc)
     return pc.commit(), history
+
+
+class _DevicePose(torch.autograd.Function):
+    """(tau; the camera) -> (world_view_transform, full_proj_transform, camera_center), float32: ONE gsr_pose_forward launch for
+    the three tensors, ONE gsr_pose_backward launch for their three gradients (a missing one is NULL = zero).  With the camera's
+    Adam state armed (track_pose) that launch also takes the optimizer step on tau, and tau gets no .grad."""
+
+    @staticmethod
+    def forward(ctx, tau, cam):
+        from diff_gaussian_rasterization import _C
+        dev = tau.device
+        view = torch.empty(4, 4, dtype=torch.float32, device=dev)
+        proj = torch.empty(4, 4, dtype=torch.float32, device=dev)
+        center = torch.empty(3, dtype=torch.float32, device=dev)
+        with _C.on_device(dev):
+            _C.check(_C.lib().gsr_pose_forward(_C.ptr(cam.base_w2c), _C.ptr(tau), _C.ptr(cam.proj_T), _C.ptr(view), _C.ptr(proj),
+                                               _C.ptr(center), _C._stream()))
+        ctx.cam = cam
+        ctx.base = cam.base_w2c              # (commit() replaces the attribute: this graph keeps the matrix it was built from)
+        ctx.set_materialize_grads(False)
+        return view, proj, center
+
+    @staticmethod
+    def backward(ctx, g_view, g_proj, g_center):
+        from diff_gaussian_rasterization import _C
+        cam = ctx.cam
+        tau = cam.tau
+        dev = tau.device
+
+        def f32(g):
+            return None if g is None else g.to(dtype=torch.float32, device=dev).contiguous()
+        g_view, g_proj, g_center = f32(g_view), f32(g_proj), f32(g_center)
+        adam = cam._adam
+        grad = None if adam is not None else torch.empty(6, dtype=torch.float64, device=dev)
+        with _C.on_device(dev):
+            _C.check(_C.lib().gsr_pose_backward(_C.ptr(ctx.base), _C.ptr(tau), _C.ptr(cam.proj_T), _C.ptr(g_view),
+                                                _C.ptr(g_proj), _C.ptr(g_center), _C.ptr(grad), _C.ptr(adam), _C._stream()))
+        if adam is not None:
+            cam._cache = None                # (tau was stepped by the kernel: autograd's version counter did not see it)
+        return grad, None
+
+
+class DevicePoseCamera:
+    """`PoseCamera` with the pose state - `base_w2c`, `proj_T` and the leaf twist `tau` - in float64 DEVICE memory and the
+    arithmetic in two HIP kernels (gsr_pose_forward / gsr_pose_backward): same attribute surface, same conventions.  The three
+    transform properties come from one autograd Function evaluated once per value of `tau` (cached on tau's version counter), so
+    a render() costs one small launch for the pose and its backward one more; `tau.grad` arrives as float64 on the device.  Works
+    with any loss and any torch optimizer over `tau`; `track_pose` additionally folds the Adam step into the backward launch.
+    There is no CPU path: a camera on the CPU needs `device=` (GsrError otherwise)."""
+
+    def __init__(self, cam, device=None, requires_grad=True):
+        from diff_gaussian_rasterization import _C
+        wv = cam.world_view_transform
+        device = torch.device(device) if device is not None else wv.device
+        if device.type != "cuda":
+            raise _C.GsrError("DevicePoseCamera keeps the pose on the HIP device (no CPU path): pass device='cuda' or a camera "
+                              "whose tensors are there - PoseCamera is the host form")
+        self.image_width, self.image_height = int(cam.image_width), int(cam.image_height)
+        self.FoVx, self.FoVy = float(cam.FoVx), float(cam.FoVy)
+        self.znear, self.zfar = cam.znear, cam.zfar
+        self.image_name = getattr(cam, "image_name", "")
+        base = getattr(cam, "base_w2c", None)
+        if base is not None and hasattr(cam, "w2c"):          # a PoseCamera / DevicePoseCamera: its corrected pose, in full precision
+            with torch.no_grad():
+                base = cam.w2c().detach()
+        else:
+            base = wv.detach().transpose(0, 1)
+        self.base_w2c = base.to(dtype=torch.float64, device=device).contiguous()
+        self.proj_T = projection_matrix(self.znear, self.zfar, self.FoVx, self.FoVy).transpose(0, 1).to(
+            dtype=torch.float64, device=device).contiguous()
+        self.tau = torch.zeros(6, dtype=torch.float64, device=device, requires_grad=requires_grad)
+        self._adam = None          # device Adam state (gsr_pose_adam) while track_pose drives this camera
+        self._cache = None         # (tau version, grad mode, the three tensors)
+
+    def _transforms(self):
+        key = (self.tau._version, torch.is_grad_enabled() and self.tau.requires_grad)
+        if self._cache is None or self._cache[0] != key:
+            self._cache = (key, _DevicePose.apply(self.tau, self))
+        return self._cache[1]
+
+    def w2c(self):
+        """The corrected world-to-camera matrix exp(tau) W2C (4x4 float64 on the device; torch ops, not on the per-iteration
+        path)."""
+        return se3_exp(self.tau) @ self.base_w2c
+
+    @property
+    def world_view_transform(self):
+        return self._transforms()[0]
+
+    @property
+    def full_proj_transform(self):
+        return self._transforms()[1]
+
+    @property
+    def camera_center(self):
+        return self._transforms()[2]
+
+    def commit(self):
+        """Folds tau into the base pose and zeroes it (once per frame: torch ops)."""
+        with torch.no_grad():
+            self.base_w2c = (se3_exp(self.tau) @ self.base_w2c).contiguous()
+            self.tau.zero_()
+        self._cache = None
+        return self
+
+
+def _pose_adam_state(device, lr, lr_decay, betas=(0.9, 0.999), eps=1e-8):
+    """gsr_pose_adam in device memory, as a float64 tensor of its eighteen 8-byte words (moments and step zero)."""
+    from diff_gaussian_rasterization import _C
+    st = _C.gsr_pose_adam()
+    st.lr, st.beta1, st.beta2, st.eps, st.lr_decay, st.step = float(lr), float(betas[0]), float(betas[1]), float(eps), \
+        float(lr_decay), 0
+    assert C.sizeof(st) == 8 * _C.POSE_ADAM_WORDS
+    host = torch.frombuffer(bytearray(bytes(st)), dtype=torch.float64)
+    return host.to(device)
+
+
+def track_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda_dssim=0.0, bg=None, pipe=None,
+               separate_sh=False, gt_depth=None, depth_weight=0.5, alpha_min=0.5):
+    """`refine_pose` with the host taken out of the loop: same loss, masks, Adam and learning-rate schedule, the pose in a
+    `DevicePoseCamera`.  Every iteration is gsr_pose_forward, render(..., camera_only=True) (with depth="z", alpha=True for
+    RGB-D), the loss, its backward - the rasterizer's camera-only backward returns the three camera gradients and nothing per
+    Gaussian - and gsr_pose_backward with the Adam step on tau, the learning-rate decay and the step count folded into that
+    launch.  Nothing is copied to the host inside the loop: each loss is written into its slot of a device tensor.  The one host
+    wait left is the forward's own instance-count check: the frames are rendered with forward_mode="exact", because a truncated
+    unverified frame would hand Adam exact-zero gradients.  `cam`: a DevicePoseCamera (refined in place) or any camera (wrapped;
+    its tensors, or `gt_image`, say which device).  Returns (the DevicePoseCamera with tau committed, losses: a DEVICE tensor
+    [iters], float32 - read it once, after the loop).  No `callback`: `refine_pose` stays for callers that need one."""
+    from diff_gaussian_rasterization import _C
+    from gaussian_renderer import render, PipelineParams
+    from .losses import l1_loss, training_loss_fused
+    if not torch.is_tensor(gt_image) or not gt_image.is_cuda:
+        raise _C.GsrError("track_pose runs on the HIP device (no CPU path): gt_image must be a device tensor - refine_pose is "
+                          "the host form")
+    if gt_depth is not None:
+        from fused_ssim import l1_mean_loss
+        if not 0.0 <= float(depth_weight) <= 1.0:
+            raise ValueError(f"depth_weight={depth_weight}: expected a value in [0, 1]")
+        gt_depth = gt_depth.detach().float().reshape(1, *gt_image.shape[-2:]).contiguous()
+        has_reading = gt_depth > 0
+    pc = cam if isinstance(cam, DevicePoseCamera) else DevicePoseCamera(cam, device=gt_image.device)
+    pipe = pipe or PipelineParams()
+    if bg is None:
+        bg = torch.zeros(3, dtype=torch.float32, device=gt_image.device)
+    gamma = math.exp(math.log(lr_final / lr) / max(1, iters - 1)) if iters > 1 else 1.0
+    losses = torch.zeros(iters, dtype=torch.float32, device=gt_image.device)
+    pc._adam = _pose_adam_state(pc.tau.device, lr, gamma)
+    pc._cache = None
+    kw = dict(separate_sh=separate_sh, camera_only=True, forward_mode="exact")
+    try:
+        for it in range(iters):
+            if gt_depth is None:
+                image = render(pc, model, pipe, bg, **kw)["render"]
+                loss = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+            else:
+                pkg = render(pc, model, pipe, bg, depth="z", alpha=True, **kw)
+                valid = (has_reading & (pkg["alpha"].detach() > alpha_min)).float()
+                loss = l1_mean_loss(pkg["depth"], gt_depth, float(depth_weight), valid)
+                if depth_weight < 1.0:
+                    image = pkg["render"]
+                    rgb = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
+                    loss = loss + (1.0 - float(depth_weight)) * rgb
+            loss.backward()                      # ... -> gsr_backward_camera_only -> gsr_pose_backward (+ Adam on tau)
+            losses[it].copy_(loss.detach().reshape(()))
+    finally:
+        pc._adam = None
+        pc._cache = None
+    return pc.commit(), losses

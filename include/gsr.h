@@ -39,6 +39,7 @@ extern "C" {
  *    gsr_knn_dist2 / gsr_knn_workspace_bytes (exact 3-nearest-neighbour distances) and gsr_unproject_rgbd /
  *    gsr_unproject_workspace_bytes (RGB-D keyframe -> points): the mapping half;
  *    gsr_render_extras.n_touched / touched_T_min (trailing fields; zero = as before): per-Gaussian visibility counts;
+ *    gsr_backward_camera_only (+ _ex), gsr_pose_adam, gsr_pose_forward, gsr_pose_backward: pose tracking on the device;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -250,6 +251,19 @@ int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int
                         void* scratch, size_t scratch_bytes, const gsr_grads* grads, const gsr_camera_grads* cam,
                         void* cam_scratch, size_t cam_scratch_bytes, void* stream);
 
+/* gsr_backward_camera WITHOUT the per-Gaussian outputs: the backward of a tracking iteration, where the map is frozen and only
+ * the pose is refined.  No gsr_grads: the projection backward stores nothing per Gaussian - at SH
+ * degree 3 about 62 floats per Gaussian that nobody would read - and only forms what the 27 camera sums need.  The sums and
+ * their order are gsr_backward_camera's: the three gradients equal, bit for bit, those of gsr_backward_camera on the same frame
+ * (called with a 16-byte aligned dL_dshs, as every caller in this repository does: the alignment decides between the 64- and the
+ * 256-Gaussian workgroup there, the alignment of `shs` alone here).  At least one pointer of `cam` must be set
+ * (GSR_ERR_INVALID_ARGUMENT otherwise); cam_scratch as for gsr_backward_camera, checked before anything is launched. */
+int gsr_backward_camera_only(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                             const void* geometry_state, const void* binning_state, const void* image_state,
+                             int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth,
+                             void* scratch, size_t scratch_bytes, const gsr_camera_grads* cam,
+                             void* cam_scratch, size_t cam_scratch_bytes, void* stream);
+
 /* gsr_backward with the optimizer step folded in (single-GPU training step: reference train.py:139 loss.backward() followed
  * by :170-179 optimizer.step(), when nothing sits between the two - no gradient exchange, no accumulation over views, no
  * densification at this iteration).  The six parameter groups of reference scene/gaussian_model.py:160-168 are updated IN PLACE
@@ -359,6 +373,11 @@ int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const 
                            const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                            const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream,
                            const gsr_render_extras* extras);
+int gsr_backward_camera_only_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                                const void* geometry_state, const void* binning_state, const void* image_state,
+                                int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
+                                size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch,
+                                size_t cam_scratch_bytes, void* stream, const gsr_render_extras* extras);
 int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
                          const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
@@ -555,6 +574,35 @@ int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth /*[H,W]
                        const float* alpha /*[H,W] or NULL*/, const float* rendered_z /*[H,W] or NULL*/, float* xyz /*[capacity,3]*/,
                        float* rgb /*[capacity,3]*/, int64_t capacity, int64_t* count_dev, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ---- tracking: the camera pose as an SE(3) correction, on the device ---- */
+
+/* The pose of a tracking iteration is W2C' = exp(tau) W2C: `base_w2c` [16] the row-major 4x4 world-to-camera matrix (column-
+ * vector convention), `tau` [6] = (rho, theta) the twist [[hat(theta), rho], [0, 0]] applied on the left, `proj_T` [16] the
+ * TRANSPOSED projection matrix.  All three are float64 in DEVICE memory and the arithmetic is float64; one single-wave launch each
+ * way, no atomics, bitwise reproducible.
+ * gsr_pose_forward writes the three float32 tensors of gsr_settings: viewmatrix = T^T, projmatrix = T^T proj_T, campos = -R^T t of
+ * T = exp(tau) base_w2c.  exp: R = I + A K + B K^2, V = I + B K + C K^2 (K = hat(theta), A = sin t / t, B = (1 - cos t) / t^2,
+ * C = (t - sin t) / t^3); where |theta|^2 < 1e-6 the Taylor polynomials in |theta|^2 up to the second order, else the closed
+ * forms with 1 - cos t = 2 sin^2(t / 2).
+ * gsr_pose_backward takes the gradients of those three tensors (float32, each may be NULL = zero: what gsr_backward_camera*
+ * returns) and writes dL/dtau [6] (float64; may be NULL when `adam` is given), exact at any tau.
+ * adam: NULL, or a gsr_pose_adam in DEVICE memory: the same launch then applies one torch.optim.Adam step (bias correction, no
+ * weight decay, no amsgrad) to `tau` IN PLACE with the stored learning rate, then multiplies the stored learning rate by lr_decay
+ * and increments the stored step - nothing per step comes from the host.  Every member is 8 bytes wide: a caller may keep the
+ * struct as 18 consecutive 64-bit words. */
+typedef struct gsr_pose_adam {
+  double exp_avg[6];
+  double exp_avg_sq[6];
+  double lr;        /* learning rate of the NEXT step; multiplied by lr_decay after each */
+  double beta1, beta2, eps;
+  double lr_decay;
+  int64_t step;     /* steps taken so far */
+} gsr_pose_adam;
+int gsr_pose_forward(const double* base_w2c, const double* tau, const double* proj_T, float* viewmatrix, float* projmatrix,
+                     float* campos, void* stream);
+int gsr_pose_backward(const double* base_w2c, double* tau, const double* proj_T, const float* dL_dviewmatrix,
+                      const float* dL_dprojmatrix, const float* dL_dcampos, double* dL_dtau, gsr_pose_adam* adam, void* stream);
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py's roofline block).  A measurement aid, process-
  * global and meant for ONE host thread driving the library at a time: enabling it while several host threads launch

@@ -8,9 +8,16 @@ A > 0.5, as scene_utils.refine_pose forms it):
    (d) RGB-D in ONE pass: render(depth="z", alpha=True);
    (e) RGB-D through the two-render workaround: the colour render, then a second full rasterization with colors_precomp =
        (z, 0, 0) and bg = (0, 1, 0) - channel 0 is D_z, channel 1 is T_final - z formed with torch from the pose's viewmatrix.
+With --device-pose, the same iterations with the pose on the device, as scene_utils.track_pose runs them (DevicePoseCamera,
+gsr_pose_forward / gsr_pose_backward with the Adam step folded in, forward_mode="exact"):
+   (f) photometric, render(camera_only=True): the track_pose iteration;
+   (g) the same with the full camera backward (camera_only off): what the camera-only backward alone is worth;
+   (h) (with --rgbd) RGB-D in one pass, camera_only=True.
+Every form is also timed as a LOOP (`*_loop_ms`: the iterations back to back, one synchronisation at the end, per iteration): the
+device forms never wait for the host inside the loop, which the per-iteration timing (a synchronisation after each) cannot show.
 Prints one JSON line (ms per iteration, medians of timed repetitions).  Per-kernel times: run under
 `rocprofv3 --kernel-trace --stats -- python tools/camera_grad_bench.py` and read preprocess_bwd vs its camera form and cam_reduce.
-    python tools/camera_grad_bench.py [--iters N] [--rgbd]   (GPU box, repo root)"""
+    python tools/camera_grad_bench.py [--iters N] [--rgbd] [--device-pose]   (GPU box, repo root)"""
 import argparse
 import json
 import os
@@ -26,6 +33,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rgbd", action="store_true", help="also time the RGB-D tracking iterations (c) - (e)")
+    ap.add_argument("--device-pose", action="store_true", help="also time the track_pose-style iterations (f) - (h)")
     a = ap.parse_args()
     from scene_utils import make_config, GaussianModel, PoseCamera, l1_loss
     from gaussian_renderer import render, PipelineParams
@@ -78,6 +86,24 @@ def main():
             opt.step()
 
         fns += [("rgbd_one_pass_iter_ms", rgbd_one_pass), ("rgbd_two_render_iter_ms", rgbd_two_render)]
+    if a.device_pose:
+        from scene_utils import DevicePoseCamera
+        from scene_utils.pose import _pose_adam_state
+        dpc = DevicePoseCamera(cam, device=dev)
+        dpc._adam = _pose_adam_state(dev, 1e-4, 1.0)       # the Adam step rides in gsr_pose_backward, as in track_pose
+
+        def device_tracking(camera_only=True):
+            l1_loss(render(dpc, frozen, pipe, bg, camera_only=camera_only, forward_mode="exact")["render"], gt).backward()
+
+        fns += [("device_pose_iter_ms", device_tracking),
+                ("device_pose_full_backward_iter_ms", lambda: device_tracking(False))]
+        if a.rgbd:
+            def device_rgbd():
+                pkg = render(dpc, frozen, pipe, bg, depth="z", alpha=True, camera_only=True, forward_mode="exact")
+                valid = (has & (pkg["alpha"].detach() > 0.5)).float()
+                (0.5 * l1_loss(pkg["render"], gt) + l1_mean_loss(pkg["depth"], gt_depth, 0.5, valid)).backward()
+
+            fns.append(("device_pose_rgbd_iter_ms", device_rgbd))
     out = {"config": 3, "P": cfg["P"], "W": cfg["W"], "H": cfg["H"]}
     for name, fn in fns:
         for _ in range(a.warmup):
@@ -93,6 +119,18 @@ def main():
             ts.append(e0.elapsed_time(e1))
         ts.sort()
         out[name] = round(ts[len(ts) // 2], 4)
+        # the same iterations back to back: three loops of `iters`, the median loop, per iteration
+        loops = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            loops.append(e0.elapsed_time(e1) / a.iters)
+        loops.sort()
+        out[name.replace("_iter_ms", "_loop_ms")] = round(loops[1], 4)
     print(json.dumps(out))
 
 
