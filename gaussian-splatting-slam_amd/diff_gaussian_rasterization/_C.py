@@ -86,6 +86,21 @@ class gsr_fused_adam(C.Structure):
     ]
 
 
+_EXTRAS = C.POINTER(gsr_render_extras)
+_SCENE = [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians)]
+# shared argument prefixes of the rasterizer's entry points (include/gsr.h), each named by what follows (settings, Gaussians):
+# geometry state + bytes, radii
+_PREPARE = _SCENE + [C.c_void_p, C.c_size_t, C.c_void_p]
+# geometry state, binning state + bytes, num_rendered, image state + bytes, color, invdepth, for_backward
+_RENDER = _SCENE + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32]
+# geometry state + bytes, radii, binning state + bytes, capacity, image state + bytes, color, invdepth, for_backward, split,
+# event, status, tile_local, stream, count
+_ASYNC = _PREPARE + [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+# radii, geometry / binning / image state, num_rendered, dL_dcolor, dL_dinvdepth, scratch + bytes
+_BACKWARD = _SCENE + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_size_t]
+_CAMERA = [C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t]      # camera gradients, reduction scratch + bytes
+
 EXPORTS = {
     # name: (restype, argtypes)
     "gsr_abi_version": (C.c_int, []),
@@ -94,80 +109,19 @@ EXPORTS = {
     "gsr_image_state_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_binning_state_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "gsr_backward_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "gsr_forward_prepare": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_void_p]),
-    "gsr_forward_prepare_geometry": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p,
-                                                 C.c_size_t, C.c_void_p, C.c_void_p]),
-    "gsr_forward_shade": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p]),
-    "gsr_forward_render": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                     C.c_int32, C.c_void_p]),
-    "gsr_forward_render_shade": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                           C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                           C.c_int32, C.c_void_p, C.c_void_p]),
-    "gsr_forward_async": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                    C.POINTER(C.c_int64)]),
-    "gsr_forward_async_culled": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                    C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
-    "gsr_forward_rerender": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                       C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32,
-                                       C.c_int32, C.c_void_p, C.c_void_p]),
-    "gsr_backward": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                               C.POINTER(gsr_grads), C.c_void_p]),
+    "gsr_forward_prepare": (C.c_int64, _PREPARE + [C.c_void_p]),
+    "gsr_forward_prepare_geometry": (C.c_int64, _PREPARE + [C.c_void_p]),
+    "gsr_forward_shade": (C.c_int, _SCENE + [C.c_void_p, C.c_void_p]),
+    "gsr_forward_render": (C.c_int, _RENDER + [C.c_void_p]),
+    "gsr_forward_render_shade": (C.c_int, _RENDER + [C.c_void_p, C.c_void_p]),                  # event, stream
+    "gsr_forward_async": (C.c_int, _ASYNC),
+    "gsr_forward_async_culled": (C.c_int, _ASYNC + [C.c_void_p, C.c_int32]),                    # tile_cull, apply
+    "gsr_forward_rerender": (C.c_int, _RENDER + [C.c_int32, C.c_void_p, C.c_void_p]),           # tile_local, status, stream
+    "gsr_backward": (C.c_int, _BACKWARD + [C.POINTER(gsr_grads), C.c_void_p]),
     "gsr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int32]),
-    "gsr_backward_camera": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                      C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
-                                      C.c_void_p]),
-    "gsr_backward_camera_only": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gsr_backward_adam": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                    C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p]),
-    # the *_ex forms: the same arguments plus a gsr_render_extras* (NULL = the form without _ex)
-    "gsr_forward_prepare_ex": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t,
-                                           C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_forward_prepare_geometry_ex": (C.c_int64, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p,
-                                                    C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_forward_render_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                        C.c_int32, C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_forward_render_shade_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                              C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                              C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_forward_async_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                       C.POINTER(C.c_int64), C.POINTER(gsr_render_extras)]),
-    "gsr_forward_async_culled_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_size_t,
-                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t,
-                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                              C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32,
-                                              C.POINTER(gsr_render_extras)]),
-    "gsr_forward_rerender_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                          C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_backward_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                  C.POINTER(gsr_grads), C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_backward_camera_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                         C.POINTER(gsr_grads), C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.POINTER(gsr_render_extras)]),
-    "gsr_backward_camera_only_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_size_t, C.POINTER(gsr_camera_grads), C.c_void_p, C.c_size_t, C.c_void_p,
-                                              C.POINTER(gsr_render_extras)]),
-    "gsr_backward_adam_ex": (C.c_int, [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                       C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p,
-                                       C.POINTER(gsr_render_extras)]),
+    "gsr_backward_camera": (C.c_int, _BACKWARD + [C.POINTER(gsr_grads)] + _CAMERA + [C.c_void_p]),
+    "gsr_backward_camera_only": (C.c_int, _BACKWARD + _CAMERA + [C.c_void_p]),
+    "gsr_backward_adam": (C.c_int, _BACKWARD + [C.POINTER(gsr_grads), C.POINTER(gsr_fused_adam), C.c_void_p]),
     "gsr_adam_step_culled_rows": (C.c_int, [C.POINTER(gsr_gaussians), C.c_void_p, C.c_int64, C.POINTER(gsr_fused_adam),
                                             C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -225,6 +179,12 @@ EXPORTS = {
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
 }
+
+# the *_ex forms: the same arguments plus a gsr_render_extras* (NULL = the form without _ex)
+for _name in ("gsr_forward_prepare", "gsr_forward_prepare_geometry", "gsr_forward_render", "gsr_forward_render_shade",
+              "gsr_forward_async", "gsr_forward_async_culled", "gsr_forward_rerender", "gsr_backward", "gsr_backward_camera",
+              "gsr_backward_camera_only", "gsr_backward_adam"):
+    EXPORTS[_name + "_ex"] = (EXPORTS[_name][0], EXPORTS[_name][1] + [_EXTRAS])
 
 ADAM_DYNAMIC_FLOATS = 18     # GSR_ADAM_DYNAMIC_FLOATS
 ABI_VERSION = 7      # GSR_ABI_VERSION of include/gsr.h
@@ -352,6 +312,22 @@ def fusedssim_backward(C1, C2, img1, img2, dL_dmap, partials=None):
 
 # ---- the low-level call forms of the absent module's `_C` (SURVEY.md 8b "Native surface"; nothing in the reference calls them
 # directly, they are kept so code written against the published extension keeps working) ----
+def _forward_on_own_buffers(s, g, P, W, H, dev):
+    """The blocking forward on buffers allocated here: gsr_forward_prepare (reads num_rendered back), a binning state of exactly
+    that size, gsr_forward_render.  -> (num_rendered, color, radii, geom, binning, img, invdepth)"""
+    l = lib()
+    color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    invdepth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+    radii = torch.zeros(P, dtype=torch.int32, device=dev)
+    geom = torch.empty(l.gsr_geometry_state_bytes(P), dtype=torch.uint8, device=dev)
+    img = torch.empty(l.gsr_image_state_bytes(W, H), dtype=torch.uint8, device=dev)
+    R = check(l.gsr_forward_prepare(C.byref(s), C.byref(g), ptr(geom), geom.numel(), ptr(radii), _stream()))
+    binning = torch.empty(l.gsr_binning_state_bytes(P, W, H, R), dtype=torch.uint8, device=dev)
+    check(l.gsr_forward_render(C.byref(s), C.byref(g), ptr(geom), ptr(binning), binning.numel(), R, ptr(img),
+                               img.numel(), ptr(color), ptr(invdepth), 1, _stream()))
+    return R, color, radii, geom, binning, img, invdepth
+
+
 def rasterize_gaussians(bg, means3D, colors_precomp, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                         projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered,
                         antialiasing, debug):
@@ -368,20 +344,10 @@ def rasterize_gaussians(bg, means3D, colors_precomp, opacity, scales, rotations,
     P, H, W = int(means3D.shape[0]), int(image_height), int(image_width)
     m3, col, op, sc, ro, cov, shs = opt(means3D), opt(colors_precomp), opt(opacity), opt(scales), opt(rotations), \
         opt(cov3D_precomp), opt(sh)
-    l = lib()
     with torch.cuda.device(dev):
         s, keep = dgr._settings_struct(rs, dev)
         g = dgr._gauss_struct(P, m3, None, shs, col, op, sc, ro, cov)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        invdepth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        radii = torch.zeros(P, dtype=torch.int32, device=dev)
-        geom = torch.empty(l.gsr_geometry_state_bytes(P), dtype=torch.uint8, device=dev)
-        img = torch.empty(l.gsr_image_state_bytes(W, H), dtype=torch.uint8, device=dev)
-        R = check(l.gsr_forward_prepare(C.byref(s), C.byref(g), ptr(geom), geom.numel(), ptr(radii), _stream()))
-        binning = torch.empty(l.gsr_binning_state_bytes(P, W, H, R), dtype=torch.uint8, device=dev)
-        check(l.gsr_forward_render(C.byref(s), C.byref(g), ptr(geom), ptr(binning), binning.numel(), R, ptr(img),
-                                   img.numel(), ptr(color), ptr(invdepth), 1, _stream()))
-    return R, color, radii, geom, binning, img, invdepth
+        return _forward_on_own_buffers(s, g, P, W, H, dev)
 
 
 def rasterize_gaussians_backward(bg, means3D, radii, colors_precomp, opacities, scales, rotations, scale_modifier,

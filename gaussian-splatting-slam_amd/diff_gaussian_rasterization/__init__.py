@@ -277,30 +277,143 @@ def _stream():
     return C.c_void_p(_C.raw_stream())
 
 
+class RasterOptions(NamedTuple):
+    """The per-call extensions of one rasterizer call (GaussianRasterizer.forward documents each), as they travel from the public
+    keyword surfaces - render(), GaussianRasterizer.forward(), rasterize_gaussians() - to the autograd Function.  A new option
+    is one field here, one check in `check_options` and one use."""
+    raw_activations: bool = False
+    fold: object = None
+    sh_ready_event: object = None
+    forward_mode: object = None
+    tile_cull: object = None
+    tile_cull_apply: bool = True
+    depth: str = "inverse"
+    alpha: bool = False
+    n_touched: bool = False
+    touched_T_min: float = 0.5
+    camera_only: bool = False
+
+
+def check_options(o):
+    """Validates a RasterOptions before any device work and returns it.  (`forward_mode` and `tile_cull` are checked where the
+    device and its pool are known, camera_only's two semantic conditions where the grad state is.)"""
+    if not isinstance(o.depth, str) or o.depth not in _C.DEPTH_KINDS:
+        raise ValueError(f"depth={o.depth!r}: expected 'inverse' (sum w / z, the default) or 'z' (sum w z)")
+    if not isinstance(o.alpha, bool):
+        raise TypeError(f"alpha={o.alpha!r}: expected a bool")
+    if not isinstance(o.n_touched, bool):
+        raise TypeError(f"n_touched={o.n_touched!r}: expected a bool")
+    t = o.touched_T_min
+    if isinstance(t, bool) or not isinstance(t, (int, float)):
+        raise TypeError(f"touched_T_min={t!r}: expected a real number in [0, 1)")
+    if not 0.0 <= t < 1.0:     # (a NaN fails it too)
+        raise ValueError(f"touched_T_min={t!r}: expected a transmittance threshold in [0, 1)")
+    if not isinstance(o.camera_only, bool):
+        raise TypeError(f"camera_only={o.camera_only!r}: expected a bool")
+    return o
+
+
+def _forward_speculative(lib, pool, ws, key, frame, mode, capturing, opts):
+    """The whole frame is enqueued for the capacity its shape has shown so far.  "exact" then waits for THIS frame's count (it
+    reaches pinned memory while the binning / compositing stages are still queued, so the device keeps working) and repeats
+    phase 2 if the capacity did not hold; "async" does not wait: the count arrives in the pinned status slot and is looked at by
+    a later call (pool.poll).  -> what the binning state was laid out for"""
+    scene, geom, radii, out, split, evh, stream, ex = frame
+    P, W, H = key
+    tile_cull = opts.tile_cull
+    R = pool.capacity_for_frame(key)
+    binning = ws.ensure_binning(lib, P, W, H, R)
+    status = pool.status_slot()
+    status[2] = _ws.STATUS_PENDING     # (overwritten by the compositing kernel when the frame's status arrives)
+    status[3] = 0                      # (word 6: set by the compositing kernel if a truncated tile list was too short)
+    status_p = C.c_void_p(status.data_ptr())
+    tlo = 1 if _ws.tile_local_binning(pool, key) else 0
+    count = C.c_int64(-1)
+    rerendered = False
+    verify = mode == "exact" or key not in pool.capacity     # ("async": a shape's first frame is verified too - its capacity
+    #                                                           is a guess, not an observation)
+    if tile_cull is not None:
+        tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        if tile_cull.dtype != torch.int32 or tile_cull.numel() != tiles or tile_cull.device != radii.device \
+                or not tile_cull.is_contiguous():
+            raise _C.GsrError(f"tile_cull: expected a contiguous int32 tensor of {tiles} tiles on {radii.device} "
+                              "(diff_gaussian_rasterization.new_tile_cull)")
+    # lists truncated by depth only where a frame may flag itself afterwards: unverified, not under capture
+    cull_apply = tile_cull is not None and bool(opts.tile_cull_apply) and not verify and not capturing and tlo == 1
+    _C.check(lib.gsr_forward_async_culled_ex(*scene, _C.ptr(geom), geom.numel(), _C.ptr(radii), _C.ptr(binning),
+                                             binning.numel(), R, *out, 1 if split else 0, evh, status_p, tlo, stream,
+                                             C.byref(count) if verify else None, _C.ptr(tile_cull),
+                                             1 if cull_apply else 0, ex))
+    if cull_apply:
+        pool.stats["culled_frames"] = pool.stats.get("culled_frames", 0) + 1
+    pool.ticket += 1
+    pool.stats["tile_local_frames"] = pool.stats.get("tile_local_frames", 0) + tlo
+    if verify:
+        n = int(count.value)
+        if n > R:
+            # the frame just enqueued was composited from a truncated list: same frame again, phase 2 only, on a binning state
+            # that holds it (stream-ordered behind the first attempt, which stays inside its buffers)
+            pool.stats["rerendered_frames"] += 1
+            rerendered = True
+            R = _ws._capacity_for(n)
+            binning = ws.ensure_binning(lib, P, W, H, R)
+            _C.check(lib.gsr_forward_rerender_ex(*scene, _C.ptr(geom), _C.ptr(binning), binning.numel(), R, *out, tlo,
+                                                 status_p, stream, ex))
+        pool.note(key, n)
+    pool.stats["exact_frames" if mode == "exact" else "async_frames"] += 1
+    # a verified frame's status (only its longest tile list is still of interest) is recognised by the sentinel above being
+    # overwritten: no event on the stream (a record costs ~6 us of device time between the compositing kernel and the loss); an
+    # unverified frame's is waited for in order, behind an event
+    if capturing:
+        pool.graph_status = (status, R, key)      # the graph's owner watches it (graph_status_slot)
+    else:
+        done = None
+        if not verify or rerendered:   # (a re-rendered frame writes its status twice: wait for the last one)
+            done = torch.cuda.Event()
+            done.record()
+        pool.pending.append((done, status, R, key, pool.ticket, verify))
+    return R
+
+
+def _forward_blocking(lib, pool, ws, key, frame):
+    """Blocking read-back of num_rendered (the published rasterizer's one host synchronisation): debug mode, prefiltered=True
+    (its "culled point" error is raised by this very call), GSR_FORWARD_MODE=sync, or no Gaussians.  -> num_rendered"""
+    scene, geom, radii, out, split, evh, stream, ex = frame
+    P, W, H = key
+    prepare = lib.gsr_forward_prepare_geometry_ex if split else lib.gsr_forward_prepare_ex
+    R = _C.check(prepare(*scene, _C.ptr(geom), geom.numel(), _C.ptr(radii), stream, ex))
+    pool.note(key, R)
+    pool.stats["sync_frames"] += 1
+    binning = ws.ensure_binning(lib, P, W, H, max(R, pool.capacity[key]))
+    if split:
+        # split forward: geometry stages, emission + tile sort, THEN wait for the SH update, shade, composite
+        _C.check(lib.gsr_forward_render_shade_ex(*scene, _C.ptr(geom), _C.ptr(binning), binning.numel(), R, *out, evh, stream,
+                                                 ex))
+    else:
+        _C.check(lib.gsr_forward_render_ex(*scene, _C.ptr(geom), _C.ptr(binning), binning.numel(), R, *out, stream, ex))
+    return R
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Input order = gradient order of the reference's autograd Function, with `dc` inserted
-    before `sh` for the `separate_sh` call form (reference gaussian_renderer/__init__.py:90-99)."""
+    before `sh` for the `separate_sh` call form (reference gaussian_renderer/__init__.py:90-99): the nine tensor inputs, then
+    PLAIN_SLOTS inputs that get no gradient (raster_settings, the call's RasterOptions, for_backward), then - camera form - the
+    three camera tensors."""
+
+    PLAIN_SLOTS = 3
 
     @staticmethod
     def forward(ctx, means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                raster_settings, raw_activations=False, for_backward=True, fold=None, sh_ready_event=None, forward_mode=None,
-                tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
-                camera_only=False, viewmatrix=None, projmatrix=None, campos=None):
-        """fold: a BackwardFold for THIS call's backward (kept on ctx).  sh_ready_event: a recorded torch.cuda.Event after which
-        `dc` / `shs` hold this step's values (the view-sharded trainer's SH all-reduce + Adam update, in flight on another
-        stream): the geometry stages run first, the stream waits for the event and only then evaluates the colours
-        (gsr_forward_prepare_geometry / gsr_forward_shade).  forward_mode: "exact" | "async" | "sync" for this call (default:
-        the process-wide mode, GSR_FORWARD_MODE / set_forward_mode).  tile_cull: this VIEW's per-tile depth cut-offs
-        (`new_tile_cull`), updated by every speculative forward and applied by unverified ones (gsr_forward_async_culled).
-        viewmatrix / projmatrix / campos: raster_settings' own tensors, passed (by rasterize_gaussians) only when one of them
-        requires grad - the camera form: the backward also returns their gradients (gsr_backward_camera).  depth / alpha: the
-        depth kind of the third output and whether a fourth, the accumulated opacity, is returned (gsr_render_extras).
-        n_touched / touched_T_min: one more output, LAST, the int32 [P] visibility counts (gsr_render_extras.n_touched).
-        camera_only: (camera form) the backward returns the three camera gradients and None for every Gaussian input
-        (gsr_backward_camera_only: no per-Gaussian gradient is formed or stored, no gradient arena is allocated)."""
+                raster_settings, opts, for_backward, viewmatrix=None, projmatrix=None, campos=None):
+        """opts: the validated RasterOptions of this call (GaussianRasterizer.forward documents the fields; `fold` is kept on
+        ctx, for THIS call's backward).  for_backward: inside forward() grad mode is always off and needs_input_grad ignores an
+        outer torch.no_grad(), so whether a backward can follow is decided by the caller, _rasterize().  viewmatrix / projmatrix
+        / campos: raster_settings' own tensors, passed only when one of them requires grad - the camera form: the backward also
+        returns their gradients (gsr_backward_camera, or gsr_backward_camera_only with opts.camera_only)."""
         lib = _C.lib()
-        depth_kind = _depth_kind(depth)
-        raw_activations = bool(raw_activations) and cov3D_precomp is None
+        depth_kind = _C.DEPTH_KINDS[opts.depth]
+        alpha, n_touched = opts.alpha, opts.n_touched
+        raw_activations = bool(opts.raw_activations) and cov3D_precomp is None
         if not means3D.is_cuda:
             raise _C.GsrError("GaussianRasterizer needs tensors on the HIP device (no CPU path)")
         dev = means3D.device
@@ -311,8 +424,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         dc, sh, colors_precomp = _f32c(dc), _f32c(sh), _f32c(colors_precomp)
         opacities, scales, rotations, cov3D_precomp = _f32c(opacities), _f32c(scales), _f32c(rotations), \
             _f32c(cov3D_precomp)
-        # (inside forward() grad mode is always off and needs_input_grad ignores an outer torch.no_grad(): whether a backward
-        # can follow is decided by the caller, rasterize_gaussians(), and arrives as `for_backward`)
         needs_grad = bool(for_backward)
 
         with _C.on_device(dev):
@@ -322,7 +433,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             # (allocated from the graph's pool, never handed to eager calls) and its status slot is left to the graph's owner
             # (`graph_status_slot`): a replay rewrites it, and a count beyond the capacity means what it means in mode "async".
             capturing = torch.cuda.is_current_stream_capturing()
-            if capturing and camera_only:
+            if capturing and opts.camera_only:
                 raise _C.GsrError("camera_only=True (camera gradients) is not supported under HIP-graph capture: run this "
                                   "iteration eagerly")
             if not capturing:
@@ -340,23 +451,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             # (uninitialised on purpose: the library zeroes the counts in front of every compositing launch)
             touched = torch.empty(P, dtype=torch.int32, device=dev) if n_touched else None
             extras = _C.gsr_render_extras(depth_kind, _C.ptr(alpha_img) if alpha else None, None,
-                                          _C.ptr(touched) if n_touched and P > 0 else None, float(touched_T_min)) \
+                                          _C.ptr(touched) if n_touched and P > 0 else None, float(opts.touched_T_min)) \
                 if (depth_kind or alpha or n_touched) else None
-            ex = C.byref(extras) if extras is not None else None
             s, keep = _settings_struct(rs, dev)
             g = _gauss_struct(P, means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                               raw_activations)
             geom = ws.ensure_geom(lib, P)
             img = ws.ensure_img(lib, W, H)
-            ev = sh_ready_event
+            ev = opts.sh_ready_event
             split = ev is not None and colors_precomp is None
             if ev is not None and not split:
                 torch.cuda.current_stream().wait_event(ev)
-            evh = C.c_void_p(ev.cuda_event) if split else None
             key = (P, W, H)
-            stream = _stream()
+            # what every forward entry point takes, in the groups they take it in: (settings, Gaussians), the geometry state,
+            # radii, (image state + bytes, the two output planes, for_backward), the split forward's flag and event, stream, extras
+            frame = ((C.byref(s), C.byref(g)), geom, radii,
+                     (_C.ptr(img), img.numel(), _C.ptr(color), _C.ptr(invdepth), 1 if needs_grad else 0),
+                     split, C.c_void_p(ev.cuda_event) if split else None, _stream(),
+                     C.byref(extras) if extras is not None else None)
             try:
-                mode = _ws.forward_mode() if forward_mode is None else forward_mode
+                mode = _ws.forward_mode() if opts.forward_mode is None else opts.forward_mode
                 if mode not in _ws._MODES:
                     raise ValueError(f"forward_mode={mode!r}: expected one of {_ws._MODES}")
                 if capturing:
@@ -368,82 +482,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                                           "(and neither debug nor prefiltered)")
                     mode = "async"
                 if mode != "sync" and not rs.debug and not rs.prefiltered and P > 0:
-                    # speculative: the whole frame is enqueued for the capacity this shape has shown so far.  "exact" then
-                    # waits for THIS frame's count (it reaches pinned memory while the binning / compositing stages are still
-                    # queued, so the device keeps working) and repeats phase 2 if the capacity did not hold; "async" does not
-                    # wait: the count arrives in the pinned status slot and is looked at by a later call (pool.poll)
-                    R = pool.capacity_for_frame(key)
-                    binning = ws.ensure_binning(lib, P, W, H, R)
-                    status = pool.status_slot()
-                    status[2] = _ws.STATUS_PENDING     # (overwritten by the compositing kernel when the frame's status arrives)
-                    status[3] = 0                      # (word 6: set by the compositing kernel if a truncated tile list was too short)
-                    tlo = 1 if _ws.tile_local_binning(pool, key) else 0
-                    count = C.c_int64(-1)
-                    rerendered = False
-                    verify = mode == "exact" or key not in pool.capacity     # ("async": a shape's first frame is verified too -
-                    #                                                           its capacity is a guess, not an observation)
-                    if tile_cull is not None:
-                        tiles = ((W + 15) // 16) * ((H + 15) // 16)
-                        if tile_cull.dtype != torch.int32 or tile_cull.numel() != tiles or tile_cull.device != dev \
-                                or not tile_cull.is_contiguous():
-                            raise _C.GsrError(f"tile_cull: expected a contiguous int32 tensor of {tiles} tiles on {dev} "
-                                              "(diff_gaussian_rasterization.new_tile_cull)")
-                    # lists truncated by depth only where a frame may flag itself afterwards: unverified, not under capture
-                    cull_apply = tile_cull is not None and bool(tile_cull_apply) and not verify and not capturing and tlo == 1
-                    _C.check(lib.gsr_forward_async_culled_ex(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(),
-                                                             _C.ptr(radii), _C.ptr(binning), binning.numel(), R, _C.ptr(img),
-                                                             img.numel(), _C.ptr(color), _C.ptr(invdepth),
-                                                             1 if needs_grad else 0, 1 if split else 0, evh,
-                                                             C.c_void_p(status.data_ptr()), tlo, stream,
-                                                             C.byref(count) if verify else None, _C.ptr(tile_cull),
-                                                             1 if cull_apply else 0, ex))
-                    if cull_apply:
-                        pool.stats["culled_frames"] = pool.stats.get("culled_frames", 0) + 1
-                    pool.ticket += 1
-                    pool.stats["tile_local_frames"] = pool.stats.get("tile_local_frames", 0) + tlo
-                    if verify:
-                        n = int(count.value)
-                        if n > R:
-                            # the frame just enqueued was composited from a truncated list: same frame again, phase 2 only, on a
-                            # binning state that holds it (stream-ordered behind the first attempt, which stays inside its buffers)
-                            pool.stats["rerendered_frames"] += 1
-                            rerendered = True
-                            R = _ws._capacity_for(n)
-                            binning = ws.ensure_binning(lib, P, W, H, R)
-                            _C.check(lib.gsr_forward_rerender_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                                 binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                                 _C.ptr(invdepth), 1 if needs_grad else 0, tlo,
-                                                                 C.c_void_p(status.data_ptr()), stream, ex))
-                        pool.note(key, n)
-                    pool.stats["exact_frames" if mode == "exact" else "async_frames"] += 1
-                    # a verified frame's status (only its longest tile list is still of interest) is recognised by the
-                    # sentinel above being overwritten: no event on the stream (a record costs ~6 us of device time between the
-                    # compositing kernel and the loss); an unverified frame's is waited for in order, behind an event
-                    done = None
-                    if capturing:
-                        pool.graph_status = (status, R, key)      # the graph's owner watches it (graph_status_slot)
-                    else:
-                        if not verify or rerendered:   # (a re-rendered frame writes its status twice: wait for the last one)
-                            done = torch.cuda.Event()
-                            done.record()
-                        pool.pending.append((done, status, R, key, pool.ticket, verify))
+                    R = _forward_speculative(lib, pool, ws, key, frame, mode, capturing, opts)
                 else:
-                    # blocking read-back of num_rendered (the published rasterizer's one host synchronisation): debug mode,
-                    # prefiltered=True (its "culled point" error is raised by this very call), or GSR_FORWARD_MODE=sync
-                    prepare = lib.gsr_forward_prepare_geometry_ex if split else lib.gsr_forward_prepare_ex
-                    R = _C.check(prepare(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii), stream, ex))
-                    pool.note(key, R)
-                    pool.stats["sync_frames"] += 1
-                    binning = ws.ensure_binning(lib, P, W, H, max(R, pool.capacity[key]))
-                    if split:
-                        # split forward: geometry stages, emission + tile sort, THEN wait for the SH update, shade, composite
-                        _C.check(lib.gsr_forward_render_shade_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                                 binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                                 _C.ptr(invdepth), 1 if needs_grad else 0, evh, stream, ex))
-                    else:
-                        _C.check(lib.gsr_forward_render_ex(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning),
-                                                           binning.numel(), R, _C.ptr(img), img.numel(), _C.ptr(color),
-                                                           _C.ptr(invdepth), 1 if needs_grad else 0, stream, ex))
+                    R = _forward_blocking(lib, pool, ws, key, frame)
             except _C.GsrError:
                 if rs.debug:   # reference README.md:168-169: with --debug a failing rasterizer call dumps its inputs
                     _dump("snapshot_fw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
@@ -451,13 +492,11 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise
         ctx.raster_settings = rs
         ctx.camera = viewmatrix is not None or projmatrix is not None or campos is not None
-        ctx.camera_only = bool(camera_only)
+        ctx.camera_only = opts.camera_only
         ctx.raw_activations = raw_activations
-        ctx.depth_kind, ctx.alpha = depth_kind, bool(alpha)      # (the counts are forward only: the backward's extras never carry them)
-        ctx.fold = fold if needs_grad else None
+        ctx.depth_kind, ctx.alpha = depth_kind, alpha      # (the counts are forward only: the backward's extras never carry them)
+        ctx.fold = opts.fold if needs_grad else None
         ctx.num_rendered = R                 # what the binning state was laid out for (the count itself, or the capacity)
-        ctx.has = (dc is not None, sh is not None, colors_precomp is not None, scales is not None,
-                   cov3D_precomp is not None)
         if needs_grad:
             ctx.lease = lease                # the state buffers stay this ctx's until it dies
         else:
@@ -470,6 +509,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_invdepth, *grad_more):
+        """Four forms, one frame: folded Adam (gsr_backward_adam: no gradient but the screen-space one is materialised), camera
+        (gsr_backward_camera), camera-only (gsr_backward_camera_only: the projection backward without a single per-Gaussian
+        store - None for every Gaussian input, `means2D` included, nothing of size P x anything allocated) and plain
+        (gsr_backward).  They differ in the entry point and in what is allocated for the gradients, nothing else."""
         # (grad_more: the opacity plane's gradient if the forward returned one, then None for the non-differentiable counts)
         grad_alpha = grad_more[0] if ctx.alpha and grad_more else None
         lib = _C.lib()
@@ -477,13 +520,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ws = ctx.lease.ws
         if ws is None:
             raise _C.GsrError("the rasterizer's forward state is gone (backward called twice without retain_graph?)")
-        geom, binning, img = ws.geom, ws.binning, ws.img
         rs = ctx.raster_settings
         R = ctx.num_rendered
         dev = means3D.device
         P = int(means3D.shape[0])
         H, W = int(rs.image_height), int(rs.image_width)
-        grad_color = _f32c(grad_color) if grad_color is not None else torch.zeros(3, H, W, device=dev)
+        grad_color = _f32c(grad_color)
         if grad_color is None:
             grad_color = torch.zeros(3, H, W, device=dev)
         grad_invdepth = _f32c(grad_invdepth)
@@ -491,14 +533,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         extras = _C.gsr_render_extras(ctx.depth_kind, None, _C.ptr(grad_alpha) if grad_alpha is not None else None) \
             if (ctx.depth_kind or grad_alpha is not None) else None
         ex = C.byref(extras) if extras is not None else None
-
-        def like(t, *shape):
-            return torch.empty(*shape, dtype=torch.float32, device=dev) if t is not None else None
-
-        if ctx.camera_only:
-            return _RasterizeGaussians._backward_camera_only(ctx, grad_color, grad_invdepth, ex)
-        fold = ctx.fold
+        fold, camera, camera_only = ctx.fold, ctx.camera, ctx.camera_only     # (camera_only: camera form, no fold)
         with _C.on_device(dev):
+            if camera:
+                if torch.cuda.is_current_stream_capturing():
+                    raise _C.GsrError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) are not "
+                                      "supported under HIP-graph capture: run this backward eagerly")
+                want = ctx.needs_input_grad[-3:]
+                cam_flat = torch.zeros(16 + 16 + 3, dtype=torch.float32, device=dev)   # (P = 0: stays zero)
+                cam_parts = (cam_flat[:16], cam_flat[16:32], cam_flat[32:])
+                cam_struct = _C.gsr_camera_grads(*[t.data_ptr() if w else None for t, w in zip(cam_parts, want)])
             stats = fold.stats if (fold is not None and not fold.stats_taken) else None    # (once per request)
             skip_rest = fold is not None and fold.skip_sh_rest and dc is not None and sh is not None and colors_precomp is None
             if stats is not None and (stats[0].shape[0] != P or not all(t.is_contiguous() and t.dtype == torch.float32
@@ -507,7 +551,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             fused, split, opt = None, False, (fold.optimizer if fold is not None else None)
             # (the camera form is not folded: gsr_backward_adam returns no camera gradient - the gradients go to `.grad`)
             if P > 0 and opt is not None and not fold.optimizer_taken and ctx.raw_activations and dc is not None \
-                    and colors_precomp is None and not ctx.camera:
+                    and colors_precomp is None and not camera:
                 split = fold.split_rows and not isinstance(opt, SparseGaussianAdam)
                 # factors kept in device memory (enable_dynamic_hyperparameters): an eager backward stores this step's values
                 # in front of its kernels; under graph capture nothing is counted or stored - whoever replays the graph does
@@ -518,37 +562,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                                            rows="with_instances" if split else None, advance=not capturing)
                 if fused is not None and dynamic and not capturing:
                     _C.check(lib.gsr_adam_set_dynamic(C.byref(fused[0]), _C.ptr(opt._gsr_dynamic), _stream()))
-            d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-            if fused is None and P > 0:
+            d_means2D = None if camera_only else torch.empty(P, 3, dtype=torch.float32, device=dev)
+            d_means3D = d_opac = d_dc = d_sh = d_col = d_scales = d_rot = d_cov = None
+            if fused is None and not camera_only:
                 # ONE allocation for the gradients, geometry first: a data-parallel caller can exchange the four geometry tensors
                 # (and dc + rest) as one contiguous span - one collective instead of four (scene_utils.parallel.GradBucket) - and
                 # the dc gradient is followed by a spare row for the camera centre of the sh_rank1 exchange (dc_grad_tail_row)
+                # (P = 0: empty tensors of the same shapes)
                 d_means3D, d_opac, d_scales, d_rot, d_dc, d_sh, d_col, d_cov = _grad_arena(dev, (
                     ((P, 3), 0), (tuple(opacities.shape) if opacities is not None else (P, 1), 0),
                     ((P, 3) if scales is not None else None, 0), ((P, 4) if rotations is not None else None, 0),
                     (tuple(dc.shape) if dc is not None else None, 3),
                     (tuple(sh.shape) if sh is not None and not skip_rest else None, 0),
                     ((P, 3) if colors_precomp is not None else None, 0), ((P, 6) if cov3D_precomp is not None else None, 0)))
-            elif fused is None:
-                d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-                d_opac = torch.empty(opacities.shape if opacities is not None else (P, 1), dtype=torch.float32, device=dev)
-                d_dc = like(dc, *(dc.shape if dc is not None else ()))
-                d_sh = None if skip_rest else like(sh, *(sh.shape if sh is not None else ()))
-                d_col = like(colors_precomp, P, 3)
-                d_scales = like(scales, P, 3)
-                d_rot = like(rotations, P, 4)
-                d_cov = like(cov3D_precomp, P, 6)
-            else:       # the optimizer step rides in the backward: no gradient but the screen-space one is materialised
-                d_means3D = d_opac = d_dc = d_sh = d_col = d_scales = d_rot = d_cov = None
-            cam_grads = (None, None, None)
-            if ctx.camera:
-                if torch.cuda.is_current_stream_capturing():
-                    raise _C.GsrError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) are not "
-                                      "supported under HIP-graph capture: run this backward eagerly")
-                want = ctx.needs_input_grad[-3:]
-                cam_flat = torch.zeros(16 + 16 + 3, dtype=torch.float32, device=dev)   # (P = 0: stays zero)
-                cam_parts = (cam_flat[:16], cam_flat[16:32], cam_flat[32:])
-                cam_struct = _C.gsr_camera_grads(*[t.data_ptr() if w else None for t, w in zip(cam_parts, want)])
             if P > 0:
                 cur = _C.raw_stream()
                 if ws.stream is not None and ws.stream != cur:
@@ -560,6 +586,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 gr = _C.gsr_grads(*[None if t is None else t.data_ptr() for t in
                                     (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov) +
                                     (stats if stats is not None else (None, None, None))])
+                # what every backward entry point starts with
+                head = (C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(ws.geom), _C.ptr(ws.binning), _C.ptr(ws.img), R,
+                        _C.ptr(grad_color), _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel())
                 try:
                     if fused is not None:
                         fold.optimizer_taken = True          # (a second backward through a retained graph must not step again)
@@ -572,25 +601,20 @@ class _RasterizeGaussians(torch.autograd.Function):
                                 side = _side_streams[dev.index] = torch.cuda.Stream(device=dev)
                             side.wait_stream(torch.cuda.current_stream())
                             with torch.cuda.stream(side):
-                                _C.check(lib.gsr_adam_step_culled_rows(C.byref(g), _C.ptr(geom), R, C.byref(fused[0]),
+                                _C.check(lib.gsr_adam_step_culled_rows(C.byref(g), _C.ptr(ws.geom), R, C.byref(fused[0]),
                                                                        _stream()))
-                        _C.check(lib.gsr_backward_adam_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
-                                                          _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
-                                                          _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(), C.byref(gr),
-                                                          C.byref(fused[0]), _stream(), ex))
+                        _C.check(lib.gsr_backward_adam_ex(*head, C.byref(gr), C.byref(fused[0]), _stream(), ex))
                         if split:
                             torch.cuda.current_stream().wait_stream(side)   # what follows here sees both halves of the update
-                    elif ctx.camera:
+                    elif camera:
                         cam_scratch = torch.empty(lib.gsr_camera_grad_scratch_bytes(P), dtype=torch.uint8, device=dev)
-                        _C.check(lib.gsr_backward_camera_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom),
-                                                            _C.ptr(binning), _C.ptr(img), R, _C.ptr(grad_color),
-                                                            _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(),
-                                                            C.byref(gr), C.byref(cam_struct), _C.ptr(cam_scratch),
-                                                            cam_scratch.numel(), _stream(), ex))
+                        tail = (C.byref(cam_struct), _C.ptr(cam_scratch), cam_scratch.numel(), _stream(), ex)
+                        if camera_only:
+                            _C.check(lib.gsr_backward_camera_only_ex(*head, *tail))
+                        else:
+                            _C.check(lib.gsr_backward_camera_ex(*head, C.byref(gr), *tail))
                     else:
-                        _C.check(lib.gsr_backward_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(geom), _C.ptr(binning),
-                                                     _C.ptr(img), R, _C.ptr(grad_color), _C.ptr(grad_invdepth),
-                                                     _C.ptr(scratch), scratch.numel(), C.byref(gr), _stream(), ex))
+                        _C.check(lib.gsr_backward_ex(*head, C.byref(gr), _stream(), ex))
                 except _C.GsrError:
                     if rs.debug:
                         _dump("snapshot_bw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
@@ -600,109 +624,46 @@ class _RasterizeGaussians(torch.autograd.Function):
             if fold is not None:
                 fold.stats_taken = fold.stats_taken or stats is not None      # (P == 0: no rows, nothing to add)
                 fold.sh_rest_skipped = bool(skip_rest)
-            if ctx.camera:
+            cam_grads = ()
+            if camera:
                 # each gradient with its input's shape, dtype and device
                 cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
                                   for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
-        return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None, None, None, None, None, None,
-                None, None, None, None, None, None) + (cam_grads if ctx.camera else ())
-
-    @staticmethod
-    def _backward_camera_only(ctx, grad_color, grad_invdepth, ex):
-        """backward() of a camera_only=True call: the compositing backward, then gsr_backward_camera_only - the projection backward
-        without a single per-Gaussian store - and the fixed-order reduction.  Returns None for every Gaussian input, `means2D`
-        included; allocates the 35 floats of the camera gradients and the reduction's scratch, nothing of size P x anything."""
-        lib = _C.lib()
-        (means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii) = ctx.saved_tensors
-        ws = ctx.lease.ws
-        rs = ctx.raster_settings
-        R = ctx.num_rendered
-        dev = means3D.device
-        P = int(means3D.shape[0])
-        with _C.on_device(dev):
-            if torch.cuda.is_current_stream_capturing():
-                raise _C.GsrError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) are not "
-                                  "supported under HIP-graph capture: run this backward eagerly")
-            want = ctx.needs_input_grad[-3:]
-            cam_flat = torch.zeros(16 + 16 + 3, dtype=torch.float32, device=dev)   # (P = 0: stays zero)
-            cam_parts = (cam_flat[:16], cam_flat[16:32], cam_flat[32:])
-            cam_struct = _C.gsr_camera_grads(*[t.data_ptr() if w else None for t, w in zip(cam_parts, want)])
-            if P > 0:
-                cur = _C.raw_stream()
-                if ws.stream is not None and ws.stream != cur:
-                    torch.cuda.current_stream().wait_stream(torch.cuda.ExternalStream(ws.stream))
-                s, keep = _settings_struct(rs, dev)
-                g = _gauss_struct(P, means3D, dc, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                  ctx.raw_activations)
-                scratch = ws.ensure_scratch(lib, P, R)
-                cam_scratch = torch.empty(lib.gsr_camera_grad_scratch_bytes(P), dtype=torch.uint8, device=dev)
-                try:
-                    _C.check(lib.gsr_backward_camera_only_ex(C.byref(s), C.byref(g), _C.ptr(radii), _C.ptr(ws.geom),
-                                                             _C.ptr(ws.binning), _C.ptr(ws.img), R, _C.ptr(grad_color),
-                                                             _C.ptr(grad_invdepth), _C.ptr(scratch), scratch.numel(),
-                                                             C.byref(cam_struct), _C.ptr(cam_scratch), cam_scratch.numel(),
-                                                             _stream(), ex))
-                except _C.GsrError:
-                    if rs.debug:
-                        _dump("snapshot_bw.dump", rs, means3D, dc, sh, colors_precomp, opacities, scales, rotations,
-                              cov3D_precomp, grad_color, grad_invdepth, radii)
-                    raise
-                ws.stream = cur
-            cam_grads = tuple(None if not w or t is None else part.reshape(t.shape).to(dtype=t.dtype, device=t.device)
-                              for part, t, w in zip(cam_parts, (rs.viewmatrix, rs.projmatrix, rs.campos), want))
-        return (None,) * 22 + cam_grads
+        return (d_means3D, d_means2D, d_dc, d_sh, d_col, d_opac, d_scales, d_rot, d_cov) + \
+            (None,) * _RasterizeGaussians.PLAIN_SLOTS + cam_grads
 
 
-def _depth_kind(depth):
-    """gsr_render_extras.depth_kind of a `depth=` argument; raises for anything but "inverse" / "z"."""
-    kind = _C.DEPTH_KINDS.get(depth) if isinstance(depth, str) else None
-    if kind is None:
-        raise ValueError(f"depth={depth!r}: expected 'inverse' (sum w / z, the default) or 'z' (sum w z)")
-    return kind
-
-
-def _check_touched(n_touched, touched_T_min):
-    """Validates the `n_touched=` / `touched_T_min=` arguments (before any device work)."""
-    if not isinstance(n_touched, bool):
-        raise TypeError(f"n_touched={n_touched!r}: expected a bool")
-    if isinstance(touched_T_min, bool) or not isinstance(touched_T_min, (int, float)):
-        raise TypeError(f"touched_T_min={touched_T_min!r}: expected a real number in [0, 1)")
-    if not 0.0 <= float(touched_T_min) < 1.0:     # (a NaN fails it too)
-        raise ValueError(f"touched_T_min={touched_T_min!r}: expected a transmittance threshold in [0, 1)")
-
-
-def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, raw_activations=False, fold=None, sh_ready_event=None, forward_mode=None,
-                        tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False,
-                        touched_T_min=0.5, camera_only=False):
-    # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
-    # what only a backward would need
-    _depth_kind(depth)                   # (validated before any device work)
-    if not isinstance(alpha, bool):
-        raise TypeError(f"alpha={alpha!r}: expected a bool")
-    _check_touched(n_touched, touched_T_min)
+def _rasterize(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, opts):
+    """The call behind every public surface; `opts`: a RasterOptions that has passed check_options."""
     tensors = (means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
     rs = raster_settings
     # camera form: the settings' viewmatrix / projmatrix / campos take part in autograd when one of them requires grad (pose
     # refinement / tracking, also with every Gaussian tensor frozen); they then travel as trailing inputs of the Function
     camera = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad
                                              for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
-    if not isinstance(camera_only, bool):
-        raise TypeError(f"camera_only={camera_only!r}: expected a bool")
-    if camera_only:
+    if opts.camera_only:
         # asked for, never inferred: render() always passes a means2D that requires grad.  Before any launch:
         if not camera:
             raise _C.GsrError("camera_only=True needs the camera form: none of the settings' viewmatrix / projmatrix / campos "
                               "requires grad (or grad mode is off)")
-        if fold is not None:
+        if opts.fold is not None:
             raise _C.GsrError("camera_only=True returns no per-Gaussian gradient: a BackwardFold (optimizer step / "
                               "densification statistics in the backward) cannot be combined with it")
+    # forward-only render (torch.no_grad(), reference render.py:49, or no input that requires grad): the library then skips
+    # what only a backward would need
     for_backward = camera or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors))
     extra = (rs.viewmatrix, rs.projmatrix, rs.campos) if camera else ()
-    return _RasterizeGaussians.apply(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, raw_activations, for_backward, fold, sh_ready_event,
-                                     forward_mode, tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min,
-                                     camera_only, *extra)
+    return _RasterizeGaussians.apply(*tensors, raster_settings, opts, for_backward, *extra)
+
+
+def rasterize_gaussians(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                        raster_settings, raw_activations=False, fold=None, sh_ready_event=None, forward_mode=None,
+                        tile_cull=None, tile_cull_apply=True, depth="inverse", alpha=False, n_touched=False,
+                        touched_T_min=0.5, camera_only=False):
+    opts = check_options(RasterOptions(raw_activations, fold, sh_ready_event, forward_mode, tile_cull, tile_cull_apply, depth,
+                                       alpha, n_touched, touched_T_min, camera_only))
+    return _rasterize(means3D, means2D, dc, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                      opts)
 
 
 def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -720,15 +681,7 @@ def pair_evaluations(raster_settings, means3D, opacities, shs=None, colors_preco
     with torch.no_grad(), torch.cuda.device(dev):
         s, keep = _settings_struct(rs, dev)
         g = _gauss_struct(P, *t, raw_activations and cov3D_precomp is None)
-        geom = torch.empty(lib.gsr_geometry_state_bytes(P), dtype=torch.uint8, device=dev)
-        img = torch.empty(lib.gsr_image_state_bytes(W, H), dtype=torch.uint8, device=dev)
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        color = torch.empty(3, H, W, device=dev)
-        invd = torch.empty(1, H, W, device=dev)
-        R = _C.check(lib.gsr_forward_prepare(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii), _stream()))
-        binning = torch.empty(lib.gsr_binning_state_bytes(P, W, H, R), dtype=torch.uint8, device=dev)
-        _C.check(lib.gsr_forward_render(C.byref(s), C.byref(g), _C.ptr(geom), _C.ptr(binning), binning.numel(), R,
-                                        _C.ptr(img), img.numel(), _C.ptr(color), _C.ptr(invd), 1, _stream()))
+        R, _, _, geom, binning, img, _ = _C._forward_on_own_buffers(s, g, P, W, H, dev)
         pairs = torch.zeros(2 * H * W, dtype=torch.int32, device=dev)
         _C.check(lib.gsr_debug_count_pairs(C.byref(s), P, _C.ptr(geom), _C.ptr(binning), R, _C.ptr(pairs), _stream()))
         pT, pN = C.c_void_p(), C.c_void_p()
@@ -767,7 +720,11 @@ class GaussianRasterizer(nn.Module):
         (nothing is armed process-wide): `raw_activations=True`: `opacities`, `scales`, `rotations` are the model's RAW
         parameters; sigmoid / exp / normalize are applied inside the projection kernel and the returned gradients are w.r.t. the
         raw parameters.  `fold`: a BackwardFold (optimizer step / densification statistics / skipped dL/dsh_rest in this call's
-        backward).  `sh_ready_event`: colours wait for this event.  `forward_mode`: "exact" | "async" | "sync" for this call.
+        backward).  `sh_ready_event`: a recorded torch.cuda.Event after which `dc` / `shs` hold this step's values (the
+        view-sharded trainer's SH all-reduce + Adam update, in flight on another stream): the geometry stages run first, the
+        stream waits for the event and only then evaluates the colours (gsr_forward_prepare_geometry / gsr_forward_shade).
+        `forward_mode`: "exact" | "async" | "sync" for this call (default: the process-wide mode, GSR_FORWARD_MODE /
+        set_forward_mode).
         `tile_cull`: `new_tile_cull(...)` tensor of the VIEW being rendered (one per camera of a training set): tile lists
         truncated by the depth each tile saturated at when the view was last rendered (include/gsr.h gsr_forward_async_culled);
         `tile_cull_apply=False`: only keep the cut-offs up to date in this call.  `depth`: what the third output holds -
@@ -784,9 +741,13 @@ class GaussianRasterizer(nn.Module):
         projmatrix / campos requires grad, GsrError otherwise - and its backward returns those gradients alone, bit for bit the
         ones of the full camera form: every Gaussian input, `means2D` included, gets None, no per-Gaussian gradient is formed
         or stored (gsr_backward_camera_only) and no gradient arena is allocated.  Not with `fold`, not under capture."""
-        _depth_kind(depth)
-        if not isinstance(alpha, bool):
-            raise TypeError(f"alpha={alpha!r}: expected a bool")
+        return self.forward_with(check_options(RasterOptions(
+            raw_activations, fold, sh_ready_event, forward_mode, tile_cull, tile_cull_apply, depth, alpha, n_touched,
+            touched_T_min, camera_only)), means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
+
+    def forward_with(self, opts, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                     cov3D_precomp=None, dc=None):
+        """forward() with the extensions as one RasterOptions that has passed check_options (what render() calls)."""
         def none_if_empty(t):
             return None if (t is None or t.numel() == 0) else t
         shs, colors_precomp, dc = none_if_empty(shs), none_if_empty(colors_precomp), none_if_empty(dc)
@@ -799,9 +760,8 @@ class GaussianRasterizer(nn.Module):
             if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                     ((scales is not None or rotations is not None) and cov3D_precomp is not None):
                 raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self.raster_settings, raw_activations, fold, sh_ready_event, forward_mode,
-                                   tile_cull, tile_cull_apply, depth, alpha, n_touched, touched_T_min, camera_only)
+        return _rasterize(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                          self.raster_settings, opts)
 
 
 from .sparse_adam import SparseGaussianAdam, FusedAdam  # noqa: E402,F401   (reference train.py:37-41)

@@ -7,7 +7,7 @@ import math
 
 import torch
 
-from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, RasterOptions, check_options
 from scene_utils.sh import eval_sh
 
 
@@ -65,27 +65,16 @@ def _screenspace_zeros(like):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, separate_sh=False,
            override_color=None, use_trained_exp=False, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
            **rasterizer_kw):
-    """`rasterizer_kw`: per-call extensions of this rasterizer, forwarded to `GaussianRasterizer.forward` (`fold`, `sh_ready_event`,
+    """`rasterizer_kw`: per-call extensions of this rasterizer, the keywords of `GaussianRasterizer.forward` (`fold`, `sh_ready_event`,
     `forward_mode`, `camera_only` - tracking against a frozen map: the backward returns the camera's gradients alone);
     none given = the reference's call forms, unchanged.  `depth="z"`: the `"depth"` key holds the view-space
     z-depth sum_i w_i z_i instead of the inverse depth; `alpha=True`: the package gains `"alpha"`, the accumulated opacity
     1 - T_final [1,H,W] - both from the same single rasterization, both differentiable.  `n_touched=True`: the package gains
     `"n_touched"`, int32 [P]: for every Gaussian the number of pixels that blend it while their transmittance before it is
     > `touched_T_min` (GaussianRasterizer.forward; scene_utils.keyframes turns it into keyframe and pruning decisions)."""
-    if depth not in ("inverse", "z"):         # (before any device work)
-        raise ValueError(f"depth={depth!r}: expected 'inverse' or 'z'")
-    if not isinstance(alpha, bool):
-        raise TypeError(f"alpha={alpha!r}: expected a bool")
-    if depth != "inverse" or alpha:
-        rasterizer_kw = dict(rasterizer_kw, depth=depth, alpha=alpha)
-    if not isinstance(n_touched, bool):
-        raise TypeError(f"n_touched={n_touched!r}: expected a bool")
-    if isinstance(touched_T_min, bool) or not isinstance(touched_T_min, (int, float)):
-        raise TypeError(f"touched_T_min={touched_T_min!r}: expected a real number in [0, 1)")
-    if not 0.0 <= touched_T_min < 1.0:        # (a NaN fails it too)
-        raise ValueError(f"touched_T_min={touched_T_min!r}: expected a transmittance threshold in [0, 1)")
-    if n_touched:
-        rasterizer_kw = dict(rasterizer_kw, n_touched=True, touched_T_min=touched_T_min)
+    # (validated here, once, before any device work: neither the model nor the camera is touched for a bad option)
+    opts = check_options(RasterOptions(depth=depth, alpha=alpha, n_touched=n_touched, touched_T_min=touched_T_min,
+                                       **rasterizer_kw))
     # zero tensor that receives the screen-space (NDC) gradient of the 2-D means (reference :26-30)
     # (a leaf here: its .grad is what the callers read; the reference's `+ 0` / retain_grad() pair gives the same .grad at
     # the price of one more launch per step)
@@ -144,16 +133,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
-    if separate_sh:
-        out = rasterizer(
-            means3D=means3D, means2D=means2D, dc=dc, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **({"raw_activations": True} if use_raw else {}),
-            **rasterizer_kw)
-    else:
-        out = rasterizer(
-            means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
-            scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **({"raw_activations": True} if use_raw else {}),
-            **rasterizer_kw)
+    # (dc is None unless separate_sh: the reference's two call forms are one here)
+    out = rasterizer.forward_with(opts._replace(raw_activations=True) if use_raw else opts, means3D, means2D, opacity, shs,
+                                  colors_precomp, scales, rotations, cov3D_precomp, dc)
     rendered_image, radii, depth_image = out[:3]
 
     if use_trained_exp:
