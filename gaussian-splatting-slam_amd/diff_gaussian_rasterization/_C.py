@@ -61,6 +61,15 @@ POSE_ADAM_WORDS = 18
 POSE_ADAM_LR, POSE_ADAM_BETA1, POSE_ADAM_BETA2, POSE_ADAM_EPS, POSE_ADAM_LR_DECAY, POSE_ADAM_STEP = 12, 13, 14, 15, 16, 17
 
 
+class gsr_exposure_adam(C.Structure):
+    # header of the exposure optimizer's DEVICE state: float exp_avg[12 V] and float exp_avg_sq[12 V] follow it
+    # (scene_utils.exposure keeps the whole state as one float32 tensor of EXPOSURE_ADAM_HEADER_FLOATS + 24 V words)
+    _fields_ = [("step", C.c_int64), ("reserved", C.c_int64)]
+
+
+EXPOSURE_ADAM_HEADER_FLOATS = 4
+
+
 class gsr_render_extras(C.Structure):
     # (ctypes zero-fills fields that are not given: three positional values leave n_touched NULL and touched_T_min 0)
     _fields_ = [("depth_kind", C.c_int32), ("out_alpha", C.c_void_p), ("dL_dalpha", C.c_void_p),
@@ -175,6 +184,11 @@ EXPORTS = {
                                                                                            C.c_size_t, C.c_void_p]),
     "gsr_pose_forward": (C.c_int, [C.c_void_p] * 7),
     "gsr_pose_backward": (C.c_int, [C.c_void_p] * 9),
+    "gsr_exposure_blocks": (C.c_int32, []),
+    "gsr_exposure_forward": (C.c_int, [C.c_int64] + [C.c_void_p] * 5),
+    # n, image, exposure, mask, dL_dout, dL_dimage, partials, dL_dexposure, exposures, views, row, adam, lr, beta1, beta2, eps, stream
+    "gsr_exposure_backward": (C.c_int, [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p] + [C.c_double] * 4 +
+                              [C.c_void_p]),
     "gsr_profile_enable": (None, [C.c_int32]),
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

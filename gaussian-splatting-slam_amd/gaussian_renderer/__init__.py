@@ -64,14 +64,17 @@ def _screenspace_zeros(like):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, separate_sh=False,
            override_color=None, use_trained_exp=False, depth="inverse", alpha=False, n_touched=False, touched_T_min=0.5,
-           **rasterizer_kw):
+           alpha_mask=None, **rasterizer_kw):
     """`rasterizer_kw`: per-call extensions of this rasterizer, the keywords of `GaussianRasterizer.forward` (`fold`, `sh_ready_event`,
     `forward_mode`, `camera_only` - tracking against a frozen map: the backward returns the camera's gradients alone);
     none given = the reference's call forms, unchanged.  `depth="z"`: the `"depth"` key holds the view-space
     z-depth sum_i w_i z_i instead of the inverse depth; `alpha=True`: the package gains `"alpha"`, the accumulated opacity
     1 - T_final [1,H,W] - both from the same single rasterization, both differentiable.  `n_touched=True`: the package gains
     `"n_touched"`, int32 [P]: for every Gaussian the number of pixels that blend it while their transmittance before it is
-    > `touched_T_min` (GaussianRasterizer.forward; scene_utils.keyframes turns it into keyframe and pruning decisions)."""
+    > `touched_T_min` (GaussianRasterizer.forward; scene_utils.keyframes turns it into keyframe and pruning decisions).
+    `alpha_mask` ([1,H,W] or [H,W] float32, the camera's mask of train.py:109-111): `"render"` is multiplied by it, in the same
+    launch as the `use_trained_exp` exposure (scene_utils.exposure; with `use_trained_exp=False` the exposure is the identity).
+    The mask is not differentiated."""
     # (validated here, once, before any device work: neither the model nor the camera is touched for a bad option)
     opts = check_options(RasterOptions(depth=depth, alpha=alpha, n_touched=n_touched, touched_T_min=touched_T_min,
                                        **rasterizer_kw))
@@ -138,10 +141,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
                                   colors_precomp, scales, rotations, cov3D_precomp, dc)
     rendered_image, radii, depth_image = out[:3]
 
-    if use_trained_exp:
-        exposure = pc.get_exposure_from_name(viewpoint_camera.image_name)
-        rendered_image = torch.matmul(rendered_image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + \
-            exposure[:3, 3, None, None]
+    if use_trained_exp or alpha_mask is not None:
+        # (reference :141-144 and the alpha-mask multiply of train.py:109-111: one HIP launch, csrc/exposure.hip)
+        from scene_utils.exposure import render_exposure
+        rendered_image = render_exposure(rendered_image, pc, viewpoint_camera, use_trained_exp, alpha_mask)
 
     pkg = RenderPackage({"render": rendered_image,
                          "viewspace_points": screenspace_points,

@@ -12,3 +12,4 @@ from .io import save_ply, load_ply, read_ply_vertices, capture, restore
 from .pose import se3_exp, PoseCamera, refine_pose, pose_error, DevicePoseCamera, track_pose
 from .mapping import unproject_rgbd, create_from_pcd, add_from_rgbd
 from .keyframes import covisibility, KeyframeWindow, prune_unobserved
+from .exposure import apply_exposure

@@ -30,6 +30,8 @@ class GaussianModel:
         self._scaling = self._rotation = self._opacity = None
         self._exposure = None
         self.exposure_mapping = {}
+        self.exposure_optimizer = None
+        self._exposure_adam = None   # device Adam state while fold_exposure_adam() is armed (scene_utils.exposure)
         self._resize_hooks = []      # called with "before" / "after" around a row insertion / removal from outside a training step (mapping.add_from_rgbd, prune_points)
 
     @classmethod

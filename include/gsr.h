@@ -40,6 +40,7 @@ extern "C" {
  *    gsr_unproject_workspace_bytes (RGB-D keyframe -> points): the mapping half;
  *    gsr_render_extras.n_touched / touched_T_min (trailing fields; zero = as before): per-Gaussian visibility counts;
  *    gsr_backward_camera_only (+ _ex), gsr_pose_adam, gsr_pose_forward, gsr_pose_backward: pose tracking on the device;
+ *    gsr_exposure_adam, gsr_exposure_blocks, gsr_exposure_forward, gsr_exposure_backward: per-view exposure and alpha mask;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -603,6 +604,32 @@ int gsr_pose_forward(const double* base_w2c, const double* tau, const double* pr
                      float* campos, void* stream);
 int gsr_pose_backward(const double* base_w2c, double* tau, const double* proj_T, const float* dL_dviewmatrix,
                       const float* dL_dprojmatrix, const float* dL_dcampos, double* dL_dtau, gsr_pose_adam* adam, void* stream);
+
+/* ---- per-view exposure: the affine colour correction of a training view and its alpha mask ---- */
+
+/* out[j,p] = m[p] ( sum_k E[k][j] I[k,p] + E[j][3] ): `image` / `out` [3,n] planar (n = H W), `exposure` E [3,4] row-major in
+ * DEVICE memory, `mask` [n] or NULL (= 1).  The index convention is the reference's (gaussian_renderer/__init__.py:141-144: the
+ * 3x3 part multiplies the pixel from the right, the bias of channel j is E[j][3]) times the alpha mask of train.py:109-111.  One
+ * elementwise launch; 16-byte accesses when n % 4 == 0 and every tensor is 16-byte aligned, 4-byte accesses otherwise.
+ * gsr_exposure_backward: dL_dimage[k,p] = m[p] sum_j E[k][j] dL_dout[j,p] (NULL: not formed) and, when `dL_dexposure` or `adam`
+ * is given, the twelve sums dE[k][j] = sum_p m I[k] g[j], dE[j][3] = sum_p m g[j] ([3,4] row-major): per-workgroup partial sums
+ * in `partials` (12 gsr_exposure_blocks() floats of scratch), added by one workgroup in index order - no float atomics, bitwise
+ * reproducible.  `dL_dexposure` [12] may be NULL when `adam` is given.
+ * adam: NULL, or a gsr_exposure_adam in DEVICE memory: this header followed by float exp_avg[12 views] and float
+ * exp_avg_sq[12 views].  The finalize launch then applies one torch.optim.Adam step (bias correction from the stored step count,
+ * no weight decay, no amsgrad) IN PLACE to all of `exposures` [views,3,4] - of which `exposure` is row `row` - with the twelve
+ * sums as the gradient of row `row` and zero for every other row (their moments decay and keep moving them, as under a dense
+ * optimizer), and increments the stored step; lr, beta1, beta2 and eps are this step's hyper-parameters (ignored without `adam`).
+ * Nothing is read back by the host in either direction. */
+typedef struct gsr_exposure_adam {
+  int64_t step;     /* steps taken so far */
+  int64_t reserved; /* zero; keeps the moments that follow 16-byte aligned */
+} gsr_exposure_adam;
+int32_t gsr_exposure_blocks(void);
+int gsr_exposure_forward(int64_t n, const float* image, const float* exposure, const float* mask, float* out, void* stream);
+int gsr_exposure_backward(int64_t n, const float* image, const float* exposure, const float* mask, const float* dL_dout,
+                          float* dL_dimage, float* partials, float* dL_dexposure, float* exposures, int32_t views, int32_t row,
+                          gsr_exposure_adam* adam, double lr, double beta1, double beta2, double eps, void* stream);
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py's roofline block).  A measurement aid, process-
  * global and meant for ONE host thread driving the library at a time: enabling it while several host threads launch
