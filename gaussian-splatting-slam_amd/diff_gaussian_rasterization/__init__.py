@@ -148,9 +148,7 @@ def _fused_adam_struct(opt, tensors, advance=True, rows=None):
         fa.lr[i] = float(groups[n]["lr"])
         fa.step[i] = (int(st["step"]) + (0 if advance else 1)) if not sparse else 1
         keep.append(st)
-    g0 = opt.param_groups[0]
-    b1, b2 = (0.9, 0.999) if sparse else g0["betas"]
-    fa.beta1, fa.beta2, fa.eps = float(b1), float(b2), float(g0["eps"])
+    fa.beta1, fa.beta2, fa.eps = launch_scalars(opt)      # (refuses groups that disagree, like the optimizers' own step())
     fa.sparse = 1 if sparse else (2 if rows == "with_instances" else 0)
     dyn = getattr(opt, "_gsr_dynamic", None)
     fa.dynamic = dyn.data_ptr() if dyn is not None else None
@@ -764,4 +762,4 @@ class GaussianRasterizer(nn.Module):
                           self.raster_settings, opts)
 
 
-from .sparse_adam import SparseGaussianAdam, FusedAdam  # noqa: E402,F401   (reference train.py:37-41)
+from .sparse_adam import SparseGaussianAdam, FusedAdam, launch_scalars  # noqa: E402,F401   (reference train.py:37-41)

@@ -22,6 +22,25 @@ def _arrays(tensors_p, tensors_g, tensors_m, tensors_v, lrs):
     return n, vp, vg, vm, vv, num, lr
 
 
+def launch_scalars(opt):
+    """(beta1, beta2, eps) of `opt` as the kernels take them: ONE value each per launch, for every tensor in it.  A group whose
+    betas or eps differ from group 0's cannot be honoured, and the sparse kernel is the reference's accelerated update with its
+    fixed betas: both are refused here, on the host, before anything is enqueued."""
+    groups = opt.param_groups
+    g0 = groups[0]
+    betas, eps = g0["betas"], g0["eps"]
+    for g in groups:        # (runs once per training step on the folded path: groups built from the defaults share one tuple)
+        if (g["betas"] is not betas and tuple(g["betas"]) != tuple(betas)) or g["eps"] != eps:
+            i = next(k for k, x in enumerate(groups) if x is g)
+            raise _C.GsrError(f"HIP Adam: parameter group {i} ({g.get('name', 'unnamed')!r}) has betas={tuple(g['betas'])}, "
+                              f"eps={g['eps']} but group 0 has betas={tuple(betas)}, eps={eps}: one launch carries one value of each")
+    b1, b2 = betas
+    if isinstance(opt, SparseGaussianAdam) and (b1 != 0.9 or b2 != 0.999):
+        raise _C.GsrError(f"SparseGaussianAdam: parameter group 0 ({g0.get('name', 'unnamed')!r}) has betas={(b1, b2)}; "
+                          "the sparse update is defined for betas=(0.9, 0.999) only")
+    return float(b1), float(b2), float(eps)
+
+
 class _GsrAdamBase(torch.optim.Adam):
     def init_state(self):
         """Create the moments of every parameter now (on the current stream) instead of lazily at the first step."""
@@ -60,11 +79,10 @@ class FusedAdam(_GsrAdamBase):
 
     @torch.no_grad()
     def step(self, only=None):
+        b1, b2, eps = launch_scalars(self)
         ps, gs, ms, vs, lrs, states = self._collect(only)
         if not ps:
             return
-        g0 = self.param_groups[0]
-        b1, b2 = g0["betas"]
         lib = _C.lib()
         for i in range(0, len(ps), 8):
             sl = slice(i, i + 8)
@@ -73,8 +91,7 @@ class FusedAdam(_GsrAdamBase):
             n, vp, vg, vm, vv, num, lr = _arrays(ps[sl], gs[sl], ms[sl], vs[sl], lrs[sl])
             steps = (C.c_int64 * n)(*[int(st["step"]) for st in states[sl]])
             with _C.on_device(ps[0].device):
-                _C.check(lib.gsr_adam_step(n, vp, vg, vm, vv, num, lr, steps, float(b1), float(b2), float(g0["eps"]),
-                                           _C._stream()))
+                _C.check(lib.gsr_adam_step(n, vp, vg, vm, vv, num, lr, steps, b1, b2, eps, _C._stream()))
 
 
 class SparseGaussianAdam(_GsrAdamBase):
@@ -83,15 +100,15 @@ class SparseGaussianAdam(_GsrAdamBase):
 
     @torch.no_grad()
     def step(self, visibility, N, only=None):
+        b1, b2, eps = launch_scalars(self)
         ps, gs, ms, vs, lrs, states = self._collect(only)
         if not ps:
             return
         vis = visibility.to(torch.uint8).contiguous()
-        g0 = self.param_groups[0]
         lib = _C.lib()
         for i in range(0, len(ps), 8):
             sl = slice(i, i + 8)
             n, vp, vg, vm, vv, num, lr = _arrays(ps[sl], gs[sl], ms[sl], vs[sl], lrs[sl])
             with _C.on_device(ps[0].device):
-                _C.check(lib.gsr_sparse_adam_step(n, vp, vg, vm, vv, num, lr, int(N), _C.ptr(vis), 0.9, 0.999,
-                                                  float(g0["eps"]), _C._stream()))
+                _C.check(lib.gsr_sparse_adam_step(n, vp, vg, vm, vv, num, lr, int(N), _C.ptr(vis), b1, b2, eps,
+                                                  _C._stream()))

@@ -148,6 +148,7 @@ class GradBucket:
 def _fused_sh_adam_args(optimizer, f_dc, f_rest):
     """gsr_fused_adam for the f_dc / f_rest groups of a dense FusedAdam (their step counters advance), or None."""
     from diff_gaussian_rasterization import _C, FusedAdam
+    from diff_gaussian_rasterization.sparse_adam import launch_scalars
     if not isinstance(optimizer, FusedAdam):
         return None
     groups = {g.get("name"): g for g in optimizer.param_groups}
@@ -172,8 +173,7 @@ def _fused_sh_adam_args(optimizer, f_dc, f_rest):
         fa.exp_avg_sq[i] = st["exp_avg_sq"].data_ptr() if p.numel() else None
         fa.lr[i] = float(groups[name]["lr"])
         fa.step[i] = int(st["step"])
-    g0 = optimizer.param_groups[0]
-    fa.beta1, fa.beta2, fa.eps = float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"])
+    fa.beta1, fa.beta2, fa.eps = launch_scalars(optimizer)
     fa.sparse = 0
     return fa, keep
 

@@ -1,7 +1,10 @@
 """GPU parity of the two callers of the hot path that the reference also takes from native modules:
 fused SSIM (oracle: the pure-PyTorch ssim() restated in oracle/loss_oracle.py, itself pinned against the reference's
-utils/loss_utils.py:ssim by tests/golden/reference_helpers.npz) and the one-launch Adam kernels (oracle: torch.optim.Adam
-on CPU; the sparse variant against a masked no-bias-correction restatement)."""
+utils/loss_utils.py:ssim by tests/golden/reference_helpers.npz) and the one-launch Adam kernels.  The two Adam tests here are
+a float32 cross-check at one size (torch.optim.Adam in float32 on the CPU; the sparse variant against a masked float32
+restatement without bias correction) - no oracle: the kernels' value tests against a float64 reference, at every size and path,
+are tests/test_adam_kernels_gpu.py (reference: tests/adam_reference.py).  The fold tests below hold every folded form of the
+step bit-equal to backward + that kernel."""
 import numpy as np
 import pytest
 import torch
@@ -193,48 +196,76 @@ def test_fold_request_travels_with_its_call_unrelated_renders_in_between_take_no
     assert all(p.grad is not None for p in model.parameters() if p.numel())    # the second one is a plain backward
 
 
+# (P, max SH degree, image, steps, a third of the cloud outside the frustum).  The first is the long-standing case.  The others are
+# where the folded f_rest update (preprocess.hip, the STAGE block: a workgroup's span of rows * S floats in 16-byte pieces, a
+# scalar tail) takes paths that P % 4 == 0 with S = 45 never reaches: P * S % 4 != 0 (the last workgroup's tail loop: 63, 2999 and
+# 3001 at S = 45, 1366 at S = 9), a last workgroup of one or a few rows, one Gaussian, S = 9 / 24 (pieces straddle rows at other
+# places), no f_rest at all (degree 0), and culled rows (sparse: pieces that straddle an updated and an untouched row; dense:
+# rows without instances).
+FOLD_CASES = [(3000, 3, (176, 112), 7, False), (1, 3, (96, 64), 5, False), (63, 3, (96, 64), 5, False), (65, 0, (96, 64), 5, False),
+              (1366, 1, (96, 64), 5, True), (1366, 2, (96, 64), 5, False), (3001, 3, (96, 64), 5, True), (2999, 3, (96, 64), 5, False)]
+
+
+@pytest.mark.parametrize("P,deg,size,steps,cull", FOLD_CASES, ids=[f"P{c[0]}-deg{c[1]}" + ("-culled" if c[4] else "") for c in FOLD_CASES])
 @pytest.mark.parametrize("kind", ["hip", "hip_sparse"])
-def test_optimizer_step_folded_into_backward_is_bit_identical(kind):
+def test_optimizer_step_folded_into_backward_is_bit_identical(kind, P, deg, size, steps, cull):
     """gsr_backward_adam (the Adam / SparseGaussianAdam update applied by the rasterizer backward's last kernel, gradients
     never stored) against backward + the one-launch optimizer kernel: parameters and both moments equal bit for bit after
     several training steps, densification statistics (means2D gradient) included."""
     import diff_gaussian_rasterization as dgr
     from gaussian_renderer import render, PipelineParams
     from scene_utils import make_gaussians, fibonacci_cameras, GaussianModel, Trainer
-    cams = fibonacci_cameras(3, 176, 112, seed=91, device="cuda")
+    cams = fibonacci_cameras(3, size[0], size[1], seed=91, device="cuda")
     bg = torch.tensor([0.1, 0.2, 0.05], device="cuda")
     pipe = PipelineParams()
-    teacher = GaussianModel.from_raw(make_gaussians(3000, 3, seed=92, scale_factor=0.7).to("cuda"), requires_grad=False)
+
+    def scene(seed):
+        raw = make_gaussians(P, deg, seed=seed, scale_factor=0.7)
+        if cull:
+            raw.xyz[::3] *= 3.0                  # a third of the cloud far outside the frustum
+        return raw
+    teacher = GaussianModel.from_raw(scene(92).to("cuda"), requires_grad=False)
     with torch.no_grad():
         gts = {i: render(c, teacher, pipe, bg)["render"].clone() for i, c in enumerate(cams)}
     runs = {}
     for fused in (False, True):
-        model = GaussianModel.from_raw(make_gaussians(3000, 3, seed=93, scale_factor=0.7).to("cuda"))
+        model = GaussianModel.from_raw(scene(93).to("cuda"))
         tr = Trainer(model, cams, gts, render, pipe, bg, separate_sh=True, optimizer=kind + ("_fused" if fused else ""))
         n0 = dgr.call_stats().get("folded_backwards", 0)
-        for it in range(7):
-            tr.step(it % 3)
+        culled = []
+        for it in range(steps):
+            o = tr.step(it % 3)
+            culled.append(int((o["radii"] == 0).sum()))
         tr.finish()
         torch.cuda.synchronize()
-        assert dgr.call_stats().get("folded_backwards", 0) - n0 == (7 if fused else 0)
+        assert dgr.call_stats().get("folded_backwards", 0) - n0 == (steps if fused else 0)
+        if cull:                                 # the case really had both kinds of row
+            assert any(0 < c < P for c in culled), culled
         st = {}
         for name, p in zip(("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation"), model.parameters()):
+            if p.numel() == 0:                   # (degree 0: f_rest is [P, 0, 3], there is nothing to step or compare)
+                continue
             s = tr.optimizer.state[p]
             st[name] = (p.detach().clone(), s["exp_avg"].clone(), s["exp_avg_sq"].clone())
+        assert len(st) == (6 if deg > 0 else 5)
         runs[fused] = (st, model.xyz_gradient_accum.clone(), model.denom.clone())
     for name in runs[False][0]:
         for a, b, what in zip(runs[False][0][name], runs[True][0][name], ("param", "exp_avg", "exp_avg_sq")):
             assert torch.equal(a, b), (name, what, float((a - b).abs().max()))
     assert torch.equal(runs[False][1], runs[True][1]) and torch.equal(runs[False][2], runs[True][2])
     # and the parameters did move
-    ref = GaussianModel.from_raw(make_gaussians(3000, 3, seed=93, scale_factor=0.7).to("cuda"))
-    assert not torch.equal(ref._features_rest, runs[True][0]["f_rest"][0])
+    ref = GaussianModel.from_raw(scene(93).to("cuda"))
+    moved = "f_rest" if deg > 0 else "f_dc"
+    assert not torch.equal({"f_rest": ref._features_rest, "f_dc": ref._features_dc}[moved], runs[True][0][moved][0])
 
 
-def test_split_dense_adam_culled_rows_on_side_stream_is_bit_identical():
+@pytest.mark.parametrize("P,deg", [(5000, 3), (1366, 3), (3001, 3), (1366, 1), (3001, 1)])
+def test_split_dense_adam_culled_rows_on_side_stream_is_bit_identical(P, deg):
     """hip_fused can split the dense update (Trainer.split_rows): rows without tile instances on a side stream during the compositing kernels
     (gsr_adam_step_culled_rows, launched by the rasterizer's backward), rows with instances in the backward (gsr_backward_adam, sparse = 2).  Against the unsplit
-    folded update (Trainer.split_rows off) on a scene where a good part of the Gaussians is off-screen."""
+    folded update (Trainer.split_rows off) on a scene where a good part of the Gaussians is off-screen.  P = 5000 is a multiple
+    of 4; 1366 and 3001 end in a workgroup whose span of f_rest is not (at S = 45 for 3001, at S = 9 for 1366: both kernels'
+    tail loops), and at S = 9 the pieces straddle rows elsewhere."""
     import diff_gaussian_rasterization as dgr
     from gaussian_renderer import render, PipelineParams
     from scene_utils import make_gaussians, fibonacci_cameras, GaussianModel, Trainer
@@ -242,7 +273,7 @@ def test_split_dense_adam_culled_rows_on_side_stream_is_bit_identical():
     bg = torch.zeros(3, device="cuda")
     pipe = PipelineParams()
     def scene(seed):
-        raw = make_gaussians(5000, 3, seed=seed, scale_factor=0.6)
+        raw = make_gaussians(P, deg, seed=seed, scale_factor=0.6)
         raw.xyz[::3] *= 3.0                      # a third of the cloud far outside the frustum
         return raw
     teacher = GaussianModel.from_raw(scene(192).to("cuda"), requires_grad=False)
@@ -259,7 +290,7 @@ def test_split_dense_adam_culled_rows_on_side_stream_is_bit_identical():
             culled += int((o["radii"] == 0).sum())
         tr.finish()
         torch.cuda.synchronize()
-        assert culled > 3000
+        assert culled > 3000 * P // 5000 and culled < 6 * P
         out[split] = [(p.detach().clone(), tr.optimizer.state[p]["exp_avg"].clone(), tr.optimizer.state[p]["exp_avg_sq"].clone())
                       for p in model.parameters()]
     for a, b in zip(out[False], out[True]):
