@@ -189,6 +189,10 @@ EXPORTS = {
     # n, image, exposure, mask, dL_dout, dL_dimage, partials, dL_dexposure, exposures, views, row, adam, lr, beta1, beta2, eps, stream
     "gsr_exposure_backward": (C.c_int, [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p] + [C.c_double] * 4 +
                               [C.c_void_p]),
+    "gsr_transform_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    # P, anchor, K, transforms, workspace + bytes, xyz, rotation, scaling, features_rest, sh_coeffs_rest, moments8 (host), stream
+    "gsr_transform_gaussians": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 +
+                                [C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
     "gsr_profile_enable": (None, [C.c_int32]),
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

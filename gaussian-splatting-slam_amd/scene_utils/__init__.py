@@ -13,3 +13,4 @@ from .pose import se3_exp, PoseCamera, refine_pose, pose_error, DevicePoseCamera
 from .mapping import unproject_rgbd, create_from_pcd, add_from_rgbd
 from .keyframes import covisibility, KeyframeWindow, prune_unobserved
 from .exposure import apply_exposure
+from .transform import transform_camera, correct_keyframes, validate_transforms

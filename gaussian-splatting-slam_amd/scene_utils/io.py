@@ -5,7 +5,8 @@
   f_dc / f_rest are stored CHANNEL-major (`transpose(1, 2).flatten`), normals are zeros, values are the RAW (pre-activation)
   parameters.  Files written here load in the upstream viewers / `GaussianModel.load_ply`, and vice versa.
 * checkpoint tuple (reference :67-99 capture / restore): (active_sh_degree, xyz, f_dc, f_rest, scaling, rotation, opacity,
-  max_radii2D, xyz_gradient_accum, denom, optimizer.state_dict(), spatial_lr_scale).
+  max_radii2D, xyz_gradient_accum, denom, optimizer.state_dict(), spatial_lr_scale); a model that tracks keyframe anchors
+  (model._anchor, scene_utils.transform) appends them as a thirteenth entry, and a twelve-entry tuple restores as before.
 """
 from __future__ import annotations
 
@@ -128,15 +129,18 @@ def load_ply(model, path: str, device="cuda"):
 
 def capture(model):
     """reference :67-82"""
-    return (model.active_sh_degree, model._xyz, model._features_dc, model._features_rest, model._scaling, model._rotation,
+    args = (model.active_sh_degree, model._xyz, model._features_dc, model._features_rest, model._scaling, model._rotation,
             model._opacity, model.max_radii2D, model.xyz_gradient_accum, model.denom, model.optimizer.state_dict(),
             getattr(model, "spatial_lr_scale", 1.0))
+    anchor = getattr(model, "_anchor", None)
+    return args if anchor is None else args + (anchor,)
 
 
 def restore(model, model_args, optimizer="hip"):
     """reference :83-99"""
     (model.active_sh_degree, model._xyz, model._features_dc, model._features_rest, model._scaling, model._rotation,
-     model._opacity, max_radii2D, xyz_gradient_accum, denom, opt_dict, model.spatial_lr_scale) = model_args
+     model._opacity, max_radii2D, xyz_gradient_accum, denom, opt_dict, model.spatial_lr_scale) = model_args[:12]
+    model._anchor = model_args[12] if len(model_args) > 12 else None
     model.training_setup(optimizer=optimizer)
     model.max_radii2D, model.xyz_gradient_accum, model.denom = max_radii2D, xyz_gradient_accum, denom
     model.optimizer.load_state_dict(opt_dict)

@@ -24,11 +24,12 @@ def _as_tensor(a):
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
 
 
-def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0):
+def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0, anchor=None):
     """reference scene/gaussian_model.py:130-153.  `points` [P,3] / `colors` [P,3] in [0,1]: tensors or numpy arrays - or, as in
     the reference, one object with `.points` / `.colors` (its BasicPointCloud) as the first argument.  The points decide the
     device: arrays are moved to the HIP device as in the reference, tensors are used where they live and must live there - CPU
-    tensors raise, there is no CPU path for the neighbour search.  Returns the model."""
+    tensors raise, there is no CPU path for the neighbour search.  `anchor`: the keyframe id the rows are labelled with
+    (model._anchor, scene_utils.transform; a model that tracks anchors labels them -1 without it).  Returns the model."""
     if hasattr(points, "points") and hasattr(points, "colors"):
         if colors is not None:                       # (pcd, spatial_lr_scale): the reference's call form
             spatial_lr_scale = colors
@@ -61,6 +62,8 @@ def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0):
     self._opacity = nn.Parameter(opacities.requires_grad_(True))
     self.max_radii2D = torch.zeros((P,), device=dev)
     self.active_sh_degree = 0
+    tracked = anchor is not None or getattr(self, "_anchor", None) is not None
+    self._anchor = torch.full((P,), -1 if anchor is None else int(anchor), dtype=torch.int32, device=dev) if tracked else None
     return self
 
 
@@ -105,7 +108,7 @@ def unproject_rgbd(cam, image, depth, alpha=None, rendered_z=None, stride=1, min
     return xyz[:n], rgb[:n]
 
 
-def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, scale="knn", **selection):
+def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, scale="knn", anchor=None, **selection):
     """Appends Gaussians for the pixels of an RGB-D keyframe that the map does not explain; returns how many.  `render_pkg`: the
     result of render(cam, self, ..., depth="z", alpha=True) (None: first keyframe, every valid reading is taken); `selection`:
     the keyword arguments of unproject_rgbd.  New rows: colour -> SH band 0, higher bands 0, identity rotation, opacity
@@ -113,7 +116,9 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
     (scale="knn") or the footprint of a pixel at the reading's depth, d 2 tanfovx / W stride (scale="pixel", no search).
     With an optimizer attached the old rows keep their Adam moments and the new rows start from zero; xyz_gradient_accum, denom
     and max_radii2D are extended with zeros (the old rows' statistics stay valid).  n == 0 changes nothing.  A model without
-    parameters yet (GaussianModel(sh_degree)) is created from the keyframe."""
+    parameters yet (GaussianModel(sh_degree)) is created from the keyframe.  `anchor`: the keyframe id the new rows are labelled
+    with in model._anchor, so that a later pose correction of that keyframe can move them (scene_utils.transform); without it
+    they get -1 if the model tracks anchors."""
     _C = _gsr()
     if self._xyz is not None and not self._xyz.is_cuda:
         raise _C.GsrError("add_from_rgbd runs in HIP kernels (no CPU path): the model must live on the HIP device")
@@ -167,6 +172,8 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
             else:
                 moments.append(None)
         _replace_params(self, tensors, moments)
+        from .transform import _extend_anchors
+        _extend_anchors(self, P, n, anchor, dev)
         if getattr(self, "xyz_gradient_accum", None) is not None:
             self.xyz_gradient_accum = torch.cat([self.xyz_gradient_accum, torch.zeros((n, 1), device=dev)], dim=0)
             self.denom = torch.cat([self.denom, torch.zeros((n, 1), device=dev)], dim=0)

@@ -32,6 +32,7 @@ class GaussianModel:
         self.exposure_mapping = {}
         self.exposure_optimizer = None
         self._exposure_adam = None   # device Adam state while fold_exposure_adam() is armed (scene_utils.exposure)
+        self._anchor = None          # int32 [P]: the keyframe every row belongs to (scene_utils.transform.set_anchors); None = not tracked
         self._resize_hooks = []      # called with "before" / "after" around a row insertion / removal from outside a training step (mapping.add_from_rgbd, prune_points)
 
     @classmethod
@@ -249,10 +250,13 @@ def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, radi
         vin = (C.c_void_p * 18)(*ins18)
         vout = (C.c_void_p * 18)(*outs18)
         rowf = (C.c_int32 * 6)(*rows)
-        src = torch.empty(newP, dtype=torch.int32, device=dev) if return_source else None
+        anchor = getattr(self, "_anchor", None)
+        src = torch.empty(newP, dtype=torch.int32, device=dev) if (return_source or anchor is not None) else None
         _C.check(lib.gsr_densify_apply(P, _C.ptr(ws), vin, vout, rowf, nk, nc, ns, int(seed) & 0xFFFFFFFF, _C.ptr(src),
                                        _C._stream()))
         _replace_params(self, outs, out_m)
+        if anchor is not None:           # clones and children belong to the keyframe of their source row
+            self._anchor = anchor.to(dev)[src.long()]
         self.xyz_gradient_accum = torch.zeros((newP, 1), device=dev)      # densification_postfix :362-364
         self.denom = torch.zeros((newP, 1), device=dev)
         self.max_radii2D = torch.zeros((newP,), device=dev)
@@ -295,6 +299,8 @@ def prune_points(self, mask):
             self.denom = self.denom[keep]
         if getattr(self, "max_radii2D", None) is not None:
             self.max_radii2D = self.max_radii2D[keep]
+        if getattr(self, "_anchor", None) is not None:
+            self._anchor = self._anchor.to(keep.device)[keep]
         for hook in getattr(self, "_resize_hooks", ()):
             hook("after")
     return n

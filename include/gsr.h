@@ -41,6 +41,7 @@ extern "C" {
  *    gsr_render_extras.n_touched / touched_T_min (trailing fields; zero = as before): per-Gaussian visibility counts;
  *    gsr_backward_camera_only (+ _ex), gsr_pose_adam, gsr_pose_forward, gsr_pose_backward: pose tracking on the device;
  *    gsr_exposure_adam, gsr_exposure_blocks, gsr_exposure_forward, gsr_exposure_backward: per-view exposure and alpha mask;
+ *    gsr_transform_workspace_bytes, gsr_transform_gaussians: the map follows keyframe pose corrections (SH bands rotated);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -630,6 +631,32 @@ int gsr_exposure_forward(int64_t n, const float* image, const float* exposure, c
 int gsr_exposure_backward(int64_t n, const float* image, const float* exposure, const float* mask, const float* dL_dout,
                           float* dL_dimage, float* partials, float* dL_dexposure, float* exposures, int32_t views, int32_t row,
                           gsr_exposure_adam* adam, double lr, double beta1, double beta2, double eps, void* stream);
+
+/* ---- map maintenance: Gaussians follow the pose corrections of their keyframes ---- */
+
+/* Moves rows of the model into a corrected world frame, in place.  `transforms` [K,4,4] row-major float64 in DEVICE memory, each
+ * x' = s R x + t: upper-left block s R with R a proper rotation and s > 0, last column t, bottom row (0, 0, 0, 1) - trusted, not
+ * checked.  `anchor` int32 [P]: row i moves by transform anchor[i]; a value < 0 or >= K leaves the row untouched - nothing is
+ * written to it.  anchor == NULL: every row moves by transform 0.  A row that moves:
+ *   xyz            s R x + t, formed in float64 from the float32 input and rounded once;
+ *   rotation       (raw quaternion, w x y z) q' = q_R (x) q, the Hamilton product with the unit quaternion of R (norm preserved);
+ *   scaling_raw    (log-scale) + ln s; NULL: skipped;
+ *   features_rest  [P, sh_coeffs_rest, 3], sh_coeffs_rest in {0, 3, 8, 15}: SH bands 1..3 are expressed in the world frame, so per
+ *                  channel and band c'_l = D_l(R) c_l with the band's (2 l + 1)^2 real-SH rotation matrix (basis and signs of the
+ *                  reference's utils/sh_utils.py); may be NULL when sh_coeffs_rest == 0;
+ *   moments8       NULL, or a HOST array of eight device pointers, each of which may be NULL: exp_avg, exp_avg_sq of xyz, of rotation,
+ *                  of scaling, of features_rest (shapes of their parameters).  The moved rows get zeros - their moments describe
+ *                  gradients in the old frame -, the other rows are not written.
+ * features_dc and opacity are invariant and not arguments.  `workspace`: gsr_transform_workspace_bytes(K) bytes, holds the
+ * per-transform table (s, R, t, quaternion, ln s, D_1..D_3; float64 arithmetic, one lane per transform); its layout is private.
+ * Two launches, no atomics, bitwise reproducible, nothing read back.  P == 0 or K == 0 launches nothing.
+ * Errors, all before any device work, all GSR_ERR_INVALID_ARGUMENT: sh_coeffs_rest outside {0, 3, 8, 15}; P < 0 or > 2^31 - 1,
+ * K < 0; workspace NULL or too small (K > 0); xyz NULL (P > 0); transforms, rotation or a needed features_rest NULL; rotation,
+ * features_rest, their moments or the workspace not 16-byte aligned. */
+size_t gsr_transform_workspace_bytes(int32_t K);
+int gsr_transform_gaussians(int64_t P, const int32_t* anchor, int32_t K, const double* transforms, void* workspace,
+                            size_t workspace_bytes, float* xyz, float* rotation, float* scaling_raw, float* features_rest,
+                            int32_t sh_coeffs_rest, float* const* moments8, void* stream);
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py's roofline block).  A measurement aid, process-
  * global and meant for ONE host thread driving the library at a time: enabling it while several host threads launch
