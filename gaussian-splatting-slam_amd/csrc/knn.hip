@@ -296,6 +296,7 @@ __global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, cons
 struct GsrUnprojectArgs {
   int H, W, Hs, Ws, stride;
   float tanfovx, tanfovy, min_depth, max_depth, alpha_below, front_margin;
+  float ox, oy;      // principal point, as the projection matrix's offsets P[0,2], P[1,2] (0: the image centre)
 };
 
 __device__ __forceinline__ bool unproject_selected(const GsrUnprojectArgs& a, size_t pix, const float* __restrict__ depth,
@@ -340,8 +341,9 @@ __global__ __launch_bounds__(256) void k_unproject_write(GsrUnprojectArgs a, con
   const float nx = __fsub_rn(__fdiv_rn((float)(2 * px + 1), (float)a.W), 1.0f);
   const float ny = __fsub_rn(__fdiv_rn((float)(2 * py + 1), (float)a.H), 1.0f);
   // view = W2C^T row-major: view-space v_i = sum_j w_j view[4 j + i] + view[12 + i]; rigid inverse w_j = sum_i view[4 j + i] (v_i - t_i)
-  const float v0 = __fsub_rn(__fmul_rn(__fmul_rn(nx, a.tanfovx), d), view[12]);
-  const float v1 = __fsub_rn(__fmul_rn(__fmul_rn(ny, a.tanfovy), d), view[13]);
+  // (nx - 0 is nx, bit for bit: the centred call computes what it always did)
+  const float v0 = __fsub_rn(__fmul_rn(__fmul_rn(__fsub_rn(nx, a.ox), a.tanfovx), d), view[12]);
+  const float v1 = __fsub_rn(__fmul_rn(__fmul_rn(__fsub_rn(ny, a.oy), a.tanfovy), d), view[13]);
   const float v2 = __fsub_rn(d, view[14]);
 #pragma unroll
   for (int j = 0; j < 3; j++)
@@ -349,6 +351,47 @@ __global__ __launch_bounds__(256) void k_unproject_write(GsrUnprojectArgs a, con
   const size_t plane = (size_t)a.H * a.W;
 #pragma unroll
   for (int ch = 0; ch < 3; ch++) rgb[3 * (size_t)o + ch] = color[ch * plane + pix];
+}
+
+static size_t unproject_workspace_bytes(int32_t W, int32_t H) {
+  const size_t n = (size_t)(W < 1 ? 1 : W) * (size_t)(H < 1 ? 1 : H);
+  return 2 * gsr_align(n * 4) + gsr_align(gsr_scan_tmp_elems(n) * 4);
+}
+
+// gsr_unproject_rgbd (ox = oy = 0) and gsr_unproject_rgbd_k: one flag pass, one scan, one write pass
+static int unproject_rgbd(const gsr_unproject_params* p, float ox, float oy, const float* depth, const float* color,
+                          const float* alpha, const float* rendered_z, float* xyz, float* rgb, int64_t capacity,
+                          int64_t* count_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!p || !depth || !color || !count_dev || !workspace || capacity < 0 || (capacity > 0 && (!xyz || !rgb)) ||
+      p->image_width < 1 || p->image_height < 1 || (int64_t)p->image_width * p->image_height > 0x3FFFFFFF || p->stride < 1 ||
+      !p->viewmatrix || !(p->tanfovx > 0.f) || !(p->tanfovy > 0.f) || !(fabsf(ox) <= 1.f) || !(fabsf(oy) <= 1.f)) {
+    gsr_set_error("unproject_rgbd: bad arguments");
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  if (workspace_bytes < unproject_workspace_bytes(p->image_width, p->image_height)) {
+    gsr_set_error("unproject_rgbd: workspace of %zu bytes, %zu needed", workspace_bytes,
+                  unproject_workspace_bytes(p->image_width, p->image_height));
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  GsrUnprojectArgs a;
+  a.H = p->image_height; a.W = p->image_width; a.stride = p->stride;
+  a.Hs = (a.H + a.stride - 1) / a.stride; a.Ws = (a.W + a.stride - 1) / a.stride;
+  a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.min_depth = p->min_depth; a.max_depth = p->max_depth;
+  a.alpha_below = p->alpha_below; a.front_margin = p->front_margin;
+  a.ox = ox; a.oy = oy;
+  const size_t full = (size_t)a.W * a.H, n = (size_t)a.Ws * a.Hs;
+  char* ws = (char*)workspace;
+  uint32_t* flags = (uint32_t*)ws;
+  uint32_t* offs = (uint32_t*)(ws + gsr_align(full * 4));
+  uint32_t* scan_tmp = (uint32_t*)(ws + 2 * gsr_align(full * 4));
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  GSR_LAUNCH("unproject_flag", k_unproject_flag, dim3(grid), dim3(256), 0, st, a, depth, alpha, rendered_z, flags);
+  gsr_scan_u32(flags, nullptr, offs, n, 0, scan_tmp, st);
+  const uint32_t cap = (uint32_t)(capacity > 0x7FFFFFFF ? 0x7FFFFFFF : capacity);
+  GSR_LAUNCH("unproject_write", k_unproject_write, dim3(grid), dim3(256), 0, st, a, depth, color, p->viewmatrix,
+             (const uint32_t*)flags, (const uint32_t*)offs, xyz, rgb, cap, count_dev);
+  return gsr_launch_status("unproject_rgbd launch");
 }
 
 extern "C" {
@@ -400,43 +443,20 @@ int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* me
   return gsr_launch_status("knn_dist2 launch");
 }
 
-size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) {
-  const size_t n = (size_t)(W < 1 ? 1 : W) * (size_t)(H < 1 ? 1 : H);
-  return 2 * gsr_align(n * 4) + gsr_align(gsr_scan_tmp_elems(n) * 4);
-}
+size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) { return unproject_workspace_bytes(W, H); }
 
 int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth, const float* color, const float* alpha,
                        const float* rendered_z, float* xyz, float* rgb, int64_t capacity, int64_t* count_dev, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  if (!p || !depth || !color || !count_dev || !workspace || capacity < 0 || (capacity > 0 && (!xyz || !rgb)) ||
-      p->image_width < 1 || p->image_height < 1 || (int64_t)p->image_width * p->image_height > 0x3FFFFFFF || p->stride < 1 ||
-      !p->viewmatrix || !(p->tanfovx > 0.f) || !(p->tanfovy > 0.f)) {
-    gsr_set_error("unproject_rgbd: bad arguments");
-    return GSR_ERR_INVALID_ARGUMENT;
-  }
-  if (workspace_bytes < gsr_unproject_workspace_bytes(p->image_width, p->image_height)) {
-    gsr_set_error("unproject_rgbd: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  gsr_unproject_workspace_bytes(p->image_width, p->image_height));
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
-  GsrUnprojectArgs a;
-  a.H = p->image_height; a.W = p->image_width; a.stride = p->stride;
-  a.Hs = (a.H + a.stride - 1) / a.stride; a.Ws = (a.W + a.stride - 1) / a.stride;
-  a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.min_depth = p->min_depth; a.max_depth = p->max_depth;
-  a.alpha_below = p->alpha_below; a.front_margin = p->front_margin;
-  const size_t full = (size_t)a.W * a.H, n = (size_t)a.Ws * a.Hs;
-  char* ws = (char*)workspace;
-  uint32_t* flags = (uint32_t*)ws;
-  uint32_t* offs = (uint32_t*)(ws + gsr_align(full * 4));
-  uint32_t* scan_tmp = (uint32_t*)(ws + 2 * gsr_align(full * 4));
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  GSR_LAUNCH("unproject_flag", k_unproject_flag, dim3(grid), dim3(256), 0, st, a, depth, alpha, rendered_z, flags);
-  gsr_scan_u32(flags, nullptr, offs, n, 0, scan_tmp, st);
-  const uint32_t cap = (uint32_t)(capacity > 0x7FFFFFFF ? 0x7FFFFFFF : capacity);
-  GSR_LAUNCH("unproject_write", k_unproject_write, dim3(grid), dim3(256), 0, st, a, depth, color, p->viewmatrix,
-             (const uint32_t*)flags, (const uint32_t*)offs, xyz, rgb, cap, count_dev);
-  return gsr_launch_status("unproject_rgbd launch");
+  return unproject_rgbd(p, 0.f, 0.f, depth, color, alpha, rendered_z, xyz, rgb, capacity, count_dev, workspace, workspace_bytes,
+                        stream);
+}
+
+int gsr_unproject_rgbd_k(const gsr_unproject_params_k* p, const float* depth, const float* color, const float* alpha,
+                         const float* rendered_z, float* xyz, float* rgb, int64_t capacity, int64_t* count_dev, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  return unproject_rgbd(p ? &p->base : nullptr, p ? p->ox : 0.f, p ? p->oy : 0.f, depth, color, alpha, rendered_z, xyz, rgb,
+                        capacity, count_dev, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -87,6 +87,10 @@ class gsr_unproject_params(C.Structure):
     ]
 
 
+class gsr_unproject_params_k(C.Structure):
+    _fields_ = [("base", gsr_unproject_params), ("ox", C.c_float), ("oy", C.c_float)]
+
+
 class gsr_fused_adam(C.Structure):
     _fields_ = [
         ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("lr", C.c_float * 6), ("step", C.c_int64 * 6),
@@ -182,6 +186,14 @@ EXPORTS = {
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),
+    "gsr_unproject_rgbd_k": (C.c_int, [C.POINTER(gsr_unproject_params_k)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                                                                               C.c_size_t, C.c_void_p]),
+    # src_w, src_h, src_color, src_depth, src_K (host), dist (host), w, h, K (host), color, depth, mask, stream
+    "gsr_frame_undistort": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_float_p, c_float_p, C.c_int32, C.c_int32,
+                                      c_float_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # w, h, levels, color, depth, mask, depth_band, color_out / depth_out / mask_out (host arrays of device pointers), stream
+    "gsr_frame_pyramid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] +
+                          [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p]),
     "gsr_pose_forward": (C.c_int, [C.c_void_p] * 7),
     "gsr_pose_backward": (C.c_int, [C.c_void_p] * 9),
     "gsr_exposure_blocks": (C.c_int32, []),

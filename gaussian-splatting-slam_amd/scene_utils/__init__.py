@@ -1,6 +1,6 @@
 """Host-side helpers around the rasterizer path: camera conventions and synthetic scenes."""
 from .cameras import MiniCam, camera_from_RT, look_at_camera, fibonacci_cameras, fov2focal, focal2fov, \
-    world_to_view, projection_matrix
+    world_to_view, projection_matrix, camera_projection, camera_from_intrinsics, camera_intrinsics, scaled_camera
 from .synthetic import RawGaussians, make_gaussians, make_config, CONFIGS
 from .model import GaussianModel
 from .sh import eval_sh, RGB2SH, SH2RGB
@@ -14,3 +14,4 @@ from .mapping import unproject_rgbd, create_from_pcd, add_from_rgbd
 from .keyframes import covisibility, KeyframeWindow, prune_unobserved
 from .exposure import apply_exposure
 from .transform import transform_camera, correct_keyframes, validate_transforms
+from .frames import Frame, FramePyramid, undistort, build_pyramid

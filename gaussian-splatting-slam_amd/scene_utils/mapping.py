@@ -1,6 +1,6 @@
 """The mapping half of a SLAM loop: new Gaussians from point clouds (reference scene/gaussian_model.py:130-153 create_from_pcd)
 and from RGB-D keyframes (the pixels the map does not explain yet, back-projected and appended to a live, optimised model).
-Back-projection / selection (gsr_unproject_rgbd) and the neighbour distances that size the new Gaussians (gsr_knn_dist2) run in
+Back-projection / selection (gsr_unproject_rgbd_k) and the neighbour distances that size the new Gaussians (gsr_knn_dist2) run in
 HIP (csrc/knn.hip); there is no CPU path."""
 from __future__ import annotations
 
@@ -95,14 +95,17 @@ def unproject_rgbd(cam, image, depth, alpha=None, rendered_z=None, stride=1, min
     stride = int(stride)
     cap = ((W + stride - 1) // stride) * ((H + stride - 1) // stride)
     lib = _C.lib()
-    p = _C.gsr_unproject_params(H, W, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), view.data_ptr(), stride,
-                                float(min_depth), float(max_depth), float(alpha_below), float(front_margin))
+    # (the principal point travels as the projection matrix's offsets; a camera without them is centred)
+    p = _C.gsr_unproject_params_k(_C.gsr_unproject_params(H, W, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5),
+                                                          view.data_ptr(), stride, float(min_depth), float(max_depth),
+                                                          float(alpha_below), float(front_margin)),
+                                  float(getattr(cam, "ox", 0.0)), float(getattr(cam, "oy", 0.0)))
     xyz = torch.empty((cap, 3), dtype=torch.float32, device=dev)
     rgb = torch.empty((cap, 3), dtype=torch.float32, device=dev)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     with _C.on_device(dev):
         ws = torch.empty(lib.gsr_unproject_workspace_bytes(W, H), dtype=torch.uint8, device=dev)
-        _C.check(lib.gsr_unproject_rgbd(C.byref(p), _C.ptr(d), _C.ptr(col), _C.ptr(a), _C.ptr(rz), _C.ptr(xyz), _C.ptr(rgb), cap,
+        _C.check(lib.gsr_unproject_rgbd_k(C.byref(p), _C.ptr(d), _C.ptr(col), _C.ptr(a), _C.ptr(rz), _C.ptr(xyz), _C.ptr(rgb), cap,
                                         _C.ptr(count), _C.ptr(ws), ws.numel(), _C._stream()))
     n = int(count.item())
     return xyz[:n], rgb[:n]

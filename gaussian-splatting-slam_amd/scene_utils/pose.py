@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from .cameras import projection_matrix
+from .cameras import camera_projection, scaled_camera
 
 
 def _hat(w):
@@ -52,6 +52,14 @@ def se3_exp(tau):
     return torch.cat([top, bottom], dim=0)
 
 
+def _copy_intrinsics(dst, cam):
+    """Image size, FoV, principal-point offsets (a camera without them: centred) and depth range of `cam` onto `dst`."""
+    dst.image_width, dst.image_height = int(cam.image_width), int(cam.image_height)
+    dst.FoVx, dst.FoVy = float(cam.FoVx), float(cam.FoVy)
+    dst.ox, dst.oy = float(getattr(cam, "ox", 0.0)), float(getattr(cam, "oy", 0.0))
+    dst.znear, dst.zfar = cam.znear, cam.zfar
+
+
 class PoseCamera:
     """A camera with the attribute surface `render()` reads (scene_utils.MiniCam, reference scene/cameras.py:74-85) whose
     `world_view_transform`, `full_proj_transform` and `camera_center` are torch functions of a base W2C and the leaf twist
@@ -62,14 +70,17 @@ class PoseCamera:
         wv = cam.world_view_transform
         dtype = dtype or wv.dtype
         device = torch.device(device) if device is not None else wv.device
-        self.image_width, self.image_height = int(cam.image_width), int(cam.image_height)
-        self.FoVx, self.FoVy = float(cam.FoVx), float(cam.FoVy)
-        self.znear, self.zfar = cam.znear, cam.zfar
         self.image_name = getattr(cam, "image_name", "")
         self.base_w2c = wv.detach().to(dtype=dtype, device=device).transpose(0, 1).contiguous()
-        self.proj_T = projection_matrix(self.znear, self.zfar, self.FoVx, self.FoVy).transpose(0, 1).to(dtype=dtype,
-                                                                                                        device=device)
+        self.set_intrinsics(cam)
         self.tau = torch.zeros(6, dtype=dtype, device=device, requires_grad=requires_grad)
+
+    def set_intrinsics(self, cam):
+        """Points this pose camera at the image size and projection of `cam` (any camera object: another pyramid level, say);
+        the pose - base_w2c, tau - and whatever optimizes it stay as they are."""
+        _copy_intrinsics(self, cam)
+        self.proj_T = camera_projection(self).transpose(0, 1).to(dtype=self.base_w2c.dtype, device=self.base_w2c.device)
+        return self
 
     def w2c(self):
         """The corrected world-to-camera matrix exp(tau) W2C (4x4, column-vector convention)."""
@@ -105,8 +116,32 @@ def pose_error(w2c_a, w2c_b):
     return float(torch.arccos(cos.clamp(-1.0, 1.0))), float((ca - cb).norm())
 
 
+def _level_plan(iters, levels, level_iters):
+    """[(level, iterations)] from the coarsest level down to 0: `level_iters` (a sequence indexed by level) or `iters` at level 0
+    and iters // 2 at every coarser one."""
+    levels = int(levels)
+    if levels < 0:
+        raise ValueError(f"levels={levels}: expected an integer >= 0")
+    if level_iters is None:
+        level_iters = [int(iters)] + [int(iters) // 2] * levels
+    level_iters = [int(n) for n in level_iters]
+    if len(level_iters) != levels + 1 or min(level_iters) < 0:
+        raise ValueError(f"level_iters={level_iters}: expected {levels + 1} counts >= 0, one per level from 0 up")
+    return [(l, level_iters[l]) for l in range(levels, -1, -1)]
+
+
+def _target_pyramid(pc, gt_image, gt_depth, mask, levels):
+    """The targets of a coarse-to-fine run: scene_utils.frames.FramePyramid (HIP) of the image, the depth and the mask.  Its
+    cameras are snapshots of `pc`'s intrinsics per level (level 0 too: `pc` itself is re-pointed while the levels run)."""
+    from .frames import Frame, FramePyramid
+    H, W = gt_image.shape[-2:]
+    return FramePyramid(Frame(gt_image.detach().float().reshape(3, H, W), None if gt_depth is None else gt_depth.reshape(H, W),
+                              None if mask is None else mask.detach().float().reshape(H, W), scaled_camera(pc, 0)), levels)
+
+
 def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda_dssim=0.0, bg=None, pipe=None,
-                separate_sh=False, callback=None, gt_depth=None, depth_weight=0.5, alpha_min=0.5):
+                separate_sh=False, callback=None, gt_depth=None, depth_weight=0.5, alpha_min=0.5, levels=0, level_iters=None,
+                mask=None):
     """Photometric (or RGB-D) pose refinement of one camera against a frozen `model` (tracking): Adam over the twist of a `PoseCamera`,
     loss = L1(render, gt_image) (lambda_dssim > 0: the fused L1 + D-SSIM training loss), learning rate decaying
     exponentially from `lr` to `lr_final`.  `cam`: a PoseCamera (refined in place) or any camera (wrapped in a float64 PoseCamera
@@ -119,29 +154,62 @@ def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambd
     ONCE with depth="z", alpha=True and minimises (1 - depth_weight) L_rgb + depth_weight mean|(D_z - gt_depth) valid|, the mean
     over all pixels (the form of the reference's Ll1depth, train.py:130; no count is read back), valid = (gt_depth > 0) &
     (A > alpha_min): pixels with a reading that the map covers (the mask is not differentiated).  gt_depth=None: the photometric
-    loss alone, exactly as before."""
-    from gaussian_renderer import render, PipelineParams
-    from .losses import l1_loss, training_loss_fused
+    loss alone, exactly as before.
+
+    `mask` [H,W] or [1,H,W] (a Frame's validity mask): multiplies `valid` and goes to render() as `alpha_mask` for the colour
+    loss.  `levels` = L > 0: coarse to fine over the FramePyramid of the targets - the same loop at level L, then L - 1 ... 0, the
+    camera re-pointed with set_intrinsics(scaled_camera(cam, l)), a fresh Adam and the learning-rate schedule restarted at every
+    level; `level_iters[l]` iterations at level l (default: `iters` at level 0, iters // 2 above); the losses of all levels are
+    returned in the order they ran.  levels=0 is the single-level loop, unchanged."""
+    from gaussian_renderer import PipelineParams
     if gt_depth is not None:
-        from fused_ssim import l1_mean_loss
         if not 0.0 <= float(depth_weight) <= 1.0:
             raise ValueError(f"depth_weight={depth_weight}: expected a value in [0, 1]")
         gt_depth = gt_depth.detach().float().reshape(1, *gt_image.shape[-2:]).contiguous()
-        has_reading = gt_depth > 0
     pc = cam if isinstance(cam, PoseCamera) else PoseCamera(cam, dtype=torch.float64, device="cpu")
     pipe = pipe or PipelineParams()
     if bg is None:
         bg = torch.zeros(3, dtype=torch.float32, device=gt_image.device)
+    kw = dict(lr=lr, lr_final=lr_final, lambda_dssim=lambda_dssim, bg=bg, pipe=pipe, separate_sh=separate_sh, callback=callback,
+              depth_weight=depth_weight, alpha_min=alpha_min)
+    if levels == 0 and level_iters is None:
+        history = _refine_level(pc, model, gt_image, gt_depth, mask, iters, **kw)
+        return pc.commit(), history
+    plan = _level_plan(iters, levels, level_iters)
+    pyr = _target_pyramid(pc, gt_image, gt_depth, mask, int(levels))
+    history = []
+    try:
+        for l, n in plan:
+            f = pyr[l]
+            pc.set_intrinsics(f.camera)
+            history += _refine_level(pc, model, f.image, None if gt_depth is None else f.depth.reshape(1, *f.depth.shape),
+                                     None if mask is None else f.mask, n, **kw)
+    finally:
+        pc.set_intrinsics(pyr[0].camera)
+    return pc.commit(), history
+
+
+def _refine_level(pc, model, gt_image, gt_depth, mask, iters, lr, lr_final, lambda_dssim, bg, pipe, separate_sh, callback,
+                  depth_weight, alpha_min):
+    """refine_pose's loop at one image size: a fresh torch Adam over pc.tau, `iters` iterations; -> the losses."""
+    from gaussian_renderer import render
+    from .losses import l1_loss, training_loss_fused
+    if gt_depth is not None:
+        from fused_ssim import l1_mean_loss
+        has_reading = gt_depth > 0
+        if mask is not None:
+            has_reading = has_reading & (mask.reshape(gt_depth.shape) > 0)
+    mkw = {} if mask is None else dict(alpha_mask=mask)
     opt = torch.optim.Adam([pc.tau], lr=lr)
     gamma = math.exp(math.log(lr_final / lr) / max(1, iters - 1)) if iters > 1 else 1.0
     history = []
     for it in range(iters):
         opt.zero_grad(set_to_none=True)
         if gt_depth is None:
-            image = render(pc, model, pipe, bg, separate_sh=separate_sh)["render"]
+            image = render(pc, model, pipe, bg, separate_sh=separate_sh, **mkw)["render"]
             loss = training_loss_fused(image, gt_image, lambda_dssim) if lambda_dssim > 0 else l1_loss(image, gt_image)
         else:
-            pkg = render(pc, model, pipe, bg, separate_sh=separate_sh, depth="z", alpha=True)
+            pkg = render(pc, model, pipe, bg, separate_sh=separate_sh, depth="z", alpha=True, **mkw)
             valid = (has_reading & (pkg["alpha"].detach() > alpha_min)).float()
             loss = l1_mean_loss(pkg["depth"], gt_depth, float(depth_weight), valid)
             if depth_weight < 1.0:
@@ -155,7 +223,7 @@ def refine_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambd
         history.append(float(loss.detach()))
         if callback is not None:
             callback(it, pc)
-    return pc.commit(), history
+    return history
 
 
 class _DevicePose(torch.autograd.Function):
@@ -213,9 +281,6 @@ class DevicePoseCamera:
         if device.type != "cuda":
             raise _C.GsrError("DevicePoseCamera keeps the pose on the HIP device (no CPU path): pass device='cuda' or a camera "
                               "whose tensors are there - PoseCamera is the host form")
-        self.image_width, self.image_height = int(cam.image_width), int(cam.image_height)
-        self.FoVx, self.FoVy = float(cam.FoVx), float(cam.FoVy)
-        self.znear, self.zfar = cam.znear, cam.zfar
         self.image_name = getattr(cam, "image_name", "")
         base = getattr(cam, "base_w2c", None)
         if base is not None and hasattr(cam, "w2c"):          # a PoseCamera / DevicePoseCamera: its corrected pose, in full precision
@@ -224,11 +289,18 @@ class DevicePoseCamera:
         else:
             base = wv.detach().transpose(0, 1)
         self.base_w2c = base.to(dtype=torch.float64, device=device).contiguous()
-        self.proj_T = projection_matrix(self.znear, self.zfar, self.FoVx, self.FoVy).transpose(0, 1).to(
-            dtype=torch.float64, device=device).contiguous()
+        self._cache = None         # (tau version, grad mode, the three tensors)
+        self.set_intrinsics(cam)
         self.tau = torch.zeros(6, dtype=torch.float64, device=device, requires_grad=requires_grad)
         self._adam = None          # device Adam state (gsr_pose_adam) while track_pose drives this camera
-        self._cache = None         # (tau version, grad mode, the three tensors)
+
+    def set_intrinsics(self, cam):
+        """Points this pose camera at the image size and projection of `cam` (any camera object: another pyramid level, say).
+        base_w2c, tau and the Adam state stay; the cached transforms are dropped."""
+        _copy_intrinsics(self, cam)
+        self.proj_T = camera_projection(self).transpose(0, 1).to(dtype=torch.float64, device=self.base_w2c.device).contiguous()
+        self._cache = None
+        return self
 
     def _transforms(self):
         key = (self.tau._version, torch.is_grad_enabled() and self.tau.requires_grad)
@@ -274,7 +346,7 @@ def _pose_adam_state(device, lr, lr_decay, betas=(0.9, 0.999), eps=1e-8):
 
 
 def track_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda_dssim=0.0, bg=None, pipe=None,
-               separate_sh=False, gt_depth=None, depth_weight=0.5, alpha_min=0.5):
+               separate_sh=False, gt_depth=None, depth_weight=0.5, alpha_min=0.5, levels=0, level_iters=None, mask=None):
     """`refine_pose` with the host taken out of the loop: same loss, masks, Adam and learning-rate schedule, the pose in a
     `DevicePoseCamera`.  Every iteration is gsr_pose_forward, render(..., camera_only=True) (with depth="z", alpha=True for
     RGB-D), the loss, its backward - the rasterizer's camera-only backward returns the three camera gradients and nothing per
@@ -283,28 +355,58 @@ def track_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda
     wait left is the forward's own instance-count check: the frames are rendered with forward_mode="exact", because a truncated
     unverified frame would hand Adam exact-zero gradients.  `cam`: a DevicePoseCamera (refined in place) or any camera (wrapped;
     its tensors, or `gt_image`, say which device).  Returns (the DevicePoseCamera with tau committed, losses: a DEVICE tensor
-    [iters], float32 - read it once, after the loop).  No `callback`: `refine_pose` stays for callers that need one."""
+    [iters], float32 - read it once, after the loop).  No `callback`: `refine_pose` stays for callers that need one.
+    `levels`, `level_iters`, `mask`: coarse-to-fine tracking and a Frame's validity mask, as in refine_pose (a fresh device Adam
+    state per level; `losses` then holds every level's, coarsest first)."""
     from diff_gaussian_rasterization import _C
-    from gaussian_renderer import render, PipelineParams
-    from .losses import l1_loss, training_loss_fused
+    from gaussian_renderer import PipelineParams
     if not torch.is_tensor(gt_image) or not gt_image.is_cuda:
         raise _C.GsrError("track_pose runs on the HIP device (no CPU path): gt_image must be a device tensor - refine_pose is "
                           "the host form")
     if gt_depth is not None:
-        from fused_ssim import l1_mean_loss
         if not 0.0 <= float(depth_weight) <= 1.0:
             raise ValueError(f"depth_weight={depth_weight}: expected a value in [0, 1]")
         gt_depth = gt_depth.detach().float().reshape(1, *gt_image.shape[-2:]).contiguous()
-        has_reading = gt_depth > 0
     pc = cam if isinstance(cam, DevicePoseCamera) else DevicePoseCamera(cam, device=gt_image.device)
     pipe = pipe or PipelineParams()
     if bg is None:
         bg = torch.zeros(3, dtype=torch.float32, device=gt_image.device)
+    kw = dict(lr=lr, lr_final=lr_final, lambda_dssim=lambda_dssim, bg=bg, pipe=pipe, separate_sh=separate_sh,
+              depth_weight=depth_weight, alpha_min=alpha_min)
+    if levels == 0 and level_iters is None:
+        losses = _track_level(pc, model, gt_image, gt_depth, mask, iters, **kw)
+        return pc.commit(), losses
+    plan = _level_plan(iters, levels, level_iters)
+    pyr = _target_pyramid(pc, gt_image, gt_depth, mask, int(levels))
+    losses = []
+    try:
+        for l, n in plan:
+            f = pyr[l]
+            pc.set_intrinsics(f.camera)
+            losses.append(_track_level(pc, model, f.image, None if gt_depth is None else f.depth.reshape(1, *f.depth.shape),
+                                       None if mask is None else f.mask, n, **kw))
+    finally:
+        pc.set_intrinsics(pyr[0].camera)
+    return pc.commit(), torch.cat(losses)
+
+
+def _track_level(pc, model, gt_image, gt_depth, mask, iters, lr, lr_final, lambda_dssim, bg, pipe, separate_sh, depth_weight,
+                 alpha_min):
+    """track_pose's loop at one image size: a fresh device Adam state, `iters` iterations; -> the losses (device tensor)."""
+    from gaussian_renderer import render
+    from .losses import l1_loss, training_loss_fused
+    if gt_depth is not None:
+        from fused_ssim import l1_mean_loss
+        has_reading = gt_depth > 0
+        if mask is not None:
+            has_reading = has_reading & (mask.reshape(gt_depth.shape) > 0)
     gamma = math.exp(math.log(lr_final / lr) / max(1, iters - 1)) if iters > 1 else 1.0
     losses = torch.zeros(iters, dtype=torch.float32, device=gt_image.device)
     pc._adam = _pose_adam_state(pc.tau.device, lr, gamma)
     pc._cache = None
     kw = dict(separate_sh=separate_sh, camera_only=True, forward_mode="exact")
+    if mask is not None:
+        kw["alpha_mask"] = mask
     try:
         for it in range(iters):
             if gt_depth is None:
@@ -323,4 +425,4 @@ def track_pose(cam, model, gt_image, iters=100, lr=3e-3, lr_final=1.5e-4, lambda
     finally:
         pc._adam = None
         pc._cache = None
-    return pc.commit(), losses
+    return losses

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .cameras import MiniCam, projection_matrix
+from .cameras import MiniCam, camera_projection
 from .model import GaussianModel
 
 _MOVED_GROUPS = ("_xyz", "_rotation", "_scaling", "_features_rest")      # the order of gsr_transform_gaussians' moments8
@@ -204,8 +204,8 @@ def transform_(self, T, ids=None, moments="reset", check=None, allow_scale=False
 def transform_camera(cam, T) -> MiniCam:
     """The camera that sees the map moved by T (x' = s R x + t) as `cam` saw the old one: R_c' = R_c R^T, centre c' = s R c + t.
     The world-to-camera matrix stays rigid, so a point's view-space coordinates - its depth too - come out s times the old ones
-    and its pixel is the same.  Intrinsics, image size, znear / zfar and the construction of full_proj_transform are those of
-    scene_utils.cameras.camera_from_RT.  Computed in float64 on the host; the result has `cam`'s dtype and device."""
+    and its pixel is the same.  Intrinsics (the principal point too), image size, znear / zfar and the construction of
+    full_proj_transform are those of scene_utils.cameras.camera_from_RT.  Computed in float64 on the host; the result has `cam`'s dtype and device."""
     if isinstance(T, torch.Tensor):
         T = T.detach().cpu().numpy()
     s, R, t = decompose(np.asarray(T, dtype=np.float64).reshape(4, 4))
@@ -218,10 +218,13 @@ def transform_camera(cam, T) -> MiniCam:
     new = np.eye(4)
     new[:3, :3], new[:3, 3] = Rc2, -Rc2 @ c2
     wv2 = torch.tensor(new, dtype=torch.float64).to(wv.dtype).transpose(0, 1)
-    proj = projection_matrix(cam.znear, cam.zfar, cam.FoVx, cam.FoVy).to(wv.dtype).transpose(0, 1)
+    proj = camera_projection(cam).to(wv.dtype).transpose(0, 1)
     full = wv2.unsqueeze(0).bmm(proj.unsqueeze(0)).squeeze(0)
-    return MiniCam(cam.image_width, cam.image_height, cam.FoVy, cam.FoVx, cam.znear, cam.zfar, wv2.to(wv.device),
-                   full.to(wv.device), cam.image_name)
+    out = MiniCam(cam.image_width, cam.image_height, cam.FoVy, cam.FoVx, cam.znear, cam.zfar, wv2.to(wv.device),
+                  full.to(wv.device), cam.image_name, ox=float(getattr(cam, "ox", 0.0)), oy=float(getattr(cam, "oy", 0.0)))
+    if hasattr(cam, "fx"):
+        out.fx, out.fy, out.cx, out.cy = cam.fx, cam.fy, cam.cx, cam.cy
+    return out
 
 
 def correct_keyframes(model, cams, corrections, **kw):

@@ -42,6 +42,8 @@ extern "C" {
  *    gsr_backward_camera_only (+ _ex), gsr_pose_adam, gsr_pose_forward, gsr_pose_backward: pose tracking on the device;
  *    gsr_exposure_adam, gsr_exposure_blocks, gsr_exposure_forward, gsr_exposure_backward: per-view exposure and alpha mask;
  *    gsr_transform_workspace_bytes, gsr_transform_gaussians: the map follows keyframe pose corrections (SH bands rotated);
+ *    gsr_unproject_params_k, gsr_unproject_rgbd_k (back-projection with a principal point), gsr_frame_undistort,
+ *    gsr_frame_pyramid: frames of a real sensor - K-matrix cameras, undistortion, validity mask, image / depth pyramid;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -576,6 +578,58 @@ int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth /*[H,W]
                        const float* alpha /*[H,W] or NULL*/, const float* rendered_z /*[H,W] or NULL*/, float* xyz /*[capacity,3]*/,
                        float* rgb /*[capacity,3]*/, int64_t capacity, int64_t* count_dev, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* The same call for a camera whose principal point is not the image centre: ox, oy are the offsets the projection matrix carries
+ * in P[0,2], P[1,2] - ox = (2 cx - (W - 1)) / W for a principal point cx in pixel-index coordinates (centre of pixel (0,0) at (0,0)),
+ * the same for y - and p_view = ((ndc_x - ox) tanfovx d, (ndc_y - oy) tanfovy d, d), each step rounded to float32 on its own.
+ * ox = oy = 0 gives the points of gsr_unproject_rgbd bit for bit.  |ox| or |oy| > 1 (or not finite): GSR_ERR_INVALID_ARGUMENT. */
+typedef struct gsr_unproject_params_k {
+  gsr_unproject_params base;
+  float ox, oy;
+} gsr_unproject_params_k;
+int gsr_unproject_rgbd_k(const gsr_unproject_params_k* p, const float* depth, const float* color, const float* alpha,
+                         const float* rendered_z, float* xyz, float* rgb, int64_t capacity, int64_t* count_dev, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ---- sensor frames: undistortion, validity mask, image / depth pyramid (csrc/frames.hip) ---- */
+
+/* Resamples a distorted sensor frame onto an ideal pinhole image, ONE launch.  Intrinsics are HOST arrays K = (fx, fy, cx, cy) in
+ * pixels with the centre of pixel (0,0) at (0,0); `dist` HOST (k1, k2, p1, p2, k3), the Brown-Conrady ("plumb_bob") model; `K` ==
+ * NULL: the target has the source's K.  Source: `src_color` [3,src_h,src_w], `src_depth` [src_h,src_w] view-space z (0 = no reading)
+ * or NULL (then `depth` is not written and may be NULL).  Target: `color` [3,h,w], `depth` [h,w], `mask` [h,w].
+ * For the target pixel (u, v), every operation rounded to float32 on its own, in this order (no contraction):
+ *   x = (u - cx') / fx',  y = (v - cy') / fy';   x2 = x x,  y2 = y y,  xy = x y,  r2 = x2 + y2;
+ *   rho = 1 + r2 (k1 + r2 (k2 + r2 k3))                                   (Horner form of 1 + k1 r^2 + k2 r^4 + k3 r^6);
+ *   xd = (x rho + (2 p1) xy) + p2 (r2 + 2 x2),   yd = (y rho + p1 (r2 + 2 y2)) + (2 p2) xy;
+ *   us = fx xd + cx,  vs = fy yd + cy.
+ * All-zero `dist` with a target K equal to the source K: the map is the identity, us = u, vs = v exactly.
+ * mask = 1 iff 0 <= us <= src_w - 1 and 0 <= vs <= src_h - 1, i.e. the bilinear taps x0 = floor(us), x1 = ceil(us), y0 = floor(vs),
+ * y1 = ceil(vs) all lie inside the source (on an integer coordinate the taps coincide); elsewhere mask, colour and depth are 0.
+ * colour: ax = us - x0, ay = vs - y0;  top = c(y0,x0) + ax (c(y0,x1) - c(y0,x0)),  bot = the same on row y1,  out = top + ay (bot - top)
+ *   - at integer coordinates the source pixel, bit for bit.
+ * depth: the source value at (floor(us + 0.5), floor(vs + 0.5)) - the nearest pixel, halves rounded up; never blended; z-depth is
+ *   what undistortion leaves unchanged, so the value is copied (0 stays 0).
+ * No atomics, nothing read back.  Errors before the launch, GSR_ERR_INVALID_ARGUMENT: a NULL src_color / src_K / dist / color / mask,
+ * src_depth without depth, a side < 1 or more than 2^30 pixels, a focal length that is not > 0, a coefficient that is not finite. */
+int gsr_frame_undistort(int32_t src_w, int32_t src_h, const float* src_color, const float* src_depth, const float* src_K,
+                        const float* dist, int32_t w, int32_t h, const float* K, float* color, float* depth, float* mask,
+                        void* stream);
+
+/* Levels 1 .. `levels` (<= 3) of the pyramid of an image [3,h,w], its depth [h,w] (or NULL) and its mask [h,w] (or NULL), ONE launch:
+ * level l is w_l x h_l = (w_(l-1) / 2) x (h_(l-1) / 2), integer division - a trailing odd row or column is dropped - and its pixel
+ * (X, Y) comes from the quad a = (2X, 2Y), b = (2X+1, 2Y), c = (2X, 2Y+1), d = (2X+1, 2Y+1) of the level below:
+ *   colour  ((a + b) + (c + d)) 0.25, float32, in that order;
+ *   depth   the valid readings are those > 0; m = the smallest; the result is the mean of the valid readings <= m (1 + depth_band)
+ *           (the product rounded once), summed in the order a, b, c, d and divided by their count; 0 if none is valid: the near
+ *           surface survives at a depth edge, a hole does not pull a reading towards 0;
+ *   mask    1 iff all four are 1, else 0.
+ * A workgroup reads one 32 x 32 block of level 0 once and writes its part of every level (coarser levels reduced through LDS).
+ * color_out / depth_out / mask_out: HOST arrays of `levels` device pointers (level 1 first); depth_out / mask_out may be NULL where
+ * the input is.  Errors before the launch, GSR_ERR_INVALID_ARGUMENT: levels outside 1 .. 3, a level whose side would reach 0
+ * (w >> levels or h >> levels == 0), NULL color / color_out or a NULL entry, depth without depth_out (mask alike),
+ * depth_band not >= 0. */
+int gsr_frame_pyramid(int32_t w, int32_t h, int32_t levels, const float* color, const float* depth, const float* mask,
+                      float depth_band, float* const* color_out, float* const* depth_out, float* const* mask_out, void* stream);
 
 /* ---- tracking: the camera pose as an SE(3) correction, on the device ---- */
 
