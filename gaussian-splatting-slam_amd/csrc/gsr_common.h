@@ -289,6 +289,14 @@ int gsr_radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1,
 // head_zeroed: the caller guarantees that the first GSR_RADIX_HEAD_WORDS words of `tmp` are zero when the sort's first kernel
 // starts (an earlier kernel of the same stream cleared them); otherwise the sort enqueues a memset of its own.
 
+// knn.hip, for pointcloud.hip
+// Bounding box of the finite coordinates of P points -> bbox[6] = min xyz, max xyz (+inf / -inf where nothing is finite);
+// `part`: gsr_knn_bbox_part_bytes() of scratch.
+void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipStream_t st);
+size_t gsr_knn_bbox_part_bytes();
+// The launches of gsr_knn_k on checked arguments; `workspace`: gsr_knn_k_workspace_bytes(P).
+void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st);
+
 // -------------------------------------------------------------------------------------------------
 // device helpers
 // -------------------------------------------------------------------------------------------------

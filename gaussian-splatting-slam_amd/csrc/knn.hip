@@ -25,6 +25,12 @@
 //   Non-finite coordinates never enter the bounding box, get Morton code 0 where the quantisation is undefined, and fail every
 //   `<` comparison: no hang, no out-of-bounds access, unspecified values for those rows.
 //
+// gsr_knn_k: the same search for k = 1 .. 32 neighbours - every squared distance in ascending order and / or the mean of their
+//   square roots (what a statistical outlier filter thresholds; csrc/pointcloud.hip).  The per-thread list is knn_insert
+//   generalised: a fully unrolled compare-exchange chain over a compile-time size K in {4, 8, 16, 32}, the smallest that holds k.
+//   The K - k slots that are not needed start at -inf and stay at the head of the list, so list[K - 1] is the k-th smallest
+//   candidate - the same pruning threshold a list of exactly k entries would give - and no register is ever indexed at run time.
+//
 // gsr_unproject_rgbd: strided pixels of a depth image -> world-space points + colours, selected by validity and (optionally) by
 //   what the map's render of the same view does not explain, compacted in row-major pixel order by a prefix sum.
 #include "gsr_common.h"
@@ -292,6 +298,91 @@ __global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, cons
   }
 }
 
+// ---- k = 1 .. 32 ------------------------------------------------------------------------------------------------------------
+// knn_insert over K slots, ascending: d bubbles up the chain, every index a compile-time constant (registers, no scratch)
+template <int K>
+__device__ __forceinline__ void knn_insert_k(float d, float (&b)[K]) {
+  if (d < b[K - 1]) {      // (false for NaN)
+    float t = d;
+#pragma unroll
+    for (int i = 0; i < K - 1; i++) {
+      const float hi = fmaxf(b[i], t);
+      b[i] = fminf(b[i], t);
+      t = hi;
+    }
+    b[K - 1] = fminf(b[K - 1], t);
+  }
+}
+template <int K>
+__device__ __forceinline__ void knn_reset_k(float (&b)[K], int pad) {      // `pad` = K - k leading slots at -inf, the rest +inf
+#pragma unroll
+  for (int i = 0; i < K; i++) b[i] = i < pad ? -KNN_INF : KNN_INF;
+}
+
+// one thread per query, as k_knn_query (every row is a query); dist2 [P,k] and / or mean [P] in ORIGINAL row order
+template <int K>
+__global__ __launch_bounds__(256) void k_knn_query_k(uint32_t P, int k, const float4* __restrict__ pts,
+                                                     const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
+                                                     uint32_t nbox, const float4* __restrict__ sup_lo,
+                                                     const float4* __restrict__ sup_hi, uint32_t nsuper,
+                                                     float* __restrict__ dist2, float* __restrict__ mean) {
+  __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  const bool active = q < P;
+  const uint32_t pos = active ? q : 0u;
+  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  const int pad = K - k;
+  float b[K];
+  knn_reset_k<K>(b, pad);
+  if (active) {
+    const uint32_t kk = (uint32_t)k;
+    const uint32_t j0 = pos >= kk ? pos - kk : 0u, j1 = min(P - 1u, pos + kk);
+    for (uint32_t j = j0; j <= j1; j++)
+      if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
+  }
+  // an upper bound of the k-th nearest distance (inf with fewer than k candidates); the sweep starts from an empty list again
+  const float bound = b[K - 1];
+  knn_reset_k<K>(b, pad);
+  for (uint32_t base = 0; base < nsuper; base += 256u) {
+    __syncthreads();
+    if (base + threadIdx.x < nsuper) {
+      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
+      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
+    }
+    __syncthreads();
+    if (!active) continue;
+    const uint32_t n = min(256u, nsuper - base);
+    for (uint32_t s = 0; s < n; s++) {
+      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b[K - 1], bound))) continue;
+      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
+      for (uint32_t bx = bb; bx < be; bx++) {
+        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= fminf(b[K - 1], bound))) continue;
+        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
+        for (uint32_t j = jb; j < je; j++)
+          if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
+      }
+    }
+  }
+  if (!active) return;
+  const size_t row = (size_t)__float_as_uint(me.w);
+  // a row with a non-finite coordinate has no neighbours: +inf distances, NaN mean (gsr_statistical_outliers drops it on that)
+  const bool finite = knn_finite(me.x) && knn_finite(me.y) && knn_finite(me.z);
+  if (dist2) {
+#pragma unroll
+    for (int i = 0; i < K; i++)
+      if (i >= pad) dist2[row * (size_t)k + (size_t)(i - pad)] = finite ? b[i] : KNN_INF;
+  }
+  if (mean) {
+    // the square roots summed in ascending order in float64; the divisor counts the point itself at distance 0
+    const uint32_t keff = min((uint32_t)k, P - 1u);
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; i++)
+      if (i >= pad && b[i] < KNN_INF) sum += sqrt((double)b[i]);
+    mean[row] = finite ? (float)(sum / (double)(keff + 1u)) : __builtin_nanf("");
+  }
+}
+
 // ---- RGB-D keyframe -> points -------------------------------------------------------------------------------------------------
 struct GsrUnprojectArgs {
   int H, W, Hs, Ws, stride;
@@ -394,6 +485,44 @@ static int unproject_rgbd(const gsr_unproject_params* p, float ox, float oy, con
   return gsr_launch_status("unproject_rgbd launch");
 }
 
+// bounding box of the finite coordinates -> bbox[6] (min xyz, max xyz; +inf / -inf without a finite value); part: float[1024][6]
+void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipStream_t st) {
+  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
+  const uint32_t bblk = nblk < (uint32_t)GSR_KNN_BBOX_BLOCKS ? nblk : (uint32_t)GSR_KNN_BBOX_BLOCKS;
+  GSR_LAUNCH("knn_bbox_partial", k_knn_bbox_partial, dim3(bblk), dim3(256), 0, st, n, points, part);
+  GSR_LAUNCH("knn_bbox_final", k_knn_bbox_final, dim3(1), dim3(256), 0, st, bblk, (const float*)part, bbox);
+}
+size_t gsr_knn_bbox_part_bytes() { return gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4); }
+
+// the launches of gsr_knn_k, arguments already checked (also the first stage of gsr_statistical_outliers, csrc/pointcloud.hip)
+void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st) {
+  const GsrKnnLayout L = knn_layout((size_t)P);
+  char* ws = (char*)workspace;
+  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
+  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
+  float* bbox = (float*)(ws + L.bbox);
+  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
+  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
+  float4* pts = (float4*)(ws + L.pts);
+  float4 *box_lo = (float4*)(ws + L.box_lo), *box_hi = (float4*)(ws + L.box_hi);
+  float4 *sup_lo = (float4*)(ws + L.sup_lo), *sup_hi = (float4*)(ws + L.sup_hi);
+  gsr_knn_bbox(P, points, (float*)(ws + L.bbox_part), bbox, st);
+  GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, key[0]);
+  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
+  GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)val[where], pts, box_lo, box_hi,
+             0u, (uint32_t*)nullptr);
+  GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)box_lo,
+             (const float4*)box_hi, sup_lo, sup_hi);
+#define KNN_QUERY_K(K)                                                                                                          \
+  GSR_LAUNCH("knn_query_k" #K, k_knn_query_k<K>, dim3(nblk), dim3(256), 0, st, n, k, (const float4*)pts, (const float4*)box_lo, \
+             (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, dist2, mean)
+  if (k <= 4) KNN_QUERY_K(4);
+  else if (k <= 8) KNN_QUERY_K(8);
+  else if (k <= 16) KNN_QUERY_K(16);
+  else KNN_QUERY_K(32);
+#undef KNN_QUERY_K
+}
+
 extern "C" {
 
 size_t gsr_knn_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1 : P)).total; }
@@ -423,9 +552,7 @@ int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* me
   uint32_t *qflag = (uint32_t*)(ws + L.qflag), *qpos = (uint32_t*)(ws + L.qpos), *qlist = (uint32_t*)(ws + L.qlist);
   const bool subset = first_query > 0;
 
-  const uint32_t bblk = nblk < (uint32_t)GSR_KNN_BBOX_BLOCKS ? nblk : (uint32_t)GSR_KNN_BBOX_BLOCKS;
-  GSR_LAUNCH("knn_bbox_partial", k_knn_bbox_partial, dim3(bblk), dim3(256), 0, st, n, points, part);
-  GSR_LAUNCH("knn_bbox_final", k_knn_bbox_final, dim3(1), dim3(256), 0, st, bblk, (const float*)part, bbox);
+  gsr_knn_bbox(P, points, part, bbox, st);
   GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, key[0]);
   const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
   GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)val[where], pts, box_lo, box_hi,
@@ -441,6 +568,24 @@ int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* me
              subset ? (const uint32_t*)qlist : (const uint32_t*)nullptr, (const float4*)pts, (const float4*)box_lo,
              (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, (uint32_t)first_query, mean_dist2);
   return gsr_launch_status("knn_dist2 launch");
+}
+
+size_t gsr_knn_k_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1 : P)).total; }
+
+int gsr_knn_k(int64_t P, const float* points, int32_t k, float* dist2_out, float* mean_dist_out, void* workspace,
+              size_t workspace_bytes, void* stream) {
+  if (P <= 0 || P > 0x3FFFFFFF || !points || !workspace || k < 1 || k > GSR_KNN_K_MAX || (!dist2_out && !mean_dist_out)) {
+    gsr_set_error("knn_k: bad arguments (P = %lld, k = %d: expected 1 .. %d and at least one output)", (long long)P, (int)k,
+                  GSR_KNN_K_MAX);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = knn_layout((size_t)P).total;
+  if (workspace_bytes < need) {
+    gsr_set_error("knn_k: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  gsr_knn_k_launch(P, points, (int)k, dist2_out, mean_dist_out, workspace, (hipStream_t)stream);
+  return gsr_launch_status("knn_k launch");
 }
 
 size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) { return unproject_workspace_bytes(W, H); }

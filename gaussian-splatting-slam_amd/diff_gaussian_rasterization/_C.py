@@ -183,6 +183,17 @@ EXPORTS = {
                                     C.c_void_p, C.POINTER(gsr_fused_adam), C.c_void_p]),
     "gsr_knn_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_knn_dist2": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, k, dist2_out, mean_dist_out, workspace + bytes, stream
+    "gsr_knn_k_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_knn_k": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, colors, voxel_size, origin (host), out_points, out_colors, out_npts, capacity, count_dev, workspace + bytes, stream
+    "gsr_voxel_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_voxel_down_sample": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, c_float_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, nb_neighbors, std_ratio, keep, mean_dist, stats_dev, workspace + bytes, stream
+    "gsr_outlier_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_statistical_outliers": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

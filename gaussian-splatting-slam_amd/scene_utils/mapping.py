@@ -24,12 +24,16 @@ def _as_tensor(a):
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
 
 
-def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0, anchor=None):
+def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0, anchor=None, voxel_size=None, nb_neighbors=None,
+                    std_ratio=2.0):
     """reference scene/gaussian_model.py:130-153.  `points` [P,3] / `colors` [P,3] in [0,1]: tensors or numpy arrays - or, as in
     the reference, one object with `.points` / `.colors` (its BasicPointCloud) as the first argument.  The points decide the
     device: arrays are moved to the HIP device as in the reference, tensors are used where they live and must live there - CPU
     tensors raise, there is no CPU path for the neighbour search.  `anchor`: the keyframe id the rows are labelled with
-    (model._anchor, scene_utils.transform; a model that tracks anchors labels them -1 without it).  Returns the model."""
+    (model._anchor, scene_utils.transform; a model that tracks anchors labels them -1 without it).  `voxel_size` /
+    `nb_neighbors` (+ `std_ratio`): condition the cloud first - voxel-grid down-sampling and / or the statistical outlier filter
+    (scene_utils.pointcloud.condition_point_cloud, the reference's process_point_cloud); None, the default, takes the cloud as it
+    is.  Returns the model."""
     if hasattr(points, "points") and hasattr(points, "colors"):
         if colors is not None:                       # (pcd, spatial_lr_scale): the reference's call form
             spatial_lr_scale = colors
@@ -41,6 +45,9 @@ def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0, anchor=None
     xyz, rgb = _as_tensor(points), _as_tensor(colors)
     if not xyz.is_cuda:
         raise _gsr().GsrError("create_from_pcd: points must be on the HIP device (the neighbour search has no CPU path)")
+    if voxel_size is not None or nb_neighbors is not None:
+        from .pointcloud import condition_point_cloud
+        xyz, rgb = condition_point_cloud(xyz, rgb.detach().to(xyz.device).float(), voxel_size, nb_neighbors, std_ratio)
     from simple_knn._C import distCUDA2
     self.spatial_lr_scale = float(spatial_lr_scale)
     dev = xyz.device
@@ -111,7 +118,8 @@ def unproject_rgbd(cam, image, depth, alpha=None, rendered_z=None, stride=1, min
     return xyz[:n], rgb[:n]
 
 
-def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, scale="knn", anchor=None, **selection):
+def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, scale="knn", anchor=None, voxel_size=None,
+                  voxel_origin=None, nb_neighbors=None, std_ratio=2.0, **selection):
     """Appends Gaussians for the pixels of an RGB-D keyframe that the map does not explain; returns how many.  `render_pkg`: the
     result of render(cam, self, ..., depth="z", alpha=True) (None: first keyframe, every valid reading is taken); `selection`:
     the keyword arguments of unproject_rgbd.  New rows: colour -> SH band 0, higher bands 0, identity rotation, opacity
@@ -121,7 +129,10 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
     and max_radii2D are extended with zeros (the old rows' statistics stay valid).  n == 0 changes nothing.  A model without
     parameters yet (GaussianModel(sh_degree)) is created from the keyframe.  `anchor`: the keyframe id the new rows are labelled
     with in model._anchor, so that a later pose correction of that keyframe can move them (scene_utils.transform); without it
-    they get -1 if the model tracks anchors."""
+    they get -1 if the model tracks anchors.  `voxel_size` (+ `voxel_origin`: one world-anchored lattice for every keyframe) /
+    `nb_neighbors` (+ `std_ratio`): the NEW points are conditioned (scene_utils.pointcloud.condition_point_cloud) before the
+    neighbour search that sizes them - one Gaussian per occupied voxel instead of one per pixel, depth-edge flying pixels
+    dropped; the map's rows are not touched.  None, the default: every selected pixel becomes a Gaussian."""
     _C = _gsr()
     if self._xyz is not None and not self._xyz.is_cuda:
         raise _C.GsrError("add_from_rgbd runs in HIP kernels (no CPU path): the model must live on the HIP device")
@@ -129,6 +140,9 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
         raise ValueError(f"scale={scale!r}: expected 'knn' or 'pixel'")
     if not 0.0 < float(init_opacity) < 1.0:
         raise ValueError(f"init_opacity={init_opacity}: expected a value in (0, 1)")
+    if voxel_size is not None or nb_neighbors is not None:
+        from .pointcloud import _check_conditioning
+        _check_conditioning(voxel_size, voxel_origin, nb_neighbors, std_ratio)
     alpha = rendered_z = None
     if render_pkg is not None:
         if "alpha" not in render_pkg:
@@ -136,6 +150,9 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
         alpha, rendered_z = render_pkg["alpha"], render_pkg["depth"]
     with torch.no_grad():
         xyz, rgb = unproject_rgbd(cam, image, depth, alpha=alpha, rendered_z=rendered_z, **selection)
+        if voxel_size is not None or nb_neighbors is not None:
+            from .pointcloud import condition_point_cloud
+            xyz, rgb = condition_point_cloud(xyz, rgb, voxel_size, nb_neighbors, std_ratio, origin=voxel_origin)
         n = int(xyz.shape[0])
         if n == 0:
             return 0

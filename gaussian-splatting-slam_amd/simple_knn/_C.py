@@ -1,5 +1,6 @@
 """The native surface of `simple_knn`: `distCUDA2(points)` as the reference calls it, and `knn_dist2(points, first_query)`,
-the same search answered only for the rows from `first_query` on (new points against map + new points)."""
+the same search answered only for the rows from `first_query` on (new points against map + new points); `knn_k(points, k)`,
+the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds)."""
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
@@ -25,6 +26,41 @@ def knn_dist2(points, first_query=0):
         ws = torch.empty(lib.gsr_knn_workspace_bytes(P), dtype=torch.uint8, device=pts.device)
         _gsr.check(lib.gsr_knn_dist2(P, _gsr.ptr(pts), first, _gsr.ptr(out), _gsr.ptr(ws), ws.numel(), _gsr._stream()))
     return out
+
+
+KNN_K_MAX = 32      # GSR_KNN_K_MAX of include/gsr.h
+
+
+def knn_k(points, k, return_dist2=True, return_mean=False):
+    """points [P,3] float on the HIP device, 1 <= k <= 32.  With k_eff = min(k, P - 1):
+    dist2 [P,k] float32: per row the k_eff smallest squared distances to the OTHER rows, ascending, then +inf;
+    mean [P] float32: (sum of their square roots) / (k_eff + 1) - the point itself counts at distance 0, as in a neighbour search
+    that returns the query; root and sum in float64 on the device, rounded once.  P == 1 gives 0.
+    Exact neighbours, the float32 distances of `knn_dist2` (k = 3: the three values whose mean it returns).  A row with a
+    non-finite coordinate gets +inf / NaN and is nobody's neighbour.  Returns dist2, mean, or (dist2, mean) as asked."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"k={k!r}: expected an int")
+    if not 1 <= k <= KNN_K_MAX:
+        raise ValueError(f"k={k}: expected 1 .. {KNN_K_MAX}")
+    if not (return_dist2 or return_mean):
+        raise ValueError("knn_k: nothing asked for (return_dist2 and return_mean both False)")
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise _gsr.GsrError("simple_knn needs a tensor on the HIP device (no CPU path)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points: expected [P, 3], got {tuple(points.shape)}")
+    pts = points.detach().float().contiguous()
+    P = int(pts.shape[0])
+    dist2 = torch.empty((P, k), dtype=torch.float32, device=pts.device) if return_dist2 else None
+    mean = torch.empty(P, dtype=torch.float32, device=pts.device) if return_mean else None
+    if P > 0:
+        lib = _gsr.lib()
+        with _gsr.on_device(pts.device):
+            ws = torch.empty(lib.gsr_knn_k_workspace_bytes(P), dtype=torch.uint8, device=pts.device)
+            _gsr.check(lib.gsr_knn_k(P, _gsr.ptr(pts), k, _gsr.ptr(dist2), _gsr.ptr(mean), _gsr.ptr(ws), ws.numel(),
+                                     _gsr._stream()))
+    if return_dist2 and return_mean:
+        return dist2, mean
+    return dist2 if return_dist2 else mean
 
 
 def distCUDA2(points):

@@ -44,6 +44,8 @@ extern "C" {
  *    gsr_transform_workspace_bytes, gsr_transform_gaussians: the map follows keyframe pose corrections (SH bands rotated);
  *    gsr_unproject_params_k, gsr_unproject_rgbd_k (back-projection with a principal point), gsr_frame_undistort,
  *    gsr_frame_pyramid: frames of a real sensor - K-matrix cameras, undistortion, validity mask, image / depth pyramid;
+ *    gsr_knn_k (k = 1 .. 32 neighbours), gsr_voxel_down_sample, gsr_statistical_outliers and their *_workspace_bytes queries:
+ *    point-cloud conditioning before a cloud seeds Gaussians;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -553,6 +555,57 @@ int gsr_sh_rank1_adam(int32_t P, int32_t n_ranks, int32_t sh_degree, int32_t sh_
 size_t gsr_knn_workspace_bytes(int64_t P);
 int gsr_knn_dist2(int64_t P, const float* points /*[P,3]*/, int64_t first_query, float* mean_dist2 /*[P - first_query]*/,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same exact search for k = 1 .. GSR_KNN_K_MAX neighbours, every row a query, answers in ORIGINAL row order.  With
+ * k_eff = min(k, P - 1):
+ *   dist2_out[i, 0 .. k_eff)  the k_eff smallest squared distances from row i to the OTHER rows, ascending (the same float32
+ *                             rounding sequence as gsr_knn_dist2: k = 3 gives the three values whose mean gsr_knn_dist2 returns);
+ *   dist2_out[i, k_eff .. k)  +inf;
+ *   mean_dist_out[i]          (sum of the square roots of those k_eff values) / (k_eff + 1): root and sum in float64 inside the
+ *                             kernel, rounded to float32 once.  The divisor counts the point itself at distance 0 - the average
+ *                             a statistical outlier filter takes over a neighbour search that returns the query too.  P == 1: 0.
+ * Either output may be NULL, not both.  A row with a non-finite coordinate gets +inf distances and a NaN mean and is nobody's
+ * neighbour.  Deterministic, no float atomics, no allocation (gsr_knn_k_workspace_bytes(P)).
+ * Errors before any launch: k outside [1, GSR_KNN_K_MAX], P <= 0 or > 2^30 - 1, NULL points / workspace, both outputs NULL:
+ * GSR_ERR_INVALID_ARGUMENT; workspace too small: GSR_ERR_STATE_TOO_SMALL. */
+#define GSR_KNN_K_MAX 32
+size_t gsr_knn_k_workspace_bytes(int64_t P);
+int gsr_knn_k(int64_t P, const float* points /*[P,3]*/, int32_t k, float* dist2_out /*[P,k] or NULL*/,
+              float* mean_dist_out /*[P] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- point-cloud conditioning: voxel-grid down-sampling, statistical outlier filter (csrc/pointcloud.hip; DESIGN.md section 4
+ * item 29) - what the reference's process_point_cloud does with Open3D before a cloud reaches create_from_pcd ---- */
+
+/* One averaged point per occupied voxel.  Lattice: per axis o_a = origin[a] (`origin`: HOST float[3]) or, with origin == NULL,
+ * o_a = min_a - 0.5 voxel_size (min_a: the smallest finite coordinate); cell index i_a = floor((p_a - o_a) / voxel_size) - one
+ * correctly rounded float32 operation each (subtract, divide, floor; 0.5 voxel_size is a float32 product), so a float32
+ * restatement assigns every point to the same voxel bit for bit.  Rows with a non-finite coordinate are dropped.  An index outside
+ * [-2^20, 2^20) on any axis sets count_dev[1] (status) non-zero and the other outputs are then meaningless.
+ * Output rows in ascending (i_z, i_y, i_x): mean position, mean colour (`colors` and `out_colors` both given, else neither is
+ * touched), `out_npts` (NULL: not wanted) the number of points of the voxel.  Sums in float64 in an order that depends on the
+ * sorted position only (the stable sort keeps a voxel's points in row order), mean formed in float64, rounded to float32 once.
+ * count_dev[0] = number of voxels (device int64; it may exceed `capacity`: rows beyond `capacity` are never written).
+ * Deterministic, no float atomics, no allocation (gsr_voxel_workspace_bytes(P)).
+ * Errors before any launch: voxel_size <= 0 or not finite, a non-finite origin, P <= 0 or > 2^30 - 1, capacity < 0, NULL points /
+ * count_dev / workspace, out_points NULL with capacity > 0, colors without out_colors (capacity > 0): GSR_ERR_INVALID_ARGUMENT;
+ * workspace too small: GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_voxel_workspace_bytes(int64_t P);
+int gsr_voxel_down_sample(int64_t P, const float* points /*[P,3]*/, const float* colors /*[P,3] or NULL*/, float voxel_size,
+                          const float* origin /*HOST [3] or NULL*/, float* out_points /*[capacity,3]*/,
+                          float* out_colors /*[capacity,3] or NULL*/, int32_t* out_npts /*[capacity] or NULL*/, int64_t capacity,
+                          int64_t* count_dev /*[2]: voxels, status*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Statistical outlier filter.  dbar_i = mean_dist_out of gsr_knn_k with k = nb_neighbors - 1 (nb_neighbors in [2, 33] counts the
+ * point itself); mu = mean of dbar over the n_valid rows whose dbar is finite (rows with a non-finite coordinate are not);
+ * sigma = sqrt(sum (dbar_i - mu)^2 / (n_valid - 1)), 0 with n_valid < 2; threshold = mu + std_ratio sigma - float64, from
+ * fixed-order per-workgroup partial sums and one final workgroup, never on the host.  keep[i] = dbar_i > 0 && dbar_i < threshold
+ * (0 for the non-finite rows).  stats_dev (device double[4], or NULL) = n_valid, mu, sigma, threshold; mean_dist (device
+ * float[P], or NULL) = dbar.  Errors before any launch: nb_neighbors outside [2, 33], std_ratio not finite, P <= 0 or > 2^30 - 1,
+ * NULL points / keep / workspace: GSR_ERR_INVALID_ARGUMENT; workspace too small: GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_outlier_workspace_bytes(int64_t P);
+int gsr_statistical_outliers(int64_t P, const float* points /*[P,3]*/, int32_t nb_neighbors, double std_ratio,
+                             uint8_t* keep /*[P]*/, float* mean_dist /*[P] or NULL*/, double* stats_dev /*[4] or NULL*/,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
