@@ -554,7 +554,8 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
     // (GSR_TILE_HIST=0: the round-3 chain, for the A/B).  The sort's head must be clear BEFORE the emission's workgroups add
     // to it: the projection kernel of this call did that, or (re-render on another binning state) a memset here.
     const char* th = getenv("GSR_TILE_HIST");
-    const bool fused_bins = tile_local && !(th && th[0] == '0');
+    // (the emission kernel's LDS histograms cover two passes = 16 tile bits: a frame of more than 65536 tiles takes the chain)
+    const bool fused_bins = tile_local && !(th && th[0] == '0') && tile_bits(tiles) <= 2 * GSR_RADIX_BITS;
     if (fused_bins && !sort_head_clean &&
         (rc = gsr_check(hipMemsetAsync(bin + BL.radix_tmp, 0, GSR_RADIX_HEAD_WORDS * 4, st), "memset sort head")))
       return rc;

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_emit_instances(int P, int grid_x, const
   // histograms (LDS, then one global add per non-zero counter into the replica blockIdx picks - gsr_common.h) and clears the
   // sort's look-back table: no k_radix_hist_all launch.  The head (histogram replicas + tickets) was zeroed by the PROJECTION
   // kernel, i.e. before any workgroup of this one can add to it.  hist_bits == 0: the head is zeroed here, for k_radix_hist_all.
-  const int hpasses = hist_bits > 0 ? gsr_radix_passes(hist_bits) : 0;     // (<= 2: tile ids have at most 16 bits)
+  const int hpasses = hist_bits > 0 ? gsr_radix_passes(hist_bits) : 0;     // (<= 2: api.hip asks for this form up to 16 tile-id bits only)
   if (hist_bits > 0) {
     for (int i = threadIdx.x; i < 2 * GSR_RADIX_SIZE; i += 256) lhist[i] = 0u;
     uint4* z = reinterpret_cast<uint4*>(sort_head + GSR_RADIX_HEAD_WORDS);      // look-back words of the sort's first pass
@@ -467,6 +467,19 @@ void gsr_launch_tile_depth_sort(int tiles, bool dual, uint2* ranges, const uint2
 #undef GSR_TLO
 }
 
+// test hook (include/gsr.h): the per-tile ordering on caller-made lists, without the walk-class counters
+extern "C" int gsr_debug_tile_depth_sort(int32_t tiles, int32_t dual, uint32_t* ranges, const uint32_t* ranges_enc,
+                                         uint32_t* point_list, uint32_t* slot_of_pos, const uint32_t* depth_key,
+                                         uint32_t* free_a, uint32_t* free_b, uint32_t* free_c, uint32_t* meta, void* stream) {
+  if (tiles <= 0 || !ranges || !point_list || !depth_key || !free_a || !free_b || !free_c || !meta || (dual && !slot_of_pos)) {
+    gsr_set_error("debug_tile_depth_sort: bad arguments");
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  gsr_launch_tile_depth_sort(tiles, dual != 0, (uint2*)ranges, (const uint2*)ranges_enc, point_list, dual ? slot_of_pos : nullptr,
+                             depth_key, free_a, free_b, free_c, meta, nullptr, (hipStream_t)stream);
+  return gsr_launch_status("debug tile depth sort");
+}
+
 // count_hist_bits > 0 (tile-local form, sort head zeroed by the projection kernel): the emission also counts the tile sort's
 // digit histograms and clears its look-back table; the encoded tile ranges (BL.ranges_enc) are what it zero-initialises then
 void gsr_launch_emit(int P, int grid_x, int tiles, char* geom, const GsrGeomLayout& GL, char* bin,
@@ -474,6 +487,10 @@ void gsr_launch_emit(int P, int grid_x, int tiles, char* geom, const GsrGeomLayo
                      const uint32_t* tile_cutoff, hipStream_t st) {
   // (the look-back words of the sort's FIRST pass; every pass clears the next one's itself - sort_scan.hip)
   const size_t lb_words = count_hist_bits > 0 ? (size_t)gsr_radix_blocks(cap) * GSR_RADIX_SIZE : 0;
+  if (count_hist_bits > 2 * GSR_RADIX_BITS) {     // the kernel's LDS histograms hold two passes: refuse, never read past them
+    gsr_note_launch_failure("emit_instances (fused histograms cover at most 16 tile-id bits)", hipErrorInvalidValue);
+    return;
+  }
   GSR_LAUNCH("emit_instances", k_emit_instances, dim3((P + 255) / 256), dim3(256), 0, st, P, grid_x,
              index_order ? (const uint32_t*)nullptr : (const uint32_t*)(geom + GL.order), (const uint32_t*)(geom + GL.offsets),
              (const uint32_t*)(geom + GL.tiles_touched),

@@ -513,3 +513,45 @@ int gsr_radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1,
   }
   return cur;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// test hooks (include/gsr.h): the scan on its own, and the sort in the form the tile-local binning uses
+// ---------------------------------------------------------------------------------------------------
+extern "C" size_t gsr_debug_scan_tmp_bytes(int64_t n) { return gsr_align(gsr_scan_tmp_elems((size_t)(n < 1 ? 1 : n)) * 4); }
+
+extern "C" int gsr_debug_scan_u32(const uint32_t* src, const uint32_t* idx, uint32_t* out, int64_t n, int32_t inclusive,
+                                  void* tmp, void* stream) {
+  if (n < 0 || n > 0xFFFFFFFFll || (n > 0 && (!src || !out || !tmp))) {
+    gsr_set_error("debug_scan_u32: bad arguments");
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  gsr_scan_u32(src, idx, out, (size_t)n, inclusive != 0, (uint32_t*)tmp, (hipStream_t)stream);
+  return gsr_launch_status("debug scan");
+}
+
+// The tile sort as gsr_forward_async(tile_local_sort = 1) runs it: histograms counted ahead of the passes (here by
+// k_radix_hist_all into replica 0, where the frame's emission kernel spreads them over all replicas), the counting kernel
+// clearing the look-back table of the FIRST pass only - like the emission kernel (gsr_launch_emit) -, every pass clearing the
+// next one's, the last pass leaving the encoded tile ranges instead of the sorted keys.
+extern "C" int gsr_debug_tile_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* w0, uint32_t* w1, int64_t n,
+                                   int32_t bits, int32_t vals_iota, const uint32_t* n_dev, uint32_t* ranges_enc, void* tmp,
+                                   void* stream) {
+  if (n < 0 || n > 0x3FFFFFFF || bits < 1 || bits > 24 || !k0 || !v0 || !k1 || !v1 || !ranges_enc || !tmp ||
+      (w0 == nullptr) != (w1 == nullptr)) {
+    gsr_set_error("debug_tile_sort: bad arguments");
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* head = (uint32_t*)tmp;
+  const int rc0 = gsr_check(hipMemsetAsync(head, 0, GSR_RADIX_HEAD_WORDS * 4, st), "memset sort head");
+  if (rc0) return rc0;
+  const uint32_t nblk = (uint32_t)gsr_radix_blocks((size_t)n);
+  const size_t lb_words = (size_t)nblk * GSR_RADIX_SIZE;      // pass 0's table; passes 1.. poll words only their predecessor cleared
+  GSR_LAUNCH("radix_hist", k_radix_hist_all, dim3(nblk < 256u ? nblk : 256u), dim3(256), 0, st, (const uint32_t*)k0, (size_t)n,
+             n_dev, (int)bits, head, head + GSR_RADIX_HEAD_WORDS, lb_words);
+  const int where = gsr_radix_sort_pairs(k0, v0, k1, v1, vals_iota != 0, (size_t)n, bits, head, st, w0, w1, n_dev,
+                                         /*head_zeroed=*/true, /*fail_flags=*/nullptr, /*hist_counted=*/true, (uint2*)ranges_enc);
+  const int rc = gsr_launch_status("debug tile sort");
+  return rc ? rc : where;
+}

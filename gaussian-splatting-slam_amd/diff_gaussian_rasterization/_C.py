@@ -148,6 +148,10 @@ EXPORTS = {
                                         C.c_void_p]),
     "gsr_debug_radix_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_debug_radix_sort": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_debug_scan_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_debug_scan_u32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gsr_debug_tile_sort": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "gsr_debug_tile_depth_sort": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "gsr_debug_image_views": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p)]),
     "gsr_debug_set_flags_min_r": (C.c_int64, [C.c_int64]),

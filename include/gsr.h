@@ -46,6 +46,8 @@ extern "C" {
  *    gsr_frame_pyramid: frames of a real sensor - K-matrix cameras, undistortion, validity mask, image / depth pyramid;
  *    gsr_knn_k (k = 1 .. 32 neighbours), gsr_voxel_down_sample, gsr_statistical_outliers and their *_workspace_bytes queries:
  *    point-cloud conditioning before a cloud seeds Gaussians;
+ *    gsr_debug_scan_tmp_bytes, gsr_debug_scan_u32, gsr_debug_tile_sort, gsr_debug_tile_depth_sort: test hooks of the binning stage's
+ *    integer building blocks;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -431,6 +433,28 @@ int gsr_debug_count_pairs(const gsr_settings* s, int32_t P, const void* geometry
 size_t gsr_debug_radix_tmp_bytes(int64_t n);
 int gsr_debug_radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* w0, uint32_t* w1, int64_t n,
                          int32_t bits, int32_t vals_iota, const uint32_t* n_dev, void* tmp, void* stream);
+/* test hook: the library's prefix sum (sort_scan.hip): out[i] = sum of src[idx ? idx[j] : j] over j < i (inclusive != 0: j <= i),
+ * modulo 2^32.  idx may be NULL; out may be src when idx is NULL.  tmp: gsr_debug_scan_tmp_bytes(n) bytes. */
+size_t gsr_debug_scan_tmp_bytes(int64_t n);
+int gsr_debug_scan_u32(const uint32_t* src, const uint32_t* idx, uint32_t* out, int64_t n, int32_t inclusive, void* tmp,
+                       void* stream);
+/* test hook: the same sort in the form the tile-local binning runs it (the digit histograms counted ahead of the passes, every
+ * pass clearing the next one's look-back table, the last pass leaving tile ranges instead of sorted keys).  Arguments as for
+ * gsr_debug_radix_sort, bits <= 24.  EVERY KEY MUST BE BELOW 2^bits (a tile id): the last pass indexes ranges_enc by the whole
+ * key, so a larger key writes out of bounds; the hook cannot check this.  tmp may hold anything (only the first pass's look-back
+ * table is cleared ahead of the passes, as in a frame).  ranges_enc: 2^bits pairs of uint32, zeroed by the caller; on return pair t holds
+ * (~first sorted position, last sorted position + 1) of key value t, (0, 0) where t does not occur.  The key buffer holding the
+ * result is NOT written by the last pass. */
+int gsr_debug_tile_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* w0, uint32_t* w1, int64_t n,
+                        int32_t bits, int32_t vals_iota, const uint32_t* n_dev, uint32_t* ranges_enc, void* tmp, void* stream);
+/* test hook: the tile-local binning's per-tile ordering (binning.hip k_tile_depth_sort) on caller-made lists.  ranges: `tiles`
+ * pairs [start, end) into point_list; with ranges_enc (pairs as gsr_debug_tile_sort leaves them) `ranges` is output only.  Every
+ * list is ordered by (depth_key[id], position in the list), id 0xFFFFFFFF counting as key 0xFFFFFFFF; dual != 0: slot_of_pos is
+ * permuted along.  free_a / free_b / free_c: scratch as long as point_list; meta: 8 words, meta[4] receives (by maximum) the
+ * longest list beyond 2048 entries. */
+int gsr_debug_tile_depth_sort(int32_t tiles, int32_t dual, uint32_t* ranges, const uint32_t* ranges_enc, uint32_t* point_list,
+                              uint32_t* slot_of_pos, const uint32_t* depth_key, uint32_t* free_a, uint32_t* free_b,
+                              uint32_t* free_c, uint32_t* meta, void* stream);
 int gsr_debug_image_views(const void* image_state, int32_t image_width, int32_t image_height,
                           const float** final_T, const uint32_t** n_contrib);
 /* The walk classes a forward with a backward to follow leaves in the image state (ABI 7): walk_cnt[classes] = tiles per class,

@@ -350,6 +350,50 @@ def test_lowlevel_async_call_matches_blocking_state(tlo, pinned, verify):
         assert int(status[2]) & 0xFFFFFFFF == (longest if longest > 2048 else 0)
 
 
+def test_lowlevel_async_frame_of_more_than_65536_tiles():
+    """A 4112 x 4096 frame has 257 x 256 = 65,792 tiles: 17 tile-id bits, a tile sort of three passes.  The emission kernel's
+    fused digit histograms cover two passes (16 bits), so from 65,537 tiles on the tile-local form takes the unfused chain
+    (k_radix_hist_all, k_finalize_bins); before that fix its third pass ranked against a histogram nobody had counted.  Both
+    binning forms must leave the blocking path's state: colour, lists (first R entries) and ranges, compared on the device."""
+    from diff_gaussian_rasterization import _C, _stream
+    P, W, H = 2000, 4112, 4096
+    a, lib, s, g, keep = _lowlevel_setup(P, W, H)
+    dev = "cuda"
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    assert tiles == 65_792
+    R = a["R"]
+    assert R > tiles                                       # (millions: the splats are hundreds of pixels wide at this size)
+    assert bool((torch.from_numpy(a["ranges"][65536:].astype("int64")).diff(dim=1) > 0).any())    # third digit not uniform
+    cap = R + 4099
+    want = {k: torch.from_numpy(a[k].view("int32").copy()).to(dev) for k in ("point_list", "ranges")}
+    want_color, want_invd = a["color"].to(dev), a["invdepth"].to(dev)
+    longest = int((a["ranges"][:, 1].astype("int64") - a["ranges"][:, 0]).max())
+    for tlo in (1, 0):
+        geom = torch.zeros(lib.gsr_geometry_state_bytes(P), dtype=torch.uint8, device=dev)
+        img = torch.zeros(lib.gsr_image_state_bytes(W, H), dtype=torch.uint8, device=dev)
+        binning = torch.zeros(lib.gsr_binning_state_bytes(P, W, H, cap), dtype=torch.uint8, device=dev)
+        radii = torch.zeros(P, dtype=torch.int32, device=dev)
+        color, invd = torch.empty(3, H, W, device=dev), torch.empty(1, H, W, device=dev)
+        status = torch.zeros(4, dtype=torch.int64).pin_memory()
+        _C.check(lib.gsr_forward_async(C.byref(s), C.byref(g), _C.ptr(geom), geom.numel(), _C.ptr(radii), _C.ptr(binning),
+                                       binning.numel(), cap, _C.ptr(img), img.numel(), _C.ptr(color), _C.ptr(invd), 1, 0, None,
+                                       C.c_void_p(status.data_ptr()), tlo, _stream(), None))
+        torch.cuda.synchronize()
+        assert int(status[1]) == R and int(status[0]) & 0xFFFFFFFF == 0, tlo
+        pb = [C.c_void_p() for _ in range(2)]
+        lib.gsr_debug_binning_views(_C.ptr(binning), W, H, cap, C.byref(pb[0]), C.byref(pb[1]))
+        off_pl, off_rg = pb[0].value - binning.data_ptr(), pb[1].value - binning.data_ptr()
+        pl = binning[off_pl:off_pl + 4 * R].view(torch.int32)
+        rg = binning[off_rg:off_rg + 8 * tiles].view(torch.int32).view(tiles, 2)
+        assert torch.equal(rg, want["ranges"]), tlo
+        assert torch.equal(pl, want["point_list"]), tlo
+        assert torch.equal(color, want_color) and torch.equal(invd, want_invd), tlo
+        if tlo:      # the longest tile list, reported by the per-tile ordering once it passes 2048 entries
+            assert int(status[2]) & 0xFFFFFFFF == (longest if longest > 2048 else 0)
+        assert torch.equal(radii.cpu(), a["radii"]), tlo
+        del geom, img, binning, color, invd
+
+
 @pytest.mark.parametrize("tlo", [0, 1])
 def test_lowlevel_verified_overflow_then_rerender_matches_blocking_state(tlo):
     """gsr_forward_async(num_rendered_out) with a third of the needed capacity reports the true count; gsr_forward_rerender on a

@@ -84,6 +84,30 @@ def test_densify_matches_reference_semantics(max_screen_size):
     assert abs(float((z[:half] * z[half:]).mean())) < 0.05
 
 
+@pytest.mark.parametrize("P", [8193, 20_000])
+def test_densify_plan_beyond_one_scan_workgroup(P):
+    """gsr_densify_plan's three prefix sums take the single-workgroup paths up to 8192 rows; from 8193 on they are reduce ->
+    scan of the chunk sums -> apply, the form every real map uses.  Counts and source rows against the oracle there."""
+    model, opt, accum, den = _setup(P=P, seed=5)
+    params = {n: getattr(model, a).detach().cpu().clone() for n, a in zip(NAMES, ATTRS)}
+    moments = {}
+    for n, a in zip(NAMES, ATTRS):
+        st = opt.state[getattr(model, a)]
+        moments[n] = (st["exp_avg"].cpu().clone(), st["exp_avg_sq"].cpu().clone())
+    extent, thr, min_op = 15.0, 0.0004, 0.005
+    ref_p, ref_m, info = DO.densify_and_prune(params, moments, accum.clone(), den.clone(), model.max_radii2D.cpu().clone(), thr,
+                                              min_op, extent, 20, model.percent_dense, normal_samples=None)
+    nk, nc, ns, src = model.densify_and_prune(thr, min_op, extent, 20, None, seed=11, return_source=True)
+    kind = info["kind"]
+    assert (nk, nc, 2 * ns) == (int((kind == 0).sum()), int((kind == 1).sum()), int((kind == 2).sum()))
+    assert nk > 100 and nc > 100 and ns > 100
+    assert torch.equal(src.cpu().long(), info["source"])                       # same rows, same order
+    assert model.get_xyz.shape[0] == nk + nc + 2 * ns
+    det = kind != 2                                                            # kept rows and clones: copied values exact
+    for n, a in zip(NAMES, ATTRS):
+        assert torch.equal(getattr(model, a).detach().cpu()[det], ref_p[n][det]), n
+
+
 def test_densify_without_optimizer_state_and_reset_opacity():
     model, opt, accum, den = _setup(P=1500, with_moments=False)
     before = model.get_opacity.detach().clone()
