@@ -33,11 +33,7 @@
 //
 // gsr_unproject_rgbd: strided pixels of a depth image -> world-space points + colours, selected by validity and (optionally) by
 //   what the map's render of the same view does not explain, compacted in row-major pixel order by a prefix sum.
-#include "gsr_common.h"
-
-#define GSR_KNN_BOX 64
-#define GSR_KNN_SUPER 64
-#define GSR_KNN_BBOX_BLOCKS 1024
+#include "knn_common.h"
 
 struct GsrKnnLayout {
   size_t bbox_part;   // float[GSR_KNN_BBOX_BLOCKS][6]
@@ -51,9 +47,6 @@ struct GsrKnnLayout {
   size_t radix_tmp;
   size_t total;
 };
-
-static inline size_t knn_nbox(size_t P) { return (P + GSR_KNN_BOX - 1) / GSR_KNN_BOX; }
-static inline size_t knn_nsuper(size_t P) { return (knn_nbox(P) + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER; }
 
 static inline GsrKnnLayout knn_layout(size_t P) {
   GsrKnnLayout L;
@@ -77,21 +70,6 @@ static inline GsrKnnLayout knn_layout(size_t P) {
   L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
   L.total = o;
   return L;
-}
-
-#define KNN_INF __builtin_huge_valf()
-
-__device__ __forceinline__ bool knn_finite(float x) { return fabsf(x) < KNN_INF; }   // false for NaN and +-inf
-
-__device__ __forceinline__ float knn_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float knn_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // min / max of six per-thread values over a 256-thread workgroup -> out[6] (thread 0 writes)
@@ -146,27 +124,11 @@ __global__ __launch_bounds__(256) void k_knn_bbox_final(uint32_t nblk, const flo
   knn_block_minmax(lo, hi, bbox);
 }
 
-__device__ __forceinline__ uint32_t knn_spread10(uint32_t x) {      // 10 bits -> every third bit of 30
-  x = (x | (x << 16)) & 0x030000FFu;
-  x = (x | (x << 8)) & 0x0300F00Fu;
-  x = (x | (x << 4)) & 0x030C30C3u;
-  x = (x | (x << 2)) & 0x09249249u;
-  return x;
-}
-// (v - lo) / (hi - lo) on a 1024-cell axis; NaN (a flat axis: 0 / 0, a non-finite coordinate) and negatives give cell 0
-__device__ __forceinline__ uint32_t knn_cell(float v, float lo, float hi) {
-  const float t = (v - lo) / (hi - lo) * 1023.0f;
-  return t >= 0.f ? (uint32_t)fminf(t, 1023.0f) : 0u;
-}
-
 __global__ __launch_bounds__(256) void k_knn_morton(uint32_t P, const float* __restrict__ pts, const float* __restrict__ bbox,
                                                     uint32_t* __restrict__ codes) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= P) return;
-  const uint32_t cx = knn_cell(pts[3 * (size_t)i], bbox[0], bbox[3]);
-  const uint32_t cy = knn_cell(pts[3 * (size_t)i + 1], bbox[1], bbox[4]);
-  const uint32_t cz = knn_cell(pts[3 * (size_t)i + 2], bbox[2], bbox[5]);
-  codes[i] = knn_spread10(cx) | (knn_spread10(cy) << 1) | (knn_spread10(cz) << 2);
+  codes[i] = knn_morton_code(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], bbox);
 }
 
 // one wave per box: gathers its 64 points into sorted order and reduces their AABB
@@ -223,21 +185,6 @@ __global__ __launch_bounds__(256) void k_knn_compact(uint32_t P, const uint32_t*
   if (j < P && qflag[j]) qlist[qpos[j]] = j;
 }
 
-// the one rounding sequence of every squared distance, point or box (see the header: the pruning relies on it)
-__device__ __forceinline__ float knn_sq(float dx, float dy, float dz) {
-  return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
-}
-__device__ __forceinline__ float knn_point_d2(const float4 q, const float4 p) {
-  return knn_sq(__fsub_rn(q.x, p.x), __fsub_rn(q.y, p.y), __fsub_rn(q.z, p.z));
-}
-__device__ __forceinline__ float knn_box_d2(const float4 q, const float4 lo, const float4 hi) {
-  // per axis max(q - hi, lo - q, 0) = |q - nearest point of the interval|; for a point p of the box |q - p| is at least that,
-  // and stays so after rounding
-  const float dx = fmaxf(0.f, fmaxf(__fsub_rn(q.x, hi.x), __fsub_rn(lo.x, q.x)));
-  const float dy = fmaxf(0.f, fmaxf(__fsub_rn(q.y, hi.y), __fsub_rn(lo.y, q.y)));
-  const float dz = fmaxf(0.f, fmaxf(__fsub_rn(q.z, hi.z), __fsub_rn(lo.z, q.z)));
-  return knn_sq(dx, dy, dz);
-}
 __device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float& b2) {
   if (d < b2) {      // (false for NaN: it never enters the min / max network below)
     const float t0 = fmaxf(b0, d);
@@ -494,25 +441,35 @@ void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipS
 }
 size_t gsr_knn_bbox_part_bytes() { return gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4); }
 
+// the structure over a cloud (knn_common.h): what every search here starts with
+void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st) {
+  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u, nbox = (uint32_t)knn_nbox(n);
+  gsr_knn_bbox(P, points, b.bbox_part, b.bbox, st);
+  GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)b.bbox, b.key[0]);
+  const int where = gsr_radix_sort_pairs(b.key[0], b.val[0], b.key[1], b.val[1], true, (size_t)n, 30, b.radix_tmp, st);
+  GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)b.val[where], b.pts, b.box_lo,
+             b.box_hi, 0u, (uint32_t*)nullptr);
+  GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)b.box_lo,
+             (const float4*)b.box_hi, b.sup_lo, b.sup_hi);
+}
+
 // the launches of gsr_knn_k, arguments already checked (also the first stage of gsr_statistical_outliers, csrc/pointcloud.hip)
 void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st) {
   const GsrKnnLayout L = knn_layout((size_t)P);
   char* ws = (char*)workspace;
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
   const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
-  float* bbox = (float*)(ws + L.bbox);
-  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
-  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
   float4* pts = (float4*)(ws + L.pts);
   float4 *box_lo = (float4*)(ws + L.box_lo), *box_hi = (float4*)(ws + L.box_hi);
   float4 *sup_lo = (float4*)(ws + L.sup_lo), *sup_hi = (float4*)(ws + L.sup_hi);
-  gsr_knn_bbox(P, points, (float*)(ws + L.bbox_part), bbox, st);
-  GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, key[0]);
-  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
-  GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)val[where], pts, box_lo, box_hi,
-             0u, (uint32_t*)nullptr);
-  GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)box_lo,
-             (const float4*)box_hi, sup_lo, sup_hi);
+  GsrKnnBuild b;
+  b.bbox_part = (float*)(ws + L.bbox_part);
+  b.bbox = (float*)(ws + L.bbox);
+  b.key[0] = (uint32_t*)(ws + L.key_a); b.key[1] = (uint32_t*)(ws + L.key_b);
+  b.val[0] = (uint32_t*)(ws + L.val_a); b.val[1] = (uint32_t*)(ws + L.val_b);
+  b.radix_tmp = (uint32_t*)(ws + L.radix_tmp);
+  b.pts = pts; b.box_lo = box_lo; b.box_hi = box_hi; b.sup_lo = sup_lo; b.sup_hi = sup_hi;
+  gsr_knn_build(P, points, b, st);
 #define KNN_QUERY_K(K)                                                                                                          \
   GSR_LAUNCH("knn_query_k" #K, k_knn_query_k<K>, dim3(nblk), dim3(256), 0, st, n, k, (const float4*)pts, (const float4*)box_lo, \
              (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, dist2, mean)

@@ -1,0 +1,530 @@
+// registration.hip - rigid registration of one point cloud to another: what the reference does with Open3D's point-to-point ICP
+// (convert_visual_merged_msg.py:187-249 pointcloud_registeration, :393-432 pointcloud_registration_gpu) before it merges a
+// message's cloud into the accumulated one.
+//
+// gsr_nn_index_build: the structure of knn.hip (knn_common.h: bounding box, 30-bit Morton sort, 64-point boxes, 64-box
+//   super-boxes) over the TARGET, once per registration - the target does not move between iterations.  The blob keeps the sorted
+//   float4 points (xyz, bits of the original row), both levels of AABBs and the bounding box; the sort's scratch lies behind them
+//   in the same blob.  A row with a non-finite coordinate is stored as NaN NaN NaN: every distance to it is NaN, which fails every
+//   comparison - it is nobody's neighbour.
+//
+// gsr_nn_search: one thread per source row, the sweep of k_knn_query_k (super-box AABBs staged through LDS 256 at a time,
+//   descent where the AABB distance does not exceed the bound).  The query is q = (float)(R s + t), formed by reg_apply below:
+//   float64, every operation rounded separately, one fixed order, rounded to float32 once per component - numpy float64 gives
+//   the same bits.  The answer is the lexicographic minimum of (float32 d2, original target row) over the finite target rows with
+//   d2 <= max_dist2: a multiset minimum, so neither distance nor row depend on the traversal, the order of the source rows or the
+//   `order` permutation.  A box is entered when its AABB distance is <= the bound (not <): a tie with a smaller row is never lost.
+//
+// gsr_icp_update: correspondences -> the next transform, nothing on the host.  A first kernel takes the target point of the
+//   first valid row as the shift every sum is formed about (a cloud at +1000 loses nothing); <= 256 workgroups then sum, over
+//   fixed slices, n, |q - p|^2, q, p and q p^T in float64 (fixed butterfly over the wave, the four wave sums in order, no float
+//   atomics); one workgroup adds the partials and one thread solves Horn's closed form: the rotation is the eigenvector of the
+//   largest eigenvalue of the symmetric 4 x 4 matrix built from the centred cross-covariance - a unit quaternion, so a reflection
+//   cannot come out - found by cyclic Jacobi with a fixed number of sweeps.  T <- dT T.
+#include "knn_common.h"
+
+#define GSR_ICP_BLOCKS 256
+#define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
+#define GSR_ICP_SWEEPS 12          // cyclic Jacobi on a 4 x 4 symmetric matrix converges quadratically: 6 - 7 sweeps reach 1e-16
+#define GSR_NN_NONE 0x7FFFFFFFu    // no neighbour yet: above every row (P <= 2^30 - 1)
+
+// ---- the index blob ---------------------------------------------------------------------------------------------------------
+struct GsrNnLayout {
+  size_t bbox;                  // float[8] min xyz, max xyz; double[3] centre at + 64
+  size_t pts;                   // float4[P]
+  size_t box_lo, box_hi;        // float4[nbox]
+  size_t sup_lo, sup_hi;        // float4[nsuper]
+  size_t keep;                  // what a search reads ends here; the rest is the build's scratch
+  size_t bbox_part, key_a, key_b, val_a, val_b, radix_tmp;
+  size_t total;
+};
+static inline GsrNnLayout nn_layout(size_t P) {
+  GsrNnLayout L;
+  size_t o = 0;
+  if (P == 0) P = 1;
+  L.bbox = o;      o += 256;
+  L.pts = o;       o += gsr_align(P * 16);
+  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.keep = o;
+  L.bbox_part = o; o += gsr_knn_bbox_part_bytes();
+  L.key_a = o;     o += gsr_align(P * 4);
+  L.key_b = o;     o += gsr_align(P * 4);
+  L.val_a = o;     o += gsr_align(P * 4);
+  L.val_b = o;     o += gsr_align(P * 4);
+  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
+  L.total = o;
+  return L;
+}
+
+// workspace of gsr_nn_query_order: codes / rows ping-pong and the sort's scratch
+struct GsrNnOrderLayout {
+  size_t key_a, key_b, val_a, val_b, radix_tmp, total;
+};
+static inline GsrNnOrderLayout nn_order_layout(size_t P) {
+  GsrNnOrderLayout L;
+  size_t o = 0;
+  if (P == 0) P = 1;
+  L.key_a = o;     o += gsr_align(P * 4);
+  L.key_b = o;     o += gsr_align(P * 4);
+  L.val_a = o;     o += gsr_align(P * 4);
+  L.val_b = o;     o += gsr_align(P * 4);
+  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
+  L.total = o;
+  return L;
+}
+
+// workspace of gsr_icp_update
+struct GsrIcpLayout {
+  size_t shift;      // double[4]: the shift, [3] = 1 when a valid row exists
+  size_t part;       // double[GSR_ICP_BLOCKS][GSR_ICP_SUMS]
+  size_t total;
+};
+static inline GsrIcpLayout icp_layout() {
+  GsrIcpLayout L;
+  L.shift = 0;
+  L.part = 256;
+  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_SUMS * 8);
+  return L;
+}
+
+// ---- q = (float)(R s + t) -----------------------------------------------------------------------------------------------------
+struct RegT {
+  double m[12];      // rows 0 .. 2 of the row-major 4 x 4
+};
+__device__ __forceinline__ RegT reg_load(const double* __restrict__ T) {
+  RegT r;
+#pragma unroll
+  for (int i = 0; i < 12; i++) r.m[i] = T ? T[i] : ((i % 5) == 0 ? 1.0 : 0.0);
+  return r;
+}
+// component i = (float)(((T[i,0] x + T[i,1] y) + T[i,2] z) + T[i,3]): three products and three sums, each rounded to float64 on
+// its own (no fused multiply-add), in this order, then ONE rounding to float32.  .w = 0.
+__device__ __forceinline__ float4 reg_apply(const RegT& T, float x, float y, float z) {
+  float q[3];
+  const double dx = (double)x, dy = (double)y, dz = (double)z;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double a = __dadd_rn(__dmul_rn(T.m[4 * i], dx), __dmul_rn(T.m[4 * i + 1], dy));
+    q[i] = (float)__dadd_rn(__dadd_rn(a, __dmul_rn(T.m[4 * i + 2], dz)), T.m[4 * i + 3]);
+  }
+  return make_float4(q[0], q[1], q[2], 0.f);
+}
+
+// ---- index ----------------------------------------------------------------------------------------------------------------------
+// rows with a non-finite coordinate become NaN NaN NaN; thread 0 also leaves the box centre (0 where the box is empty)
+__global__ __launch_bounds__(256) void k_nn_finish_index(uint32_t P, float4* __restrict__ pts, float* __restrict__ bbox) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j == 0u) {
+    double* c = (double*)(bbox + 16);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const double m = 0.5 * ((double)bbox[a] + (double)bbox[3 + a]);
+      c[a] = fabs(m) < (double)KNN_INF ? m : 0.0;
+    }
+  }
+  if (j >= P) return;
+  const float4 p = pts[j];
+  if (!(knn_finite(p.x) && knn_finite(p.y) && knn_finite(p.z))) {
+    const float nan = __builtin_nanf("");
+    pts[j] = make_float4(nan, nan, nan, p.w);
+  }
+}
+
+// Morton code, in the target's box, of every transformed source row (the key of the `order` permutation)
+__global__ __launch_bounds__(256) void k_nn_query_codes(uint32_t Ps, const float* __restrict__ src, const double* __restrict__ T_dev,
+                                                        const float* __restrict__ bbox, uint32_t* __restrict__ codes) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= Ps) return;
+  const RegT T = reg_load(T_dev);
+  const float4 q = reg_apply(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]);
+  codes[i] = knn_morton_code(q.x, q.y, q.z, bbox);
+}
+
+__global__ __launch_bounds__(256) void k_nn_transform(uint32_t P, const float* __restrict__ src, const double* __restrict__ T_dev,
+                                                      float* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P) return;
+  const RegT T = reg_load(T_dev);
+  const float4 q = reg_apply(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]);
+  out[3 * (size_t)i] = q.x;
+  out[3 * (size_t)i + 1] = q.y;
+  out[3 * (size_t)i + 2] = q.z;
+}
+
+// (d2, row) < (bd, br) lexicographically; false for a NaN d2
+__device__ __forceinline__ void nn_take(float d2, uint32_t row, float& bd, uint32_t& br) {
+  if (d2 < bd || (d2 == bd && row < br)) {
+    bd = d2;
+    br = row;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_nn_search(uint32_t Pt, uint32_t Ps, const float* __restrict__ src,
+                                                   const uint32_t* __restrict__ order, const double* __restrict__ T_dev,
+                                                   float max_dist2, const float4* __restrict__ pts,
+                                                   const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
+                                                   uint32_t nbox, const float4* __restrict__ sup_lo,
+                                                   const float4* __restrict__ sup_hi, uint32_t nsuper,
+                                                   int32_t* __restrict__ idx_out, float* __restrict__ dist2_out) {
+  __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  uint32_t row = t < Ps ? (order ? order[t] : t) : 0u;
+  // (an `order` entry outside the cloud is not followed: that thread answers nothing)
+  const bool active = t < Ps && row < Ps;
+  if (!active) row = 0u;
+  const RegT T = reg_load(T_dev);
+  const float4 me = reg_apply(T, src[3 * (size_t)row], src[3 * (size_t)row + 1], src[3 * (size_t)row + 2]);
+  const bool finite = knn_finite(me.x) && knn_finite(me.y) && knn_finite(me.z);
+  // the bound starts at max_dist2 with no row: a candidate AT max_dist2 is taken (valid iff d2 <= max_dist2), one beyond never
+  float bd = max_dist2;
+  uint32_t br = GSR_NN_NONE;
+  for (uint32_t base = 0; base < nsuper; base += 256u) {
+    __syncthreads();
+    if (base + threadIdx.x < nsuper) {
+      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
+      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
+    }
+    __syncthreads();
+    if (!active || !finite) continue;
+    const uint32_t n = min(256u, nsuper - base);
+    for (uint32_t s = 0; s < n; s++) {
+      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= bd)) continue;
+      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
+      for (uint32_t b = bb; b < be; b++) {
+        if (!(knn_box_d2(me, box_lo[b], box_hi[b]) <= bd)) continue;
+        const uint32_t jb = b * (uint32_t)GSR_KNN_BOX, je = min(Pt, jb + (uint32_t)GSR_KNN_BOX);
+        for (uint32_t j = jb; j < je; j++) {
+          const float4 p = pts[j];
+          nn_take(knn_point_d2(me, p), __float_as_uint(p.w), bd, br);
+        }
+      }
+    }
+  }
+  if (!active) return;
+  const bool valid = br != GSR_NN_NONE;
+  idx_out[row] = valid ? (int32_t)br : -1;
+  if (dist2_out) dist2_out[row] = valid ? bd : KNN_INF;
+}
+
+// ---- one ICP update ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double reg_wave_sum(double v) {      // the same total in every lane (a + b == b + a bit for bit)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// GSR_ICP_SUMS per-thread values summed over a 256-thread workgroup; the result is valid in thread 0
+__device__ __forceinline__ void reg_block_sum(double (&s)[GSR_ICP_SUMS]) {
+  __shared__ double sh[4][GSR_ICP_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = reg_wave_sum(s[a]);
+  if (gsr_lane() == 0) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_SUMS; a++) sh[threadIdx.x >> 6][a] = s[a];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
+}
+
+// the pair of row i, or false: no correspondence, an index outside the target, a non-finite point on either side
+__device__ __forceinline__ bool icp_pair(uint32_t i, const float* __restrict__ src, uint32_t Pt, const float* __restrict__ tgt,
+                                         const int32_t* __restrict__ idx, const RegT& T, float4& q, float4& p) {
+  const int32_t k = idx[i];
+  if (k < 0 || (uint32_t)k >= Pt) return false;
+  q = reg_apply(T, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]);
+  p = make_float4(tgt[3 * (size_t)k], tgt[3 * (size_t)k + 1], tgt[3 * (size_t)k + 2], 0.f);
+  return knn_finite(q.x) && knn_finite(q.y) && knn_finite(q.z) && knn_finite(p.x) && knn_finite(p.y) && knn_finite(p.z);
+}
+
+// one workgroup: the target point of the first valid row -> shift[0..2], shift[3] = 1 (no valid row: zeros)
+__global__ __launch_bounds__(256) void k_icp_shift(uint32_t Ps, const float* __restrict__ src, uint32_t Pt,
+                                                   const float* __restrict__ tgt, const int32_t* __restrict__ idx,
+                                                   const double* __restrict__ T_dev, double* __restrict__ shift) {
+  __shared__ uint32_t s_first;
+  const RegT T = reg_load(T_dev);
+  if (threadIdx.x == 0) s_first = 0xFFFFFFFFu;
+  __syncthreads();
+  for (uint32_t base = 0; base < Ps; base += 256u) {      // (uniform over the workgroup)
+    const uint32_t i = base + threadIdx.x;
+    float4 q, p;
+    if (i < Ps && icp_pair(i, src, Pt, tgt, idx, T, q, p)) atomicMin(&s_first, i);      // (integer minimum: order-independent)
+    __syncthreads();
+    const uint32_t found = s_first;
+    __syncthreads();      // (everybody has read it before the next round may lower it)
+    if (found != 0xFFFFFFFFu) break;
+  }
+  if (threadIdx.x != 0) return;
+  const uint32_t f = s_first;
+  if (f == 0xFFFFFFFFu) {
+    shift[0] = shift[1] = shift[2] = shift[3] = 0.0;
+    return;
+  }
+  const size_t k = (size_t)idx[f];
+  shift[0] = (double)tgt[3 * k];
+  shift[1] = (double)tgt[3 * k + 1];
+  shift[2] = (double)tgt[3 * k + 2];
+  shift[3] = 1.0;
+}
+
+__global__ __launch_bounds__(256) void k_icp_partial(uint32_t Ps, const float* __restrict__ src, uint32_t Pt,
+                                                     const float* __restrict__ tgt, const int32_t* __restrict__ idx,
+                                                     const double* __restrict__ T_dev, const double* __restrict__ shift,
+                                                     double* __restrict__ part) {
+  const RegT T = reg_load(T_dev);
+  const double c0 = shift[0], c1 = shift[1], c2 = shift[2];
+  double s[GSR_ICP_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = 0.0;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < Ps; i += gridDim.x * 256u) {
+    float4 qf, pf;
+    if (!icp_pair(i, src, Pt, tgt, idx, T, qf, pf)) continue;
+    // (float32 values: the differences below are exact in float64)
+    const double q[3] = {(double)qf.x - c0, (double)qf.y - c1, (double)qf.z - c2};
+    const double p[3] = {(double)pf.x - c0, (double)pf.y - c1, (double)pf.z - c2};
+    const double ex = (double)qf.x - (double)pf.x, ey = (double)qf.y - (double)pf.y, ez = (double)qf.z - (double)pf.z;
+    s[0] += 1.0;
+    s[1] += (ex * ex + ey * ey) + ez * ez;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      s[2 + a] += q[a];
+      s[5 + a] += p[a];
+#pragma unroll
+      for (int b = 0; b < 3; b++) s[8 + 3 * a + b] += q[a] * p[b];
+    }
+  }
+  reg_block_sum(s);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_SUMS + a] = s[a];
+  }
+}
+
+// one workgroup: the partials, then thread 0 solves and composes
+__global__ __launch_bounds__(256) void k_icp_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
+                                                   const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                   double* __restrict__ stats) {
+  __shared__ double A[4][4], V[4][4];      // thread 0 only: indexed at run time, which registers cannot be
+  double s[GSR_ICP_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = 0.0;
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_SUMS + a];
+  }
+  reg_block_sum(s);
+  if (threadIdx.x != 0) return;
+  const double n = s[0];
+  stats[0] = n;
+  stats[1] = n / (double)Ps;
+  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
+  stats[4] = s[1];
+  stats[5] = stats[6] = stats[7] = 0.0;
+  if (n < 3.0) {
+    stats[3] = 1.0;      // too few correspondences: T stays
+    return;
+  }
+  // centred cross-covariance M[a][b] = sum (q_a - qbar_a)(p_b - pbar_b), about the shift
+  double qb[3], pb[3], M[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    qb[a] = s[2 + a] / n;
+    pb[a] = s[5 + a] / n;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+#pragma unroll
+    for (int b = 0; b < 3; b++) M[a][b] = s[8 + 3 * a + b] - s[2 + a] * pb[b];
+  }
+  // Horn 1987: the quaternion (w, x, y, z) of the rotation that takes q to p maximises v^T N v
+  A[0][0] = M[0][0] + M[1][1] + M[2][2];
+  A[1][1] = M[0][0] - M[1][1] - M[2][2];
+  A[2][2] = -M[0][0] + M[1][1] - M[2][2];
+  A[3][3] = -M[0][0] - M[1][1] + M[2][2];
+  A[0][1] = A[1][0] = M[1][2] - M[2][1];
+  A[0][2] = A[2][0] = M[2][0] - M[0][2];
+  A[0][3] = A[3][0] = M[0][1] - M[1][0];
+  A[1][2] = A[2][1] = M[0][1] + M[1][0];
+  A[1][3] = A[3][1] = M[2][0] + M[0][2];
+  A[2][3] = A[3][2] = M[1][2] + M[2][1];
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < GSR_ICP_SWEEPS; sweep++) {
+    for (int p = 0; p < 3; p++) {
+      for (int q = p + 1; q < 4; q++) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        A[p][p] -= t * apq;
+        A[q][q] += t * apq;
+        A[p][q] = A[q][p] = 0.0;
+        for (int k = 0; k < 4; k++) {
+          if (k != p && k != q) {
+            const double akp = A[k][p], akq = A[k][q];
+            A[k][p] = A[p][k] = c * akp - sn * akq;
+            A[k][q] = A[q][k] = sn * akp + c * akq;
+          }
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - sn * vkq;
+          V[k][q] = sn * vkp + c * vkq;
+        }
+      }
+    }
+  }
+  int best = 0;
+  for (int k = 1; k < 4; k++)
+    if (A[k][k] > A[best][best]) best = k;
+  double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
+  const double norm = sqrt(((w * w + x * x) + y * y) + z * z);
+  stats[5] = A[best][best];
+  if (!(norm > 0.5 && norm < 2.0)) {      // (a NaN too: sums that overflowed)
+    stats[3] = 2.0;
+    return;
+  }
+  w /= norm; x /= norm; y /= norm; z /= norm;
+  double R[3][3];
+  R[0][0] = 1.0 - 2.0 * (y * y + z * z); R[0][1] = 2.0 * (x * y - w * z);       R[0][2] = 2.0 * (x * z + w * y);
+  R[1][0] = 2.0 * (x * y + w * z);       R[1][1] = 1.0 - 2.0 * (x * x + z * z); R[1][2] = 2.0 * (y * z - w * x);
+  R[2][0] = 2.0 * (x * z - w * y);       R[2][1] = 2.0 * (y * z + w * x);       R[2][2] = 1.0 - 2.0 * (x * x + y * y);
+  // dT x = R (x - (c + qbar)) + (c + pbar)
+  double td[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const double cq0 = shift[0] + qb[0], cq1 = shift[1] + qb[1], cq2 = shift[2] + qb[2];
+    td[a] = (shift[a] + pb[a]) - ((R[a][0] * cq0 + R[a][1] * cq1) + R[a][2] * cq2);
+  }
+  // T <- dT T
+  double Tn[12];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      Tn[4 * a + b] = ((R[a][0] * T_dev[b] + R[a][1] * T_dev[4 + b]) + R[a][2] * T_dev[8 + b]) + (b == 3 ? td[a] : 0.0);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) T_dev[i] = Tn[i];
+  T_dev[12] = T_dev[13] = T_dev[14] = 0.0;
+  T_dev[15] = 1.0;
+  stats[3] = 0.0;
+}
+
+static bool reg_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
+
+extern "C" {
+
+size_t gsr_nn_index_bytes(int64_t Pt) { return nn_layout((size_t)(Pt < 1 ? 1 : Pt)).total; }
+
+int gsr_nn_index_build(int64_t Pt, const float* target, void* index, size_t index_bytes, void* stream) {
+  if (reg_bad_size(Pt) || !target || !index) {
+    gsr_set_error("nn_index_build: bad arguments (Pt = %lld)", (long long)Pt);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrNnLayout L = nn_layout((size_t)Pt);
+  if (index_bytes < L.total) {
+    gsr_set_error("nn_index_build: index of %zu bytes, %zu needed", index_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ix = (char*)index;
+  GsrKnnBuild b;
+  b.bbox_part = (float*)(ix + L.bbox_part);
+  b.bbox = (float*)(ix + L.bbox);
+  b.key[0] = (uint32_t*)(ix + L.key_a); b.key[1] = (uint32_t*)(ix + L.key_b);
+  b.val[0] = (uint32_t*)(ix + L.val_a); b.val[1] = (uint32_t*)(ix + L.val_b);
+  b.radix_tmp = (uint32_t*)(ix + L.radix_tmp);
+  b.pts = (float4*)(ix + L.pts);
+  b.box_lo = (float4*)(ix + L.box_lo); b.box_hi = (float4*)(ix + L.box_hi);
+  b.sup_lo = (float4*)(ix + L.sup_lo); b.sup_hi = (float4*)(ix + L.sup_hi);
+  gsr_knn_build(Pt, target, b, st);
+  const uint32_t n = (uint32_t)Pt;
+  GSR_LAUNCH("nn_finish_index", k_nn_finish_index, dim3((n + 255u) / 256u), dim3(256), 0, st, n, b.pts, b.bbox);
+  return gsr_launch_status("nn_index_build launch");
+}
+
+size_t gsr_nn_order_workspace_bytes(int64_t Ps) { return nn_order_layout((size_t)(Ps < 1 ? 1 : Ps)).total; }
+
+int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* source, const double* T_dev, int32_t* order_out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (reg_bad_size(Pt) || reg_bad_size(Ps) || !index || !source || !order_out || !workspace) {
+    gsr_set_error("nn_query_order: bad arguments (Pt = %lld, Ps = %lld)", (long long)Pt, (long long)Ps);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrNnOrderLayout L = nn_order_layout((size_t)Ps);
+  if (workspace_bytes < L.total) {
+    gsr_set_error("nn_query_order: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const uint32_t n = (uint32_t)Ps;
+  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
+  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
+  const float* bbox = (const float*)((const char*)index + nn_layout((size_t)Pt).bbox);
+  GSR_LAUNCH("nn_query_codes", k_nn_query_codes, dim3((n + 255u) / 256u), dim3(256), 0, st, n, source, T_dev, bbox, key[0]);
+  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
+  (void)hipMemcpyAsync(order_out, val[where], (size_t)n * 4, hipMemcpyDeviceToDevice, st);
+  return gsr_launch_status("nn_query_order launch");
+}
+
+int gsr_nn_search(int64_t Pt, const void* index, int64_t Ps, const float* source, const double* T_dev, float max_dist2,
+                  const int32_t* order, int32_t* idx_out, float* dist2_out, void* stream) {
+  if (reg_bad_size(Pt) || reg_bad_size(Ps) || !index || !source || !idx_out || !(max_dist2 >= 0.f)) {
+    gsr_set_error("nn_search: bad arguments (Pt = %lld, Ps = %lld, max_dist2 = %g)", (long long)Pt, (long long)Ps,
+                  (double)max_dist2);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrNnLayout L = nn_layout((size_t)Pt);
+  const char* ix = (const char*)index;
+  const uint32_t nt = (uint32_t)Pt, ns = (uint32_t)Ps;
+  GSR_LAUNCH("nn_search", k_nn_search, dim3((ns + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, nt, ns, source,
+             (const uint32_t*)order, T_dev, max_dist2, (const float4*)(ix + L.pts), (const float4*)(ix + L.box_lo),
+             (const float4*)(ix + L.box_hi), (uint32_t)knn_nbox(nt), (const float4*)(ix + L.sup_lo),
+             (const float4*)(ix + L.sup_hi), (uint32_t)knn_nsuper(nt), idx_out, dist2_out);
+  return gsr_launch_status("nn_search launch");
+}
+
+int gsr_transform_points(int64_t P, const float* points, const double* T_dev, float* out, void* stream) {
+  if (reg_bad_size(P) || !points || !out) {
+    gsr_set_error("transform_points: bad arguments (P = %lld)", (long long)P);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const uint32_t n = (uint32_t)P;
+  GSR_LAUNCH("nn_transform", k_nn_transform, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n, points, T_dev, out);
+  return gsr_launch_status("transform_points launch");
+}
+
+size_t gsr_icp_workspace_bytes(int64_t Ps) {
+  (void)Ps;      // (the partial sums of at most GSR_ICP_BLOCKS workgroups: the size does not grow with the cloud)
+  return icp_layout().total;
+}
+
+int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* target, const int32_t* idx, double* T_dev,
+                   double* stats_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  if (reg_bad_size(Ps) || reg_bad_size(Pt) || !source || !target || !idx || !T_dev || !stats_dev || !workspace) {
+    gsr_set_error("icp_update: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrIcpLayout L = icp_layout();
+  if (workspace_bytes < L.total) {
+    gsr_set_error("icp_update: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  double* shift = (double*)(ws + L.shift);
+  double* part = (double*)(ws + L.part);
+  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
+  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
+  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
+  GSR_LAUNCH("icp_partial", k_icp_partial, dim3(sblk), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev,
+             (const double*)shift, part);
+  GSR_LAUNCH("icp_final", k_icp_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part, (const double*)shift, T_dev,
+             stats_dev);
+  return gsr_launch_status("icp_update launch");
+}
+
+}  // extern "C"

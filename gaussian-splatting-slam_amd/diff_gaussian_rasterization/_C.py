@@ -198,6 +198,22 @@ EXPORTS = {
     "gsr_outlier_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_statistical_outliers": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    # Pt, target, index + bytes, stream
+    "gsr_nn_index_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_nn_index_build": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # Pt, index, Ps, source, T_dev, max_dist2, order, idx_out, dist2_out, stream
+    "gsr_nn_search": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    # Pt, index, Ps, source, T_dev, order_out, workspace + bytes, stream
+    "gsr_nn_order_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_nn_query_order": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    # P, points, T_dev, out, stream
+    "gsr_transform_points": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # Ps, source, Pt, target, idx, T_dev, stats_dev, workspace + bytes, stream
+    "gsr_icp_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_icp_update": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

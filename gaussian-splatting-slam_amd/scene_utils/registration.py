@@ -1,0 +1,324 @@
+"""Rigid registration of one point cloud to another: a nearest-neighbour index with row numbers and point-to-point ICP - what the
+reference's pointcloud_registeration / pointcloud_registration_gpu (convert_visual_merged_msg.py:187-249, :393-432) do with Open3D
+before a message's cloud is merged into the accumulated one.  Everything runs in HIP (csrc/registration.hip over the structure of
+csrc/knn.hip); there is no CPU path.  Arguments are validated before any device work.
+
+The transformed point is q = (float32)(R s + t) evaluated in float64 in one fixed order (include/gsr.h), so a float64 restatement
+reproduces every query bit for bit; the neighbour is the lexicographic minimum of (float32 d2, target row)."""
+from __future__ import annotations
+
+import math
+import numbers
+from typing import NamedTuple
+
+import torch
+
+from .pointcloud import _check_cloud, _check_voxel_size, voxel_down_sample
+
+USE_QUERY_ORDER = True      # registration_icp Morton-sorts the queries once (profiles/README.md, registration_bench: measured)
+
+
+def _gsr():
+    from diff_gaussian_rasterization import _C
+    return _C
+
+
+class RegistrationResult(NamedTuple):
+    transformation: torch.Tensor      # float64 [4,4] on the device: x_target ~ T x_source
+    fitness: float                    # valid correspondences / source rows, under `transformation`
+    inlier_rmse: float                # sqrt(mean squared distance of the valid correspondences), under `transformation`
+    iterations: int                   # ICP updates applied
+    converged: bool                   # the stopping rule fired (always False with check_every=0)
+    correspondences: torch.Tensor     # int32 [Ps]: target row of every source row under `transformation`, -1 = none
+
+
+def _check_distance(name, value, allow_inf):
+    if isinstance(value, bool) or not isinstance(value, numbers.Real):
+        raise TypeError(f"{name}={value!r}: expected a number")
+    if math.isnan(value) or value < 0 or (math.isinf(value) and not allow_inf):
+        raise ValueError(f"{name}={value}: expected a value >= 0" + ("" if allow_inf else ", finite"))
+    return float(value)
+
+
+def _check_icp(relative_fitness, relative_rmse, max_iteration, check_every):
+    for n, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise TypeError(f"{n}={v!r}: expected a number")
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"{n}={v}: expected a finite value >= 0")
+    for n, v, lo in (("max_iteration", max_iteration, 1), ("check_every", check_every, 0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"{n}={v!r}: expected an int")
+        if v < lo:
+            raise ValueError(f"{n}={v}: expected >= {lo}")
+
+
+def _check_transform(T, name="transformation"):
+    """None, or anything that gives a [4,4] matrix -> None / (tensor or array as given); shape and type only"""
+    if T is None:
+        return None
+    if not isinstance(T, torch.Tensor):
+        T = torch.as_tensor(T, dtype=torch.float64)
+    if tuple(T.shape) != (4, 4) or not T.is_floating_point():
+        raise ValueError(f"{name}: expected a floating-point [4,4] matrix, got {T.dtype} {tuple(T.shape)}")
+    return T
+
+
+def _sq(distance):
+    """float32 square of a distance, as the kernel compares it (+inf stays +inf)"""
+    d = torch.tensor(distance, dtype=torch.float32)
+    return float(d * d)
+
+
+def _device_T(T, dev):
+    """a fresh contiguous float64 [4,4] on `dev` (the identity for None): ICP updates it in place"""
+    if T is None:
+        return torch.eye(4, dtype=torch.float64, device=dev)
+    return T.detach().to(device=dev, dtype=torch.float64).contiguous().clone()
+
+
+def _nonempty(pts, who, what):
+    if int(pts.shape[0]) == 0:
+        raise ValueError(f"{who}: the {what} cloud is empty")
+
+
+class NeighborIndex:
+    """The search structure over a target cloud (points [Pt,3] float on the HIP device), built once.  `query` may then be called
+    any number of times; the target's rows keep their numbers."""
+
+    def __init__(self, target):
+        pts, _ = _check_cloud(target, None, "NeighborIndex")
+        _nonempty(pts, "NeighborIndex", "target")
+        _C = _gsr()
+        lib = _C.lib()
+        self.points = pts
+        self.size = int(pts.shape[0])
+        self.device = pts.device
+        with _C.on_device(self.device):
+            self.blob = torch.empty(lib.gsr_nn_index_bytes(self.size), dtype=torch.uint8, device=self.device)
+            _C.check(lib.gsr_nn_index_build(self.size, _C.ptr(pts), _C.ptr(self.blob), self.blob.numel(), _C._stream()))
+
+    def _source(self, points, who):
+        pts, _ = _check_cloud(points, None, who)
+        if pts.device != self.device:
+            raise ValueError(f"{who}: points on {pts.device}, the index on {self.device}")
+        return pts
+
+    def query_order(self, points, transform=None):
+        """int32 [P]: the rows of `points` sorted by the Morton code of T p in the target's bounding box - handed to `query` as
+        `order`, it gives the lanes of a wave neighbouring queries.  It never changes an answer."""
+        T = _check_transform(transform, "transform")
+        pts = self._source(points, "NeighborIndex.query_order")
+        P = int(pts.shape[0])
+        order = torch.empty(P, dtype=torch.int32, device=self.device)
+        if P:
+            _C = _gsr()
+            lib = _C.lib()
+            Td = None if T is None else _device_T(T, self.device)
+            with _C.on_device(self.device):
+                ws = torch.empty(lib.gsr_nn_order_workspace_bytes(P), dtype=torch.uint8, device=self.device)
+                _C.check(lib.gsr_nn_query_order(self.size, _C.ptr(self.blob), P, _C.ptr(pts), _C.ptr(Td), _C.ptr(order), _C.ptr(ws),
+                                                ws.numel(), _C._stream()))
+        return order
+
+    def _search(self, pts, Td, max_dist2, order, idx, dist2):
+        _C = _gsr()
+        with _C.on_device(self.device):
+            _C.check(_C.lib().gsr_nn_search(self.size, _C.ptr(self.blob), int(pts.shape[0]), _C.ptr(pts), _C.ptr(Td), max_dist2,
+                                            _C.ptr(order), _C.ptr(idx), _C.ptr(dist2), _C._stream()))
+
+    def query(self, points, transform=None, max_distance=math.inf, order=None):
+        """-> (idx int32 [P], dist2 float32 [P]): for every row of `points`, moved by `transform` ([4,4], None = identity), the
+        row of its nearest target point and the squared distance; among equal float32 distances the smallest row.  idx = -1 and
+        dist2 = +inf where the distance exceeds `max_distance` or the row is not finite."""
+        md = _check_distance("max_distance", max_distance, True)
+        T = _check_transform(transform, "transform")
+        pts = self._source(points, "NeighborIndex.query")
+        P = int(pts.shape[0])
+        if order is not None:
+            if not isinstance(order, torch.Tensor) or order.dtype != torch.int32 or tuple(order.shape) != (P,):
+                raise ValueError(f"order: expected an int32 tensor of shape ({P},)")
+            order = order.to(self.device).contiguous()
+        idx = torch.empty(P, dtype=torch.int32, device=self.device)
+        dist2 = torch.empty(P, dtype=torch.float32, device=self.device)
+        if P:
+            self._search(pts, None if T is None else _device_T(T, self.device), _sq(md), order, idx, dist2)
+        return idx, dist2
+
+
+def nn_search(query, target, transform=None, max_distance=math.inf):
+    """NeighborIndex(target).query(query, ...) in one call (also `simple_knn.nn_search`)."""
+    md = _check_distance("max_distance", max_distance, True)
+    T = _check_transform(transform, "transform")
+    return NeighborIndex(target).query(query, T, md)
+
+
+def transform_points(points, transformation):
+    """float32 [P,3]: every row moved by the [4,4] `transformation`, q = (float32)(R p + t) as the search evaluates it."""
+    T = _check_transform(transformation)
+    pts, _ = _check_cloud(points, None, "transform_points")
+    out = torch.empty_like(pts)
+    P = int(pts.shape[0])
+    if P:
+        _C = _gsr()
+        Td = None if T is None else _device_T(T, pts.device)
+        with _C.on_device(pts.device):
+            _C.check(_C.lib().gsr_transform_points(P, _C.ptr(pts), _C.ptr(Td), _C.ptr(out), _C._stream()))
+    return out
+
+
+class _Updater:
+    """gsr_icp_update on fixed clouds: the workspace is allocated once"""
+
+    def __init__(self, src, tgt):
+        _C = _gsr()
+        self.src, self.tgt = src, tgt
+        with _C.on_device(src.device):
+            self.ws = torch.empty(_C.lib().gsr_icp_workspace_bytes(int(src.shape[0])), dtype=torch.uint8, device=src.device)
+
+    def __call__(self, idx, Td, stats):
+        _C = _gsr()
+        with _C.on_device(self.src.device):
+            _C.check(_C.lib().gsr_icp_update(int(self.src.shape[0]), _C.ptr(self.src), int(self.tgt.shape[0]), _C.ptr(self.tgt),
+                                             _C.ptr(idx), _C.ptr(Td), _C.ptr(stats), _C.ptr(self.ws), self.ws.numel(),
+                                             _C._stream()))
+
+
+def icp_update(source, target, correspondences, transformation):
+    """One ICP update from given correspondences (int32 [Ps], -1 = none) -> (new transformation float64 [4,4] on the device,
+    stats float64 [8] on the device: n, fitness, inlier_rmse, status, sum of squared distances, ...; include/gsr.h
+    gsr_icp_update).  n, fitness and inlier_rmse describe the transformation that was passed in.  No read-back."""
+    T = _check_transform(transformation)
+    src, _ = _check_cloud(source, None, "icp_update")
+    tgt, _ = _check_cloud(target, None, "icp_update")
+    _nonempty(src, "icp_update", "source")
+    _nonempty(tgt, "icp_update", "target")
+    idx = correspondences
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or tuple(idx.shape) != (int(src.shape[0]),):
+        raise ValueError(f"correspondences: expected an int32 tensor of shape ({int(src.shape[0])},)")
+    Td = _device_T(T, src.device)
+    stats = torch.zeros(8, dtype=torch.float64, device=src.device)
+    _Updater(src, tgt.to(src.device))(idx.to(src.device).contiguous(), Td, stats)
+    return Td, stats
+
+
+def _prepare(source, target, max_correspondence_distance, T, index, who):
+    md = _check_distance("max_correspondence_distance", max_correspondence_distance, True)
+    T = _check_transform(T, "init" if who == "registration_icp" else "transformation")
+    if index is not None and not isinstance(index, NeighborIndex):
+        raise TypeError(f"index={index!r}: expected a NeighborIndex")
+    src, _ = _check_cloud(source, None, who)
+    _nonempty(src, who, "source")
+    if index is None:
+        index = NeighborIndex(target)
+    elif target is not None:
+        tgt, _ = _check_cloud(target, None, who)
+        if int(tgt.shape[0]) != index.size:
+            raise ValueError(f"{who}: target has {int(tgt.shape[0])} rows, the index {index.size}")
+    if src.device != index.device:
+        raise ValueError(f"{who}: source on {src.device}, target on {index.device}")
+    return src, index, _sq(md), T
+
+
+def _evaluate(src, index, md2, Td, order, updater):
+    """closing search under Td -> (fitness, rmse, idx); Td is not changed.  One read-back."""
+    P = int(src.shape[0])
+    idx = torch.empty(P, dtype=torch.int32, device=src.device)
+    index._search(src, Td, md2, order, idx, None)
+    stats = torch.zeros(8, dtype=torch.float64, device=src.device)
+    updater(idx, Td.clone(), stats)
+    s = stats.tolist()
+    return s[1], s[2], idx
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None, index=None):
+    """Fitness and inlier RMSE of `transformation` (None = identity) as Open3D's evaluate_registration defines them:
+    correspondences = nearest target point within max_correspondence_distance.  iterations = 0."""
+    src, index, md2, T = _prepare(source, target, max_correspondence_distance, transformation, index, "evaluate_registration")
+    Td = _device_T(T, src.device)
+    fitness, rmse, idx = _evaluate(src, index, md2, Td, None, _Updater(src, index.points))
+    return RegistrationResult(Td, fitness, rmse, 0, False, idx)
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
+                     max_iteration=30, check_every=1, index=None, use_order=None):
+    """Point-to-point ICP of `source` onto `target` (both [P,3] float on the HIP device) from `init` (None = identity).
+
+    Iteration k searches the neighbours under T_k, sums them and replaces T_k by T_{k+1} on the device; its fitness and RMSE
+    describe T_k.  Every `check_every` iterations they are read back, and the loop stops - as Open3D's does - once both
+    |fitness_k - fitness_{k-1}| < relative_fitness and |rmse_k - rmse_{k-1}| < relative_rmse; the update of iteration k has
+    been applied by then, and the result's fitness, RMSE and correspondences come from one closing search under the returned
+    transformation.  check_every=0 enqueues max_iteration iterations without a read-back and reads once at the end.
+    index: a NeighborIndex of `target` to reuse (`target` may then be None).  use_order: Morton-sort the queries once, from
+    `init` (None: the measured default, USE_QUERY_ORDER); no result bit depends on it.
+    An iteration with fewer than three correspondences leaves the transformation as it is."""
+    _check_icp(relative_fitness, relative_rmse, max_iteration, check_every)
+    src, index, md2, T = _prepare(source, target, max_correspondence_distance, init, index, "registration_icp")
+    dev, P = src.device, int(src.shape[0])
+    Td = _device_T(T, dev)
+    order = index.query_order(src, Td) if (USE_QUERY_ORDER if use_order is None else use_order) else None
+    updater = _Updater(src, index.points)
+    idx = torch.empty(P, dtype=torch.int32, device=dev)
+    stats = torch.zeros((max_iteration, 8), dtype=torch.float64, device=dev)
+    iterations, converged = 0, False
+    for k in range(max_iteration):
+        index._search(src, Td, md2, order, idx, None)
+        updater(idx, Td, stats[k])
+        iterations = k + 1
+        if check_every and k >= 1 and (k + 1) % check_every == 0:
+            prev, cur = stats[k - 1:k + 1, 1:3].tolist()
+            if abs(cur[0] - prev[0]) < relative_fitness and abs(cur[1] - prev[1]) < relative_rmse:
+                converged = True
+                break
+    fitness, rmse, idx = _evaluate(src, index, md2, Td, order, updater)
+    return RegistrationResult(Td, fitness, rmse, iterations, converged, idx)
+
+
+def register_and_merge(source, source_colors, target, target_colors, voxel_size=0.05, max_correspondence_distance=None,
+                       merge_voxel_size=None, **icp):
+    """The reference's pointcloud_registeration: down-sample both clouds (voxel_down_sample, voxel_size), ICP of the down-sampled
+    source onto the down-sampled target from the identity (max_correspondence_distance=None: 5 * voxel_size; further keywords
+    go to registration_icp), move the FULL source by the result, concatenate it with the target (source rows first) and, with
+    merge_voxel_size, down-sample the merged cloud.  Colours: both or neither.  -> (points, colors or None, result)."""
+    v = _check_voxel_size(voxel_size)
+    mv = None if merge_voxel_size is None else _check_voxel_size(merge_voxel_size)
+    md = 5.0 * v if max_correspondence_distance is None else _check_distance("max_correspondence_distance",
+                                                                             max_correspondence_distance, True)
+    if (source_colors is None) != (target_colors is None):
+        raise ValueError("register_and_merge: colours for both clouds or for neither")
+    if "init" in icp or "index" in icp:
+        raise TypeError("register_and_merge: starts from the identity and builds its own index (init / index not accepted)")
+    src, scol = _check_cloud(source, source_colors, "register_and_merge")
+    tgt, tcol = _check_cloud(target, target_colors, "register_and_merge")
+    src_down, _ = voxel_down_sample(src, None, v)
+    tgt_down, _ = voxel_down_sample(tgt, None, v)
+    result = registration_icp(src_down, tgt_down, md, **icp)
+    points = torch.cat([transform_points(src, result.transformation), tgt.to(src.device)])
+    colors = None if scol is None else torch.cat([scol, tcol.to(src.device)])
+    if mv is not None:
+        points, colors = voxel_down_sample(points, colors, mv)
+    return points, colors, result
+
+
+def align_map(model, target_points, max_correspondence_distance, ids=None, voxel_size=None, **icp):
+    """Registers the model's means - with `ids`, only the rows anchored to those keyframes - to `target_points` and moves the
+    model by the result through `model.transform_(T, ids=ids)`: rotations, SH bands and moments follow as that call defines.
+    voxel_size: down-sample the means first (the target is taken as given).  -> RegistrationResult."""
+    md = _check_distance("max_correspondence_distance", max_correspondence_distance, True)
+    v = None if voxel_size is None else _check_voxel_size(voxel_size)
+    xyz = model.get_xyz
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+        raise _gsr().GsrError("align_map runs in HIP kernels (no CPU path): the model must live on the HIP device")
+    src = xyz.detach()
+    if ids is not None:
+        ids = [int(i) for i in ids]
+        if getattr(model, "_anchor", None) is None:
+            raise ValueError("align_map: `ids` given but the model has no anchors (set_anchors, add_from_rgbd(anchor=...))")
+        wanted = torch.tensor(ids, dtype=torch.int32, device=src.device)
+        src = src[torch.isin(model._anchor.to(src.device), wanted)]
+    if v is not None:
+        src, _ = voxel_down_sample(src, None, v)
+    result = registration_icp(src, target_points, md, **icp)
+    T = result.transformation
+    model.transform_(T if ids is None else T.unsqueeze(0).expand(len(ids), 4, 4).contiguous(), ids=ids)
+    return result

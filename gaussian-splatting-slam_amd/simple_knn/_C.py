@@ -1,6 +1,9 @@
 """The native surface of `simple_knn`: `distCUDA2(points)` as the reference calls it, and `knn_dist2(points, first_query)`,
 the same search answered only for the rows from `first_query` on (new points against map + new points); `knn_k(points, k)`,
-the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds)."""
+the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds);
+`nn_search(query, target)`, the nearest row of ANOTHER cloud with its row number (csrc/registration.hip)."""
+import math
+
 import torch
 
 from diff_gaussian_rasterization import _C as _gsr
@@ -66,3 +69,11 @@ def knn_k(points, k, return_dist2=True, return_mean=False):
 def distCUDA2(points):
     """reference scene/gaussian_model.py:140: mean squared distance of every point to its three nearest neighbours."""
     return knn_dist2(points, 0)
+
+
+def nn_search(query, target, transform=None, max_distance=math.inf):
+    """-> (idx int32 [P], dist2 float32 [P]): for every row of `query` (moved by the [4,4] `transform`, None = identity) the row of
+    its nearest point of `target` and the squared distance; -1 / +inf beyond `max_distance`.  `scene_utils.NeighborIndex` keeps
+    the structure over `target` for repeated searches."""
+    from scene_utils.registration import nn_search as _nn_search
+    return _nn_search(query, target, transform, max_distance)

@@ -48,6 +48,8 @@ extern "C" {
  *    point-cloud conditioning before a cloud seeds Gaussians;
  *    gsr_debug_scan_tmp_bytes, gsr_debug_scan_u32, gsr_debug_tile_sort, gsr_debug_tile_depth_sort: test hooks of the binning stage's
  *    integer building blocks;
+ *    gsr_nn_index_bytes, gsr_nn_index_build, gsr_nn_search, gsr_nn_order_workspace_bytes, gsr_nn_query_order, gsr_transform_points,
+ *    gsr_icp_workspace_bytes, gsr_icp_update: nearest neighbours of one cloud in another, with the row, and point-to-point ICP;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -630,6 +632,68 @@ size_t gsr_outlier_workspace_bytes(int64_t P);
 int gsr_statistical_outliers(int64_t P, const float* points /*[P,3]*/, int32_t nb_neighbors, double std_ratio,
                              uint8_t* keep /*[P]*/, float* mean_dist /*[P] or NULL*/, double* stats_dev /*[4] or NULL*/,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- registration of one cloud to another: nearest-neighbour index, point-to-point ICP (csrc/registration.hip; DESIGN.md
+ * section 4 item 30) - what the reference's pointcloud_registeration does with Open3D before it merges two clouds ---- */
+
+/* The transformed point every entry below means by "q = T s": with T a row-major 4 x 4 in DEVICE float64 (NULL: the identity),
+ *   q_i = (float)(((T[i,0] s_x + T[i,1] s_y) + T[i,2] s_z) + T[i,3]),   i = 0, 1, 2
+ * - every product and every sum one correctly rounded float64 operation (no fused multiply-add), in exactly this order, then ONE
+ * rounding to float32.  A float64 restatement that keeps the order gives the same bits.  Row 3 of T is never read. */
+
+/* Index over a target cloud, built once and searched many times (the target of a registration does not move).  `index`: caller's
+ * device memory of gsr_nn_index_bytes(Pt) bytes, 256-byte aligned; opaque - the points in Morton order as float4 (xyz, original
+ * row), the AABBs of 64-point boxes and of 64-box super-boxes, the bounding box of the finite coordinates and its centre, then
+ * the build's scratch.  A row with a non-finite coordinate is never anybody's neighbour.  Deterministic, no allocation.
+ * Errors before any launch: Pt outside [1, 2^30 - 1], NULL target / index: GSR_ERR_INVALID_ARGUMENT; index_bytes too small:
+ * GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_nn_index_bytes(int64_t Pt);
+int gsr_nn_index_build(int64_t Pt, const float* target /*[Pt,3]*/, void* index, size_t index_bytes, void* stream);
+
+/* Exact nearest neighbour in the indexed target of every q = T s, s a row of `source`, answers in ORIGINAL row order.  Distances
+ * are the float32 values of gsr_knn_k (differences, then fma(dz,dz, fma(dy,dy, dx*dx))).  The answer of a row is the
+ * lexicographic minimum of (d2, target row) over the finite target rows: among equal float32 distances the smallest row wins,
+ * so the row as well as the distance is independent of the traversal - two runs, any permutation of the source rows and any
+ * `order` give the same bits.  A correspondence is valid iff d2 <= max_dist2 (+inf allowed; it also is the initial pruning
+ * bound); otherwise, and for a source row whose q is not finite, idx_out = -1 and dist2_out = +inf.
+ * order (device int32[Ps], or NULL): a permutation of the source rows; thread t answers row order[t], so that the lanes of a
+ * wave can be given neighbouring queries (gsr_nn_query_order).  It changes no output bit.  Entries outside [0, Ps) are skipped.
+ * Errors before the launch: Pt / Ps outside [1, 2^30 - 1], NULL index / source / idx_out, max_dist2 negative or NaN:
+ * GSR_ERR_INVALID_ARGUMENT.  (The index is not sized here: it must be the one gsr_nn_index_build filled for this Pt.) */
+int gsr_nn_search(int64_t Pt, const void* index, int64_t Ps, const float* source /*[Ps,3]*/,
+                  const double* T_dev /*[16] row-major, or NULL*/, float max_dist2, const int32_t* order /*[Ps] or NULL*/,
+                  int32_t* idx_out /*[Ps]*/, float* dist2_out /*[Ps] or NULL*/, void* stream);
+
+/* order_out[Ps]: the source rows sorted (stably) by the 30-bit Morton code of q = T s in the index's bounding box - queries outside
+ * the box fall into the cells of its faces.  Errors before any launch: sizes outside [1, 2^30 - 1], NULL index / source /
+ * order_out / workspace: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_nn_order_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_nn_order_workspace_bytes(int64_t Ps);
+int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* source /*[Ps,3]*/,
+                       const double* T_dev /*[16] or NULL*/, int32_t* order_out /*[Ps]*/, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* out[i] = q = T points[i] as defined above (what a registration applies to the full-resolution cloud once it has T).  `out` may
+ * be `points`.  Errors before the launch: P outside [1, 2^30 - 1], NULL points / out: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_transform_points(int64_t P, const float* points /*[P,3]*/, const double* T_dev /*[16] or NULL*/, float* out /*[P,3]*/,
+                         void* stream);
+
+/* One point-to-point ICP update on the device.  Row i takes part iff 0 <= idx[i] < Pt and both q_i = T s_i and
+ * p_i = target[idx[i]] are finite.  Over those n rows, in float64, about a shift taken from the target (a cloud far from the
+ * origin loses nothing): sum |q - p|^2, sum q, sum p, sum q p^T - at most 256 workgroups over fixed slices, a fixed butterfly
+ * inside the wave, wave and workgroup sums added in order, no float atomics: deterministic.  One thread then finds the rigid dT
+ * (no scale) that minimises sum |dT q - p|^2 by Horn's closed form - the rotation is the unit eigenvector of the largest
+ * eigenvalue of the symmetric 4 x 4 matrix of the centred cross-covariance, found by cyclic Jacobi with a fixed number of sweeps
+ * and normalised again before the matrix is formed, so dT is a proper rotation whatever the data (a planar cloud too) - and
+ * stores T <- dT T (row 3 = 0 0 0 1).
+ * stats_dev[8] = n, fitness = n / Ps, inlier_rmse = sqrt(sum |q - p|^2 / n) (0 with n = 0), status, sum |q - p|^2, the largest
+ * eigenvalue, 0, 0.  n, fitness and inlier_rmse describe the INCOMING T (Open3D's convention: the correspondence set of the
+ * search that produced idx).  status: 0 = T updated; 1 = n < 3, T unchanged; 2 = no usable eigenvector (sums not finite), T
+ * unchanged.  Errors before any launch: sizes outside [1, 2^30 - 1], NULL source / target / idx / T_dev / stats_dev / workspace:
+ * GSR_ERR_INVALID_ARGUMENT; workspace below gsr_icp_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+size_t gsr_icp_workspace_bytes(int64_t Ps);
+int gsr_icp_update(int64_t Ps, const float* source /*[Ps,3]*/, int64_t Pt, const float* target /*[Pt,3]*/,
+                   const int32_t* idx /*[Ps]*/, double* T_dev /*[16] in/out*/, double* stats_dev /*[8] out*/, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
