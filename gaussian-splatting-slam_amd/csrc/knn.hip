@@ -246,26 +246,7 @@ __global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, cons
 }
 
 // ---- k = 1 .. 32 ------------------------------------------------------------------------------------------------------------
-// knn_insert over K slots, ascending: d bubbles up the chain, every index a compile-time constant (registers, no scratch)
-template <int K>
-__device__ __forceinline__ void knn_insert_k(float d, float (&b)[K]) {
-  if (d < b[K - 1]) {      // (false for NaN)
-    float t = d;
-#pragma unroll
-    for (int i = 0; i < K - 1; i++) {
-      const float hi = fmaxf(b[i], t);
-      b[i] = fminf(b[i], t);
-      t = hi;
-    }
-    b[K - 1] = fminf(b[K - 1], t);
-  }
-}
-template <int K>
-__device__ __forceinline__ void knn_reset_k(float (&b)[K], int pad) {      // `pad` = K - k leading slots at -inf, the rest +inf
-#pragma unroll
-  for (int i = 0; i < K; i++) b[i] = i < pad ? -KNN_INF : KNN_INF;
-}
-
+// (knn_insert_k / knn_reset_k, the per-thread list over K slots: knn_common.h - normals.hip runs the same sweep)
 // one thread per query, as k_knn_query (every row is a query); dist2 [P,k] and / or mean [P] in ORIGINAL row order
 template <int K>
 __global__ __launch_bounds__(256) void k_knn_query_k(uint32_t P, int k, const float4* __restrict__ pts,

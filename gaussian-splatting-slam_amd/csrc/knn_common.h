@@ -27,6 +27,51 @@ struct GsrKnnBuild {
 // knn.hip: bounding box, 30-bit Morton codes, the stable sort, boxes, super-boxes - the launches gsr_knn_k starts with
 void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st);
 
+// ---- a structure kept in ONE caller-owned blob (registration.hip: the target's index; normals.hip: the workspace): what a search
+// reads first, the build's scratch behind it ----
+struct GsrNnLayout {
+  size_t bbox;                  // float[8] min xyz, max xyz; double[3] centre at + 64
+  size_t pts;                   // float4[P]
+  size_t box_lo, box_hi;        // float4[nbox]
+  size_t sup_lo, sup_hi;        // float4[nsuper]
+  size_t keep;                  // what a search reads ends here; the rest is the build's scratch
+  size_t bbox_part, key_a, key_b, val_a, val_b, radix_tmp;
+  size_t total;
+};
+static inline GsrNnLayout nn_layout(size_t P) {
+  GsrNnLayout L;
+  size_t o = 0;
+  if (P == 0) P = 1;
+  L.bbox = o;      o += 256;
+  L.pts = o;       o += gsr_align(P * 16);
+  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
+  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.keep = o;
+  L.bbox_part = o; o += gsr_knn_bbox_part_bytes();
+  L.key_a = o;     o += gsr_align(P * 4);
+  L.key_b = o;     o += gsr_align(P * 4);
+  L.val_a = o;     o += gsr_align(P * 4);
+  L.val_b = o;     o += gsr_align(P * 4);
+  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
+  L.total = o;
+  return L;
+}
+// the buffers of gsr_knn_build inside a blob of that layout
+static inline GsrKnnBuild nn_build_views(char* blob, const GsrNnLayout& L) {
+  GsrKnnBuild b;
+  b.bbox_part = (float*)(blob + L.bbox_part);
+  b.bbox = (float*)(blob + L.bbox);
+  b.key[0] = (uint32_t*)(blob + L.key_a); b.key[1] = (uint32_t*)(blob + L.key_b);
+  b.val[0] = (uint32_t*)(blob + L.val_a); b.val[1] = (uint32_t*)(blob + L.val_b);
+  b.radix_tmp = (uint32_t*)(blob + L.radix_tmp);
+  b.pts = (float4*)(blob + L.pts);
+  b.box_lo = (float4*)(blob + L.box_lo); b.box_hi = (float4*)(blob + L.box_hi);
+  b.sup_lo = (float4*)(blob + L.sup_lo); b.sup_hi = (float4*)(blob + L.sup_hi);
+  return b;
+}
+
 #ifdef __HIPCC__
 #define KNN_INF __builtin_huge_valf()
 
@@ -77,5 +122,33 @@ __device__ __forceinline__ float knn_box_d2(const float4 q, const float4 lo, con
   const float dy = fmaxf(0.f, fmaxf(__fsub_rn(q.y, hi.y), __fsub_rn(lo.y, q.y)));
   const float dz = fmaxf(0.f, fmaxf(__fsub_rn(q.z, hi.z), __fsub_rn(lo.z, q.z)));
   return knn_sq(dx, dy, dz);
+}
+
+// a row with a non-finite coordinate as the blob structures store it: NaN NaN NaN, the original row kept in .w - every distance
+// to it is NaN, which fails every comparison: nobody's neighbour
+__device__ __forceinline__ float4 knn_mask_non_finite(const float4 p) {
+  if (knn_finite(p.x) && knn_finite(p.y) && knn_finite(p.z)) return p;
+  const float nan = __builtin_nanf("");
+  return make_float4(nan, nan, nan, p.w);
+}
+
+// knn_insert over K slots, ascending: d bubbles up the chain, every index a compile-time constant (registers, no scratch)
+template <int K>
+__device__ __forceinline__ void knn_insert_k(float d, float (&b)[K]) {
+  if (d < b[K - 1]) {      // (false for NaN)
+    float t = d;
+#pragma unroll
+    for (int i = 0; i < K - 1; i++) {
+      const float hi = fmaxf(b[i], t);
+      b[i] = fminf(b[i], t);
+      t = hi;
+    }
+    b[K - 1] = fminf(b[K - 1], t);
+  }
+}
+template <int K>
+__device__ __forceinline__ void knn_reset_k(float (&b)[K], int pad) {      // `pad` = K - k leading slots at -inf, the rest +inf
+#pragma unroll
+  for (int i = 0; i < K; i++) b[i] = i < pad ? -KNN_INF : KNN_INF;
 }
 #endif

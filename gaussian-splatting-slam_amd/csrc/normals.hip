@@ -1,0 +1,236 @@
+// normals.hip - surface normals of a point cloud: what the reference takes from Open3D's
+// estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (convert_visual_merged_msg.py:181, :193-196, :348) - the input of a
+// point-to-plane registration (csrc/registration.hip, gsr_icp_update_plane).
+//
+// gsr_estimate_normals: the structure of knn.hip (knn_common.h) over the cloud, rows with a non-finite coordinate turned into
+//   NaN NaN NaN (every distance to them is NaN and fails every comparison: nobody's neighbour), then ONE launch, one thread per
+//   query in Morton order, two sweeps over the same boxes:
+//   1. the bound.  k = max_nn - 1 (max_nn counts the point itself).  The register top-K sweep of k_knn_query_k, distances only,
+//      seeded by the Morton window, gives d_k, the k-th smallest d2 to the other finite rows (+inf with fewer than k).  Only
+//      min(r2, d_k) is needed, so the sweep also prunes at r2: with d_k <= r2 all k smallest values lie below r2 and are seen;
+//      otherwise the list's last slot holds something above r2 or +inf, and the minimum is r2 either way.
+//   2. the sums.  bound = min(r2, d_k) is now a FIXED pruning radius (it prunes from the first box).  Every row j != i with
+//      d2(i,j) <= bound is a member - rows tied at the bound all are, so no row tie-break is needed and no neighbour index is ever
+//      stored.  delta = p_j - p_i per component in float32 (__fsub_rn), promoted; S1 = sum delta and S2 = sum delta delta^T (six
+//      values) in float64, in sorted-position order: fixed for a given input, so two runs give the same bits.  The point itself
+//      contributes delta = 0 and counts: n = 1 + members.
+//   Then C = S2 / n - (S1 / n)(S1 / n)^T and cyclic Jacobi on the symmetric 3 x 3 in float64, a fixed number of sweeps, every
+//   index a compile-time constant (registers, no scratch); eigenvalues ascending; the normal is the eigenvector of the smallest,
+//   normalised again in float64 and rounded to float32 once.  Sign: towards the viewpoint (n.(v - p) >= 0), or without one the
+//   component of largest magnitude positive.  n < 3: (0, 0, 1) and zero eigenvalues, whatever the viewpoint.  A non-finite row:
+//   NaN normal and eigenvalues, count 0.
+//   The top-K registers of sweep 1 are dead in sweep 2, where the nine float64 sums live: one launch holds both.
+#include "knn_common.h"
+
+#define GSR_NORMALS_SWEEPS 8      // cyclic Jacobi on a 3 x 3 symmetric matrix: quadratic once the off-diagonal is small; 5 - 6 reach 1e-16
+
+// rows with a non-finite coordinate become NaN NaN NaN (.w, the original row, stays)
+__global__ __launch_bounds__(256) void k_normals_mask(uint32_t P, float4* __restrict__ pts) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= P) return;
+  pts[j] = knn_mask_non_finite(pts[j]);
+}
+
+// one Jacobi rotation in the (p, q) plane of a symmetric 3 x 3: app, aqq, apq the plane's entries, akp / akq the two entries that
+// couple the third index k to it, (v0p, v0q) .. (v2p, v2q) the rows of the eigenvector matrix's columns p and q
+__device__ __forceinline__ void normals_rotate(double& app, double& aqq, double& apq, double& akp, double& akq, double& v0p,
+                                               double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double kp = akp, kq = akq;
+  akp = c * kp - s * kq;
+  akq = s * kp + c * kq;
+  double a, b;
+  a = v0p; b = v0q; v0p = c * a - s * b; v0q = s * a + c * b;
+  a = v1p; b = v1q; v1p = c * a - s * b; v1q = s * a + c * b;
+  a = v2p; b = v2q; v2p = c * a - s * b; v2q = s * a + c * b;
+}
+
+struct GsrNormalsView {
+  float x, y, z;
+  int32_t on;
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void k_normals(uint32_t P, int k, float r2, GsrNormalsView view, const float4* __restrict__ pts,
+                                                 const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
+                                                 uint32_t nbox, const float4* __restrict__ sup_lo,
+                                                 const float4* __restrict__ sup_hi, uint32_t nsuper, float* __restrict__ normals,
+                                                 int32_t* __restrict__ count_out, float* __restrict__ eig_out) {
+  __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  const bool active = q < P;
+  const uint32_t pos = active ? q : 0u;
+  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  // ---- sweep 1: min(r2, d_k) ----
+  float bound;
+  {
+    const int pad = K - k;
+    float b[K];
+    knn_reset_k<K>(b, pad);
+    if (active) {
+      const uint32_t kk = (uint32_t)k;
+      const uint32_t j0 = pos >= kk ? pos - kk : 0u, j1 = min(P - 1u, pos + kk);
+      for (uint32_t j = j0; j <= j1; j++)
+        if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
+    }
+    // an upper bound of d_k from the Morton window, cut at r2; the sweep starts from an empty list again
+    const float seed = fminf(b[K - 1], r2);
+    knn_reset_k<K>(b, pad);
+    for (uint32_t base = 0; base < nsuper; base += 256u) {
+      __syncthreads();
+      if (base + threadIdx.x < nsuper) {
+        s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
+        s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
+      }
+      __syncthreads();
+      if (!active) continue;
+      const uint32_t n = min(256u, nsuper - base);
+      for (uint32_t s = 0; s < n; s++) {
+        if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b[K - 1], seed))) continue;
+        const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
+        for (uint32_t bx = bb; bx < be; bx++) {
+          if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= fminf(b[K - 1], seed))) continue;
+          const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
+          for (uint32_t j = jb; j < je; j++)
+            if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
+        }
+      }
+    }
+    bound = fminf(b[K - 1], r2);
+  }
+  // ---- sweep 2: the sums over { j != i : d2 <= bound } ----
+  double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+  uint32_t members = 0u;
+  for (uint32_t base = 0; base < nsuper; base += 256u) {
+    __syncthreads();
+    if (base + threadIdx.x < nsuper) {
+      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
+      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
+    }
+    __syncthreads();
+    if (!active) continue;
+    const uint32_t n = min(256u, nsuper - base);
+    for (uint32_t s = 0; s < n; s++) {
+      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= bound)) continue;
+      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
+      for (uint32_t bx = bb; bx < be; bx++) {
+        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= bound)) continue;
+        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
+        for (uint32_t j = jb; j < je; j++) {
+          const float4 p = pts[j];
+          const float fx = __fsub_rn(me.x, p.x), fy = __fsub_rn(me.y, p.y), fz = __fsub_rn(me.z, p.z);
+          if (j == pos || !(knn_sq(fx, fy, fz) <= bound)) continue;      // (NaN: not a member)
+          // delta = p_j - p_i = -(p_i - p_j), exactly
+          const double dx = -(double)fx, dy = -(double)fy, dz = -(double)fz;
+          members++;
+          s1x += dx; s1y += dy; s1z += dz;
+          sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
+          syy += dy * dy; syz += dy * dz; szz += dz * dz;
+        }
+      }
+    }
+  }
+  if (!active) return;
+  const size_t row = (size_t)__float_as_uint(me.w);
+  const bool finite = knn_finite(me.x) && knn_finite(me.y) && knn_finite(me.z);
+  const uint32_t count = finite ? members + 1u : 0u;
+  if (count_out) count_out[row] = (int32_t)count;
+  float nx = 0.f, ny = 0.f, nz = 1.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+  if (!finite) {
+    nx = ny = nz = e0 = e1 = e2 = __builtin_nanf("");
+  } else if (count >= 3u) {
+    const double n = (double)count;
+    const double mx = s1x / n, my = s1y / n, mz = s1z / n;
+    double a00 = sxx / n - mx * mx, a01 = sxy / n - mx * my, a02 = sxz / n - mx * mz;
+    double a11 = syy / n - my * my, a12 = syz / n - my * mz, a22 = szz / n - mz * mz;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < GSR_NORMALS_SWEEPS; sweep++) {
+      normals_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);      // (0, 1), third index 2
+      normals_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);      // (0, 2), third index 1
+      normals_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);      // (1, 2), third index 0
+    }
+    // the column of the smallest diagonal entry (the first on ties), and the three values in ascending order
+    const bool c0 = a00 <= a11 && a00 <= a22, c1 = !c0 && a11 <= a22;
+    double wx = c0 ? v00 : (c1 ? v01 : v02), wy = c0 ? v10 : (c1 ? v11 : v12), wz = c0 ? v20 : (c1 ? v21 : v22);
+    const double lo = fmin(a00, fmin(a11, a22)), hi = fmax(a00, fmax(a11, a22));
+    const double mid = fmax(fmin(a00, a11), fmin(fmax(a00, a11), a22));
+    const double norm = sqrt((wx * wx + wy * wy) + wz * wz);
+    wx /= norm; wy /= norm; wz /= norm;
+    nx = (float)wx; ny = (float)wy; nz = (float)wz;
+    e0 = (float)lo; e1 = (float)mid; e2 = (float)hi;
+    bool flip;
+    if (view.on) {
+      const double d = (wx * ((double)view.x - (double)me.x) + wy * ((double)view.y - (double)me.y)) +
+                       wz * ((double)view.z - (double)me.z);
+      flip = d < 0.0;
+    } else {
+      const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
+      const float lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+      flip = lead < 0.f;
+    }
+    if (flip) {
+      nx = -nx; ny = -ny; nz = -nz;
+    }
+  }
+  normals[3 * row] = nx;
+  normals[3 * row + 1] = ny;
+  normals[3 * row + 2] = nz;
+  if (eig_out) {
+    eig_out[3 * row] = e0;
+    eig_out[3 * row + 1] = e1;
+    eig_out[3 * row + 2] = e2;
+  }
+}
+
+extern "C" {
+
+size_t gsr_normals_workspace_bytes(int64_t P) { return nn_layout((size_t)(P < 1 ? 1 : P)).total; }
+
+int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t max_nn, const float* viewpoint, float* normals,
+                         int32_t* count_out, float* eigenvalues_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (P <= 0 || P > 0x3FFFFFFF || !points || !normals || !workspace || max_nn < 3 || max_nn > GSR_KNN_K_MAX + 1 ||
+      !(radius > 0.f) ||
+      (viewpoint && !(fabsf(viewpoint[0]) < KNN_INF && fabsf(viewpoint[1]) < KNN_INF && fabsf(viewpoint[2]) < KNN_INF))) {
+    gsr_set_error("estimate_normals: bad arguments (P = %lld, radius = %g: expected > 0, max_nn = %d: expected 3 .. %d, a finite "
+                  "viewpoint or none)", (long long)P, (double)radius, (int)max_nn, GSR_KNN_K_MAX + 1);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrNnLayout L = nn_layout((size_t)P);      // (the layout of a target index: knn_common.h)
+  if (workspace_bytes < L.total) {
+    gsr_set_error("estimate_normals: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const GsrKnnBuild b = nn_build_views(ws, L);
+  gsr_knn_build(P, points, b, st);
+  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
+  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
+  GSR_LAUNCH("normals_mask", k_normals_mask, dim3(nblk), dim3(256), 0, st, n, b.pts);
+  const float r2 = radius * radius;      // the float32 square (+inf stays, and a large radius may become, +inf)
+  GsrNormalsView view;
+  view.on = viewpoint ? 1 : 0;
+  view.x = viewpoint ? viewpoint[0] : 0.f;
+  view.y = viewpoint ? viewpoint[1] : 0.f;
+  view.z = viewpoint ? viewpoint[2] : 0.f;
+  const int k = (int)max_nn - 1;
+#define NORMALS_K(K)                                                                                                          \
+  GSR_LAUNCH("normals_k" #K, k_normals<K>, dim3(nblk), dim3(256), 0, st, n, k, r2, view, (const float4*)b.pts,                \
+             (const float4*)b.box_lo, (const float4*)b.box_hi, nbox, (const float4*)b.sup_lo, (const float4*)b.sup_hi, nsuper, \
+             normals, count_out, eigenvalues_out)
+  if (k <= 4) NORMALS_K(4);
+  else if (k <= 8) NORMALS_K(8);
+  else if (k <= 16) NORMALS_K(16);
+  else NORMALS_K(32);
+#undef NORMALS_K
+  return gsr_launch_status("estimate_normals launch");
+}
+
+}  // extern "C"

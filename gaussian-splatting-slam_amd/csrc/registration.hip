@@ -25,39 +25,12 @@
 
 #define GSR_ICP_BLOCKS 256
 #define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
+#define GSR_ICP_PLANE_SUMS 30      // n, sum d2, sum r^2, J^T r [6], upper triangle of J^T J [21]
+#define GSR_ICP_PIVOT_MIN 1e-12    // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
 #define GSR_ICP_SWEEPS 12          // cyclic Jacobi on a 4 x 4 symmetric matrix converges quadratically: 6 - 7 sweeps reach 1e-16
 #define GSR_NN_NONE 0x7FFFFFFFu    // no neighbour yet: above every row (P <= 2^30 - 1)
 
-// ---- the index blob ---------------------------------------------------------------------------------------------------------
-struct GsrNnLayout {
-  size_t bbox;                  // float[8] min xyz, max xyz; double[3] centre at + 64
-  size_t pts;                   // float4[P]
-  size_t box_lo, box_hi;        // float4[nbox]
-  size_t sup_lo, sup_hi;        // float4[nsuper]
-  size_t keep;                  // what a search reads ends here; the rest is the build's scratch
-  size_t bbox_part, key_a, key_b, val_a, val_b, radix_tmp;
-  size_t total;
-};
-static inline GsrNnLayout nn_layout(size_t P) {
-  GsrNnLayout L;
-  size_t o = 0;
-  if (P == 0) P = 1;
-  L.bbox = o;      o += 256;
-  L.pts = o;       o += gsr_align(P * 16);
-  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
-  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
-  L.keep = o;
-  L.bbox_part = o; o += gsr_knn_bbox_part_bytes();
-  L.key_a = o;     o += gsr_align(P * 4);
-  L.key_b = o;     o += gsr_align(P * 4);
-  L.val_a = o;     o += gsr_align(P * 4);
-  L.val_b = o;     o += gsr_align(P * 4);
-  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
-  L.total = o;
-  return L;
-}
+// (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
 
 // workspace of gsr_nn_query_order: codes / rows ping-pong and the sort's scratch
 struct GsrNnOrderLayout {
@@ -79,14 +52,14 @@ static inline GsrNnOrderLayout nn_order_layout(size_t P) {
 // workspace of gsr_icp_update
 struct GsrIcpLayout {
   size_t shift;      // double[4]: the shift, [3] = 1 when a valid row exists
-  size_t part;       // double[GSR_ICP_BLOCKS][GSR_ICP_SUMS]
+  size_t part;       // double[GSR_ICP_BLOCKS][GSR_ICP_PLANE_SUMS] (the point-to-point update uses GSR_ICP_SUMS of each row's)
   size_t total;
 };
 static inline GsrIcpLayout icp_layout() {
   GsrIcpLayout L;
   L.shift = 0;
   L.part = 256;
-  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_SUMS * 8);
+  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_PLANE_SUMS * 8);
   return L;
 }
 
@@ -126,11 +99,7 @@ __global__ __launch_bounds__(256) void k_nn_finish_index(uint32_t P, float4* __r
     }
   }
   if (j >= P) return;
-  const float4 p = pts[j];
-  if (!(knn_finite(p.x) && knn_finite(p.y) && knn_finite(p.z))) {
-    const float nan = __builtin_nanf("");
-    pts[j] = make_float4(nan, nan, nan, p.w);
-  }
+  pts[j] = knn_mask_non_finite(pts[j]);
 }
 
 // Morton code, in the target's box, of every transformed source row (the key of the `order` permutation)
@@ -215,18 +184,19 @@ __device__ __forceinline__ double reg_wave_sum(double v) {      // the same tota
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-// GSR_ICP_SUMS per-thread values summed over a 256-thread workgroup; the result is valid in thread 0
-__device__ __forceinline__ void reg_block_sum(double (&s)[GSR_ICP_SUMS]) {
-  __shared__ double sh[4][GSR_ICP_SUMS];
+// N per-thread values summed over a 256-thread workgroup; the result is valid in thread 0
+template <int N>
+__device__ __forceinline__ void reg_block_sum(double (&s)[N]) {
+  __shared__ double sh[4][N];
 #pragma unroll
-  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = reg_wave_sum(s[a]);
+  for (int a = 0; a < N; a++) s[a] = reg_wave_sum(s[a]);
   if (gsr_lane() == 0) {
 #pragma unroll
-    for (int a = 0; a < GSR_ICP_SUMS; a++) sh[threadIdx.x >> 6][a] = s[a];
+    for (int a = 0; a < N; a++) sh[threadIdx.x >> 6][a] = s[a];
   }
   __syncthreads();
 #pragma unroll
-  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
+  for (int a = 0; a < N; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
 }
 
 // the pair of row i, or false: no correspondence, an index outside the target, a non-finite point on either side
@@ -412,6 +382,146 @@ __global__ __launch_bounds__(256) void k_icp_final(uint32_t nblk, uint32_t Ps, c
   stats[3] = 0.0;
 }
 
+// ---- one point-to-plane update ------------------------------------------------------------------------------------------------------
+// per workgroup: s[0] = n, s[1] = sum |q - p|^2, s[2] = sum r^2, s[3..8] = J^T r, s[9..29] = J^T J rows 0 .. 5 from the diagonal on
+__global__ __launch_bounds__(256) void k_icp_plane_partial(uint32_t Ps, const float* __restrict__ src, uint32_t Pt,
+                                                           const float* __restrict__ tgt, const float* __restrict__ nrm,
+                                                           const int32_t* __restrict__ idx, const double* __restrict__ T_dev,
+                                                           const double* __restrict__ shift, double* __restrict__ part) {
+  const RegT T = reg_load(T_dev);
+  const double c0 = shift[0], c1 = shift[1], c2 = shift[2];
+  double s[GSR_ICP_PLANE_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] = 0.0;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < Ps; i += gridDim.x * 256u) {
+    float4 qf, pf;
+    if (!icp_pair(i, src, Pt, tgt, idx, T, qf, pf)) continue;
+    const size_t k = (size_t)idx[i];
+    const float n0 = nrm[3 * k], n1 = nrm[3 * k + 1], n2 = nrm[3 * k + 2];
+    if (!(knn_finite(n0) && knn_finite(n1) && knn_finite(n2))) continue;
+    // (float32 values: the differences below are exact in float64)
+    const double q[3] = {(double)qf.x - c0, (double)qf.y - c1, (double)qf.z - c2};
+    const double e[3] = {(double)qf.x - (double)pf.x, (double)qf.y - (double)pf.y, (double)qf.z - (double)pf.z};
+    const double n[3] = {(double)n0, (double)n1, (double)n2};
+    const double res = (e[0] * n[0] + e[1] * n[1]) + e[2] * n[2];
+    const double J[6] = {q[1] * n[2] - q[2] * n[1], q[2] * n[0] - q[0] * n[2], q[0] * n[1] - q[1] * n[0], n[0], n[1], n[2]};
+    s[0] += 1.0;
+    s[1] += (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    s[2] += res * res;
+    int o = 9;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      s[3 + a] += J[a] * res;
+#pragma unroll
+      for (int b = a; b < 6; b++) s[o++] += J[a] * J[b];
+    }
+  }
+  reg_block_sum(s);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_PLANE_SUMS + a] = s[a];
+  }
+}
+
+// one workgroup: the partials, then thread 0 solves and composes
+__global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
+                                                         const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                         double* __restrict__ stats) {
+  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
+  double s[GSR_ICP_PLANE_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] = 0.0;
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_PLANE_SUMS + a];
+  }
+  reg_block_sum(s);
+  if (threadIdx.x != 0) return;
+  const double n = s[0];
+  stats[0] = n;
+  stats[1] = n / (double)Ps;
+  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
+  stats[4] = s[1];
+  stats[5] = s[2];
+  stats[6] = stats[7] = 0.0;
+  if (n < 6.0) {
+    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
+    return;
+  }
+  {
+    int o = 9;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      g[a] = -s[3 + a];
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        A[a][b] = A[b][a] = s[o];
+        o++;
+      }
+    }
+  }
+  // J^T J = L D L^T, L unit lower triangular; every pivot is held against its own diagonal entry (scale-free per unknown)
+  for (int j = 0; j < 6; j++) {
+    double d = A[j][j];
+    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * D[k];
+    if (!(fabs(d) < (double)KNN_INF) || !(d > GSR_ICP_PIVOT_MIN * A[j][j])) {
+      stats[3] = 2.0;      // the correspondences do not fix this unknown (one plane, or sums that overflowed): T stays
+      return;
+    }
+    D[j] = d;
+    L[j][j] = 1.0;
+    for (int i = j + 1; i < 6; i++) {
+      double v = A[i][j];
+      for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * D[k];
+      L[i][j] = v / d;
+    }
+  }
+  for (int i = 0; i < 6; i++) {      // L y = g
+    double v = g[i];
+    for (int k = 0; k < i; k++) v -= L[i][k] * x[k];
+    x[i] = v;
+  }
+  for (int i = 0; i < 6; i++) x[i] /= D[i];
+  for (int i = 5; i >= 0; i--) {      // L^T x = y / D
+    double v = x[i];
+    for (int k = i + 1; k < 6; k++) v -= L[k][i] * x[k];
+    x[i] = v;
+  }
+  double ok = 0.0;
+  for (int i = 0; i < 6; i++) ok += x[i];
+  if (!(fabs(ok) < (double)KNN_INF)) {
+    stats[3] = 2.0;
+    return;
+  }
+  // dR = Rz(gamma) Ry(beta) Rx(alpha)
+  double sa, ca, sb, cb, sg, cg;
+  sincos(x[0], &sa, &ca);
+  sincos(x[1], &sb, &cb);
+  sincos(x[2], &sg, &cg);
+  double R[3][3];
+  R[0][0] = cb * cg; R[0][1] = sa * sb * cg - ca * sg; R[0][2] = ca * sb * cg + sa * sg;
+  R[1][0] = cb * sg; R[1][1] = sa * sb * sg + ca * cg; R[1][2] = ca * sb * sg - sa * cg;
+  R[2][0] = -sb;     R[2][1] = sa * cb;                R[2][2] = ca * cb;
+  // dT y = dR (y - c) + t + c
+  double td[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    td[a] = (x[3 + a] + shift[a]) - ((R[a][0] * shift[0] + R[a][1] * shift[1]) + R[a][2] * shift[2]);
+  // T <- dT T
+  double Tn[12];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      Tn[4 * a + b] = ((R[a][0] * T_dev[b] + R[a][1] * T_dev[4 + b]) + R[a][2] * T_dev[8 + b]) + (b == 3 ? td[a] : 0.0);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) T_dev[i] = Tn[i];
+  T_dev[12] = T_dev[13] = T_dev[14] = 0.0;
+  T_dev[15] = 1.0;
+  stats[3] = 0.0;
+}
+
 static bool reg_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
 
 extern "C" {
@@ -430,15 +540,7 @@ int gsr_nn_index_build(int64_t Pt, const float* target, void* index, size_t inde
   }
   hipStream_t st = (hipStream_t)stream;
   char* ix = (char*)index;
-  GsrKnnBuild b;
-  b.bbox_part = (float*)(ix + L.bbox_part);
-  b.bbox = (float*)(ix + L.bbox);
-  b.key[0] = (uint32_t*)(ix + L.key_a); b.key[1] = (uint32_t*)(ix + L.key_b);
-  b.val[0] = (uint32_t*)(ix + L.val_a); b.val[1] = (uint32_t*)(ix + L.val_b);
-  b.radix_tmp = (uint32_t*)(ix + L.radix_tmp);
-  b.pts = (float4*)(ix + L.pts);
-  b.box_lo = (float4*)(ix + L.box_lo); b.box_hi = (float4*)(ix + L.box_hi);
-  b.sup_lo = (float4*)(ix + L.sup_lo); b.sup_hi = (float4*)(ix + L.sup_hi);
+  const GsrKnnBuild b = nn_build_views(ix, L);
   gsr_knn_build(Pt, target, b, st);
   const uint32_t n = (uint32_t)Pt;
   GSR_LAUNCH("nn_finish_index", k_nn_finish_index, dim3((n + 255u) / 256u), dim3(256), 0, st, n, b.pts, b.bbox);
@@ -525,6 +627,33 @@ int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* tar
   GSR_LAUNCH("icp_final", k_icp_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part, (const double*)shift, T_dev,
              stats_dev);
   return gsr_launch_status("icp_update launch");
+}
+
+int gsr_icp_update_plane(int64_t Ps, const float* source, int64_t Pt, const float* target, const float* target_normals,
+                         const int32_t* idx, double* T_dev, double* stats_dev, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (reg_bad_size(Ps) || reg_bad_size(Pt) || !source || !target || !target_normals || !idx || !T_dev || !stats_dev ||
+      !workspace) {
+    gsr_set_error("icp_update_plane: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrIcpLayout L = icp_layout();
+  if (workspace_bytes < L.total) {
+    gsr_set_error("icp_update_plane: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  double* shift = (double*)(ws + L.shift);
+  double* part = (double*)(ws + L.part);
+  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
+  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
+  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
+  GSR_LAUNCH("icp_plane_partial", k_icp_plane_partial, dim3(sblk), dim3(256), 0, st, ns, source, nt, target, target_normals, idx,
+             (const double*)T_dev, (const double*)shift, part);
+  GSR_LAUNCH("icp_plane_final", k_icp_plane_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part,
+             (const double*)shift, T_dev, stats_dev);
+  return gsr_launch_status("icp_update_plane launch");
 }
 
 }  // extern "C"

@@ -214,6 +214,13 @@ EXPORTS = {
     "gsr_icp_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_icp_update": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    # Ps, source, Pt, target, target_normals, idx, T_dev, stats_dev, workspace + bytes, stream
+    "gsr_icp_update_plane": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, radius, max_nn, viewpoint (host), normals, count_out, eigenvalues_out, workspace + bytes, stream
+    "gsr_normals_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_estimate_normals": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_int32, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

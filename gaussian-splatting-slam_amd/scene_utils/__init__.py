@@ -15,6 +15,7 @@ from .keyframes import covisibility, KeyframeWindow, prune_unobserved
 from .exposure import apply_exposure
 from .transform import transform_camera, correct_keyframes, validate_transforms
 from .frames import Frame, FramePyramid, undistort, build_pyramid
-from .pointcloud import voxel_down_sample, statistical_outlier_mask, remove_statistical_outliers, condition_point_cloud
+from .pointcloud import voxel_down_sample, statistical_outlier_mask, remove_statistical_outliers, condition_point_cloud, \
+    estimate_normals
 from .registration import NeighborIndex, RegistrationResult, nn_search, transform_points, icp_update, evaluate_registration, \
     registration_icp, register_and_merge, align_map

@@ -1,6 +1,7 @@
 """Conditioning of a sensor point cloud before it seeds Gaussians: voxel-grid down-sampling and the statistical outlier filter -
 the reference's process_point_cloud (submodules/ros_workspace/src/gs_slam_msgs/scripts/pointcloud_pcd.py:163-209:
-voxel_down_sample, then remove_statistical_outlier, both Open3D there).  Everything runs in HIP (csrc/pointcloud.hip, the
+voxel_down_sample, then remove_statistical_outlier, both Open3D there) - and surface normals, the reference's estimate_normals
+calls (convert_visual_merged_msg.py:181, :193-196, :348).  Everything runs in HIP (csrc/pointcloud.hip, csrc/normals.hip, the
 neighbour search of csrc/knn.hip); there is no CPU path.  Arguments are validated before any device work."""
 from __future__ import annotations
 
@@ -47,6 +48,27 @@ def _check_filter(nb_neighbors, std_ratio):
     if not math.isfinite(std_ratio):
         raise ValueError(f"std_ratio={std_ratio}: expected a finite value")
     return int(nb_neighbors), float(std_ratio)
+
+
+def _check_normals(radius, max_nn, viewpoint=None):
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+        raise TypeError(f"radius={radius!r}: expected a number")
+    if math.isnan(radius) or not radius > 0:
+        raise ValueError(f"radius={radius}: expected a value > 0 (inf: limited by max_nn only)")
+    if isinstance(max_nn, bool) or not isinstance(max_nn, numbers.Integral):
+        raise TypeError(f"max_nn={max_nn!r}: expected an int")
+    if not 3 <= max_nn <= NB_NEIGHBORS_MAX:
+        raise ValueError(f"max_nn={max_nn}: expected 3 .. {NB_NEIGHBORS_MAX}")
+    if viewpoint is not None:
+        if isinstance(viewpoint, torch.Tensor):
+            viewpoint = viewpoint.detach().cpu().tolist()
+        try:
+            viewpoint = [float(c) for c in viewpoint]
+        except TypeError:
+            raise TypeError(f"viewpoint={viewpoint!r}: expected three numbers") from None
+        if len(viewpoint) != 3 or not all(math.isfinite(c) for c in viewpoint):
+            raise ValueError(f"viewpoint={viewpoint!r}: expected three finite values")
+    return float(radius), int(max_nn), viewpoint
 
 
 def _check_conditioning(voxel_size, origin, nb_neighbors, std_ratio):
@@ -143,3 +165,27 @@ def condition_point_cloud(points, colors, voxel_size=0.05, nb_neighbors=20, std_
     if nb_neighbors is not None:
         pts, col, _ = remove_statistical_outliers(pts, col, nb_neighbors, std_ratio)
     return pts, col
+
+
+def estimate_normals(points, radius=0.1, max_nn=30, viewpoint=None, return_stats=False):
+    """float32 [P,3] on the device: per row the unit normal of the plane through its hybrid neighbourhood - the rows within
+    `radius` (inf: no limit), cut at the max_nn nearest, the point itself counted (Open3D's KDTreeSearchParamHybrid; rows tied at
+    the cut-off distance are all kept) - the eigenvector of the smallest eigenvalue of their covariance, in float64 on the device
+    (include/gsr.h gsr_estimate_normals).  Sign: towards `viewpoint` (three values) or, without one, the component of largest
+    magnitude positive.  Fewer than three rows in the neighbourhood: (0, 0, 1).  A row with a non-finite coordinate: NaN.
+    `return_stats`: also (count int32 [P], the neighbourhood's size; eigenvalues float32 [P,3], ascending).  No read-back."""
+    r, nn, v = _check_normals(radius, max_nn, viewpoint)
+    pts, _ = _check_cloud(points, None, "estimate_normals")
+    _C = _gsr()
+    P, dev = int(pts.shape[0]), pts.device
+    normals = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    count = torch.empty(P, dtype=torch.int32, device=dev) if return_stats else None
+    eig = torch.empty((P, 3), dtype=torch.float32, device=dev) if return_stats else None
+    if P > 0:
+        lib = _C.lib()
+        view = (C.c_float * 3)(*v) if v is not None else None
+        with _C.on_device(dev):
+            ws = torch.empty(lib.gsr_normals_workspace_bytes(P), dtype=torch.uint8, device=dev)
+            _C.check(lib.gsr_estimate_normals(P, _C.ptr(pts), r, nn, view, _C.ptr(normals), _C.ptr(count), _C.ptr(eig), _C.ptr(ws),
+                                              ws.numel(), _C._stream()))
+    return (normals, count, eig) if return_stats else normals

@@ -1,4 +1,5 @@
-"""Rigid registration of one point cloud to another: a nearest-neighbour index with row numbers and point-to-point ICP - what the
+"""Rigid registration of one point cloud to another: a nearest-neighbour index with row numbers and ICP, point-to-point (the
+default) or point-to-plane on the target's normals - what the
 reference's pointcloud_registeration / pointcloud_registration_gpu (convert_visual_merged_msg.py:187-249, :393-432) do with Open3D
 before a message's cloud is merged into the accumulated one.  Everything runs in HIP (csrc/registration.hip over the structure of
 csrc/knn.hip); there is no CPU path.  Arguments are validated before any device work.
@@ -13,7 +14,7 @@ from typing import NamedTuple
 
 import torch
 
-from .pointcloud import _check_cloud, _check_voxel_size, voxel_down_sample
+from .pointcloud import _check_cloud, _check_normals, _check_voxel_size, estimate_normals, voxel_down_sample
 
 USE_QUERY_ORDER = True      # registration_icp Morton-sorts the queries once (profiles/README.md, registration_bench: measured)
 
@@ -51,6 +52,34 @@ def _check_icp(relative_fitness, relative_rmse, max_iteration, check_every):
             raise TypeError(f"{n}={v!r}: expected an int")
         if v < lo:
             raise ValueError(f"{n}={v}: expected >= {lo}")
+
+
+ESTIMATIONS = ("point_to_point", "point_to_plane")
+
+
+def _check_estimation(estimation):
+    if not isinstance(estimation, str):
+        raise TypeError(f"estimation={estimation!r}: expected one of {ESTIMATIONS}")
+    if estimation not in ESTIMATIONS:
+        raise ValueError(f"estimation={estimation!r}: expected one of {ESTIMATIONS}")
+    return estimation == "point_to_plane"
+
+
+def _rows(cloud):
+    return int(cloud.shape[0]) if isinstance(cloud, torch.Tensor) and cloud.dim() == 2 else None
+
+
+def _check_target_normals(normals, rows=None):
+    """None, or a floating-point [rows,3] tensor on the HIP device -> contiguous float32; type and shape first"""
+    if normals is None:
+        return None
+    if not isinstance(normals, torch.Tensor) or not normals.is_floating_point() or normals.dim() != 2 or \
+            normals.shape[1] != 3 or (rows is not None and int(normals.shape[0]) != rows):
+        raise ValueError("target_normals: expected a floating-point tensor of shape "
+                         f"({'Pt' if rows is None else rows}, 3), one row per target row")
+    if not normals.is_cuda:
+        raise _gsr().GsrError("target_normals must live on the HIP device (no CPU path)")
+    return normals.detach().float().contiguous()
 
 
 def _check_transform(T, name="transformation"):
@@ -168,27 +197,35 @@ def transform_points(points, transformation):
 
 
 class _Updater:
-    """gsr_icp_update on fixed clouds: the workspace is allocated once"""
+    """gsr_icp_update - with the target's normals gsr_icp_update_plane - on fixed clouds: the workspace is allocated once"""
 
-    def __init__(self, src, tgt):
+    def __init__(self, src, tgt, normals=None):
         _C = _gsr()
-        self.src, self.tgt = src, tgt
+        self.src, self.tgt, self.normals = src, tgt, normals
         with _C.on_device(src.device):
             self.ws = torch.empty(_C.lib().gsr_icp_workspace_bytes(int(src.shape[0])), dtype=torch.uint8, device=src.device)
 
     def __call__(self, idx, Td, stats):
         _C = _gsr()
         with _C.on_device(self.src.device):
+            if self.normals is not None:
+                _C.check(_C.lib().gsr_icp_update_plane(int(self.src.shape[0]), _C.ptr(self.src), int(self.tgt.shape[0]),
+                                                       _C.ptr(self.tgt), _C.ptr(self.normals), _C.ptr(idx), _C.ptr(Td),
+                                                       _C.ptr(stats), _C.ptr(self.ws), self.ws.numel(), _C._stream()))
+                return
             _C.check(_C.lib().gsr_icp_update(int(self.src.shape[0]), _C.ptr(self.src), int(self.tgt.shape[0]), _C.ptr(self.tgt),
                                              _C.ptr(idx), _C.ptr(Td), _C.ptr(stats), _C.ptr(self.ws), self.ws.numel(),
                                              _C._stream()))
 
 
-def icp_update(source, target, correspondences, transformation):
+def icp_update(source, target, correspondences, transformation, target_normals=None):
     """One ICP update from given correspondences (int32 [Ps], -1 = none) -> (new transformation float64 [4,4] on the device,
     stats float64 [8] on the device: n, fitness, inlier_rmse, status, sum of squared distances, ...; include/gsr.h
-    gsr_icp_update).  n, fitness and inlier_rmse describe the transformation that was passed in.  No read-back."""
+    gsr_icp_update).  n, fitness and inlier_rmse describe the transformation that was passed in.  No read-back.
+    target_normals ([Pt,3] float on the device): the point-to-plane update instead (gsr_icp_update_plane; stats[5] = the sum of
+    the squared point-to-plane residuals, status 1 below six correspondences, 2 when they do not fix all six unknowns)."""
     T = _check_transform(transformation)
+    nrm = _check_target_normals(target_normals, _rows(target))
     src, _ = _check_cloud(source, None, "icp_update")
     tgt, _ = _check_cloud(target, None, "icp_update")
     _nonempty(src, "icp_update", "source")
@@ -198,7 +235,7 @@ def icp_update(source, target, correspondences, transformation):
         raise ValueError(f"correspondences: expected an int32 tensor of shape ({int(src.shape[0])},)")
     Td = _device_T(T, src.device)
     stats = torch.zeros(8, dtype=torch.float64, device=src.device)
-    _Updater(src, tgt.to(src.device))(idx.to(src.device).contiguous(), Td, stats)
+    _Updater(src, tgt.to(src.device), None if nrm is None else nrm.to(src.device))(idx.to(src.device).contiguous(), Td, stats)
     return Td, stats
 
 
@@ -241,8 +278,9 @@ def evaluate_registration(source, target, max_correspondence_distance, transform
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
-                     max_iteration=30, check_every=1, index=None, use_order=None):
-    """Point-to-point ICP of `source` onto `target` (both [P,3] float on the HIP device) from `init` (None = identity).
+                     max_iteration=30, check_every=1, index=None, use_order=None, estimation="point_to_point",
+                     target_normals=None, normal_radius=None, normal_max_nn=30):
+    """ICP of `source` onto `target` (both [P,3] float on the HIP device) from `init` (None = identity).
 
     Iteration k searches the neighbours under T_k, sums them and replaces T_k by T_{k+1} on the device; its fitness and RMSE
     describe T_k.  Every `check_every` iterations they are read back, and the loop stops - as Open3D's does - once both
@@ -251,13 +289,30 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
     transformation.  check_every=0 enqueues max_iteration iterations without a read-back and reads once at the end.
     index: a NeighborIndex of `target` to reuse (`target` may then be None).  use_order: Morton-sort the queries once, from
     `init` (None: the measured default, USE_QUERY_ORDER); no result bit depends on it.
-    An iteration with fewer than three correspondences leaves the transformation as it is."""
+    An iteration with fewer than three correspondences leaves the transformation as it is.
+    estimation: "point_to_point" (Kabsch on the pairs) or "point_to_plane" (the residual along the target's normal: on floors,
+    walls and road surfaces, where pairs slide along the plane, it needs far fewer iterations).  Point-to-plane takes
+    `target_normals` ([Pt,3], one per target row) or estimates them once on the target with estimate_normals(normal_radius,
+    normal_max_nn) - normal_radius is then required; both at once, or either with "point_to_point", is a ValueError.  An iteration with fewer than six correspondences, or with planes that do not
+    fix all six unknowns, leaves the transformation as it is.  Fitness and RMSE are the Euclidean ones for both estimators."""
     _check_icp(relative_fitness, relative_rmse, max_iteration, check_every)
+    plane = _check_estimation(estimation)
+    if not plane and (target_normals is not None or normal_radius is not None):
+        raise ValueError('registration_icp: target_normals / normal_radius given, but estimation="point_to_point" uses no normals')
+    if target_normals is not None and normal_radius is not None:
+        raise ValueError("registration_icp: target_normals and normal_radius both given - pass the normals or have them estimated")
+    nrm = _check_target_normals(target_normals, index.size if isinstance(index, NeighborIndex) else _rows(target))
+    if plane and nrm is None:
+        if normal_radius is None:
+            raise ValueError('registration_icp: estimation="point_to_plane" needs target_normals, or normal_radius to estimate them')
+        _check_normals(normal_radius, normal_max_nn)
     src, index, md2, T = _prepare(source, target, max_correspondence_distance, init, index, "registration_icp")
     dev, P = src.device, int(src.shape[0])
     Td = _device_T(T, dev)
     order = index.query_order(src, Td) if (USE_QUERY_ORDER if use_order is None else use_order) else None
-    updater = _Updater(src, index.points)
+    if plane and nrm is None:
+        nrm = estimate_normals(index.points, normal_radius, normal_max_nn)
+    updater = _Updater(src, index.points, nrm.to(dev) if plane else None)
     idx = torch.empty(P, dtype=torch.int32, device=dev)
     stats = torch.zeros((max_iteration, 8), dtype=torch.float64, device=dev)
     iterations, converged = 0, False
@@ -275,12 +330,15 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
 
 
 def register_and_merge(source, source_colors, target, target_colors, voxel_size=0.05, max_correspondence_distance=None,
-                       merge_voxel_size=None, **icp):
+                       merge_voxel_size=None, estimation="point_to_point", **icp):
     """The reference's pointcloud_registeration: down-sample both clouds (voxel_down_sample, voxel_size), ICP of the down-sampled
     source onto the down-sampled target from the identity (max_correspondence_distance=None: 5 * voxel_size; further keywords
     go to registration_icp), move the FULL source by the result, concatenate it with the target (source rows first) and, with
-    merge_voxel_size, down-sample the merged cloud.  Colours: both or neither.  -> (points, colors or None, result)."""
+    merge_voxel_size, down-sample the merged cloud.  Colours: both or neither.  -> (points, colors or None, result).
+    estimation="point_to_plane": the down-sampled target's normals are estimated with radius = 2 * voxel_size, max_nn = 30 - the
+    reference's estimate_normals calls at :193-196 - and the registration is point-to-plane."""
     v = _check_voxel_size(voxel_size)
+    plane = _check_estimation(estimation)
     mv = None if merge_voxel_size is None else _check_voxel_size(merge_voxel_size)
     md = 5.0 * v if max_correspondence_distance is None else _check_distance("max_correspondence_distance",
                                                                              max_correspondence_distance, True)
@@ -288,10 +346,14 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
         raise ValueError("register_and_merge: colours for both clouds or for neither")
     if "init" in icp or "index" in icp:
         raise TypeError("register_and_merge: starts from the identity and builds its own index (init / index not accepted)")
+    if plane and ("target_normals" in icp or "normal_radius" in icp or "normal_max_nn" in icp):
+        raise TypeError("register_and_merge: estimates the down-sampled target's normals itself (radius 2 * voxel_size, max_nn 30)")
     src, scol = _check_cloud(source, source_colors, "register_and_merge")
     tgt, tcol = _check_cloud(target, target_colors, "register_and_merge")
     src_down, _ = voxel_down_sample(src, None, v)
     tgt_down, _ = voxel_down_sample(tgt, None, v)
+    if plane:
+        icp = dict(icp, estimation="point_to_plane", normal_radius=2.0 * v, normal_max_nn=30)
     result = registration_icp(src_down, tgt_down, md, **icp)
     points = torch.cat([transform_points(src, result.transformation), tgt.to(src.device)])
     colors = None if scol is None else torch.cat([scol, tcol.to(src.device)])

@@ -1,7 +1,8 @@
 """The native surface of `simple_knn`: `distCUDA2(points)` as the reference calls it, and `knn_dist2(points, first_query)`,
 the same search answered only for the rows from `first_query` on (new points against map + new points); `knn_k(points, k)`,
 the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds);
-`nn_search(query, target)`, the nearest row of ANOTHER cloud with its row number (csrc/registration.hip)."""
+`nn_search(query, target)`, the nearest row of ANOTHER cloud with its row number (csrc/registration.hip);
+`estimate_normals(points, radius, max_nn)`, the normal of every row from its hybrid neighbourhood (csrc/normals.hip)."""
 import math
 
 import torch
@@ -77,3 +78,10 @@ def nn_search(query, target, transform=None, max_distance=math.inf):
     the structure over `target` for repeated searches."""
     from scene_utils.registration import nn_search as _nn_search
     return _nn_search(query, target, transform, max_distance)
+
+
+def estimate_normals(points, radius=0.1, max_nn=30, viewpoint=None, return_stats=False):
+    """-> normals float32 [P,3] (with return_stats also count int32 [P] and eigenvalues float32 [P,3]): the covariance normal of
+    the rows within `radius`, cut at the max_nn nearest - `scene_utils.estimate_normals`."""
+    from scene_utils.pointcloud import estimate_normals as _estimate_normals
+    return _estimate_normals(points, radius, max_nn, viewpoint, return_stats)

@@ -50,6 +50,8 @@ extern "C" {
  *    integer building blocks;
  *    gsr_nn_index_bytes, gsr_nn_index_build, gsr_nn_search, gsr_nn_order_workspace_bytes, gsr_nn_query_order, gsr_transform_points,
  *    gsr_icp_workspace_bytes, gsr_icp_update: nearest neighbours of one cloud in another, with the row, and point-to-point ICP;
+ *    gsr_normals_workspace_bytes, gsr_estimate_normals (surface normals from a hybrid radius / max-count neighbourhood) and
+ *    gsr_icp_update_plane (the point-to-plane update; gsr_icp_workspace_bytes grew);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -689,11 +691,57 @@ int gsr_transform_points(int64_t P, const float* points /*[P,3]*/, const double*
  * eigenvalue, 0, 0.  n, fitness and inlier_rmse describe the INCOMING T (Open3D's convention: the correspondence set of the
  * search that produced idx).  status: 0 = T updated; 1 = n < 3, T unchanged; 2 = no usable eigenvector (sums not finite), T
  * unchanged.  Errors before any launch: sizes outside [1, 2^30 - 1], NULL source / target / idx / T_dev / stats_dev / workspace:
- * GSR_ERR_INVALID_ARGUMENT; workspace below gsr_icp_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+ * GSR_ERR_INVALID_ARGUMENT; workspace below gsr_icp_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation.
+ * gsr_icp_workspace_bytes serves gsr_icp_update_plane too and grew with it (30 partial sums per workgroup instead of 17: 61 696
+ * bytes, was 35 072); BOTH entries check against it, so a caller must ask the query and not keep the earlier figure. */
 size_t gsr_icp_workspace_bytes(int64_t Ps);
 int gsr_icp_update(int64_t Ps, const float* source /*[Ps,3]*/, int64_t Pt, const float* target /*[Pt,3]*/,
                    const int32_t* idx /*[Ps]*/, double* T_dev /*[16] in/out*/, double* stats_dev /*[8] out*/, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* One point-to-plane ICP update on the device: gsr_icp_update with the residual r_i = (q_i - p_i).n_i, n_i =
+ * target_normals[idx[i]].  Row i takes part iff 0 <= idx[i] < Pt and q_i = T s_i, p_i = target[idx[i]] and n_i are all finite.
+ * Everything is formed about the shift c of gsr_icp_update (the target point of the first row whose q and p are finite): with
+ * q' = q - c and p' = p - c, r_i = (q'_i - p'_i).n_i and J_i = [q'_i x n_i, n_i].  Over the n rows, in float64 and with the
+ * summation structure of gsr_icp_update (deterministic, no float atomics): the 21 entries of the upper triangle of J^T J, the 6
+ * of J^T r, n, sum |q - p|^2 and sum r^2.  One thread solves J^T J x = -J^T r by LDL^T; x = (alpha, beta, gamma, t),
+ * dR = Rz(gamma) Ry(beta) Rx(alpha) (what Open3D's TransformVector6dToMatrix4d forms: a product of exact rotations),
+ * dT = Tr(c) [dR, t] Tr(-c), and T <- dT T (row 3 = 0 0 0 1).
+ * stats_dev[8] = n, fitness = n / Ps, inlier_rmse = sqrt(sum |q - p|^2 / n) (the Euclidean one, Open3D's convention for every
+ * estimator; 0 with n = 0), status, sum |q - p|^2, sum r^2, 0, 0 - all of the INCOMING T.  status: 0 = T updated; 1 = n < 6, T
+ * unchanged; 2 = a pivot of the factorisation is not finite or is <= 1e-12 x its own diagonal entry of J^T J (the planes met do
+ * not fix that unknown - a single plane, say - or sums overflowed), T unchanged.
+ * Errors before any launch: sizes outside [1, 2^30 - 1], NULL source / target / target_normals / idx / T_dev / stats_dev /
+ * workspace: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_icp_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+int gsr_icp_update_plane(int64_t Ps, const float* source /*[Ps,3]*/, int64_t Pt, const float* target /*[Pt,3]*/,
+                         const float* target_normals /*[Pt,3]*/, const int32_t* idx /*[Ps]*/, double* T_dev /*[16] in/out*/,
+                         double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- surface normals (csrc/normals.hip) - what the reference takes from Open3D's
+ * estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) ---- */
+
+/* Normal of every row from the covariance of a hybrid neighbourhood, defined so that nothing depends on traversal or scheduling.
+ * d2(i,j): the float32 squared distance of gsr_knn_k.  k = max_nn - 1 (max_nn in [3, GSR_KNN_K_MAX + 1] counts the point itself);
+ * d_k = the k-th smallest d2 from row i to the OTHER finite rows, +inf if fewer than k exist; bound = min(r2, d_k), r2 the float32
+ * square of `radius` (> 0; +inf: count-limited only).  N_i = {i} + {j != i : d2(i,j) <= bound}: rows tied at the bound are ALL
+ * members, so count_i = |N_i| may exceed max_nn at exact ties - the one departure from Open3D's hybrid search; duplicates at
+ * distance 0 are members.
+ * delta_j = p_j - p_i per component in float32, promoted; S1 = sum delta, S2 = sum delta delta^T in float64 in the order of the
+ * sorted structure (fixed for a given input: two runs give identical bits); C = S2 / n - (S1 / n)(S1 / n)^T, n = count_i.
+ * Eigen-solve: cyclic Jacobi on the symmetric 3 x 3 in float64, a fixed number of sweeps.  eigenvalues_out: ascending.  The normal
+ * is the unit eigenvector of the smallest eigenvalue, normalised again in float64, rounded to float32 once.
+ * Sign: with `viewpoint` v (HOST float[3]) n.(v - p_i) >= 0 (Open3D's orient_normals_towards_camera_location); with NULL the
+ * component of largest magnitude (the first on ties) is positive.
+ * count_i < 3: n = (0, 0, 1) - whatever the viewpoint - and eigenvalues 0 (Open3D's fallback).  A row with a non-finite
+ * coordinate gets a NaN normal, NaN eigenvalues and count 0, and is nobody's neighbour.
+ * No float atomics, no allocation (gsr_normals_workspace_bytes(P)).  Errors before any launch: max_nn outside [3, 33], radius
+ * <= 0 or NaN, a non-finite viewpoint, P outside [1, 2^30 - 1], NULL points / normals / workspace: GSR_ERR_INVALID_ARGUMENT;
+ * workspace too small: GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_normals_workspace_bytes(int64_t P);
+int gsr_estimate_normals(int64_t P, const float* points /*[P,3]*/, float radius, int32_t max_nn,
+                         const float* viewpoint /*HOST [3] or NULL*/, float* normals /*[P,3]*/, int32_t* count_out /*[P] or NULL*/,
+                         float* eigenvalues_out /*[P,3] ascending, or NULL*/, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
