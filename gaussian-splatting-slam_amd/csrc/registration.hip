@@ -20,14 +20,14 @@
 //   fixed slices, n, |q - p|^2, q, p and q p^T in float64 (fixed butterfly over the wave, the four wave sums in order, no float
 //   atomics); one workgroup adds the partials and one thread solves Horn's closed form: the rotation is the eigenvector of the
 //   largest eigenvalue of the symmetric 4 x 4 matrix built from the centred cross-covariance - a unit quaternion, so a reflection
-//   cannot come out - found by cyclic Jacobi with a fixed number of sweeps.  T <- dT T.
+//   cannot come out - found by cyclic Jacobi with a fixed number of sweeps (horn_common.h, shared with features.hip).  T <- dT T.
 #include "knn_common.h"
+#include "horn_common.h"
 
 #define GSR_ICP_BLOCKS 256
 #define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
 #define GSR_ICP_PLANE_SUMS 30      // n, sum d2, sum r^2, J^T r [6], upper triangle of J^T J [21]
 #define GSR_ICP_PIVOT_MIN 1e-12    // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
-#define GSR_ICP_SWEEPS 12          // cyclic Jacobi on a 4 x 4 symmetric matrix converges quadratically: 6 - 7 sweeps reach 1e-16
 #define GSR_NN_NONE 0x7FFFFFFFu    // no neighbour yet: above every row (P <= 2^30 - 1)
 
 // (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
@@ -308,58 +308,11 @@ __global__ __launch_bounds__(256) void k_icp_final(uint32_t nblk, uint32_t Ps, c
 #pragma unroll
     for (int b = 0; b < 3; b++) M[a][b] = s[8 + 3 * a + b] - s[2 + a] * pb[b];
   }
-  // Horn 1987: the quaternion (w, x, y, z) of the rotation that takes q to p maximises v^T N v
-  A[0][0] = M[0][0] + M[1][1] + M[2][2];
-  A[1][1] = M[0][0] - M[1][1] - M[2][2];
-  A[2][2] = -M[0][0] + M[1][1] - M[2][2];
-  A[3][3] = -M[0][0] - M[1][1] + M[2][2];
-  A[0][1] = A[1][0] = M[1][2] - M[2][1];
-  A[0][2] = A[2][0] = M[2][0] - M[0][2];
-  A[0][3] = A[3][0] = M[0][1] - M[1][0];
-  A[1][2] = A[2][1] = M[0][1] + M[1][0];
-  A[1][3] = A[3][1] = M[2][0] + M[0][2];
-  A[2][3] = A[3][2] = M[1][2] + M[2][1];
-  for (int i = 0; i < 4; i++)
-    for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < GSR_ICP_SWEEPS; sweep++) {
-    for (int p = 0; p < 3; p++) {
-      for (int q = p + 1; q < 4; q++) {
-        const double apq = A[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-        A[p][p] -= t * apq;
-        A[q][q] += t * apq;
-        A[p][q] = A[q][p] = 0.0;
-        for (int k = 0; k < 4; k++) {
-          if (k != p && k != q) {
-            const double akp = A[k][p], akq = A[k][q];
-            A[k][p] = A[p][k] = c * akp - sn * akq;
-            A[k][q] = A[q][k] = sn * akp + c * akq;
-          }
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - sn * vkq;
-          V[k][q] = sn * vkp + c * vkq;
-        }
-      }
-    }
-  }
-  int best = 0;
-  for (int k = 1; k < 4; k++)
-    if (A[k][k] > A[best][best]) best = k;
-  double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
-  const double norm = sqrt(((w * w + x * x) + y * y) + z * z);
-  stats[5] = A[best][best];
-  if (!(norm > 0.5 && norm < 2.0)) {      // (a NaN too: sums that overflowed)
+  double R[3][3];
+  if (!horn_rotation(M, HornMat4{A}, HornMat4{V}, R, stats[5])) {      // (horn_common.h)
     stats[3] = 2.0;
     return;
   }
-  w /= norm; x /= norm; y /= norm; z /= norm;
-  double R[3][3];
-  R[0][0] = 1.0 - 2.0 * (y * y + z * z); R[0][1] = 2.0 * (x * y - w * z);       R[0][2] = 2.0 * (x * z + w * y);
-  R[1][0] = 2.0 * (x * y + w * z);       R[1][1] = 1.0 - 2.0 * (x * x + z * z); R[1][2] = 2.0 * (y * z - w * x);
-  R[2][0] = 2.0 * (x * z - w * y);       R[2][1] = 2.0 * (y * z + w * x);       R[2][2] = 1.0 - 2.0 * (x * x + y * y);
   // dT x = R (x - (c + qbar)) + (c + pbar)
   double td[3];
 #pragma unroll

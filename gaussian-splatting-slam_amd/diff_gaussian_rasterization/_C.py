@@ -99,6 +99,16 @@ class gsr_fused_adam(C.Structure):
     ]
 
 
+class gsr_ransac_debug(C.Structure):
+    _fields_ = [("samples", C.c_void_p), ("status", C.c_void_p), ("T", C.c_void_p)]
+
+
+FPFH_WIDTH = 33              # GSR_FPFH_WIDTH
+FEATURE_NN_TILE = 128        # GSR_FEATURE_NN_TILE
+RANSAC_N_MAX = 8             # GSR_RANSAC_N_MAX
+RANSAC_MAX_TRIALS = 1 << 20  # GSR_RANSAC_MAX_TRIALS
+RANSAC_BEST_WORDS = 20       # sizeof(gsr_ransac_best) / 8: count, sum_d2, trial, T[16], trials_checked
+
 _EXTRAS = C.POINTER(gsr_render_extras)
 _SCENE = [C.POINTER(gsr_settings), C.POINTER(gsr_gaussians)]
 # shared argument prefixes of the rasterizer's entry points (include/gsr.h), each named by what follows (settings, Gaussians):
@@ -221,6 +231,21 @@ EXPORTS = {
     "gsr_normals_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_estimate_normals": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_int32, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, normals, radius, max_nn, fpfh, spfh_counts, count, workspace + bytes, stream
+    "gsr_fpfh_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_compute_fpfh": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    # Nq, query, Nt, target, width, idx_out, dist2_out, workspace + bytes, stream
+    "gsr_feature_nn_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_feature_nn_tiles_per_split": (C.c_int32, [C.c_int64, C.c_int64]),
+    "gsr_feature_nn": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
+    # Ps, source, Pt, target, M, pairs, max_distance, ransac_n, edge_length_threshold, seed, t0, n, best, workspace + bytes,
+    # debug (host struct), stream
+    "gsr_ransac_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gsr_ransac_feature_matching": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
+                                              C.c_int32, C.c_float, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.POINTER(gsr_ransac_debug), C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

@@ -18,4 +18,5 @@ from .frames import Frame, FramePyramid, undistort, build_pyramid
 from .pointcloud import voxel_down_sample, statistical_outlier_mask, remove_statistical_outliers, condition_point_cloud, \
     estimate_normals
 from .registration import NeighborIndex, RegistrationResult, nn_search, transform_points, icp_update, evaluate_registration, \
-    registration_icp, register_and_merge, align_map
+    registration_icp, register_and_merge, align_map, compute_fpfh_feature, feature_nn, match_features, \
+    registration_ransac_based_on_feature_matching, global_registration, ransac_trials

@@ -5,7 +5,10 @@ before a message's cloud is merged into the accumulated one.  Everything runs in
 csrc/knn.hip); there is no CPU path.  Arguments are validated before any device work.
 
 The transformed point is q = (float32)(R s + t) evaluated in float64 in one fixed order (include/gsr.h), so a float64 restatement
-reproduces every query bit for bit; the neighbour is the lexicographic minimum of (float32 d2, target row)."""
+reproduces every query bit for bit; the neighbour is the lexicographic minimum of (float32 d2, target row).
+
+For clouds that are not roughly aligned: FPFH features, feature matching and RANSAC over the matches (csrc/features.hip) - the
+lines the reference has commented out at :198-213 - whose result starts ICP (`register_and_merge(global_init=True)`)."""
 from __future__ import annotations
 
 import math
@@ -329,14 +332,284 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
     return RegistrationResult(Td, fitness, rmse, iterations, converged, idx)
 
 
+# ---- global registration: FPFH features, matching, RANSAC (csrc/features.hip) ------------------------------------------------------
+FPFH_WIDTH = 33
+
+
+def _check_int(name, value, lo, hi=None):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
+        raise TypeError(f"{name}={value!r}: expected an int")
+    if value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name}={value}: expected {lo} .. {hi}" if hi is not None else f"{name}={value}: expected >= {lo}")
+    return int(value)
+
+
+def _check_seed(seed):
+    return _check_int("seed", seed, 0, 2 ** 64 - 1)
+
+
+def _check_fpfh(radius, max_nn):
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+        raise TypeError(f"radius={radius!r}: expected a number")
+    if math.isnan(radius) or not radius > 0:
+        raise ValueError(f"radius={radius}: expected a value > 0")
+    if isinstance(max_nn, bool) or not isinstance(max_nn, numbers.Integral):
+        raise TypeError(f"max_nn={max_nn!r}: expected an int")
+    if max_nn != 0 and not 3 <= max_nn <= 33:
+        raise ValueError(f"max_nn={max_nn}: expected 3 .. 33, or 0 for the radius alone")
+    if max_nn == 0 and math.isinf(radius):
+        raise ValueError("max_nn=0 (the radius alone) needs a finite radius")
+    return float(radius), int(max_nn)
+
+
+def _feature_shape(feature, name, rows=None):
+    if not isinstance(feature, torch.Tensor) or not feature.is_floating_point() or feature.dim() != 2 or \
+            feature.shape[1] != FPFH_WIDTH or (rows is not None and int(feature.shape[0]) != rows):
+        raise ValueError(f"{name}: expected a floating-point tensor of shape ({'N' if rows is None else rows}, {FPFH_WIDTH})")
+
+
+def _check_feature(feature, name, rows=None):
+    """a floating-point [rows,33] tensor on the HIP device -> contiguous float32; type and shape first"""
+    _feature_shape(feature, name, rows)
+    if not feature.is_cuda:
+        raise _gsr().GsrError(f"{name} must live on the HIP device (no CPU path)")
+    return feature.detach().float().contiguous()
+
+
+def _check_ransac(max_correspondence_distance, ransac_n, edge_length_threshold, max_iteration, confidence, seed, batch):
+    md = _check_distance("max_correspondence_distance", max_correspondence_distance, False)
+    n = _check_int("ransac_n", ransac_n, 3, 8)
+    for name, v, hi in (("edge_length_threshold", edge_length_threshold, 1.0), ("confidence", confidence, 1.0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise TypeError(f"{name}={v!r}: expected a number")
+        if not 0.0 <= v <= hi:      # (false for NaN)
+            raise ValueError(f"{name}={v}: expected 0 .. {hi}")
+    _check_int("max_iteration", max_iteration, 1)
+    _check_int("batch", batch, 1, 1 << 20)
+    return md, n, float(edge_length_threshold), float(confidence), _check_seed(seed)
+
+
+def _check_pairs(pairs):
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs: expected an int32 tensor of shape (M, 2): source row, target row")
+    if not pairs.is_cuda:
+        raise _gsr().GsrError("pairs must live on the HIP device (no CPU path)")
+    return pairs.contiguous()
+
+
+def compute_fpfh_feature(points, normals, radius, max_nn=0, return_stats=False):
+    """float32 [P,33] on the device: the fast point feature histogram of every row from its normals ([P,3]) - Open3D's
+    compute_fpfh_feature, defined bin by bin in include/gsr.h (gsr_compute_fpfh).  The neighbourhood is estimate_normals' (radius,
+    cut at the max_nn nearest, ties all kept), or with max_nn=0 the finite radius alone - how Open3D's (5 * voxel, 100) call is
+    served: a ball of five voxel sizes on a voxel-sampled surface holds fewer than 100 rows.  Rows are features (Open3D stores the
+    transpose).  A row with a non-finite point or normal: NaN, and nobody's neighbour.  `return_stats`: also (spfh_counts int32
+    [P,33], count int32 [P] - the neighbourhood's size, the row included).  No read-back."""
+    r, nn = _check_fpfh(radius, max_nn)
+    nrm = _check_target_normals(normals, _rows(points))
+    pts, _ = _check_cloud(points, None, "compute_fpfh_feature")
+    if nrm is None:
+        raise ValueError("normals: expected a floating-point tensor of shape (P, 3), one row per point")
+    _C = _gsr()
+    P, dev = int(pts.shape[0]), pts.device
+    out = torch.empty((P, FPFH_WIDTH), dtype=torch.float32, device=dev)
+    counts = torch.empty((P, FPFH_WIDTH), dtype=torch.int32, device=dev) if return_stats else None
+    count = torch.empty(P, dtype=torch.int32, device=dev) if return_stats else None
+    if P > 0:
+        lib = _C.lib()
+        nrm = nrm.to(dev)
+        with _C.on_device(dev):
+            ws = torch.empty(lib.gsr_fpfh_workspace_bytes(P), dtype=torch.uint8, device=dev)
+            _C.check(lib.gsr_compute_fpfh(P, _C.ptr(pts), _C.ptr(nrm), r, nn, _C.ptr(out), _C.ptr(counts), _C.ptr(count),
+                                          _C.ptr(ws), ws.numel(), _C._stream()))
+    return (out, counts, count) if return_stats else out
+
+
+def feature_nn(query_feature, target_feature):
+    """-> (idx int32 [Nq], dist2 float32 [Nq]): the target row nearest to every query row in the 33-dimensional feature space
+    (float32 squared distance; among equal distances the smallest row).  A query with a NaN: -1 / NaN; target rows with a NaN
+    never win."""
+    _feature_shape(query_feature, "query_feature")
+    _feature_shape(target_feature, "target_feature")
+    q = _check_feature(query_feature, "query_feature")
+    t = _check_feature(target_feature, "target_feature")
+    if q.device != t.device:
+        raise ValueError(f"feature_nn: query on {q.device}, target on {t.device}")
+    Nq, Nt = int(q.shape[0]), int(t.shape[0])
+    idx = torch.full((Nq,), -1, dtype=torch.int32, device=q.device)
+    dist2 = torch.full((Nq,), math.inf, dtype=torch.float32, device=q.device)
+    if Nq and Nt:
+        _C = _gsr()
+        lib = _C.lib()
+        with _C.on_device(q.device):
+            ws = torch.empty(lib.gsr_feature_nn_workspace_bytes(Nq), dtype=torch.uint8, device=q.device)
+            _C.check(lib.gsr_feature_nn(Nq, _C.ptr(q), Nt, _C.ptr(t), FPFH_WIDTH, _C.ptr(idx), _C.ptr(dist2), _C.ptr(ws),
+                                        ws.numel(), _C._stream()))
+    return idx, dist2
+
+
+def match_features(source_feature, target_feature, mutual_filter=False):
+    """int32 [M,2] on the device, ascending source row: (i, j) with j the target feature nearest to source feature i.
+    mutual_filter: only the pairs whose target row j has i as ITS nearest source feature (a second search, roles swapped)."""
+    if not isinstance(mutual_filter, bool):
+        raise TypeError(f"mutual_filter={mutual_filter!r}: expected a bool")
+    _feature_shape(source_feature, "source_feature")
+    _feature_shape(target_feature, "target_feature")
+    s = _check_feature(source_feature, "source_feature")
+    t = _check_feature(target_feature, "target_feature")
+    fwd, _ = feature_nn(s, t)
+    rows = torch.arange(int(s.shape[0]), dtype=torch.int32, device=s.device)
+    keep = fwd >= 0
+    if mutual_filter and int(t.shape[0]):
+        back, _ = feature_nn(t, s)
+        keep = keep & (back[fwd.clamp(min=0).long()] == rows)
+    return torch.stack([rows[keep], fwd[keep]], dim=1).contiguous()
+
+
+def new_ransac_record(device):
+    """a fresh gsr_ransac_best on `device` as int64 [20] (words 1 and 3 .. 18 hold float64 bits): count -1, sum_d2 +inf, trial -1,
+    T = identity, trials_checked 0"""
+    rec = torch.zeros(20, dtype=torch.float64)
+    rec[1] = math.inf
+    rec[3:19] = torch.eye(4, dtype=torch.float64).reshape(-1)
+    rec = rec.view(torch.int64)
+    rec[0] = -1
+    rec[2] = -1
+    return rec.to(device)
+
+
+def read_ransac_record(record):
+    """-> dict(count, sum_d2, trial, T float64 [4,4] (host), trials_checked) - one read-back"""
+    r = record.cpu()
+    f = r.view(torch.float64)
+    return dict(count=int(r[0]), sum_d2=float(f[1]), trial=int(r[2]), T=f[3:19].reshape(4, 4).clone(), trials_checked=int(r[19]))
+
+
+def ransac_trials(source, target, pairs, max_correspondence_distance, ransac_n, edge_length_threshold, seed, first_trial, trials,
+                  record=None, debug=False):
+    """Trials [first_trial, first_trial + trials) of gsr_ransac_feature_matching against `record` (new_ransac_record; updated in
+    place and returned).  debug: also (samples int32 [trials,8], status int32 [trials], T float64 [trials,4,4]) of the
+    hypothesis stage.  No read-back."""
+    md, n, theta, _, sd = _check_ransac(max_correspondence_distance, ransac_n, edge_length_threshold, 1, 1.0, seed, 1)
+    t0 = _check_int("first_trial", first_trial, 0)
+    cnt = _check_int("trials", trials, 1, 1 << 20)
+    prs = _check_pairs(pairs)
+    src, _ = _check_cloud(source, None, "ransac_trials")
+    tgt, _ = _check_cloud(target, None, "ransac_trials")
+    _nonempty(src, "ransac_trials", "source")
+    _nonempty(tgt, "ransac_trials", "target")
+    M, dev = int(prs.shape[0]), src.device
+    if M == 0:
+        raise ValueError("ransac_trials: no pairs")
+    if record is None:
+        record = new_ransac_record(dev)
+    _C = _gsr()
+    lib = _C.lib()
+    dbg = None
+    out = None
+    if debug:
+        out = (torch.empty((cnt, 8), dtype=torch.int32, device=dev), torch.empty(cnt, dtype=torch.int32, device=dev),
+               torch.empty((cnt, 4, 4), dtype=torch.float64, device=dev))
+        dbg = _C.gsr_ransac_debug(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+    with _C.on_device(dev):
+        ws = torch.empty(lib.gsr_ransac_workspace_bytes(M, cnt), dtype=torch.uint8, device=dev)
+        _C.check(lib.gsr_ransac_feature_matching(int(src.shape[0]), _C.ptr(src), int(tgt.shape[0]), _C.ptr(tgt.to(dev)), M,
+                                                 _C.ptr(prs.to(dev)), md, n, theta, sd, t0, cnt, _C.ptr(record), _C.ptr(ws),
+                                                 ws.numel(), dbg, _C._stream()))
+    return (record,) + out if debug else record
+
+
+def _ransac_enough(done, inliers, M, ransac_n, confidence):
+    """Open3D's rule: done >= log(1 - confidence) / log(1 - (inliers / M) ** ransac_n).  The denominator is log1p(-p): for a
+    p below 1e-16 (eight samples at an inlier share of a thousandth) 1 - p rounds to 1 and its logarithm to 0; and where even
+    log1p gives 0 (p = 0, or below the smallest float) no number of trials is enough: keep going."""
+    ratio = max(inliers, 0) / M
+    if ratio >= 1.0:
+        return True
+    den = math.log1p(-(ratio ** ransac_n))
+    return den < 0.0 and done >= math.log(1.0 - confidence) / den
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
+                                                  max_correspondence_distance, ransac_n=3, edge_length_threshold=0.9,
+                                                  max_iteration=100000, confidence=0.999, seed=0, batch=16384, pairs=None):
+    """Open3D's call of the same name -> RegistrationResult (iterations = trials run, converged = some trial survived).
+    Correspondences: match_features(source_feature, target_feature, mutual_filter) - with fewer than ransac_n mutual pairs the
+    unfiltered ones, as Open3D does - or `pairs` (int32 [M,2]; the features may then be None).  Trials of ransac_n sampled pairs
+    each (a counter-based generator: trial t is a function of (seed, t) alone), checked by edge length (0 switches it off) and
+    distance, scored by their inliers over all pairs; they run in batches of `batch`, and after each the best is read back and
+    the loop stops once trials >= log(1 - confidence) / log(1 - (inliers / pairs) ** ransac_n).  confidence=1.0 runs
+    max_iteration trials without a read-back.  The winner is the lexicographic best of (inliers max, sum of squared inlier
+    distances min, trial min): the result depends on `batch` only through where the loop stops.  Fitness, RMSE and
+    correspondences are evaluate_registration's under the winner; without a surviving trial the identity."""
+    md, n, theta, conf, sd = _check_ransac(max_correspondence_distance, ransac_n, edge_length_threshold, max_iteration,
+                                           confidence, seed, batch)
+    if not isinstance(mutual_filter, bool):
+        raise TypeError(f"mutual_filter={mutual_filter!r}: expected a bool")
+    if pairs is None:
+        _feature_shape(source_feature, "source_feature", _rows(source))
+        _feature_shape(target_feature, "target_feature", _rows(target))
+    elif not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs: expected an int32 tensor of shape (M, 2): source row, target row")
+    src, _ = _check_cloud(source, None, "registration_ransac_based_on_feature_matching")
+    tgt, _ = _check_cloud(target, None, "registration_ransac_based_on_feature_matching")
+    _nonempty(src, "registration_ransac_based_on_feature_matching", "source")
+    _nonempty(tgt, "registration_ransac_based_on_feature_matching", "target")
+    dev = src.device
+    if pairs is not None:
+        pairs = _check_pairs(pairs)
+    else:
+        pairs = match_features(source_feature, target_feature, mutual_filter)
+        if mutual_filter and int(pairs.shape[0]) < n:
+            pairs = match_features(source_feature, target_feature, False)
+    M = int(pairs.shape[0])
+    record = new_ransac_record(dev)
+    done = 0
+    while M >= n and done < max_iteration:
+        cnt = min(batch, max_iteration - done)
+        ransac_trials(src, tgt, pairs, md, n, theta, sd, done, cnt, record)
+        done += cnt
+        if conf < 1.0 and _ransac_enough(done, int(record[0].item()), M, n, conf):
+            break
+    best = read_ransac_record(record)
+    found = best["count"] >= 0
+    res = evaluate_registration(src, tgt, md, best["T"] if found else None)
+    return RegistrationResult(res.transformation, res.fitness, res.inlier_rmse, done, found, res.correspondences)
+
+
+def global_registration(source, target, voxel_size, seed=0, **ransac):
+    """The reference's commented pipeline on clouds that are already down-sampled at `voxel_size`: normals (radius 2 v, max_nn 30,
+    towards the cloud's mean - a rule that turns with the cloud, which the default sign rule does not), FPFH (radius 5 v,
+    radius-only), mutual matching, RANSAC (1.5 v, ransac_n 4, edge length 0.9) -> RegistrationResult."""
+    v = _check_voxel_size(voxel_size)
+    _check_seed(seed)
+    src, _ = _check_cloud(source, None, "global_registration")
+    tgt, _ = _check_cloud(target, None, "global_registration")
+    feats = []
+    for pts in (src, tgt):
+        ok = torch.isfinite(pts).all(dim=1)
+        centre = pts[ok].double().mean(dim=0).tolist() if bool(ok.any()) else [0.0, 0.0, 0.0]
+        nrm = estimate_normals(pts, 2.0 * v, 30, viewpoint=centre)
+        feats.append(compute_fpfh_feature(pts, nrm, 5.0 * v))
+    ransac = dict(dict(ransac_n=4, edge_length_threshold=0.9, seed=seed), **ransac)
+    return registration_ransac_based_on_feature_matching(src, tgt, feats[0], feats[1], True, 1.5 * v, **ransac)
+
+
 def register_and_merge(source, source_colors, target, target_colors, voxel_size=0.05, max_correspondence_distance=None,
-                       merge_voxel_size=None, estimation="point_to_point", **icp):
+                       merge_voxel_size=None, estimation="point_to_point", global_init=False, global_seed=0, **icp):
     """The reference's pointcloud_registeration: down-sample both clouds (voxel_down_sample, voxel_size), ICP of the down-sampled
     source onto the down-sampled target from the identity (max_correspondence_distance=None: 5 * voxel_size; further keywords
     go to registration_icp), move the FULL source by the result, concatenate it with the target (source rows first) and, with
     merge_voxel_size, down-sample the merged cloud.  Colours: both or neither.  -> (points, colors or None, result).
     estimation="point_to_plane": the down-sampled target's normals are estimated with radius = 2 * voxel_size, max_nn = 30 - the
-    reference's estimate_normals calls at :193-196 - and the registration is point-to-plane."""
+    reference's estimate_normals calls at :193-196 - and the registration is point-to-plane.
+    global_init=True: ICP starts from a global registration of the down-sampled clouds instead of the identity - the reference's
+    commented pipeline at :198-213: normals (radius 2 * voxel_size, max_nn 30, oriented towards the cloud's mean so that they
+    turn with the cloud), compute_fpfh_feature (radius 5 * voxel_size, radius-only), mutual matching and
+    registration_ransac_based_on_feature_matching (1.5 * voxel_size, ransac_n 4, edge length 0.9, seed `global_seed`).  With
+    False nothing of that runs and every output bit is what it was."""
+    if not isinstance(global_init, bool):
+        raise TypeError(f"global_init={global_init!r}: expected a bool")
+    _check_seed(global_seed)
     v = _check_voxel_size(voxel_size)
     plane = _check_estimation(estimation)
     mv = None if merge_voxel_size is None else _check_voxel_size(merge_voxel_size)
@@ -354,6 +627,8 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
     tgt_down, _ = voxel_down_sample(tgt, None, v)
     if plane:
         icp = dict(icp, estimation="point_to_plane", normal_radius=2.0 * v, normal_max_nn=30)
+    if global_init:
+        icp = dict(icp, init=global_registration(src_down, tgt_down, v, seed=global_seed).transformation)
     result = registration_icp(src_down, tgt_down, md, **icp)
     points = torch.cat([transform_points(src, result.transformation), tgt.to(src.device)])
     colors = None if scol is None else torch.cat([scol, tcol.to(src.device)])

@@ -2,7 +2,8 @@
 the same search answered only for the rows from `first_query` on (new points against map + new points); `knn_k(points, k)`,
 the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds);
 `nn_search(query, target)`, the nearest row of ANOTHER cloud with its row number (csrc/registration.hip);
-`estimate_normals(points, radius, max_nn)`, the normal of every row from its hybrid neighbourhood (csrc/normals.hip)."""
+`estimate_normals(points, radius, max_nn)`, the normal of every row from its hybrid neighbourhood (csrc/normals.hip);
+`compute_fpfh(points, normals, radius, max_nn)`, the 33-bin point feature histogram of every row (csrc/features.hip)."""
 import math
 
 import torch
@@ -85,3 +86,11 @@ def estimate_normals(points, radius=0.1, max_nn=30, viewpoint=None, return_stats
     the rows within `radius`, cut at the max_nn nearest - `scene_utils.estimate_normals`."""
     from scene_utils.pointcloud import estimate_normals as _estimate_normals
     return _estimate_normals(points, radius, max_nn, viewpoint, return_stats)
+
+
+def compute_fpfh(points, normals, radius, max_nn=0, return_stats=False):
+    """-> fpfh float32 [P,33] (with return_stats also spfh_counts int32 [P,33] and count int32 [P]): the fast point feature
+    histogram of every row over the rows within `radius` (max_nn > 0: cut at the max_nn nearest) -
+    `scene_utils.compute_fpfh_feature`."""
+    from scene_utils.registration import compute_fpfh_feature as _compute_fpfh_feature
+    return _compute_fpfh_feature(points, normals, radius, max_nn, return_stats)

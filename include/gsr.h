@@ -52,6 +52,8 @@ extern "C" {
  *    gsr_icp_workspace_bytes, gsr_icp_update: nearest neighbours of one cloud in another, with the row, and point-to-point ICP;
  *    gsr_normals_workspace_bytes, gsr_estimate_normals (surface normals from a hybrid radius / max-count neighbourhood) and
  *    gsr_icp_update_plane (the point-to-plane update; gsr_icp_workspace_bytes grew);
+ *    gsr_fpfh_workspace_bytes, gsr_compute_fpfh, gsr_feature_nn_workspace_bytes, gsr_feature_nn_tiles_per_split, gsr_feature_nn,
+ *    gsr_ransac_workspace_bytes, gsr_ransac_feature_matching: global registration from feature matches (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -742,6 +744,96 @@ int gsr_estimate_normals(int64_t P, const float* points /*[P,3]*/, float radius,
                          const float* viewpoint /*HOST [3] or NULL*/, float* normals /*[P,3]*/, int32_t* count_out /*[P] or NULL*/,
                          float* eigenvalues_out /*[P,3] ascending, or NULL*/, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ---- global registration (csrc/features.hip) - what the reference's commented pipeline would take
+ * from Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching.  Every result is a function of the input
+ * only, never of traversal, scheduling or launch shape; no float atomics, no allocation. ---- */
+
+#define GSR_FPFH_WIDTH 33              /* three blocks of 11 bins */
+
+/* Fast point feature histogram of every row.
+ * Neighbourhood: N_i of gsr_estimate_normals exactly (float32 d2, bound = min(r2, d_k), rows tied at the bound all belong,
+ * duplicates are members), max_nn in [3, GSR_KNN_K_MAX + 1]; or max_nn = 0: radius only, bound = r2, `radius` finite - the
+ * departure that serves Open3D's (5 voxel, 100) call: on a voxel-sampled surface a ball of five voxel sizes holds fewer than
+ * 100 rows almost everywhere, so the cut at 100 never acts.  Others_i = N_i \ {i}, m_i = |Others_i|.  A row whose point or normal
+ * has a non-finite component is masked before the structure is built (it takes no part in the bounding box, the sort or the
+ * boxes, so no other row's bits depend on where it lies): fpfh NaN, counts 0, count 0, nobody's neighbour.
+ * Pair feature of (i, j), all in float64: delta = p_j - p_i per component in float32, promoted; normals promoted;
+ * d2 = (dx dx + dy dy) + dz dz, d = sqrt(d2).  d2 = 0: (0, 0, 0).  Otherwise a1 = n_i.delta / d, a2 = n_j.delta / d; if
+ * |a1| < |a2| (strictly) (n1, n2, delta) <- (n_j, n_i, -delta) and f2 = -a2, else n1 = n_i, n2 = n_j, f2 = a1.  v = delta x n1;
+ * |v| = 0: (0, 0, 0); else v <- v / |v|, w = n1 x v, f1 = v.n2, f0 = atan2(w.n2, n1.n2).  Bins, each clamped to [0, 10]:
+ * floor(11 (f0 + pi) / (2 pi)) in block 0, floor(11 (f1 + 1) / 2) in block 1, floor(11 (f2 + 1) / 2) in block 2.
+ * spfh_counts[i][b]: the number of j in Others_i whose feature falls into bin b - integers, exact, independent of any order.
+ * SPFH_i(b) = 100 c / m_i.  FPFH_i: A_b = sum over j in Others_i with d2 > 0 of SPFH_j(b) / d2 - evaluated as
+ * c_j(b) (100 / (m_j d2)) - in float64 in the order of the sorted structure (fixed for a given input); each block of 11 scaled
+ * by 100 / (sum of its A_b) where that sum is not 0; SPFH_i(b) added; ONE rounding to float32.  m_i = 0: a zero row.
+ * count[i] = |N_i| = m_i + 1 (0 for a masked row).
+ * Errors before any launch: P outside [1, 2^30 - 1], NULL points / normals / fpfh / workspace, radius <= 0 or NaN, max_nn outside
+ * {0} + [3, 33], max_nn = 0 with an infinite radius: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_fpfh_workspace_bytes(P):
+ * GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_fpfh_workspace_bytes(int64_t P);
+int gsr_compute_fpfh(int64_t P, const float* points /*[P,3]*/, const float* normals /*[P,3]*/, float radius, int32_t max_nn,
+                     float* fpfh /*[P,33]*/, int32_t* spfh_counts /*[P,33] or NULL*/, int32_t* count /*[P] or NULL*/,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Nearest target feature of every query feature, brute force.  d2(q, t) = sum over b ascending of (q_b - t_b)^2 in float32:
+ * e = q_b - t_b rounded, d2 = fma(e, e, d2) from d2 = 0.  idx_out[i] = the row of the lexicographic minimum of (d2, row) over the
+ * target rows whose d2 is not NaN, dist2_out[i] its d2: a target row with a NaN never wins, identical rows give the smallest.
+ * A query with a NaN: -1 and NaN; no target row without a NaN: -1 and +inf.
+ * Target rows pass through LDS GSR_FEATURE_NN_TILE at a time; with few queries the target's tiles are split over a second grid
+ * dimension in runs of gsr_feature_nn_tiles_per_split(Nq, Nt) tiles (aiming at GSR_FEATURE_NN_WORKGROUPS workgroups), and the
+ * partial minima meet in one 64-bit integer atomicMin per query on (bits of d2, row): no output bit depends on the split.
+ * `width` must be GSR_FPFH_WIDTH.  Errors before any launch: sizes outside [1, 2^30 - 1], NULL query / target / idx_out /
+ * workspace, another width: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_feature_nn_workspace_bytes(Nq): GSR_ERR_STATE_TOO_SMALL. */
+#define GSR_FEATURE_NN_TILE 128
+#define GSR_FEATURE_NN_WORKGROUPS 512
+size_t gsr_feature_nn_workspace_bytes(int64_t Nq);
+int32_t gsr_feature_nn_tiles_per_split(int64_t Nq, int64_t Nt);
+int gsr_feature_nn(int64_t Nq, const float* query /*[Nq,33]*/, int64_t Nt, const float* target /*[Nt,33]*/, int32_t width,
+                   int32_t* idx_out /*[Nq]*/, float* dist2_out /*[Nq] or NULL*/, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* RANSAC over given correspondences (Open3D's registration_ransac_based_on_feature_matching after the matching): trials
+ * [t0, t0 + n) against the DEVICE record `best`, which the call improves on - consecutive calls over consecutive ranges give
+ * exactly what one call over the union gives.  A fresh record: count = -1, sum_d2 = +inf, trial = -1, T = identity,
+ * trials_checked = 0.  All geometry in float64 from the float32 coordinates.
+ * A pair (source row, target row) that names a row outside its cloud or a non-finite point is unusable: a trial that samples it
+ * is rejected, and it is never an inlier; nothing is read out of bounds.
+ * Trial t: sample s = 0 .. ransac_n - 1 picks pair ((mix(seed + (8 t + s + 1) 0x9E3779B97F4A7C15) >> 32) M) >> 32, mix the
+ * splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31), all
+ * mod 2^64.  Status, the first that applies: 1 two samples coincide; 2 a sampled pair is unusable; 3 (edge_length_threshold
+ * theta > 0) some sample pair (a, b) fails |s_a - s_b| >= theta |t_a - t_b| or |t_a - t_b| >= theta |s_a - s_b|; 4 no rotation
+ * (sums not finite); 5 some sample has |T s - t|^2 > max_distance^2; 0 survives.  T: Horn's quaternion form on the samples'
+ * centred cross-covariance (the routine of gsr_icp_update), t = tbar - R sbar.
+ * Score of a survivor, over ALL M pairs in their order: a usable pair is an inlier iff |T s - t|^2 <= max_distance^2
+ * ((double)max_distance squared in float64); count, and sum_d2 over the inliers in float64.  The winner is the lexicographic
+ * best of (count max, sum_d2 min, trial min) over the survivors and the incoming record; trials_checked grows by the number of
+ * survivors.  Without a survivor the record is not written.
+ * debug (NULL in production): per trial of this call the samples (-1 beyond ransac_n), the status and T (rows 0 .. 2 zero unless
+ * status is 0 or 5) - any of the three pointers may be NULL.
+ * Errors before any launch: sizes outside [1, 2^30 - 1], NULL source / target / pairs / best / workspace, max_distance negative,
+ * NaN or infinite, ransac_n outside [3, GSR_RANSAC_N_MAX], theta outside [0, 1], t0 outside [0, 2^56] (8 t + 8 must not wrap a
+ * signed 64-bit trial number), n outside [1, GSR_RANSAC_MAX_TRIALS]:
+ * GSR_ERR_INVALID_ARGUMENT; workspace below gsr_ransac_workspace_bytes(M, n): GSR_ERR_STATE_TOO_SMALL. */
+#define GSR_RANSAC_N_MAX 8
+#define GSR_RANSAC_MAX_TRIALS (1 << 20)
+typedef struct gsr_ransac_best {
+  int64_t count;
+  double sum_d2;
+  int64_t trial;
+  double T[16];            /* row-major 4 x 4 */
+  int64_t trials_checked;  /* survivors scored so far */
+} gsr_ransac_best;
+typedef struct gsr_ransac_debug {
+  int32_t* samples;        /* device [n,8] or NULL */
+  int32_t* status;         /* device [n] or NULL */
+  double* T;               /* device [n,16] or NULL */
+} gsr_ransac_debug;
+size_t gsr_ransac_workspace_bytes(int64_t M, int64_t n);
+int gsr_ransac_feature_matching(int64_t Ps, const float* source /*[Ps,3]*/, int64_t Pt, const float* target /*[Pt,3]*/, int64_t M,
+                                const int32_t* pairs /*[M,2]*/, float max_distance, int32_t ransac_n, float edge_length_threshold,
+                                uint64_t seed, int64_t t0, int64_t n, gsr_ransac_best* best /*device, in/out*/, void* workspace,
+                                size_t workspace_bytes, const gsr_ransac_debug* debug /*HOST struct or NULL*/, void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
