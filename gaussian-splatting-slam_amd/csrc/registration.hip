@@ -23,6 +23,7 @@
 //   cannot come out - found by cyclic Jacobi with a fixed number of sweeps (horn_common.h, shared with features.hip).  T <- dT T.
 #include "knn_common.h"
 #include "horn_common.h"
+#include "rigid_common.h"
 
 #define GSR_ICP_BLOCKS 256
 #define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
@@ -63,28 +64,7 @@ static inline GsrIcpLayout icp_layout() {
   return L;
 }
 
-// ---- q = (float)(R s + t) -----------------------------------------------------------------------------------------------------
-struct RegT {
-  double m[12];      // rows 0 .. 2 of the row-major 4 x 4
-};
-__device__ __forceinline__ RegT reg_load(const double* __restrict__ T) {
-  RegT r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.m[i] = T ? T[i] : ((i % 5) == 0 ? 1.0 : 0.0);
-  return r;
-}
-// component i = (float)(((T[i,0] x + T[i,1] y) + T[i,2] z) + T[i,3]): three products and three sums, each rounded to float64 on
-// its own (no fused multiply-add), in this order, then ONE rounding to float32.  .w = 0.
-__device__ __forceinline__ float4 reg_apply(const RegT& T, float x, float y, float z) {
-  float q[3];
-  const double dx = (double)x, dy = (double)y, dz = (double)z;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const double a = __dadd_rn(__dmul_rn(T.m[4 * i], dx), __dmul_rn(T.m[4 * i + 1], dy));
-    q[i] = (float)__dadd_rn(__dadd_rn(a, __dmul_rn(T.m[4 * i + 2], dz)), T.m[4 * i + 3]);
-  }
-  return make_float4(q[0], q[1], q[2], 0.f);
-}
+// ---- q = (float)(R s + t): RegT, reg_load, reg_apply (rigid_common.h, shared with pointcloud2.hip) -----------------------------
 
 // ---- index ----------------------------------------------------------------------------------------------------------------------
 // rows with a non-finite coordinate become NaN NaN NaN; thread 0 also leaves the box centre (0 where the box is empty)

@@ -103,6 +103,16 @@ class gsr_ransac_debug(C.Structure):
     _fields_ = [("samples", C.c_void_p), ("status", C.c_void_p), ("T", C.c_void_p)]
 
 
+class gsr_pc2_layout(C.Structure):
+    # HOST struct: the layout of a sensor_msgs/PointCloud2 byte buffer (datatype = ROS's PointField code, 1 .. 8)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
+                ("is_bigendian", C.c_int32), ("offset", C.c_int32 * 3), ("datatype", C.c_int32 * 3),
+                ("color_offset", C.c_int32), ("color_datatype", C.c_int32)]
+
+
+PC2_CHUNK = 256              # points per workgroup of gsr_pc2_decode (csrc/pointcloud2.hip)
+PC2_LDS_BYTES = 256 * 64 + 64      # its staging buffer: a chunk whose byte span exceeds it is read straight from global memory
+
 FPFH_WIDTH = 33              # GSR_FPFH_WIDTH
 FEATURE_NN_TILE = 128        # GSR_FEATURE_NN_TILE
 RANSAC_N_MAX = 8             # GSR_RANSAC_N_MAX
@@ -246,6 +256,14 @@ EXPORTS = {
     "gsr_ransac_feature_matching": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                               C.c_int32, C.c_float, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.POINTER(gsr_ransac_debug), C.c_void_p]),
+    # layout (host), data + bytes, T_dev, min_y, max_range2, skip_nans, out_points, out_colors, out_index, cap, count_dev,
+    # workspace + bytes, stream
+    "gsr_pc2_decode_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_pc2_decode": (C.c_int, [C.POINTER(gsr_pc2_layout), C.c_void_p, C.c_size_t, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, colors, out, stream
+    "gsr_pc2_encode": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_debug_pc2_force_direct": (C.c_int32, [C.c_int32]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

@@ -20,3 +20,5 @@ from .pointcloud import voxel_down_sample, statistical_outlier_mask, remove_stat
 from .registration import NeighborIndex, RegistrationResult, nn_search, transform_points, icp_update, evaluate_registration, \
     registration_icp, register_and_merge, align_map, compute_fpfh_feature, feature_nn, match_features, \
     registration_ransac_based_on_feature_matching, global_registration, ransac_trials
+from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, process_pointcloud, accumulate_pointclouds, \
+    encode_pointcloud2

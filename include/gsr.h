@@ -54,6 +54,8 @@ extern "C" {
  *    gsr_icp_update_plane (the point-to-plane update; gsr_icp_workspace_bytes grew);
  *    gsr_fpfh_workspace_bytes, gsr_compute_fpfh, gsr_feature_nn_workspace_bytes, gsr_feature_nn_tiles_per_split, gsr_feature_nn,
  *    gsr_ransac_workspace_bytes, gsr_ransac_feature_matching: global registration from feature matches (additions only);
+ *    gsr_pc2_layout, gsr_pc2_decode_workspace_bytes, gsr_pc2_decode, gsr_pc2_encode, gsr_debug_pc2_force_direct: a
+ *    sensor_msgs/PointCloud2 byte buffer decoded, cropped, posed and compacted on the device, and its inverse (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -834,6 +836,71 @@ int gsr_ransac_feature_matching(int64_t Ps, const float* source /*[Ps,3]*/, int6
                                 const int32_t* pairs /*[M,2]*/, float max_distance, int32_t ransac_n, float edge_length_threshold,
                                 uint64_t seed, int64_t t0, int64_t n, gsr_ransac_best* best /*device, in/out*/, void* workspace,
                                 size_t workspace_bytes, const gsr_ransac_debug* debug /*HOST struct or NULL*/, void* stream);
+
+/* ---- sensor_msgs/PointCloud2 on the device (csrc/pointcloud2.hip): what the reference's
+ * process_pointcloud / read_pointcloud do point by point with `struct` in Python before a cloud reaches Open3D ---- */
+
+/* The layout of a message's byte buffer (HOST struct).  Point n = v * width + u starts at byte v * row_step + u * point_step.
+ * datatype: ROS's PointField code - 1 INT8, 2 UINT8, 3 INT16, 4 UINT16, 5 INT32, 6 UINT32, 7 FLOAT32, 8 FLOAT64.  Field offsets
+ * need not be aligned to the field's size, point_step need not be a multiple of 4, row_step may exceed width * point_step. */
+#define GSR_PC2_INT8 1
+#define GSR_PC2_UINT8 2
+#define GSR_PC2_INT16 3
+#define GSR_PC2_UINT16 4
+#define GSR_PC2_INT32 5
+#define GSR_PC2_UINT32 6
+#define GSR_PC2_FLOAT32 7
+#define GSR_PC2_FLOAT64 8
+typedef struct gsr_pc2_layout {
+  uint32_t width, height, point_step, row_step;
+  int32_t is_bigendian;
+  int32_t offset[3];       /* of x, y, z inside a point */
+  int32_t datatype[3];
+  int32_t color_offset;    /* -1: the message has no colour */
+  int32_t color_datatype;  /* FLOAT32, UINT32 or INT32: the packed 0x00RRGGBB word ROS calls rgb / rgba */
+} gsr_pc2_layout;
+
+/* Decode, crop, pose and compact a PointCloud2 byte buffer (`data`: DEVICE bytes, any alignment).  Per point n, in this order:
+ *  1. x, y, z are read in the message's byte order and converted to float32: FLOAT32 bit for bit (NaN payloads survive), FLOAT64
+ *     and the 32-bit integers by ONE round-to-nearest-even conversion, the small integers exactly - numpy.astype(float32).
+ *  2. skip_nans != 0: the row is dropped if x, y or z is NaN, or if the message has a FLOAT32 colour field whose bit pattern is a
+ *     NaN (what sensor_msgs.point_cloud2.read_points(field_names = x, y, z, rgb, skip_nans = True) drops; it applies whether or
+ *     not out_colors is given).  +-inf is no NaN.  With skip_nans == 0 NaN rows pass: every comparison of step 3 is false for them.
+ *  3. crop on the sensor-frame values, BEFORE the pose.  Height: dropped iff (double)y < min_y (-inf: off).  Range: dropped iff
+ *     d2 > max_range2 (+inf: off), d2 = ((double)x * x + (double)y * y) + (double)z * z - the squares are exact in float64, the two
+ *     sums round once each, no fused multiply-add.  A caller with a range r passes max_range2 = (double)r * (double)r.  This is
+ *     the library's OWN definition of the crop: it is not a claim of bit parity with numpy.linalg.norm(...) > r at the boundary.
+ *  4. pose: q = T s as defined above for registration (T_dev: DEVICE float64[16] row-major; NULL: the coordinates pass with their
+ *     bits) - the same bits as gsr_transform_points on the kept rows.
+ *  5. colour (out_colors given): the colour word w in the message's byte order, r = (w >> 16) & 255, g = (w >> 8) & 255,
+ *     b = w & 255, every channel (float)byte / 255.0f - one correctly rounded float32 division.
+ * The kept rows come out in message order (a stable compaction: ballot and prefix inside a workgroup, gsr_scan_u32 over the
+ * workgroup counts): out_points, out_colors (or NULL), out_index (int32, or NULL) = the kept row's n.  count_dev[0] = rows kept,
+ * count_dev[1] = 1 iff more than `cap` were kept: nothing is written at or beyond row `cap`, the count stays the true one.
+ * Deterministic, no float atomics, no allocation; no byte at or beyond data_bytes (or in front of data) is ever read.
+ * Errors before any launch: NULL layout / data / count_dev / workspace, out_points NULL with cap > 0, cap < 0, a datatype outside
+ * 1 .. 8, a colour datatype that is not FLOAT32 / UINT32 / INT32, out_colors without a colour field, a field that does not fit
+ * inside point_step, row_step < width * point_step, width * height outside [1, 2^30 - 1], (height - 1) * row_step + width *
+ * point_step > data_bytes, NaN min_y / max_range2: GSR_ERR_INVALID_ARGUMENT; workspace below
+ * gsr_pc2_decode_workspace_bytes(width * height): GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_pc2_decode_workspace_bytes(int64_t N);
+int gsr_pc2_decode(const gsr_pc2_layout* layout /*HOST*/, const void* data, size_t data_bytes, const double* T_dev /*[16] or NULL*/,
+                   double min_y, double max_range2, int32_t skip_nans, float* out_points /*[cap,3]*/,
+                   float* out_colors /*[cap,3] or NULL*/, int32_t* out_index /*[cap] or NULL*/, int64_t cap,
+                   int64_t* count_dev /*[2]: kept, status*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The inverse for the canonical layout - little-endian, x / y / z FLOAT32 at 0 / 4 / 8, packed rgb FLOAT32 at 12, point_step 16,
+ * height 1: out[16 P] device bytes (4-byte aligned).  Coordinates keep their bits.  Colour byte = (int)(min(max(c, 0), 1) * 255.0f
+ * + 0.5f), product and sum rounded separately, a NaN colour gives 0; word = r << 16 | g << 8 | b; colors == NULL: word 0.
+ * Errors before the launch: P outside [1, 2^30 - 1], NULL points / out, a misaligned out: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_pc2_encode(int64_t P, const float* points /*[P,3]*/, const float* colors /*[P,3] or NULL*/, void* out /*[16 P]*/,
+                   void* stream);
+
+/* test / measurement hook: on != 0 makes gsr_pc2_decode read every field straight from global memory (the path that otherwise
+ * serves only the runs of points whose byte span exceeds the LDS staging buffer); 0 restores the default.  Returns the previous
+ * setting.  Both paths give identical bits.  The switch is ONE process-wide variable, read when gsr_pc2_decode is called: it is
+ * not meant for concurrent callers, and a caller that sets it restores it. */
+int32_t gsr_debug_pc2_force_direct(int32_t on);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
