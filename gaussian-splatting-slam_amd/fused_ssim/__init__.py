@@ -91,6 +91,8 @@ class _L1Mean(torch.autograd.Function):
         m = mask.detach().float().expand_as(x).contiguous() if mask is not None else None
         if x.shape != y.shape:
             raise ValueError("l1_mean_loss: shapes differ")
+        # the forward reads float4s: a contiguous view that starts inside a buffer (buf[1:]) is copied to an aligned one
+        x, y, m = (t.clone() if t is not None and t.data_ptr() & 15 else t for t in (x, y, m))
         partials = torch.empty(int(lib.gsr_l1_mean_blocks()), dtype=torch.float32, device=x.device)
         out = torch.empty((), dtype=torch.float32, device=x.device)
         with _C.on_device(x.device):

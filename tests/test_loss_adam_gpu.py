@@ -4,7 +4,9 @@ utils/loss_utils.py:ssim by tests/golden/reference_helpers.npz) and the one-laun
 a float32 cross-check at one size (torch.optim.Adam in float32 on the CPU; the sparse variant against a masked float32
 restatement without bias correction) - no oracle: the kernels' value tests against a float64 reference, at every size and path,
 are tests/test_adam_kernels_gpu.py (reference: tests/adam_reference.py).  The fold tests below hold every folded form of the
-step bit-equal to backward + that kernel."""
+step bit-equal to backward + that kernel.  The loss tests here compare means and norms; the loss kernels' per-pixel and per-tile
+tests against a float64 reference (every edge size, tile count and image class, a bound per pixel) are
+tests/test_loss_kernels_gpu.py (reference: tests/loss_reference.py)."""
 import numpy as np
 import pytest
 import torch
