@@ -113,6 +113,21 @@ class gsr_pc2_layout(C.Structure):
 PC2_CHUNK = 256              # points per workgroup of gsr_pc2_decode (csrc/pointcloud2.hip)
 PC2_LDS_BYTES = 256 * 64 + 64      # its staging buffer: a chunk whose byte span exceeds it is read straight from global memory
 
+
+class gsr_image_layout(C.Structure):
+    # HOST struct: the layout of a sensor_msgs/Image byte buffer (encoding = a GSR_IMG_* code)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("step", C.c_uint32), ("encoding", C.c_int32),
+                ("is_bigendian", C.c_int32)]
+
+
+# GSR_IMG_*: the names of sensor_msgs/image_encodings.h (16UC1 is also the code of a mono16 image read as depth)
+IMAGE_ENCODINGS = {"rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4, "mono8": 5, "rgb16": 6, "bgr16": 7, "rgba16": 8, "bgra16": 9,
+                   "mono16": 10, "bayer_rggb8": 11, "bayer_bggr8": 12, "bayer_gbrg8": 13, "bayer_grbg8": 14, "bayer_rggb16": 15,
+                   "bayer_bggr16": 16, "bayer_gbrg16": 17, "bayer_grbg16": 18, "16UC1": 19, "32FC1": 20}
+IMG_TILE_W = 256             # GSR_IMG_TILE_W: pixels of one row per workgroup of gsr_image_decode (csrc/image.hip)
+IMG_TILE_H = 1               # rows per workgroup: rows are not tiled (Bayer stages the rows above and below as halo)
+DEPTH_REGISTER_CAP = 8       # columns / rows of a footprint of gsr_depth_register before it is cut
+
 FPFH_WIDTH = 33              # GSR_FPFH_WIDTH
 FEATURE_NN_TILE = 128        # GSR_FEATURE_NN_TILE
 RANSAC_N_MAX = 8             # GSR_RANSAC_N_MAX
@@ -264,6 +279,16 @@ EXPORTS = {
     # P, points, colors, out, stream
     "gsr_pc2_encode": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_debug_pc2_force_direct": (C.c_int32, [C.c_int32]),
+    # layout (host), data + bytes, depth_scale, depth_lo, depth_hi, out, stream
+    "gsr_image_decode": (C.c_int, [C.POINTER(gsr_image_layout), C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                   C.c_void_p]),
+    # W, H, image, out_bytes, stream
+    "gsr_image_encode_rgb8": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # Wd, Hd, depth, Kd[4] (host), Kc[4] (host), T_cd[12] (host float64), Wc, Hc, out, status_dev, workspace + bytes, stream
+    "gsr_depth_register_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_depth_register": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),

@@ -24,6 +24,15 @@ def focal2fov(focal: float, pixels: int) -> float:
     return 2.0 * math.atan(pixels / (2.0 * focal))
 
 
+def qvec2rotmat(qvec) -> np.ndarray:
+    """COLMAP's quaternion (w, x, y, z) -> rotation matrix, float64 (the reference reads a pose message's rotation through it,
+    scene/dataset_readers.py:365); the quaternion is taken as given, not normalised."""
+    w, x, y, z = (float(c) for c in qvec)
+    return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
+                     [2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x],
+                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y]], dtype=np.float64)
+
+
 def world_to_view(R: np.ndarray, t: np.ndarray, translate=(0.0, 0.0, 0.0), scale: float = 1.0) -> np.ndarray:
     Rt = np.zeros((4, 4), dtype=np.float64)
     Rt[:3, :3] = np.asarray(R, dtype=np.float64).T

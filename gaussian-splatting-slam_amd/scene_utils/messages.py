@@ -312,3 +312,348 @@ def encode_pointcloud2(points, colors=None):
     fields = [PointField("x", 0, PointField.FLOAT32, 1), PointField("y", 4, PointField.FLOAT32, 1),
               PointField("z", 8, PointField.FLOAT32, 1), PointField("rgb", 12, PointField.FLOAT32, 1)]
     return PointCloud2(1, P, fields, False, 16, 16 * P, data, False)
+
+
+# ---- sensor_msgs/Image, CameraInfo, TransformStamped: the other three members of a /Visual_Merged message -----------------------------
+# What the reference's imgmsg_to_pli (scene/dataset_readers.py:278-309) does on the host for rgb8 / bgr8 / mono8 - ignoring `step`
+# (a padded row breaks its reshape) and `is_bigendian`, and passing every frame through a JPEG on disk: three defects that are
+# not followed - here in HIP (csrc/image.hip; the rules: include/gsr.h, gsr_image_decode) for the colour, Bayer and depth
+# encodings, followed by the registration of a depth image into the colour camera and Frame.from_sensor.
+
+# name -> bytes per pixel; the names of sensor_msgs/image_encodings.h
+IMAGE_BYTES_PER_PIXEL = {"rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4, "mono8": 1, "rgb16": 6, "bgr16": 6, "rgba16": 8, "bgra16": 8,
+                         "mono16": 2, "bayer_rggb8": 1, "bayer_bggr8": 1, "bayer_gbrg8": 1, "bayer_grbg8": 1, "bayer_rggb16": 2,
+                         "bayer_bggr16": 2, "bayer_gbrg16": 2, "bayer_grbg16": 2, "16UC1": 2, "32FC1": 4}
+DEPTH_ENCODINGS = ("16UC1", "32FC1")      # depth unless as_depth=False; mono16 is depth where the caller says so
+MAX_FOCAL_RATIO = 4.0                     # register_depth: fx_c <= 4 fx_d keeps every footprint inside the kernel's 8 x 8
+
+
+class Image:
+    """A plain record with the attributes of sensor_msgs/Image.  data: what PointCloud2.data takes."""
+    __slots__ = ("height", "width", "encoding", "is_bigendian", "step", "data")
+
+    def __init__(self, height, width, encoding, is_bigendian, step, data):
+        self.height, self.width, self.encoding, self.is_bigendian, self.step, self.data = height, width, encoding, is_bigendian, \
+            step, data
+
+
+class CameraInfo:
+    """A plain record with the attributes of sensor_msgs/CameraInfo that camera_info_intrinsics reads.  K: 9 values, row-major."""
+    __slots__ = ("height", "width", "distortion_model", "D", "K", "R", "P")
+
+    def __init__(self, height, width, distortion_model, D, K, R=None, P=None):
+        self.height, self.width, self.distortion_model, self.D, self.K, self.R, self.P = height, width, distortion_model, D, K, R, P
+
+
+def _check_image(msg, what="msg"):
+    """the message's header -> (dict of gsr_image_layout values + name and bpp, bytes the layout needs); type before value"""
+    try:
+        height, width, encoding, step, big, _ = msg.height, msg.width, msg.encoding, msg.step, msg.is_bigendian, msg.data
+    except AttributeError as e:
+        raise TypeError(f"{what}: expected an Image (height, width, encoding, is_bigendian, step, data): {e}") from None
+    height, width, step = _check_size("height", height), _check_size("width", width), _check_size("step", step)
+    if not isinstance(encoding, str):
+        raise TypeError(f"{what}.encoding={encoding!r}: expected a string")
+    if encoding not in IMAGE_BYTES_PER_PIXEL:
+        raise ValueError(f"{what}.encoding={encoding!r}: supported are {', '.join(IMAGE_BYTES_PER_PIXEL)}")
+    bpp = IMAGE_BYTES_PER_PIXEL[encoding]
+    if step < width * bpp:
+        raise ValueError(f"step={step}: below width * bytes per pixel = {width * bpp}")
+    if width * height > MAX_POINTS:
+        raise ValueError(f"width * height = {width * height}: at most 2^30 - 1 pixels")
+    if encoding.startswith("bayer_") and (width < 2 or height < 2):
+        raise ValueError(f"a Bayer image of {width} x {height}: at least 2 x 2")
+    lay = {"height": height, "width": width, "step": step, "encoding": encoding, "bpp": bpp, "is_bigendian": 1 if big else 0}
+    return lay, ((height - 1) * step + width * bpp if width * height else 0)
+
+
+def _check_depth_options(encoding, depth_scale, depth_range, as_depth):
+    """-> (is depth, scale, lo, hi); type before value"""
+    if as_depth is not None and not isinstance(as_depth, bool):
+        raise TypeError(f"as_depth={as_depth!r}: expected True, False or None")
+    if depth_scale is not None and (isinstance(depth_scale, bool) or not isinstance(depth_scale, numbers.Real)):
+        raise TypeError(f"depth_scale={depth_scale!r}: expected a number or None")
+    lo = hi = None
+    if depth_range is not None:
+        try:
+            lo, hi = depth_range
+        except (TypeError, ValueError):
+            raise TypeError(f"depth_range={depth_range!r}: expected (lo, hi), either may be None") from None
+        for v in (lo, hi):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real)):
+                raise TypeError(f"depth_range={depth_range!r}: expected numbers or None")
+    can_depth = encoding in DEPTH_ENCODINGS or encoding == "mono16"
+    if as_depth is True and not can_depth:
+        raise ValueError(f"as_depth=True: {encoding!r} holds no depth (16UC1, 32FC1 and mono16 do)")
+    if as_depth is False and encoding in DEPTH_ENCODINGS:
+        raise ValueError(f"as_depth=False: {encoding!r} holds nothing but depth")
+    is_depth = encoding in DEPTH_ENCODINGS if as_depth is None else as_depth
+    if not is_depth:
+        if depth_scale is not None or depth_range is not None:
+            raise ValueError(f"depth_scale / depth_range given, but {encoding!r} is decoded as colour")
+        return False, 1.0, -math.inf, math.inf
+    scale = (1.0 if encoding == "32FC1" else 0.001) if depth_scale is None else float(depth_scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"depth_scale={depth_scale}: expected a finite value > 0")
+    lo = -math.inf if lo is None else float(lo)
+    hi = math.inf if hi is None else float(hi)
+    if math.isnan(lo) or math.isnan(hi) or lo > hi:
+        raise ValueError(f"depth_range={depth_range}: expected lo <= hi, no NaN")
+    return True, scale, lo, hi
+
+
+def decode_image(msg, depth_scale=None, depth_range=None, as_depth=None):
+    """-> float32 [3,H,W] (colour, Bayer: channels in [0, 1]) or [H,W] (depth in metres, 0 = no reading) on the HIP device.
+    as_depth=None: depth for 16UC1 and 32FC1, colour for everything else; as_depth=True reads a mono16 image as depth.
+    depth_scale=None: 0.001 for the 16-bit forms (millimetres), 1.0 for 32FC1; depth_range=(lo, hi) zeroes what lies outside after
+    the scaling (None: that bound is off).  The scale and the bounds act as float32.  Host data is uploaded once, a device uint8
+    tensor is used in place, at any alignment.  One launch, no read-back.  An image of zero pixels returns an empty tensor."""
+    lay, need = _check_image(msg)
+    is_depth, scale, lo, hi = _check_depth_options(lay["encoding"], depth_scale, depth_range, as_depth)
+    where, data = _check_data(msg.data, need)
+    _C = _gsr()
+    W, H = lay["width"], lay["height"]
+    if where == "host":
+        data = _upload(data) if W * H else None
+    dev = data.device if data is not None else torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((H, W) if is_depth else (3, H, W), dtype=torch.float32, device=dev)
+    if W * H > 0:
+        code = _C.IMAGE_ENCODINGS["16UC1" if is_depth and lay["encoding"] == "mono16" else lay["encoding"]]
+        L = _C.gsr_image_layout(W, H, lay["step"], code, lay["is_bigendian"])
+        with _C.on_device(dev):
+            _C.check(_C.lib().gsr_image_decode(C.byref(L), _C.ptr(data), data.numel(), scale, lo, hi, _C.ptr(out), _C._stream()))
+    return out
+
+
+def encode_image(image):
+    """-> Image in rgb8 (step = 3 W, little-endian) whose data is a uint8 tensor on the HIP device: what the reference sends to its
+    viewer (train.py:80).  `image`: float32 [3,H,W] on the device; a byte is (uint8)(min(max(c, 0), 1) * 255) - truncated, as
+    .byte() does there - and 0 for a NaN."""
+    if not isinstance(image, torch.Tensor):
+        raise TypeError(f"image: expected a tensor, got {type(image).__name__}")
+    if image.dtype != torch.float32:
+        raise TypeError(f"image: expected float32, got {image.dtype}")
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"image: expected [3,H,W], got {tuple(image.shape)}")
+    H, W = int(image.shape[1]), int(image.shape[2])
+    if W * H > MAX_POINTS:
+        raise ValueError(f"image: {W} x {H}: at most 2^30 - 1 pixels")
+    _C = _gsr()
+    if not image.is_cuda:
+        raise _C.GsrError("encode_image needs the image on the HIP device (no CPU path)")
+    src = image.detach().contiguous()
+    data = torch.empty(3 * W * H, dtype=torch.uint8, device=src.device)
+    if W * H > 0:
+        with _C.on_device(src.device):
+            _C.check(_C.lib().gsr_image_encode_rgb8(W, H, _C.ptr(src), _C.ptr(data), _C._stream()))
+    return Image(H, W, "rgb8", False, 3 * W, data)
+
+
+def _numbers(v, name):
+    """a flat list of floats from a sequence, an array or a tensor"""
+    import numpy as np
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    try:
+        arr = np.asarray(v)
+    except Exception:
+        raise TypeError(f"{name}={v!r}: expected numbers") from None
+    if arr.dtype == object or arr.dtype.kind not in "fiu":
+        raise TypeError(f"{name}={v!r}: expected numbers")
+    return [float(c) for c in arr.reshape(-1)]
+
+
+def camera_info_intrinsics(info):
+    """sensor_msgs/CameraInfo -> (K float64 [3,3] (numpy), dist (k1, k2, p1, p2, k3) or None, (W, H)): what Frame.from_sensor
+    takes - the step the reference has commented out (dataset_readers.py:313-320) in favour of hard-coded intrinsics.
+    distortion_model: `plumb_bob` with up to 5 coefficients; `rational_polynomial` only if coefficients 5 and later are all
+    zero (gsr_frame_undistort has five); an empty model, or an all-zero D, gives None.  fx and fy must be positive."""
+    import numpy as np
+    try:
+        height, width, model, D, K = info.height, info.width, info.distortion_model, info.D, info.K
+    except AttributeError as e:
+        raise TypeError(f"info: expected a CameraInfo (height, width, distortion_model, D, K): {e}") from None
+    height, width = _check_size("height", height), _check_size("width", width)
+    if not isinstance(model, str):
+        raise TypeError(f"distortion_model={model!r}: expected a string")
+    k = _numbers(K, "K")
+    d = _numbers(D, "D") if D is not None else []
+    if len(k) != 9:
+        raise ValueError(f"K: expected 9 values (row-major 3 x 3), got {len(k)}")
+    if not all(math.isfinite(c) for c in k + d):
+        raise ValueError("K / D: expected finite values")
+    if not (k[0] > 0.0 and k[4] > 0.0):
+        raise ValueError(f"K: fx = {k[0]}, fy = {k[4]}: expected positive focal lengths")
+    if model not in ("", "plumb_bob", "rational_polynomial"):
+        raise ValueError(f"distortion_model={model!r}: expected plumb_bob, rational_polynomial (with zero higher terms) or none")
+    if model == "plumb_bob" and len(d) > 5:
+        raise ValueError(f"D: plumb_bob has at most 5 coefficients, got {len(d)}")
+    if model == "rational_polynomial" and any(c != 0.0 for c in d[5:]):
+        raise ValueError("D: rational_polynomial with a non-zero k4, k5 or k6: the undistortion has (k1, k2, p1, p2, k3) only")
+    dist = None
+    if model != "" and any(c != 0.0 for c in d[:5]):
+        dist = tuple((d[:5] + [0.0] * 5)[:5])
+    return np.array(k, dtype=np.float64).reshape(3, 3), dist, (width, height)
+
+
+def pose_from_transform(tf, convention="w2c"):
+    """geometry_msgs/TransformStamped (anything with .transform.rotation and .transform.translation), or a (quaternion_xyzw,
+    translation) pair -> float64 [4,4] world-to-camera matrix on the host.  convention="w2c": the message IS the COLMAP
+    world-to-camera pose, the reading of initCameraExtrinsics / initSceneInfo (dataset_readers.py:333-338, 365-366);
+    "c2w": the message is the camera's pose in the world and is inverted."""
+    if not isinstance(convention, str):
+        raise TypeError(f"convention={convention!r}: expected 'w2c' or 'c2w'")
+    if hasattr(tf, "transform"):
+        try:
+            q, t = tf.transform.rotation, tf.transform.translation
+        except AttributeError as e:
+            raise TypeError(f"tf: expected .transform.rotation and .transform.translation: {e}") from None
+    else:
+        try:
+            q, t = tf
+        except (TypeError, ValueError):
+            raise TypeError(f"tf={tf!r}: expected a TransformStamped or a (quaternion_xyzw, translation) pair") from None
+    if convention not in ("w2c", "c2w"):
+        raise ValueError(f"convention={convention!r}: expected 'w2c' or 'c2w'")
+    M = pose_matrix(q, t)
+    if convention == "c2w":      # the rigid inverse: (R^T, -R^T t)
+        Rt = M[:3, :3].t().contiguous()
+        M = torch.eye(4, dtype=torch.float64)
+        M[:3, :3] = Rt
+        M[:3, 3] = -(Rt @ pose_matrix(q, t)[:3, 3])
+    return M
+
+
+def _check_t34(T, name):
+    """None (identity) or a [4,4] / [3,4] matrix -> 12 floats, rows 0 .. 2"""
+    if T is None:
+        return [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+    if not isinstance(T, torch.Tensor):
+        try:
+            T = torch.as_tensor(T, dtype=torch.float64)
+        except Exception:
+            raise TypeError(f"{name}={T!r}: expected a [4,4] or [3,4] matrix") from None
+    if tuple(T.shape) not in ((4, 4), (3, 4)) or not T.is_floating_point():
+        raise ValueError(f"{name}: expected a floating-point [4,4] or [3,4] matrix, got {T.dtype} {tuple(T.shape)}")
+    vals = [float(v) for v in T.detach().cpu().double()[:3].reshape(-1)]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{name}: expected finite values")
+    return vals
+
+
+def _check_wh(size, name):
+    try:
+        W, H = size
+    except (TypeError, ValueError):
+        raise TypeError(f"{name}={size!r}: expected (W, H)") from None
+    W, H = _check_size(f"{name}[0]", W), _check_size(f"{name}[1]", H)
+    if W < 1 or H < 1 or W * H > MAX_POINTS:
+        raise ValueError(f"{name}={size}: expected sides >= 1 and at most 2^30 - 1 pixels")
+    return W, H
+
+
+def register_depth(depth, K_depth, K_color, depth_to_color=None, size=None):
+    """gsr_depth_register: `depth` float32 [Hd,Wd] (metres, 0 = no reading) of the depth camera `K_depth` on the HIP device ->
+    [Hc,Wc] as the colour camera `K_color` of `size` = (Wc, Hc) (default: the depth image's) sees it - "aligned depth to
+    colour", which track_pose(gt_depth=...) and add_from_rgbd assume.  depth_to_color: [4,4] or [3,4], depth-camera frame ->
+    colour-camera frame (None: the identity).  Every reading covers the rectangle between its two projected pixel corners; the
+    nearest reading wins; a pixel none reaches is 0.  Both cameras are ideal pinholes.  fx_c > 4 fx_d or fy_c > 4 fy_d: ValueError
+    (a footprint would exceed the kernel's 8 x 8).  One read-back (the status word)."""
+    from .frames import _k4
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError(f"depth: expected a tensor, got {type(depth).__name__}")
+    if depth.dtype != torch.float32:
+        raise TypeError(f"depth: expected float32, got {depth.dtype}")
+    T = _check_t34(depth_to_color, "depth_to_color")
+    if depth.dim() == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if depth.dim() != 2 or depth.numel() < 1 or depth.numel() > MAX_POINTS:
+        raise ValueError(f"depth: expected [H,W] with 1 .. 2^30 - 1 pixels, got {tuple(depth.shape)}")
+    Hd, Wd = int(depth.shape[0]), int(depth.shape[1])
+    Wc, Hc = (Wd, Hd) if size is None else _check_wh(size, "size")
+    kd, kc = _k4(K_depth, "K_depth"), _k4(K_color, "K_color")
+    for name, k in (("K_depth", kd), ("K_color", kc)):
+        if not all(math.isfinite(v) for v in k) or not (k[0] > 0.0 and k[1] > 0.0):
+            raise ValueError(f"{name}: (fx, fy, cx, cy) = {k}: expected finite values, fx and fy positive")
+    if kc[0] > MAX_FOCAL_RATIO * kd[0] or kc[1] > MAX_FOCAL_RATIO * kd[1]:
+        raise ValueError(f"K_color: focal lengths ({kc[0]}, {kc[1]}) above {MAX_FOCAL_RATIO:g} x K_depth's ({kd[0]}, {kd[1]}): a "
+                         "reading's footprint would exceed 8 x 8 colour pixels")
+    _C = _gsr()
+    if not depth.is_cuda:
+        raise _C.GsrError("register_depth needs the depth image on the HIP device (no CPU path)")
+    src = depth.detach().contiguous()
+    dev = src.device
+    out = torch.empty((Hc, Wc), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lib = _C.lib()
+    with _C.on_device(dev):
+        ws = torch.empty(lib.gsr_depth_register_workspace_bytes(Wc, Hc), dtype=torch.uint8, device=dev)
+        _C.check(lib.gsr_depth_register(Wd, Hd, _C.ptr(src), (C.c_float * 4)(*kd), (C.c_float * 4)(*kc), (C.c_double * 12)(*T),
+                                        Wc, Hc, _C.ptr(out), _C.ptr(status), _C.ptr(ws), ws.numel(), _C._stream()))
+    if int(status.item()) & 1:
+        raise _C.GsrError("register_depth: a reading's footprint exceeded 8 x 8 colour pixels and was cut")
+    return out
+
+
+def frame_from_messages(image, camera_info, transform=None, depth=None, depth_info=None, depth_to_color=None, size=None,
+                        new_K=None, depth_range=None, convention="w2c", name=""):
+    """Message bytes in, a Frame on the device out: decode_image(image); with `depth` (an Image in 16UC1, 32FC1 or mono16)
+    decode_image(depth, depth_range=..., as_depth=True) and - if `depth_info` (the depth camera's CameraInfo) or `depth_to_color`
+    is given - register_depth into the colour camera (missing depth_info: the colour camera's intrinsics; missing depth_to_color:
+    the identity); a depth that is already aligned (neither given) must have the image's size and skips that step.  Then
+    Frame.from_sensor with camera_info's K and distortion, pose_from_transform(transform, convention) (None: the identity),
+    `size` and `new_K`.  Everything is validated before the first launch.  Registration takes both cameras as ideal pinholes: a
+    distorted camera on either side of it raises ValueError."""
+    from .frames import Frame
+    lay, _ = _check_image(image, "image")
+    if not isinstance(convention, str):
+        raise TypeError(f"convention={convention!r}: expected 'w2c' or 'c2w'")
+    if _check_depth_options(lay["encoding"], None, None, None)[0]:
+        raise ValueError(f"image.encoding={lay['encoding']!r}: a depth encoding where the colour image is expected")
+    K, dist, wh = camera_info_intrinsics(camera_info)
+    if wh != (lay["width"], lay["height"]):
+        raise ValueError(f"camera_info is {wh[0]} x {wh[1]}, the image {lay['width']} x {lay['height']}")
+    if lay["width"] * lay["height"] < 1:
+        raise ValueError("image: no pixels")
+    pose = None if transform is None else pose_from_transform(transform, convention)
+    if size is not None:
+        _check_wh(size, "size")
+    register = depth is not None and (depth_info is not None or depth_to_color is not None)
+    if depth is None and (depth_info is not None or depth_to_color is not None or depth_range is not None):
+        raise ValueError("depth_info / depth_to_color / depth_range given without a depth image")
+    if depth is not None:
+        dlay, _ = _check_image(depth, "depth")
+        _check_depth_options(dlay["encoding"], None, depth_range, True)
+        dwh = (dlay["width"], dlay["height"])
+        Kd = K
+        if depth_info is not None:
+            Kd, ddist, iwh = camera_info_intrinsics(depth_info)
+            if iwh != dwh:
+                raise ValueError(f"depth_info is {iwh[0]} x {iwh[1]}, the depth image {dwh[0]} x {dwh[1]}")
+            if ddist is not None:
+                raise ValueError("depth_info: a distorted depth camera: register_depth takes ideal pinholes")
+        elif dwh != wh:
+            raise ValueError(f"depth is {dwh[0]} x {dwh[1]}, the image {wh[0]} x {wh[1]}: pass depth_info to register it")
+        if register:
+            if dist is not None:
+                raise ValueError("camera_info: a distorted colour camera: register_depth takes ideal pinholes")
+            _check_t34(depth_to_color, "depth_to_color")
+            if K[0, 0] > MAX_FOCAL_RATIO * Kd[0, 0] or K[1, 1] > MAX_FOCAL_RATIO * Kd[1, 1]:
+                raise ValueError(f"camera_info: focal lengths above {MAX_FOCAL_RATIO:g} x the depth camera's")
+    img = decode_image(image)
+    d = None
+    if depth is not None:
+        d = decode_image(depth, depth_range=depth_range, as_depth=True)
+        if register:
+            d = register_depth(d, Kd, K, depth_to_color, wh)
+    return Frame.from_sensor(img, d, K, dist, pose=pose, size=size, new_K=new_K, name=name)
+
+
+def frame_from_visual_merged(msg, **kw):
+    """gs_slam_msgs/visual_merged_msg (anything with .Image, .CameraInfo and .CameraPose, the names read at
+    dataset_readers.py:333, 359) -> frame_from_messages(msg.Image, msg.CameraInfo, msg.CameraPose, **kw)."""
+    try:
+        image, info, pose = msg.Image, msg.CameraInfo, msg.CameraPose
+    except AttributeError as e:
+        raise TypeError(f"msg: expected .Image, .CameraInfo and .CameraPose: {e}") from None
+    return frame_from_messages(image, info, pose, **kw)

@@ -56,6 +56,9 @@ extern "C" {
  *    gsr_ransac_workspace_bytes, gsr_ransac_feature_matching: global registration from feature matches (additions only);
  *    gsr_pc2_layout, gsr_pc2_decode_workspace_bytes, gsr_pc2_decode, gsr_pc2_encode, gsr_debug_pc2_force_direct: a
  *    sensor_msgs/PointCloud2 byte buffer decoded, cropped, posed and compacted on the device, and its inverse (additions only);
+ *    gsr_image_layout, gsr_image_decode, gsr_image_encode_rgb8, gsr_depth_register_workspace_bytes, gsr_depth_register: a
+ *    sensor_msgs/Image byte buffer (colour, Bayer, depth) decoded on the device, its rgb8 inverse, and a depth image moved into
+ *    the colour camera (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -901,6 +904,90 @@ int gsr_pc2_encode(int64_t P, const float* points /*[P,3]*/, const float* colors
  * setting.  Both paths give identical bits.  The switch is ONE process-wide variable, read when gsr_pc2_decode is called: it is
  * not meant for concurrent callers, and a caller that sets it restores it. */
 int32_t gsr_debug_pc2_force_direct(int32_t on);
+
+/* ---- sensor_msgs/Image on the device (csrc/image.hip): what the reference's imgmsg_to_pli
+ * (scene/dataset_readers.py:278-309) does on the host for rgb8 / bgr8 / mono8, with `step` and `is_bigendian` honoured ---- */
+
+/* The encodings, named as in sensor_msgs/image_encodings.h.  GSR_IMG_16UC1 is also what a caller passes for a mono16 image that
+ * holds depth. */
+#define GSR_IMG_RGB8 1
+#define GSR_IMG_BGR8 2
+#define GSR_IMG_RGBA8 3
+#define GSR_IMG_BGRA8 4
+#define GSR_IMG_MONO8 5
+#define GSR_IMG_RGB16 6
+#define GSR_IMG_BGR16 7
+#define GSR_IMG_RGBA16 8
+#define GSR_IMG_BGRA16 9
+#define GSR_IMG_MONO16 10
+#define GSR_IMG_BAYER_RGGB8 11
+#define GSR_IMG_BAYER_BGGR8 12
+#define GSR_IMG_BAYER_GBRG8 13
+#define GSR_IMG_BAYER_GRBG8 14
+#define GSR_IMG_BAYER_RGGB16 15
+#define GSR_IMG_BAYER_BGGR16 16
+#define GSR_IMG_BAYER_GBRG16 17
+#define GSR_IMG_BAYER_GRBG16 18
+#define GSR_IMG_16UC1 19
+#define GSR_IMG_32FC1 20
+/* The layout of a message's byte buffer (HOST struct).  Pixel (x, y) starts at byte y * step + x * bpp, bpp = channels * bytes per
+ * channel (3, 4, 1 / 6, 8, 2 for the colour forms, 1 / 2 for Bayer, 2 and 4 for depth).  step may exceed width * bpp. */
+typedef struct gsr_image_layout {
+  uint32_t width, height, step;
+  int32_t encoding;        /* GSR_IMG_* */
+  int32_t is_bigendian;    /* byte order of the 16-bit words and of the 32FC1 float */
+} gsr_image_layout;
+#define GSR_IMG_TILE_W 256 /* pixels of one row that a workgroup stages and decodes */
+
+/* Decode a sensor_msgs/Image byte buffer (`data`: DEVICE bytes, any alignment).  Every value is a fixed sequence of correctly
+ * rounded float32 operations, none fused:
+ *  colour (rgb8 .. mono16): out = planar [3,H,W]; channel = (float)sample / 255.0f, or / 65535.0f for the 16-bit forms whose word
+ *     is assembled in the message's byte order.  Alpha is dropped, mono goes to all three planes.
+ *  Bayer: out = planar [3,H,W].  The name spells the colours of pixels (0,0), (1,0) of row 0, then (0,1), (1,1) of row 1 (ROS's
+ *     convention, not OpenCV's).  Bilinear over the 3 x 3 window: the site's own colour is its sample (n = 1); a colour found on
+ *     the two horizontal or the two vertical neighbours is their mean (n = 2); a colour found on the four edge or the four
+ *     diagonal neighbours is their mean (n = 4).  A tap outside the image is reflected without repeating the edge (-1 -> 1,
+ *     W -> W - 2), which keeps the Bayer phase.  The taps are summed as integers and divided once:
+ *     (float)sum / (float)(n * 255), or n * 65535.  Needs width >= 2 and height >= 2.
+ *  depth, 16UC1: out = [H,W]; d = (float)u16 * depth_scale, byte order honoured.
+ *  depth, 32FC1: the float f by its bits, byte order honoured; d = f * depth_scale; d = 0 where f is NaN, +-inf or <= 0.
+ *  both depth forms, after the scaling and in float32: d = 0 where d is not a finite value > 0 (raw 0 stays 0, the library's "no
+ *     reading"); then d = 0 where d < depth_lo or d > depth_hi (-inf / +inf turn a bound off).
+ * No byte at or beyond data_bytes (or in front of data) is ever read.  No allocation, no atomics.  Zero pixels: no launch.
+ * Errors before any launch: NULL layout / data / out, an unknown encoding, width * height above 2^30 - 1, a Bayer image below
+ * 2 x 2, (depth) a depth_scale that is not finite and > 0 or a NaN bound, step < width * bpp,
+ * (height - 1) * step + width * bpp > data_bytes: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_image_decode(const gsr_image_layout* layout /*HOST*/, const void* data, size_t data_bytes, float depth_scale, float depth_lo,
+                     float depth_hi, float* out /*[3,H,W] or [H,W]*/, void* stream);
+
+/* The inverse for publishing a render: planar [3,H,W] float32 -> interleaved rgb8, step = 3 W (out_bytes: 3 W H device bytes,
+ * 4-byte aligned).  byte = (uint8)(min(max(c, 0), 1) * 255.0f): one rounded product, then truncation - what .byte() does in the
+ * reference's train.py:80; a NaN gives 0.
+ * Errors before the launch: sides < 1, W * H above 2^30 - 1, NULL image / out_bytes, a misaligned out_bytes:
+ * GSR_ERR_INVALID_ARGUMENT. */
+int gsr_image_encode_rgb8(int32_t W, int32_t H, const float* image /*[3,H,W]*/, void* out_bytes /*[3 W H]*/, void* stream);
+
+/* Move a depth image [Hd,Wd] of the depth camera (intrinsics Kd = fx, fy, cx, cy; HOST) into the colour camera (Kc, Wc x Hc):
+ * "aligned depth to colour".  T_cd: HOST float64[12], the row-major 3 x 4 matrix from the depth-camera frame to the colour-camera
+ * frame.  Per depth pixel (u, v) with a reading d > 0, for the centre (u, v) and the two pixel corners (u - 0.5, v - 0.5),
+ * (u + 0.5, v + 0.5), every step one correctly rounded float32 operation:
+ *   x = ((uc - cx_d) / fx_d) * d, y = ((vc - cy_d) / fy_d) * d, z = d;  (x', y', z') = T_cd (x, y, z) as "q = T s" above (products
+ *   and sums in float64 in that order, one rounding to float32);  px = fx_c * (x' / z') + cx_c, py = fy_c * (y' / z') + cy_c.
+ * The reading is skipped if the centre's z' is not a finite value > 0, or if px or py of either corner is not finite.  Each
+ * corner is rounded, floorf(p + 0.5f), and clamped IN FLOAT to [-1, Wc] / [-1, Hc] before the conversion to int.  Every colour
+ * pixel of the inclusive rectangle spanned by the two rounded corners (either may be the low one) that lies inside the image
+ * takes the MINIMUM of its value and the centre's z' - librealsense's footprint rule; with equal cameras a 2 x 2 splat.  The
+ * minimum is an integer atomicMin on the bits of z' (positive floats order as their bits): independent of the order of arrival,
+ * bit-exact from run to run.  The part of a rectangle inside the image is cut to its first 8 columns and 8 rows; a cut sets bit 0
+ * of status_dev[0] (device int32, cleared by the call).  A pixel no reading reached is 0.  The workspace (one uint32 per colour
+ * pixel) is initialised by the call.  No float atomics, no allocation.
+ * Errors before any launch: a NULL pointer, a side < 1, Wd * Hd or Wc * Hc above 2^30 - 1, an intrinsic or an entry of T_cd that
+ * is not finite, fx or fy <= 0: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_depth_register_workspace_bytes(Wc, Hc):
+ * GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_depth_register_workspace_bytes(int32_t Wc, int32_t Hc);
+int gsr_depth_register(int32_t Wd, int32_t Hd, const float* depth /*[Hd,Wd]*/, const float* Kd /*HOST [4]*/,
+                       const float* Kc /*HOST [4]*/, const double* T_cd /*HOST [12]*/, int32_t Wc, int32_t Hc, float* out /*[Hc,Wc]*/,
+                       int32_t* status_dev /*[1]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
