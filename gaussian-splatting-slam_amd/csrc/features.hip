@@ -4,10 +4,11 @@
 //
 // gsr_compute_fpfh: a copy of the cloud with the rows whose point OR normal is not finite turned into NaN NaN NaN (nobody's
 //   neighbour, and no part of the bounding box or the sort), the structure of knn.hip over THAT copy, the normals gathered into
-//   sorted order, then up to three sweeps over the boxes k_normals walks:
-//   1. k_fpfh_bound<K>: min(r2, d_k) per row, the first sweep of k_normals (skipped for max_nn = 0, where the bound is r2);
-//   2. k_fpfh_spfh: per row the 3 x 11 histogram of the pair features of its members, as INTEGER counts - exact and independent
-//      of the order the members are met in - kept by sorted position, with m = the number of members;
+//   sorted order, then up to three sweeps (knn_sweep, knn_common.h) over the boxes:
+//   1. k_fpfh_bound<K>: min(r2, d_k) per row by knn_topk_bound (skipped for max_nn = 0, where the bound is r2);
+//   2. k_fpfh_spfh: per row (knn_member_walk here and in 3.) the 3 x 11 histogram of the pair features of its members, as
+//      INTEGER counts - exact and independent of the order the members are met in - kept by sorted position, with m = the
+//      number of members;
 //   3. k_fpfh_sum: per row sum SPFH_j / d2 over its members in float64, in sorted-structure order, the three blocks scaled to
 //      100, the row's own SPFH added, one rounding to float32.
 //   The 33 bins of a thread are indexed at run time: they live in LDS as bins[b][thread] (consecutive lanes, consecutive words),
@@ -34,7 +35,6 @@
 #define GSR_FEAT_WGS GSR_FEATURE_NN_WORKGROUPS     // workgroups aimed at: two per CU
 #define GSR_RANSAC_BLOCK 64
 #define GSR_RANSAC_TILE 256        // pairs per LDS tile of the scoring kernel
-#define GSR_NONE 0x7FFFFFFFu
 #define GSR_PI 3.14159265358979323846
 
 // ==== FPFH ==========================================================================================================================
@@ -87,50 +87,16 @@ __global__ __launch_bounds__(256) void k_fpfh_prepare(uint32_t P, float4* __rest
   nrm[j] = make_float4(normals[3 * row], normals[3 * row + 1], normals[3 * row + 2], 0.f);
 }
 
-// min(r2, d_k): the first sweep of k_normals (normals.hip), per sorted position
+// min(r2, d_k) per sorted position: what k_normals (normals.hip) takes from the same call
 template <int K>
-__global__ __launch_bounds__(256) void k_fpfh_bound(uint32_t P, int k, float r2, const float4* __restrict__ pts,
-                                                    const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
-                                                    uint32_t nbox, const float4* __restrict__ sup_lo,
-                                                    const float4* __restrict__ sup_hi, uint32_t nsuper,
-                                                    float* __restrict__ bound) {
+__global__ __launch_bounds__(256) void k_fpfh_bound(GsrKnnTree t, int k, float r2, float* __restrict__ bound) {
   __shared__ float4 s_lo[256], s_hi[256];
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  const bool active = q < P;
+  const bool active = q < t.P;
   const uint32_t pos = active ? q : 0u;
-  const float4 me = pts[pos];
-  const int pad = K - k;
   float b[K];
-  knn_reset_k<K>(b, pad);
-  if (active) {
-    const uint32_t kk = (uint32_t)k;
-    const uint32_t j0 = pos >= kk ? pos - kk : 0u, j1 = min(P - 1u, pos + kk);
-    for (uint32_t j = j0; j <= j1; j++)
-      if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-  }
-  const float seed = fminf(b[K - 1], r2);
-  knn_reset_k<K>(b, pad);
-  for (uint32_t base = 0; base < nsuper; base += 256u) {
-    __syncthreads();
-    if (base + threadIdx.x < nsuper) {
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-    }
-    __syncthreads();
-    if (!active) continue;
-    const uint32_t n = min(256u, nsuper - base);
-    for (uint32_t s = 0; s < n; s++) {
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b[K - 1], seed))) continue;
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-      for (uint32_t bx = bb; bx < be; bx++) {
-        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= fminf(b[K - 1], seed))) continue;
-        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
-        for (uint32_t j = jb; j < je; j++)
-          if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-      }
-    }
-  }
-  if (active) bound[pos] = fminf(b[K - 1], r2);
+  const float d = knn_topk_bound<K, 256>(t, t.pts[pos], pos, active, k, r2, s_lo, s_hi, b);
+  if (active) bound[pos] = d;
 }
 
 __device__ __forceinline__ int fpfh_bin(double scaled) {      // floor, clamped to 0 .. 10 (a NaN: 0)
@@ -165,34 +131,11 @@ __device__ __forceinline__ void fpfh_pair(double dx, double dy, double dz, const
   b2 = fpfh_bin(11.0 * (f2 + 1.0) / 2.0);
 }
 
-// the walk both kernels below share: every j != pos of the sorted structure with d2(pos, j) <= bound, in sorted order; BODY
-// sees j and the float32 differences fx, fy, fz = p_i - p_j
-#define FPFH_WALK(...)                                                                                              \
-  for (uint32_t base = 0; base < nsuper; base += (uint32_t)GSR_FPFH_BLOCK) {                                       \
-    __syncthreads();                                                                                                \
-    if (base + threadIdx.x < nsuper) {                                                                              \
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];                                                               \
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];                                                               \
-    }                                                                                                               \
-    __syncthreads();                                                                                                \
-    if (!active) continue;                                                                                          \
-    const uint32_t ns = min((uint32_t)GSR_FPFH_BLOCK, nsuper - base);                                               \
-    for (uint32_t s = 0; s < ns; s++) {                                                                             \
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= bound)) continue;                                                   \
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);       \
-      for (uint32_t bx = bb; bx < be; bx++) {                                                                       \
-        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= bound)) continue;                                           \
-        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);                    \
-        for (uint32_t j = jb; j < je; j++) {                                                                        \
-          const float4 p = pts[j];                                                                                  \
-          const float fx = __fsub_rn(me.x, p.x), fy = __fsub_rn(me.y, p.y), fz = __fsub_rn(me.z, p.z);              \
-          if (j == pos || !(knn_sq(fx, fy, fz) <= bound)) continue;      /* (NaN: not a member) */                  \
-          __VA_ARGS__                                                                                               \
-        }                                                                                                           \
-      }                                                                                                             \
-    }                                                                                                               \
-  }
-
+// (a masked row is NaN in every component: it walks nothing)
+// The one search kernel that takes the tree's arrays as arguments of its own and puts the GsrKnnTree together itself: its visit
+// writes memory (the LDS bins), and only loads through `const ... __restrict__` kernel arguments stay scalar loads next to that -
+// through pointers read out of a by-value struct the wave-uniform loads of the box AABBs and points become vector loads (measured:
+// 5 - 6 % of the kernel, profiles/knn_sweep_refactor.txt).
 __global__ __launch_bounds__(GSR_FPFH_BLOCK) void k_fpfh_spfh(uint32_t P, float r2, const float* __restrict__ bound_of,
                                                               const float4* __restrict__ pts, const float4* __restrict__ nrm,
                                                               const float4* __restrict__ box_lo,
@@ -203,24 +146,27 @@ __global__ __launch_bounds__(GSR_FPFH_BLOCK) void k_fpfh_spfh(uint32_t P, float 
                                                               int32_t* __restrict__ counts_out, int32_t* __restrict__ count_out) {
   __shared__ float4 s_lo[GSR_FPFH_BLOCK], s_hi[GSR_FPFH_BLOCK];
   __shared__ int32_t bins[GSR_FPFH_BINS * GSR_FPFH_BLOCK];
+  const GsrKnnTree t{pts, box_lo, box_hi, sup_lo, sup_hi, P, nbox, nsuper};
   const uint32_t q = blockIdx.x * (uint32_t)GSR_FPFH_BLOCK + threadIdx.x;
-  const bool live = q < P;
+  const bool live = q < t.P;
   const uint32_t pos = live ? q : 0u;
-  const float4 me = pts[pos];
-  const bool active = live && knn_finite(me.x);      // (a masked row is NaN in every component: it walks nothing)
+  const float4 me = t.pts[pos];
+  const bool active = live && knn_finite(me.x);
   const float4 ni = nrm[pos];
   const float bound = bound_of ? bound_of[pos] : r2;
 #pragma unroll
   for (int b = 0; b < GSR_FPFH_BINS; b++) bins[b * GSR_FPFH_BLOCK + threadIdx.x] = 0;
   int32_t members = 0;
-  FPFH_WALK({
-    int b0, b1, b2;
-    fpfh_pair(-(double)fx, -(double)fy, -(double)fz, ni, nrm[j], b0, b1, b2);
-    members++;
-    bins[b0 * GSR_FPFH_BLOCK + threadIdx.x]++;
-    bins[(11 + b1) * GSR_FPFH_BLOCK + threadIdx.x]++;
-    bins[(22 + b2) * GSR_FPFH_BLOCK + threadIdx.x]++;
-  })
+  knn_member_walk<GSR_FPFH_BLOCK>(
+      t, me, pos, active, bound, s_lo, s_hi,
+      [&](const uint32_t j, const float fx, const float fy, const float fz) __attribute__((always_inline)) {
+        int b0, b1, b2;
+        fpfh_pair(-(double)fx, -(double)fy, -(double)fz, ni, nrm[j], b0, b1, b2);
+        members++;
+        bins[b0 * GSR_FPFH_BLOCK + threadIdx.x]++;
+        bins[(11 + b1) * GSR_FPFH_BLOCK + threadIdx.x]++;
+        bins[(22 + b2) * GSR_FPFH_BLOCK + threadIdx.x]++;
+      });
   if (!live) return;
   const size_t row = (size_t)__float_as_uint(me.w);
   const bool finite = active;
@@ -233,36 +179,35 @@ __global__ __launch_bounds__(GSR_FPFH_BLOCK) void k_fpfh_spfh(uint32_t P, float 
   }
 }
 
-__global__ __launch_bounds__(GSR_FPFH_BLOCK) void k_fpfh_sum(uint32_t P, float r2, const float* __restrict__ bound_of,
-                                                             const float4* __restrict__ pts, const float4* __restrict__ box_lo,
-                                                             const float4* __restrict__ box_hi, uint32_t nbox,
-                                                             const float4* __restrict__ sup_lo, const float4* __restrict__ sup_hi,
-                                                             uint32_t nsuper, const int32_t* __restrict__ spfh,
+__global__ __launch_bounds__(GSR_FPFH_BLOCK) void k_fpfh_sum(GsrKnnTree t, float r2, const float* __restrict__ bound_of,
+                                                             const int32_t* __restrict__ spfh,
                                                              const int32_t* __restrict__ m_of, float* __restrict__ fpfh) {
   __shared__ float4 s_lo[GSR_FPFH_BLOCK], s_hi[GSR_FPFH_BLOCK];
   __shared__ double acc[GSR_FPFH_BINS * GSR_FPFH_BLOCK];
   const uint32_t q = blockIdx.x * (uint32_t)GSR_FPFH_BLOCK + threadIdx.x;
-  const bool live = q < P;
+  const bool live = q < t.P;
   const uint32_t pos = live ? q : 0u;
-  const float4 me = pts[pos];
+  const float4 me = t.pts[pos];
   const bool active = live && knn_finite(me.x);
   const float bound = bound_of ? bound_of[pos] : r2;
 #pragma unroll
   for (int b = 0; b < GSR_FPFH_BINS; b++) acc[b * GSR_FPFH_BLOCK + threadIdx.x] = 0.0;
-  FPFH_WALK({
-    const double dx = (double)fx, dy = (double)fy, dz = (double)fz;
-    const double d2 = (dx * dx + dy * dy) + dz * dz;
-    const int32_t mj = m_of[j];
-    if (d2 > 0.0 && mj > 0) {
-      // SPFH_j(b) / d2 = 100 c / (m_j d2); an empty bin adds +0 to a sum that is >= +0: skipped
-      const double w = 100.0 / ((double)mj * d2);
-      const int32_t* __restrict__ cj = spfh + (size_t)j * GSR_FPFH_BINS;
-      for (int b = 0; b < GSR_FPFH_BINS; b++) {
-        const int32_t c = cj[b];
-        if (c != 0) acc[b * GSR_FPFH_BLOCK + threadIdx.x] += (double)c * w;
-      }
-    }
-  })
+  knn_member_walk<GSR_FPFH_BLOCK>(
+      t, me, pos, active, bound, s_lo, s_hi,
+      [&](const uint32_t j, const float fx, const float fy, const float fz) __attribute__((always_inline)) {
+        const double dx = (double)fx, dy = (double)fy, dz = (double)fz;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const int32_t mj = m_of[j];
+        if (d2 > 0.0 && mj > 0) {
+          // SPFH_j(b) / d2 = 100 c / (m_j d2); an empty bin adds +0 to a sum that is >= +0: skipped
+          const double w = 100.0 / ((double)mj * d2);
+          const int32_t* __restrict__ cj = spfh + (size_t)j * GSR_FPFH_BINS;
+          for (int b = 0; b < GSR_FPFH_BINS; b++) {
+            const int32_t c = cj[b];
+            if (c != 0) acc[b * GSR_FPFH_BLOCK + threadIdx.x] += (double)c * w;
+          }
+        }
+      });
   if (!live) return;
   const size_t row = (size_t)__float_as_uint(me.w);
   float* __restrict__ out = fpfh + row * GSR_FPFH_BINS;
@@ -622,8 +567,6 @@ __global__ __launch_bounds__(256) void k_ransac_best(uint64_t t0, const uint32_t
   best[RB_T + 15] = 1.0;
 }
 
-static bool feat_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
-
 extern "C" {
 
 size_t gsr_fpfh_workspace_bytes(int64_t P) { return fpfh_layout((size_t)(P < 1 ? 1 : P)).total; }
@@ -631,7 +574,7 @@ size_t gsr_fpfh_workspace_bytes(int64_t P) { return fpfh_layout((size_t)(P < 1 ?
 int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float radius, int32_t max_nn, float* fpfh,
                      int32_t* spfh_counts, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream) {
   const bool radius_only = max_nn == 0;
-  if (feat_bad_size(P) || !points || !normals || !fpfh || !workspace || !(radius > 0.f) ||
+  if (gsr_bad_size(P) || !points || !normals || !fpfh || !workspace || !(radius > 0.f) ||
       !(radius_only ? radius < KNN_INF : (max_nn >= 3 && max_nn <= GSR_KNN_K_MAX + 1))) {
     gsr_set_error("compute_fpfh: bad arguments (P = %lld, radius = %g: expected > 0, max_nn = %d: expected 3 .. %d, or 0 with a "
                   "finite radius)", (long long)P, (double)radius, (int)max_nn, GSR_KNN_K_MAX + 1);
@@ -645,12 +588,12 @@ int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const GsrKnnBuild b = nn_build_views(ws, L.nn);
-  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
+  const GsrKnnTree t = knn_tree(b, (size_t)P);
+  const uint32_t n = t.P, nblk = (n + 255u) / 256u;
   float* masked = (float*)(ws + L.masked);
   GSR_LAUNCH("fpfh_mask", k_fpfh_mask, dim3(nblk), dim3(256), 0, st, n, points, normals, masked);
   gsr_knn_build(P, masked, b, st);
   const uint32_t fblk = (n + GSR_FPFH_BLOCK - 1u) / GSR_FPFH_BLOCK;
-  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
   float4* nrm = (float4*)(ws + L.nrm);
   float* bound = radius_only ? nullptr : (float*)(ws + L.bound);
   int32_t* spfh = (int32_t*)(ws + L.spfh);
@@ -659,29 +602,21 @@ int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float
   const float r2 = radius * radius;      // the float32 square (+inf stays, and a large radius may become, +inf)
   if (!radius_only) {
     const int k = (int)max_nn - 1;
-#define FPFH_BOUND_K(K)                                                                                                     \
-  GSR_LAUNCH("fpfh_bound_k" #K, k_fpfh_bound<K>, dim3(nblk), dim3(256), 0, st, n, k, r2, (const float4*)b.pts,              \
-             (const float4*)b.box_lo, (const float4*)b.box_hi, nbox, (const float4*)b.sup_lo, (const float4*)b.sup_hi, nsuper, \
-             bound)
-    if (k <= 4) FPFH_BOUND_K(4);
-    else if (k <= 8) FPFH_BOUND_K(8);
-    else if (k <= 16) FPFH_BOUND_K(16);
-    else FPFH_BOUND_K(32);
+#define FPFH_BOUND_K(K) GSR_LAUNCH("fpfh_bound_k" #K, k_fpfh_bound<K>, dim3(nblk), dim3(256), 0, st, t, k, r2, bound)
+    GSR_KNN_PICK_K(k, FPFH_BOUND_K);
 #undef FPFH_BOUND_K
   }
-  GSR_LAUNCH("fpfh_spfh", k_fpfh_spfh, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, n, r2, (const float*)bound, (const float4*)b.pts,
-             (const float4*)nrm, (const float4*)b.box_lo, (const float4*)b.box_hi, nbox, (const float4*)b.sup_lo,
-             (const float4*)b.sup_hi, nsuper, spfh, m_of, spfh_counts, count_out);
-  GSR_LAUNCH("fpfh_sum", k_fpfh_sum, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, n, r2, (const float*)bound, (const float4*)b.pts,
-             (const float4*)b.box_lo, (const float4*)b.box_hi, nbox, (const float4*)b.sup_lo, (const float4*)b.sup_hi, nsuper,
-             (const int32_t*)spfh, (const int32_t*)m_of, fpfh);
+  GSR_LAUNCH("fpfh_spfh", k_fpfh_spfh, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, t.P, r2, (const float*)bound, t.pts,
+             (const float4*)nrm, t.box_lo, t.box_hi, t.nbox, t.sup_lo, t.sup_hi, t.nsuper, spfh, m_of, spfh_counts, count_out);
+  GSR_LAUNCH("fpfh_sum", k_fpfh_sum, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, t, r2, (const float*)bound, (const int32_t*)spfh,
+             (const int32_t*)m_of, fpfh);
   return gsr_launch_status("compute_fpfh launch");
 }
 
 size_t gsr_feature_nn_workspace_bytes(int64_t Nq) { return gsr_align((size_t)(Nq < 1 ? 1 : Nq) * 8); }
 
 int32_t gsr_feature_nn_tiles_per_split(int64_t Nq, int64_t Nt) {
-  if (feat_bad_size(Nq) || feat_bad_size(Nt)) return 0;
+  if (gsr_bad_size(Nq) || gsr_bad_size(Nt)) return 0;
   const uint64_t qblk = ((uint64_t)Nq + GSR_FEAT_BLOCK - 1) / GSR_FEAT_BLOCK, ntiles = ((uint64_t)Nt + GSR_FEAT_TILE - 1) / GSR_FEAT_TILE;
   uint64_t splits = (GSR_FEAT_WGS + qblk - 1) / qblk;
   if (splits > ntiles) splits = ntiles;
@@ -691,7 +626,7 @@ int32_t gsr_feature_nn_tiles_per_split(int64_t Nq, int64_t Nt) {
 
 int gsr_feature_nn(int64_t Nq, const float* query, int64_t Nt, const float* target, int32_t width, int32_t* idx_out,
                    float* dist2_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (feat_bad_size(Nq) || feat_bad_size(Nt) || !query || !target || !idx_out || !workspace || width != GSR_FPFH_BINS) {
+  if (gsr_bad_size(Nq) || gsr_bad_size(Nt) || !query || !target || !idx_out || !workspace || width != GSR_FPFH_BINS) {
     gsr_set_error("feature_nn: bad arguments (Nq = %lld, Nt = %lld, width = %d: expected %d)", (long long)Nq, (long long)Nt,
                   (int)width, GSR_FPFH_BINS);
     return GSR_ERR_INVALID_ARGUMENT;
@@ -723,7 +658,7 @@ int gsr_ransac_feature_matching(int64_t Ps, const float* source, int64_t Pt, con
                                 float max_distance, int32_t ransac_n, float edge_length_threshold, uint64_t seed, int64_t t0,
                                 int64_t n, gsr_ransac_best* best, void* workspace, size_t workspace_bytes,
                                 const gsr_ransac_debug* debug, void* stream) {
-  if (feat_bad_size(Ps) || feat_bad_size(Pt) || feat_bad_size(M) || !source || !target || !pairs || !best || !workspace ||
+  if (gsr_bad_size(Ps) || gsr_bad_size(Pt) || gsr_bad_size(M) || !source || !target || !pairs || !best || !workspace ||
       !(max_distance >= 0.f && max_distance < KNN_INF) || ransac_n < 3 || ransac_n > GSR_RANSAC_N_MAX ||
       !(edge_length_threshold >= 0.f && edge_length_threshold <= 1.f) || t0 < 0 || n < 1 || n > GSR_RANSAC_MAX_TRIALS ||
       t0 > (int64_t)1 << 56) {

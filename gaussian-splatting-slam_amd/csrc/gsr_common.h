@@ -78,6 +78,9 @@ struct GsrImgLayout {
   size_t total;
 };
 
+// a row count the point-cloud entry points take: 1 .. 2^30 - 1
+static inline bool gsr_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
+
 static inline __host__ __device__ size_t gsr_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline __host__ __device__ size_t gsr_igrad_bytes(size_t cap) { return gsr_align((cap < 1 ? 1 : cap) * 16 * 3); }
 // the validity flags of the gradient records (see GSR_IGRAD_F4): right behind the `cap` records
@@ -302,6 +305,31 @@ void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float
 // -------------------------------------------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int gsr_lane() { return threadIdx.x & 63; }
+
+#define KNN_INF __builtin_huge_valf()
+__device__ __forceinline__ bool knn_finite(float x) { return fabsf(x) < KNN_INF; }   // false for NaN and +-inf
+
+// float64 sums in one fixed order (no float atomics): a butterfly over the wave - the same total in every lane, a + b == b + a
+// bit for bit - then for N per-thread values of a 256-thread workgroup lane 0 of each wave through LDS and the four wave sums in
+// order.  The result is valid in thread 0.  (A kernel that calls it again puts a __syncthreads() in between: one LDS array.)
+__device__ __forceinline__ double gsr_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int N>
+__device__ __forceinline__ void gsr_block_sum(double (&s)[N]) {
+  __shared__ double sh[4][N];
+#pragma unroll
+  for (int a = 0; a < N; a++) s[a] = gsr_wave_sum(s[a]);
+  if (gsr_lane() == 0) {
+#pragma unroll
+    for (int a = 0; a < N; a++) sh[threadIdx.x >> 6][a] = s[a];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < N; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
+}
 
 // Number of instances the binning / compositing stages work on: min(num_rendered, capacity).  num_rendered lives on the
 // DEVICE (geometry state `meta[2..3]`, 64-bit, written by k_sum_tiles); `cap` is what the caller's binning state was sized

@@ -9,14 +9,12 @@
 //      points (one wave builds one box: its AABB by cross-lane min / max) and SUPER-BOXES of GSR_KNN_SUPER = 64 consecutive
 //      boxes (4096 points);
 //   4. one thread per query, queries in Morton order so that the lanes of a wave accept the same boxes: an upper bound of the
-//      third-nearest distance from the six neighbours in Morton order, then a sweep over ALL super-boxes (their AABBs staged
-//      through LDS, 256 at a time), descending into the boxes of a super-box and the points of a box only where the AABB
-//      distance does not exceed min(bound, current third best).
-//   The structure only prunes.  A box is skipped when its AABB distance is GREATER than the threshold, and that distance is formed
-//   with the same rounding sequence as a point distance (differences, then fma(dz,dz, fma(dy,dy, dx*dx))): rounding is monotone,
-//   so the fp32 AABB distance never exceeds the fp32 distance of a point inside - no neighbour can be lost to rounding.  The answer
-//   of a query is the three smallest values of a multiset that does not depend on the traversal: two runs, and runs with a
-//   different first_query, give the same bits.
+//      third-nearest distance from the six neighbours in Morton order, then knn_sweep (knn_common.h: ALL super-boxes, their
+//      AABBs staged through LDS 256 at a time, descending only where the AABB distance does not exceed the radius) with the
+//      radius min(bound, current third best).
+//   The structure only prunes (the rounding argument stands next to knn_sweep).  The answer of a query is the three smallest
+//   values of a multiset that does not depend on the traversal: two runs, and runs with a different first_query, give the same
+//   bits.
 //   Box size: 64 = one wave builds a box, and a leaf visit is 64 distance evaluations against a box test of about the same cost
 //   as two of them; with 64 x 64 the sweep at 5 M points is 1.2 k super-box tests per query (a single level of 64-point boxes
 //   would be 78 k).  Distances are (a-b).(a-b) from differences: scenes sit far from the origin.
@@ -26,8 +24,9 @@
 //   `<` comparison: no hang, no out-of-bounds access, unspecified values for those rows.
 //
 // gsr_knn_k: the same search for k = 1 .. 32 neighbours - every squared distance in ascending order and / or the mean of their
-//   square roots (what a statistical outlier filter thresholds; csrc/pointcloud.hip).  The per-thread list is knn_insert
-//   generalised: a fully unrolled compare-exchange chain over a compile-time size K in {4, 8, 16, 32}, the smallest that holds k.
+//   square roots (what a statistical outlier filter thresholds; csrc/pointcloud.hip): knn_topk_bound (knn_common.h) without a
+//   cut.  The per-thread list is knn_insert generalised: a fully unrolled compare-exchange chain over a compile-time size K in
+//   {4, 8, 16, 32}, the smallest that holds k (GSR_KNN_PICK_K).
 //   The K - k slots that are not needed start at -inf and stay at the head of the list, so list[K - 1] is the k-th smallest
 //   candidate - the same pruning threshold a list of exactly k entries would give - and no register is ever indexed at run time.
 //
@@ -35,39 +34,23 @@
 //   what the map's render of the same view does not explain, compacted in row-major pixel order by a prefix sum.
 #include "knn_common.h"
 
+// the workspace of gsr_knn_dist2 and gsr_knn_k: the structure's blob (knn_common.h), then what a subset of queries needs
 struct GsrKnnLayout {
-  size_t bbox_part;   // float[GSR_KNN_BBOX_BLOCKS][6]
-  size_t bbox;        // float[8]: min xyz, max xyz
-  size_t key_a, key_b, val_a, val_b;   // u32[P] each: Morton codes / point indices, ping-pong
-  size_t pts;         // float4[P]: sorted points (x, y, z, bits of the original index)
-  size_t box_lo, box_hi;   // float4[nbox]
-  size_t sup_lo, sup_hi;   // float4[nsuper]
+  GsrNnLayout nn;
   size_t qflag, qpos, qlist;   // u32[P] each: first_query > 0 only - query flags in sorted order, their scan, the compacted list
   size_t scan_tmp;
-  size_t radix_tmp;
   size_t total;
 };
 
 static inline GsrKnnLayout knn_layout(size_t P) {
   GsrKnnLayout L;
-  size_t o = 0;
   if (P == 0) P = 1;
-  L.bbox_part = o; o += gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4);
-  L.bbox = o;      o += 256;
-  L.key_a = o;     o += gsr_align(P * 4);
-  L.key_b = o;     o += gsr_align(P * 4);
-  L.val_a = o;     o += gsr_align(P * 4);
-  L.val_b = o;     o += gsr_align(P * 4);
-  L.pts = o;       o += gsr_align(P * 16);
-  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
-  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
+  L.nn = nn_layout(P);
+  size_t o = L.nn.total;
   L.qflag = o;     o += gsr_align(P * 4);
   L.qpos = o;      o += gsr_align(P * 4);
   L.qlist = o;     o += gsr_align(P * 4);
   L.scan_tmp = o;  o += gsr_align(gsr_scan_tmp_elems(P) * 4);
-  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
   L.total = o;
   return L;
 }
@@ -195,46 +178,29 @@ __device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float&
   }
 }
 
-__global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, const uint32_t* __restrict__ qlist,
-                                                   const float4* __restrict__ pts, const float4* __restrict__ box_lo,
-                                                   const float4* __restrict__ box_hi, uint32_t nbox,
-                                                   const float4* __restrict__ sup_lo, const float4* __restrict__ sup_hi,
-                                                   uint32_t nsuper, uint32_t first_query, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_knn_query(GsrKnnTree t, uint32_t nq, const uint32_t* __restrict__ qlist,
+                                                   uint32_t first_query, float* __restrict__ out) {
   __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t P = t.P;
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   const bool active = q < nq;
   const uint32_t pos = active ? (qlist ? qlist[q] : q) : 0u;
-  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  const float4 me = t.pts[pos];          // (pos < P always: P >= 1)
   float b0 = KNN_INF, b1 = KNN_INF, b2 = KNN_INF;
   if (active) {
     const uint32_t j0 = pos >= 3u ? pos - 3u : 0u, j1 = min(P - 1u, pos + 3u);
     for (uint32_t j = j0; j <= j1; j++)
-      if (j != pos) knn_insert(knn_point_d2(me, pts[j]), b0, b1, b2);
+      if (j != pos) knn_insert(knn_point_d2(me, t.pts[j]), b0, b1, b2);
   }
   // an upper bound of the third-nearest distance (inf with fewer than three candidates); the sweep starts from an empty
   // list again, so no candidate is counted twice
   const float bound = b2;
   b0 = b1 = b2 = KNN_INF;
-  for (uint32_t base = 0; base < nsuper; base += 256u) {
-    __syncthreads();
-    if (base + threadIdx.x < nsuper) {
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-    }
-    __syncthreads();
-    if (!active) continue;
-    const uint32_t n = min(256u, nsuper - base);
-    for (uint32_t s = 0; s < n; s++) {
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b2, bound))) continue;
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-      for (uint32_t b = bb; b < be; b++) {
-        if (!(knn_box_d2(me, box_lo[b], box_hi[b]) <= fminf(b2, bound))) continue;
-        const uint32_t jb = b * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
-        for (uint32_t j = jb; j < je; j++)
-          if (j != pos) knn_insert(knn_point_d2(me, pts[j]), b0, b1, b2);
-      }
-    }
-  }
+  knn_sweep<256>(
+      t, me, active, s_lo, s_hi, [&]() __attribute__((always_inline)) { return fminf(b2, bound); },
+      [&](const uint32_t j, const float4 p) __attribute__((always_inline)) {
+        if (j != pos) knn_insert(knn_point_d2(me, p), b0, b1, b2);
+      });
   if (active) {
     float r;
     if (P >= 4u) r = __fdiv_rn(__fadd_rn(__fadd_rn(b0, b1), b2), 3.0f);
@@ -246,51 +212,18 @@ __global__ __launch_bounds__(256) void k_knn_query(uint32_t P, uint32_t nq, cons
 }
 
 // ---- k = 1 .. 32 ------------------------------------------------------------------------------------------------------------
-// (knn_insert_k / knn_reset_k, the per-thread list over K slots: knn_common.h - normals.hip runs the same sweep)
 // one thread per query, as k_knn_query (every row is a query); dist2 [P,k] and / or mean [P] in ORIGINAL row order
 template <int K>
-__global__ __launch_bounds__(256) void k_knn_query_k(uint32_t P, int k, const float4* __restrict__ pts,
-                                                     const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
-                                                     uint32_t nbox, const float4* __restrict__ sup_lo,
-                                                     const float4* __restrict__ sup_hi, uint32_t nsuper,
-                                                     float* __restrict__ dist2, float* __restrict__ mean) {
+__global__ __launch_bounds__(256) void k_knn_query_k(GsrKnnTree t, int k, float* __restrict__ dist2, float* __restrict__ mean) {
   __shared__ float4 s_lo[256], s_hi[256];
+  const uint32_t P = t.P;
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   const bool active = q < P;
   const uint32_t pos = active ? q : 0u;
-  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  const float4 me = t.pts[pos];          // (pos < P always: P >= 1)
   const int pad = K - k;
   float b[K];
-  knn_reset_k<K>(b, pad);
-  if (active) {
-    const uint32_t kk = (uint32_t)k;
-    const uint32_t j0 = pos >= kk ? pos - kk : 0u, j1 = min(P - 1u, pos + kk);
-    for (uint32_t j = j0; j <= j1; j++)
-      if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-  }
-  // an upper bound of the k-th nearest distance (inf with fewer than k candidates); the sweep starts from an empty list again
-  const float bound = b[K - 1];
-  knn_reset_k<K>(b, pad);
-  for (uint32_t base = 0; base < nsuper; base += 256u) {
-    __syncthreads();
-    if (base + threadIdx.x < nsuper) {
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-    }
-    __syncthreads();
-    if (!active) continue;
-    const uint32_t n = min(256u, nsuper - base);
-    for (uint32_t s = 0; s < n; s++) {
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b[K - 1], bound))) continue;
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-      for (uint32_t bx = bb; bx < be; bx++) {
-        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= fminf(b[K - 1], bound))) continue;
-        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
-        for (uint32_t j = jb; j < je; j++)
-          if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-      }
-    }
-  }
+  knn_topk_bound<K, 256>(t, me, pos, active, k, KNN_INF, s_lo, s_hi, b);      // (no cut: the whole list is the answer)
   if (!active) return;
   const size_t row = (size_t)__float_as_uint(me.w);
   // a row with a non-finite coordinate has no neighbours: +inf distances, NaN mean (gsr_statistical_outliers drops it on that)
@@ -422,42 +355,26 @@ void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipS
 }
 size_t gsr_knn_bbox_part_bytes() { return gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4); }
 
-// the structure over a cloud (knn_common.h): what every search here starts with
-void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st) {
+// the structure over a cloud (knn_common.h): what every search starts with
+void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st, uint32_t first_query, uint32_t* qflag) {
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u, nbox = (uint32_t)knn_nbox(n);
   gsr_knn_bbox(P, points, b.bbox_part, b.bbox, st);
   GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)b.bbox, b.key[0]);
   const int where = gsr_radix_sort_pairs(b.key[0], b.val[0], b.key[1], b.val[1], true, (size_t)n, 30, b.radix_tmp, st);
   GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)b.val[where], b.pts, b.box_lo,
-             b.box_hi, 0u, (uint32_t*)nullptr);
+             b.box_hi, first_query, qflag);
   GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)b.box_lo,
              (const float4*)b.box_hi, b.sup_lo, b.sup_hi);
 }
 
 // the launches of gsr_knn_k, arguments already checked (also the first stage of gsr_statistical_outliers, csrc/pointcloud.hip)
 void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st) {
-  const GsrKnnLayout L = knn_layout((size_t)P);
-  char* ws = (char*)workspace;
-  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
-  float4* pts = (float4*)(ws + L.pts);
-  float4 *box_lo = (float4*)(ws + L.box_lo), *box_hi = (float4*)(ws + L.box_hi);
-  float4 *sup_lo = (float4*)(ws + L.sup_lo), *sup_hi = (float4*)(ws + L.sup_hi);
-  GsrKnnBuild b;
-  b.bbox_part = (float*)(ws + L.bbox_part);
-  b.bbox = (float*)(ws + L.bbox);
-  b.key[0] = (uint32_t*)(ws + L.key_a); b.key[1] = (uint32_t*)(ws + L.key_b);
-  b.val[0] = (uint32_t*)(ws + L.val_a); b.val[1] = (uint32_t*)(ws + L.val_b);
-  b.radix_tmp = (uint32_t*)(ws + L.radix_tmp);
-  b.pts = pts; b.box_lo = box_lo; b.box_hi = box_hi; b.sup_lo = sup_lo; b.sup_hi = sup_hi;
+  const GsrKnnBuild b = nn_build_views((char*)workspace, knn_layout((size_t)P).nn);
   gsr_knn_build(P, points, b, st);
-#define KNN_QUERY_K(K)                                                                                                          \
-  GSR_LAUNCH("knn_query_k" #K, k_knn_query_k<K>, dim3(nblk), dim3(256), 0, st, n, k, (const float4*)pts, (const float4*)box_lo, \
-             (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, dist2, mean)
-  if (k <= 4) KNN_QUERY_K(4);
-  else if (k <= 8) KNN_QUERY_K(8);
-  else if (k <= 16) KNN_QUERY_K(16);
-  else KNN_QUERY_K(32);
+  const GsrKnnTree t = knn_tree(b, (size_t)P);
+  const uint32_t nblk = (t.P + 255u) / 256u;
+#define KNN_QUERY_K(K) GSR_LAUNCH("knn_query_k" #K, k_knn_query_k<K>, dim3(nblk), dim3(256), 0, st, t, k, dist2, mean)
+  GSR_KNN_PICK_K(k, KNN_QUERY_K);
 #undef KNN_QUERY_K
 }
 
@@ -467,7 +384,7 @@ size_t gsr_knn_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1
 
 int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* mean_dist2, void* workspace,
                   size_t workspace_bytes, void* stream) {
-  if (P <= 0 || P > 0x3FFFFFFF || !points || !mean_dist2 || !workspace || first_query < 0 || first_query >= P) {
+  if (gsr_bad_size(P) || !points || !mean_dist2 || !workspace || first_query < 0 || first_query >= P) {
     gsr_set_error("knn_dist2: bad arguments (P = %lld, first_query = %lld)", (long long)P, (long long)first_query);
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -478,33 +395,19 @@ int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* me
   }
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
+  const GsrKnnBuild b = nn_build_views(ws, L.nn);
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
-  float* part = (float*)(ws + L.bbox_part);
-  float* bbox = (float*)(ws + L.bbox);
-  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
-  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
-  float4* pts = (float4*)(ws + L.pts);
-  float4 *box_lo = (float4*)(ws + L.box_lo), *box_hi = (float4*)(ws + L.box_hi);
-  float4 *sup_lo = (float4*)(ws + L.sup_lo), *sup_hi = (float4*)(ws + L.sup_hi);
   uint32_t *qflag = (uint32_t*)(ws + L.qflag), *qpos = (uint32_t*)(ws + L.qpos), *qlist = (uint32_t*)(ws + L.qlist);
   const bool subset = first_query > 0;
 
-  gsr_knn_bbox(P, points, part, bbox, st);
-  GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, key[0]);
-  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
-  GSR_LAUNCH("knn_boxes", k_knn_boxes, dim3(nblk), dim3(256), 0, st, n, points, (const uint32_t*)val[where], pts, box_lo, box_hi,
-             (uint32_t)first_query, subset ? qflag : (uint32_t*)nullptr);
-  GSR_LAUNCH("knn_supers", k_knn_supers, dim3((nbox + 255u) / 256u), dim3(256), 0, st, nbox, (const float4*)box_lo,
-             (const float4*)box_hi, sup_lo, sup_hi);
+  gsr_knn_build(P, points, b, st, (uint32_t)first_query, subset ? qflag : nullptr);
   const uint32_t nq = (uint32_t)(P - first_query);
   if (subset) {
     gsr_scan_u32(qflag, nullptr, qpos, (size_t)n, 0, (uint32_t*)(ws + L.scan_tmp), st);
     GSR_LAUNCH("knn_compact", k_knn_compact, dim3(nblk), dim3(256), 0, st, n, (const uint32_t*)qflag, (const uint32_t*)qpos, qlist);
   }
-  GSR_LAUNCH("knn_query", k_knn_query, dim3((nq + 255u) / 256u), dim3(256), 0, st, n, nq,
-             subset ? (const uint32_t*)qlist : (const uint32_t*)nullptr, (const float4*)pts, (const float4*)box_lo,
-             (const float4*)box_hi, nbox, (const float4*)sup_lo, (const float4*)sup_hi, nsuper, (uint32_t)first_query, mean_dist2);
+  GSR_LAUNCH("knn_query", k_knn_query, dim3((nq + 255u) / 256u), dim3(256), 0, st, knn_tree(b, (size_t)P), nq,
+             subset ? (const uint32_t*)qlist : (const uint32_t*)nullptr, (uint32_t)first_query, mean_dist2);
   return gsr_launch_status("knn_dist2 launch");
 }
 
@@ -512,7 +415,7 @@ size_t gsr_knn_k_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ?
 
 int gsr_knn_k(int64_t P, const float* points, int32_t k, float* dist2_out, float* mean_dist_out, void* workspace,
               size_t workspace_bytes, void* stream) {
-  if (P <= 0 || P > 0x3FFFFFFF || !points || !workspace || k < 1 || k > GSR_KNN_K_MAX || (!dist2_out && !mean_dist_out)) {
+  if (gsr_bad_size(P) || !points || !workspace || k < 1 || k > GSR_KNN_K_MAX || (!dist2_out && !mean_dist_out)) {
     gsr_set_error("knn_k: bad arguments (P = %lld, k = %d: expected 1 .. %d and at least one output)", (long long)P, (int)k,
                   GSR_KNN_K_MAX);
     return GSR_ERR_INVALID_ARGUMENT;

@@ -4,16 +4,14 @@
 //
 // gsr_estimate_normals: the structure of knn.hip (knn_common.h) over the cloud, rows with a non-finite coordinate turned into
 //   NaN NaN NaN (every distance to them is NaN and fails every comparison: nobody's neighbour), then ONE launch, one thread per
-//   query in Morton order, two sweeps over the same boxes:
-//   1. the bound.  k = max_nn - 1 (max_nn counts the point itself).  The register top-K sweep of k_knn_query_k, distances only,
-//      seeded by the Morton window, gives d_k, the k-th smallest d2 to the other finite rows (+inf with fewer than k).  Only
-//      min(r2, d_k) is needed, so the sweep also prunes at r2: with d_k <= r2 all k smallest values lie below r2 and are seen;
-//      otherwise the list's last slot holds something above r2 or +inf, and the minimum is r2 either way.
-//   2. the sums.  bound = min(r2, d_k) is now a FIXED pruning radius (it prunes from the first box).  Every row j != i with
-//      d2(i,j) <= bound is a member - rows tied at the bound all are, so no row tie-break is needed and no neighbour index is ever
-//      stored.  delta = p_j - p_i per component in float32 (__fsub_rn), promoted; S1 = sum delta and S2 = sum delta delta^T (six
-//      values) in float64, in sorted-position order: fixed for a given input, so two runs give the same bits.  The point itself
-//      contributes delta = 0 and counts: n = 1 + members.
+//   query in Morton order, two sweeps (knn_sweep, knn_common.h) over the same boxes and one LDS allocation:
+//   1. the bound.  k = max_nn - 1 (max_nn counts the point itself).  knn_topk_bound, cut at r2, gives min(r2, d_k), d_k the k-th
+//      smallest d2 to the other finite rows (+inf with fewer than k).
+//   2. the sums.  bound = min(r2, d_k) is now a FIXED pruning radius (it prunes from the first box).  knn_member_walk: every
+//      row j != i with d2(i,j) <= bound is a member - rows tied at the bound all are, so no row tie-break is needed and no
+//      neighbour index is ever stored.  delta = p_j - p_i per component in float32 (__fsub_rn), promoted; S1 = sum delta and S2
+//      = sum delta delta^T (six values) in float64, in sorted-position order: fixed for a given input, so two runs give the
+//      same bits.  The point itself contributes delta = 0 and counts: n = 1 + members.
 //   Then C = S2 / n - (S1 / n)(S1 / n)^T and cyclic Jacobi on the symmetric 3 x 3 in float64, a fixed number of sweeps, every
 //   index a compile-time constant (registers, no scratch); eigenvalues ascending; the normal is the eigenvector of the smallest,
 //   normalised again in float64 and rounded to float32 once.  Sign: towards the viewpoint (n.(v - p) >= 0), or without one the
@@ -57,85 +55,31 @@ struct GsrNormalsView {
 };
 
 template <int K>
-__global__ __launch_bounds__(256) void k_normals(uint32_t P, int k, float r2, GsrNormalsView view, const float4* __restrict__ pts,
-                                                 const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
-                                                 uint32_t nbox, const float4* __restrict__ sup_lo,
-                                                 const float4* __restrict__ sup_hi, uint32_t nsuper, float* __restrict__ normals,
+__global__ __launch_bounds__(256) void k_normals(GsrKnnTree t, int k, float r2, GsrNormalsView view, float* __restrict__ normals,
                                                  int32_t* __restrict__ count_out, float* __restrict__ eig_out) {
   __shared__ float4 s_lo[256], s_hi[256];
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  const bool active = q < P;
+  const bool active = q < t.P;
   const uint32_t pos = active ? q : 0u;
-  const float4 me = pts[pos];          // (pos < P always: P >= 1)
+  const float4 me = t.pts[pos];          // (pos < P always: P >= 1)
   // ---- sweep 1: min(r2, d_k) ----
   float bound;
   {
-    const int pad = K - k;
     float b[K];
-    knn_reset_k<K>(b, pad);
-    if (active) {
-      const uint32_t kk = (uint32_t)k;
-      const uint32_t j0 = pos >= kk ? pos - kk : 0u, j1 = min(P - 1u, pos + kk);
-      for (uint32_t j = j0; j <= j1; j++)
-        if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-    }
-    // an upper bound of d_k from the Morton window, cut at r2; the sweep starts from an empty list again
-    const float seed = fminf(b[K - 1], r2);
-    knn_reset_k<K>(b, pad);
-    for (uint32_t base = 0; base < nsuper; base += 256u) {
-      __syncthreads();
-      if (base + threadIdx.x < nsuper) {
-        s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-        s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-      }
-      __syncthreads();
-      if (!active) continue;
-      const uint32_t n = min(256u, nsuper - base);
-      for (uint32_t s = 0; s < n; s++) {
-        if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= fminf(b[K - 1], seed))) continue;
-        const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-        for (uint32_t bx = bb; bx < be; bx++) {
-          if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= fminf(b[K - 1], seed))) continue;
-          const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
-          for (uint32_t j = jb; j < je; j++)
-            if (j != pos) knn_insert_k<K>(knn_point_d2(me, pts[j]), b);
-        }
-      }
-    }
-    bound = fminf(b[K - 1], r2);
+    bound = knn_topk_bound<K, 256>(t, me, pos, active, k, r2, s_lo, s_hi, b);
   }
   // ---- sweep 2: the sums over { j != i : d2 <= bound } ----
   double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
   uint32_t members = 0u;
-  for (uint32_t base = 0; base < nsuper; base += 256u) {
-    __syncthreads();
-    if (base + threadIdx.x < nsuper) {
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-    }
-    __syncthreads();
-    if (!active) continue;
-    const uint32_t n = min(256u, nsuper - base);
-    for (uint32_t s = 0; s < n; s++) {
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= bound)) continue;
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-      for (uint32_t bx = bb; bx < be; bx++) {
-        if (!(knn_box_d2(me, box_lo[bx], box_hi[bx]) <= bound)) continue;
-        const uint32_t jb = bx * (uint32_t)GSR_KNN_BOX, je = min(P, jb + (uint32_t)GSR_KNN_BOX);
-        for (uint32_t j = jb; j < je; j++) {
-          const float4 p = pts[j];
-          const float fx = __fsub_rn(me.x, p.x), fy = __fsub_rn(me.y, p.y), fz = __fsub_rn(me.z, p.z);
-          if (j == pos || !(knn_sq(fx, fy, fz) <= bound)) continue;      // (NaN: not a member)
-          // delta = p_j - p_i = -(p_i - p_j), exactly
-          const double dx = -(double)fx, dy = -(double)fy, dz = -(double)fz;
-          members++;
-          s1x += dx; s1y += dy; s1z += dz;
-          sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
-          syy += dy * dy; syz += dy * dz; szz += dz * dz;
-        }
-      }
-    }
-  }
+  knn_member_walk<256>(t, me, pos, active, bound, s_lo, s_hi,
+                       [&](const uint32_t, const float fx, const float fy, const float fz) __attribute__((always_inline)) {
+                         // delta = p_j - p_i = -(p_i - p_j), exactly
+                         const double dx = -(double)fx, dy = -(double)fy, dz = -(double)fz;
+                         members++;
+                         s1x += dx; s1y += dy; s1z += dz;
+                         sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
+                         syy += dy * dy; syz += dy * dz; szz += dz * dz;
+                       });
   if (!active) return;
   const size_t row = (size_t)__float_as_uint(me.w);
   const bool finite = knn_finite(me.x) && knn_finite(me.y) && knn_finite(me.z);
@@ -195,7 +139,7 @@ size_t gsr_normals_workspace_bytes(int64_t P) { return nn_layout((size_t)(P < 1 
 
 int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t max_nn, const float* viewpoint, float* normals,
                          int32_t* count_out, float* eigenvalues_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (P <= 0 || P > 0x3FFFFFFF || !points || !normals || !workspace || max_nn < 3 || max_nn > GSR_KNN_K_MAX + 1 ||
+  if (gsr_bad_size(P) || !points || !normals || !workspace || max_nn < 3 || max_nn > GSR_KNN_K_MAX + 1 ||
       !(radius > 0.f) ||
       (viewpoint && !(fabsf(viewpoint[0]) < KNN_INF && fabsf(viewpoint[1]) < KNN_INF && fabsf(viewpoint[2]) < KNN_INF))) {
     gsr_set_error("estimate_normals: bad arguments (P = %lld, radius = %g: expected > 0, max_nn = %d: expected 3 .. %d, a finite "
@@ -211,9 +155,9 @@ int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t m
   char* ws = (char*)workspace;
   const GsrKnnBuild b = nn_build_views(ws, L);
   gsr_knn_build(P, points, b, st);
-  const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  const uint32_t nbox = (uint32_t)knn_nbox(n), nsuper = (uint32_t)knn_nsuper(n);
-  GSR_LAUNCH("normals_mask", k_normals_mask, dim3(nblk), dim3(256), 0, st, n, b.pts);
+  const GsrKnnTree t = knn_tree(b, (size_t)P);
+  const uint32_t nblk = (t.P + 255u) / 256u;
+  GSR_LAUNCH("normals_mask", k_normals_mask, dim3(nblk), dim3(256), 0, st, t.P, b.pts);
   const float r2 = radius * radius;      // the float32 square (+inf stays, and a large radius may become, +inf)
   GsrNormalsView view;
   view.on = viewpoint ? 1 : 0;
@@ -221,14 +165,9 @@ int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t m
   view.y = viewpoint ? viewpoint[1] : 0.f;
   view.z = viewpoint ? viewpoint[2] : 0.f;
   const int k = (int)max_nn - 1;
-#define NORMALS_K(K)                                                                                                          \
-  GSR_LAUNCH("normals_k" #K, k_normals<K>, dim3(nblk), dim3(256), 0, st, n, k, r2, view, (const float4*)b.pts,                \
-             (const float4*)b.box_lo, (const float4*)b.box_hi, nbox, (const float4*)b.sup_lo, (const float4*)b.sup_hi, nsuper, \
-             normals, count_out, eigenvalues_out)
-  if (k <= 4) NORMALS_K(4);
-  else if (k <= 8) NORMALS_K(8);
-  else if (k <= 16) NORMALS_K(16);
-  else NORMALS_K(32);
+#define NORMALS_K(K) \
+  GSR_LAUNCH("normals_k" #K, k_normals<K>, dim3(nblk), dim3(256), 0, st, t, k, r2, view, normals, count_out, eigenvalues_out)
+  GSR_KNN_PICK_K(k, NORMALS_K);
 #undef NORMALS_K
   return gsr_launch_status("estimate_normals launch");
 }

@@ -11,10 +11,11 @@
 //      a linearised key "where the extent fits" would cost a read-back to choose it; three sorts of 21-bit keys never need one;
 //   4. head flags (first row of a run of equal cell words), gsr_scan_u32 -> voxel ids, run starts;
 //   5. segmented reduction split by run length, as k_tile_depth_sort splits by list length: a run of <= GSR_VOXEL_SHORT rows is
-//      summed by one thread; a longer one is appended to a list (integer atomic: the list's order changes nothing that is stored)
-//      and summed by a whole workgroup - thread t takes rows t, t + 256, ..., then a fixed butterfly over the wave and the four
-//      wave sums in order.  Sums in float64, mean in float64, rounded to float32 once.  Which path a run takes and the order of
-//      its additions depend on its sorted rows only: two runs give the same bits.
+//      summed by one thread; a longer one is appended to a list (integer atomic: the list's order changes nothing that is
+//      stored) and summed by a whole workgroup - thread t takes rows t, t + 256, ..., then gsr_block_sum (gsr_common.h: a fixed
+//      butterfly over the wave and the four wave sums in order).  Sums in float64, mean in float64, rounded to float32
+//      once.  Which path a run takes and the order of its additions depend on its sorted rows only: two runs give the same
+//      bits.
 //
 // gsr_statistical_outliers: mean distance to the nb - 1 nearest neighbours (gsr_knn_k_launch), its mean and standard deviation
 //   over the finite rows in float64 (fixed slices per workgroup, one final workgroup - the pattern of gsr_l1_mean_*), two passes
@@ -26,9 +27,6 @@
 #define GSR_VOXEL_DROPPED 0xFFFFFFFFFFFFFFFFull
 #define GSR_VOXEL_LONG_BLOCKS 1024
 #define GSR_STAT_BLOCKS 256
-
-#define PC_INF __builtin_huge_valf()
-__device__ __forceinline__ bool pc_finite(float x) { return fabsf(x) < PC_INF; }
 
 struct GsrVoxelLayout {
   size_t bbox_part, bbox;
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(256) void k_voxel_cell(uint32_t P, const float* __r
     const float p = pts[3 * (size_t)i + a];
     const float o = g.has_origin ? g.origin[a] : __fsub_rn(bbox[a], __fmul_rn(0.5f, g.voxel));
     const float f = floorf(__fdiv_rn(__fsub_rn(p, o), g.voxel));
-    if (!pc_finite(p)) keep = false;
+    if (!knn_finite(p)) keep = false;
     else if (!(f >= -(float)GSR_VOXEL_BIAS && f < (float)GSR_VOXEL_BIAS)) range = false;      // (a NaN index too)
     else c |= (unsigned long long)(uint32_t)((int)f + GSR_VOXEL_BIAS) << (21 * a);
   }
@@ -170,18 +168,11 @@ __global__ __launch_bounds__(256) void k_voxel_reduce_short(uint32_t P, const in
   voxel_store(out, v, s, len);
 }
 
-__device__ __forceinline__ double pc_wave_sum(double v) {      // the same total in every lane (a + b == b + a bit for bit)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one workgroup per listed voxel
 __global__ __launch_bounds__(256) void k_voxel_reduce_long(const uint32_t* __restrict__ meta, const uint32_t* __restrict__ longlist,
                                                            const uint32_t* __restrict__ start, const uint32_t* __restrict__ perm,
                                                            const float* __restrict__ pts, const float* __restrict__ cols,
                                                            GsrVoxelOut out) {
-  __shared__ double sh[4][6];
   const uint32_t nlong = meta[0];
   for (uint32_t li = blockIdx.x; li < nlong; li += gridDim.x) {      // (uniform over the workgroup)
     const uint32_t v = longlist[li];
@@ -196,19 +187,9 @@ __global__ __launch_bounds__(256) void k_voxel_reduce_long(const uint32_t* __res
         for (int a = 0; a < 3; a++) s[3 + a] += (double)cols[3 * i + a];
       }
     }
-#pragma unroll
-    for (int a = 0; a < 6; a++) s[a] = pc_wave_sum(s[a]);
-    if (gsr_lane() == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) sh[threadIdx.x >> 6][a] = s[a];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
-      voxel_store(out, v, s, s1 - s0);
-    }
-    __syncthreads();
+    gsr_block_sum(s);
+    if (threadIdx.x == 0) voxel_store(out, v, s, s1 - s0);
+    __syncthreads();      // (the next round writes the sum's LDS again)
   }
 }
 
@@ -232,42 +213,28 @@ static inline GsrOutlierLayout outlier_layout(size_t P) {
   return L;
 }
 
-// two per-thread values summed over a 256-thread workgroup; the result is valid in thread 0
-__device__ __forceinline__ void pc_block_sum2(double& a, double& b) {
-  __shared__ double sh[4][2];
-  a = pc_wave_sum(a);
-  b = pc_wave_sum(b);
-  if (gsr_lane() == 0) {
-    sh[threadIdx.x >> 6][0] = a;
-    sh[threadIdx.x >> 6][1] = b;
-  }
-  __syncthreads();
-  a = ((sh[0][0] + sh[1][0]) + sh[2][0]) + sh[3][0];
-  b = ((sh[0][1] + sh[1][1]) + sh[2][1]) + sh[3][1];
-}
-
 // MODE 0: (sum of dbar, number of finite dbar) of this workgroup's rows; MODE 1: (sum of (dbar - mu)^2, 0)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_outlier_partial(uint32_t P, const float* __restrict__ dbar,
                                                          const double* __restrict__ stats, double* __restrict__ part) {
   const double mu = MODE == 1 ? stats[1] : 0.0;
-  double s = 0.0, c = 0.0;
+  double s[2] = {0.0, 0.0};      // the sum, the count
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < P; i += gridDim.x * 256u) {
     const float d = dbar[i];
-    if (pc_finite(d)) {
+    if (knn_finite(d)) {
       if (MODE == 0) {
-        s += (double)d;
-        c += 1.0;
+        s[0] += (double)d;
+        s[1] += 1.0;
       } else {
         const double e = __dsub_rn((double)d, mu);
-        s = __dadd_rn(s, __dmul_rn(e, e));
+        s[0] = __dadd_rn(s[0], __dmul_rn(e, e));
       }
     }
   }
-  pc_block_sum2(s, c);
+  gsr_block_sum(s);
   if (threadIdx.x == 0) {
-    part[2 * (size_t)blockIdx.x] = s;
-    part[2 * (size_t)blockIdx.x + 1] = c;
+    part[2 * (size_t)blockIdx.x] = s[0];
+    part[2 * (size_t)blockIdx.x + 1] = s[1];
   }
 }
 
@@ -275,19 +242,19 @@ __global__ __launch_bounds__(256) void k_outlier_partial(uint32_t P, const float
 template <int MODE>
 __global__ __launch_bounds__(256) void k_outlier_final(uint32_t nblk, const double* __restrict__ part, double std_ratio,
                                                        double* __restrict__ stats) {
-  double s = 0.0, c = 0.0;
+  double s[2] = {0.0, 0.0};      // the sum, the count
   for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-    s += part[2 * (size_t)b];
-    c += part[2 * (size_t)b + 1];
+    s[0] += part[2 * (size_t)b];
+    s[1] += part[2 * (size_t)b + 1];
   }
-  pc_block_sum2(s, c);
+  gsr_block_sum(s);
   if (threadIdx.x != 0) return;
   if (MODE == 0) {
-    stats[0] = c;
-    stats[1] = c > 0.0 ? s / c : 0.0;
+    stats[0] = s[1];
+    stats[1] = s[1] > 0.0 ? s[0] / s[1] : 0.0;
   } else {
     const double n = stats[0], mu = stats[1];
-    const double sigma = n >= 2.0 ? sqrt(s / (n - 1.0)) : 0.0;
+    const double sigma = n >= 2.0 ? sqrt(s[0] / (n - 1.0)) : 0.0;
     stats[2] = sigma;
     stats[3] = __dadd_rn(mu, __dmul_rn(std_ratio, sigma));
   }
@@ -308,9 +275,9 @@ size_t gsr_voxel_workspace_bytes(int64_t P) { return voxel_layout((size_t)(P < 1
 int gsr_voxel_down_sample(int64_t P, const float* points, const float* colors, float voxel_size, const float* origin,
                           float* out_points, float* out_colors, int32_t* out_npts, int64_t capacity, int64_t* count_dev,
                           void* workspace, size_t workspace_bytes, void* stream) {
-  const bool origin_ok = !origin || (fabsf(origin[0]) < PC_INF && fabsf(origin[1]) < PC_INF && fabsf(origin[2]) < PC_INF);
-  if (P <= 0 || P > 0x3FFFFFFF || !points || !count_dev || !workspace || capacity < 0 || (capacity > 0 && !out_points) ||
-      (capacity > 0 && colors && !out_colors) || !(voxel_size > 0.f) || !(voxel_size < PC_INF) || !origin_ok) {
+  const bool origin_ok = !origin || (fabsf(origin[0]) < KNN_INF && fabsf(origin[1]) < KNN_INF && fabsf(origin[2]) < KNN_INF);
+  if (gsr_bad_size(P) || !points || !count_dev || !workspace || capacity < 0 || (capacity > 0 && !out_points) ||
+      (capacity > 0 && colors && !out_colors) || !(voxel_size > 0.f) || !(voxel_size < KNN_INF) || !origin_ok) {
     gsr_set_error("voxel_down_sample: bad arguments (P = %lld, voxel_size = %g, capacity = %lld)", (long long)P,
                   (double)voxel_size, (long long)capacity);
     return GSR_ERR_INVALID_ARGUMENT;
@@ -373,8 +340,8 @@ size_t gsr_outlier_workspace_bytes(int64_t P) { return outlier_layout((size_t)(P
 
 int gsr_statistical_outliers(int64_t P, const float* points, int32_t nb_neighbors, double std_ratio, uint8_t* keep,
                              float* mean_dist, double* stats_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  if (P <= 0 || P > 0x3FFFFFFF || !points || !keep || !workspace || nb_neighbors < 2 || nb_neighbors > GSR_KNN_K_MAX + 1 ||
-      !(fabs(std_ratio) < (double)PC_INF)) {
+  if (gsr_bad_size(P) || !points || !keep || !workspace || nb_neighbors < 2 || nb_neighbors > GSR_KNN_K_MAX + 1 ||
+      !(fabs(std_ratio) < (double)KNN_INF)) {
     gsr_set_error("statistical_outliers: bad arguments (P = %lld, nb_neighbors = %d: expected 2 .. %d, std_ratio = %g)",
                   (long long)P, (int)nb_neighbors, GSR_KNN_K_MAX + 1, std_ratio);
     return GSR_ERR_INVALID_ARGUMENT;

@@ -8,19 +8,21 @@
 //   in the same blob.  A row with a non-finite coordinate is stored as NaN NaN NaN: every distance to it is NaN, which fails every
 //   comparison - it is nobody's neighbour.
 //
-// gsr_nn_search: one thread per source row, the sweep of k_knn_query_k (super-box AABBs staged through LDS 256 at a time,
-//   descent where the AABB distance does not exceed the bound).  The query is q = (float)(R s + t), formed by reg_apply below:
-//   float64, every operation rounded separately, one fixed order, rounded to float32 once per component - numpy float64 gives
-//   the same bits.  The answer is the lexicographic minimum of (float32 d2, original target row) over the finite target rows with
-//   d2 <= max_dist2: a multiset minimum, so neither distance nor row depend on the traversal, the order of the source rows or the
-//   `order` permutation.  A box is entered when its AABB distance is <= the bound (not <): a tie with a smaller row is never lost.
+// gsr_nn_search: one thread per source row, knn_sweep of knn_common.h (super-box AABBs staged through LDS 256 at a time,
+//   descent where the AABB distance does not exceed the bound) with the best distance so far as the radius.  The query is q =
+//   (float)(R s + t), formed by reg_apply below: float64, every operation rounded separately, one fixed order, rounded to
+//   float32 once per component - numpy float64 gives the same bits.  The answer is the lexicographic minimum of (float32 d2,
+//   original target row) over the finite target rows with d2 <= max_dist2: a multiset minimum, so neither distance nor row
+//   depend on the traversal, the order of the source rows or the `order` permutation.  A box is entered when its AABB distance
+//   is <= the bound (not <): a tie with a smaller row is never lost.
 //
 // gsr_icp_update: correspondences -> the next transform, nothing on the host.  A first kernel takes the target point of the
 //   first valid row as the shift every sum is formed about (a cloud at +1000 loses nothing); <= 256 workgroups then sum, over
-//   fixed slices, n, |q - p|^2, q, p and q p^T in float64 (fixed butterfly over the wave, the four wave sums in order, no float
-//   atomics); one workgroup adds the partials and one thread solves Horn's closed form: the rotation is the eigenvector of the
-//   largest eigenvalue of the symmetric 4 x 4 matrix built from the centred cross-covariance - a unit quaternion, so a reflection
-//   cannot come out - found by cyclic Jacobi with a fixed number of sweeps (horn_common.h, shared with features.hip).  T <- dT T.
+//   fixed slices, n, |q - p|^2, q, p and q p^T in float64 (gsr_block_sum, gsr_common.h: a fixed order, no float atomics); one
+//   workgroup adds the partials and one thread solves Horn's closed form: the rotation is the eigenvector of the largest
+//   eigenvalue of the symmetric 4 x 4 matrix built from the centred cross-covariance - a unit quaternion, so a reflection
+//   cannot come out - found by cyclic Jacobi with a fixed number of sweeps (horn_common.h, shared with features.hip).  T <- dT
+//   T.
 #include "knn_common.h"
 #include "horn_common.h"
 #include "rigid_common.h"
@@ -29,7 +31,6 @@
 #define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
 #define GSR_ICP_PLANE_SUMS 30      // n, sum d2, sum r^2, J^T r [6], upper triangle of J^T J [21]
 #define GSR_ICP_PIVOT_MIN 1e-12    // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
-#define GSR_NN_NONE 0x7FFFFFFFu    // no neighbour yet: above every row (P <= 2^30 - 1)
 
 // (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
 
@@ -103,82 +104,41 @@ __global__ __launch_bounds__(256) void k_nn_transform(uint32_t P, const float* _
   out[3 * (size_t)i + 2] = q.z;
 }
 
-// (d2, row) < (bd, br) lexicographically; false for a NaN d2
+// (d2, row) < (bd, br) lexicographically; false for a NaN d2.  (Two selects, no branch: the inner loop of the search)
 __device__ __forceinline__ void nn_take(float d2, uint32_t row, float& bd, uint32_t& br) {
-  if (d2 < bd || (d2 == bd && row < br)) {
-    bd = d2;
-    br = row;
-  }
+  const bool take = (d2 < bd) | ((d2 == bd) & (row < br));
+  bd = take ? d2 : bd;
+  br = take ? row : br;
 }
 
-__global__ __launch_bounds__(256) void k_nn_search(uint32_t Pt, uint32_t Ps, const float* __restrict__ src,
+__global__ __launch_bounds__(256) void k_nn_search(GsrKnnTree t, uint32_t Ps, const float* __restrict__ src,
                                                    const uint32_t* __restrict__ order, const double* __restrict__ T_dev,
-                                                   float max_dist2, const float4* __restrict__ pts,
-                                                   const float4* __restrict__ box_lo, const float4* __restrict__ box_hi,
-                                                   uint32_t nbox, const float4* __restrict__ sup_lo,
-                                                   const float4* __restrict__ sup_hi, uint32_t nsuper,
-                                                   int32_t* __restrict__ idx_out, float* __restrict__ dist2_out) {
+                                                   float max_dist2, int32_t* __restrict__ idx_out,
+                                                   float* __restrict__ dist2_out) {
   __shared__ float4 s_lo[256], s_hi[256];
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  uint32_t row = t < Ps ? (order ? order[t] : t) : 0u;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  uint32_t row = i < Ps ? (order ? order[i] : i) : 0u;
   // (an `order` entry outside the cloud is not followed: that thread answers nothing)
-  const bool active = t < Ps && row < Ps;
+  const bool active = i < Ps && row < Ps;
   if (!active) row = 0u;
   const RegT T = reg_load(T_dev);
   const float4 me = reg_apply(T, src[3 * (size_t)row], src[3 * (size_t)row + 1], src[3 * (size_t)row + 2]);
   const bool finite = knn_finite(me.x) && knn_finite(me.y) && knn_finite(me.z);
   // the bound starts at max_dist2 with no row: a candidate AT max_dist2 is taken (valid iff d2 <= max_dist2), one beyond never
   float bd = max_dist2;
-  uint32_t br = GSR_NN_NONE;
-  for (uint32_t base = 0; base < nsuper; base += 256u) {
-    __syncthreads();
-    if (base + threadIdx.x < nsuper) {
-      s_lo[threadIdx.x] = sup_lo[base + threadIdx.x];
-      s_hi[threadIdx.x] = sup_hi[base + threadIdx.x];
-    }
-    __syncthreads();
-    if (!active || !finite) continue;
-    const uint32_t n = min(256u, nsuper - base);
-    for (uint32_t s = 0; s < n; s++) {
-      if (!(knn_box_d2(me, s_lo[s], s_hi[s]) <= bd)) continue;
-      const uint32_t bb = (base + s) * (uint32_t)GSR_KNN_SUPER, be = min(nbox, bb + (uint32_t)GSR_KNN_SUPER);
-      for (uint32_t b = bb; b < be; b++) {
-        if (!(knn_box_d2(me, box_lo[b], box_hi[b]) <= bd)) continue;
-        const uint32_t jb = b * (uint32_t)GSR_KNN_BOX, je = min(Pt, jb + (uint32_t)GSR_KNN_BOX);
-        for (uint32_t j = jb; j < je; j++) {
-          const float4 p = pts[j];
-          nn_take(knn_point_d2(me, p), __float_as_uint(p.w), bd, br);
-        }
-      }
-    }
-  }
+  uint32_t br = GSR_NONE;
+  knn_sweep<256>(
+      t, me, active && finite, s_lo, s_hi, [&]() __attribute__((always_inline)) { return bd; },
+      [&](const uint32_t, const float4 p) __attribute__((always_inline)) {
+        nn_take(knn_point_d2(me, p), __float_as_uint(p.w), bd, br);
+      });
   if (!active) return;
-  const bool valid = br != GSR_NN_NONE;
+  const bool valid = br != GSR_NONE;
   idx_out[row] = valid ? (int32_t)br : -1;
   if (dist2_out) dist2_out[row] = valid ? bd : KNN_INF;
 }
 
 // ---- one ICP update ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double reg_wave_sum(double v) {      // the same total in every lane (a + b == b + a bit for bit)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// N per-thread values summed over a 256-thread workgroup; the result is valid in thread 0
-template <int N>
-__device__ __forceinline__ void reg_block_sum(double (&s)[N]) {
-  __shared__ double sh[4][N];
-#pragma unroll
-  for (int a = 0; a < N; a++) s[a] = reg_wave_sum(s[a]);
-  if (gsr_lane() == 0) {
-#pragma unroll
-    for (int a = 0; a < N; a++) sh[threadIdx.x >> 6][a] = s[a];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < N; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
-}
-
 // the pair of row i, or false: no correspondence, an index outside the target, a non-finite point on either side
 __device__ __forceinline__ bool icp_pair(uint32_t i, const float* __restrict__ src, uint32_t Pt, const float* __restrict__ tgt,
                                          const int32_t* __restrict__ idx, const RegT& T, float4& q, float4& p) {
@@ -245,7 +205,7 @@ __global__ __launch_bounds__(256) void k_icp_partial(uint32_t Ps, const float* _
       for (int b = 0; b < 3; b++) s[8 + 3 * a + b] += q[a] * p[b];
     }
   }
-  reg_block_sum(s);
+  gsr_block_sum(s);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int a = 0; a < GSR_ICP_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_SUMS + a] = s[a];
@@ -264,7 +224,7 @@ __global__ __launch_bounds__(256) void k_icp_final(uint32_t nblk, uint32_t Ps, c
 #pragma unroll
     for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_SUMS + a];
   }
-  reg_block_sum(s);
+  gsr_block_sum(s);
   if (threadIdx.x != 0) return;
   const double n = s[0];
   stats[0] = n;
@@ -349,7 +309,7 @@ __global__ __launch_bounds__(256) void k_icp_plane_partial(uint32_t Ps, const fl
       for (int b = a; b < 6; b++) s[o++] += J[a] * J[b];
     }
   }
-  reg_block_sum(s);
+  gsr_block_sum(s);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_PLANE_SUMS + a] = s[a];
@@ -368,7 +328,7 @@ __global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t
 #pragma unroll
     for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_PLANE_SUMS + a];
   }
-  reg_block_sum(s);
+  gsr_block_sum(s);
   if (threadIdx.x != 0) return;
   const double n = s[0];
   stats[0] = n;
@@ -455,14 +415,12 @@ __global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t
   stats[3] = 0.0;
 }
 
-static bool reg_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
-
 extern "C" {
 
 size_t gsr_nn_index_bytes(int64_t Pt) { return nn_layout((size_t)(Pt < 1 ? 1 : Pt)).total; }
 
 int gsr_nn_index_build(int64_t Pt, const float* target, void* index, size_t index_bytes, void* stream) {
-  if (reg_bad_size(Pt) || !target || !index) {
+  if (gsr_bad_size(Pt) || !target || !index) {
     gsr_set_error("nn_index_build: bad arguments (Pt = %lld)", (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -484,7 +442,7 @@ size_t gsr_nn_order_workspace_bytes(int64_t Ps) { return nn_order_layout((size_t
 
 int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* source, const double* T_dev, int32_t* order_out,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  if (reg_bad_size(Pt) || reg_bad_size(Ps) || !index || !source || !order_out || !workspace) {
+  if (gsr_bad_size(Pt) || gsr_bad_size(Ps) || !index || !source || !order_out || !workspace) {
     gsr_set_error("nn_query_order: bad arguments (Pt = %lld, Ps = %lld)", (long long)Pt, (long long)Ps);
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -507,23 +465,20 @@ int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* s
 
 int gsr_nn_search(int64_t Pt, const void* index, int64_t Ps, const float* source, const double* T_dev, float max_dist2,
                   const int32_t* order, int32_t* idx_out, float* dist2_out, void* stream) {
-  if (reg_bad_size(Pt) || reg_bad_size(Ps) || !index || !source || !idx_out || !(max_dist2 >= 0.f)) {
+  if (gsr_bad_size(Pt) || gsr_bad_size(Ps) || !index || !source || !idx_out || !(max_dist2 >= 0.f)) {
     gsr_set_error("nn_search: bad arguments (Pt = %lld, Ps = %lld, max_dist2 = %g)", (long long)Pt, (long long)Ps,
                   (double)max_dist2);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrNnLayout L = nn_layout((size_t)Pt);
-  const char* ix = (const char*)index;
-  const uint32_t nt = (uint32_t)Pt, ns = (uint32_t)Ps;
-  GSR_LAUNCH("nn_search", k_nn_search, dim3((ns + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, nt, ns, source,
-             (const uint32_t*)order, T_dev, max_dist2, (const float4*)(ix + L.pts), (const float4*)(ix + L.box_lo),
-             (const float4*)(ix + L.box_hi), (uint32_t)knn_nbox(nt), (const float4*)(ix + L.sup_lo),
-             (const float4*)(ix + L.sup_hi), (uint32_t)knn_nsuper(nt), idx_out, dist2_out);
+  const GsrKnnTree t = nn_tree(index, (size_t)Pt);
+  const uint32_t ns = (uint32_t)Ps;
+  GSR_LAUNCH("nn_search", k_nn_search, dim3((ns + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, t, ns, source,
+             (const uint32_t*)order, T_dev, max_dist2, idx_out, dist2_out);
   return gsr_launch_status("nn_search launch");
 }
 
 int gsr_transform_points(int64_t P, const float* points, const double* T_dev, float* out, void* stream) {
-  if (reg_bad_size(P) || !points || !out) {
+  if (gsr_bad_size(P) || !points || !out) {
     gsr_set_error("transform_points: bad arguments (P = %lld)", (long long)P);
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -539,7 +494,7 @@ size_t gsr_icp_workspace_bytes(int64_t Ps) {
 
 int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* target, const int32_t* idx, double* T_dev,
                    double* stats_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  if (reg_bad_size(Ps) || reg_bad_size(Pt) || !source || !target || !idx || !T_dev || !stats_dev || !workspace) {
+  if (gsr_bad_size(Ps) || gsr_bad_size(Pt) || !source || !target || !idx || !T_dev || !stats_dev || !workspace) {
     gsr_set_error("icp_update: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;
   }
@@ -565,7 +520,7 @@ int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* tar
 int gsr_icp_update_plane(int64_t Ps, const float* source, int64_t Pt, const float* target, const float* target_normals,
                          const int32_t* idx, double* T_dev, double* stats_dev, void* workspace, size_t workspace_bytes,
                          void* stream) {
-  if (reg_bad_size(Ps) || reg_bad_size(Pt) || !source || !target || !target_normals || !idx || !T_dev || !stats_dev ||
+  if (gsr_bad_size(Ps) || gsr_bad_size(Pt) || !source || !target || !target_normals || !idx || !T_dev || !stats_dev ||
       !workspace) {
     gsr_set_error("icp_update_plane: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;

@@ -30,6 +30,25 @@ def knn_dist2_bruteforce(points, first_query=0, chunk=None, device="cpu"):
     return out.cpu()
 
 
+def last_sorted_row(points):
+    """points float32 [P,3], all finite -> the row that the neighbour structure of csrc/knn.hip sorts LAST: the largest 30-bit
+    Morton code of the cells (v - lo) / (hi - lo) * 1023 (float32, one rounding per operation) in the cloud's bounding box, on
+    equal codes the largest row (the sort is stable).  With P = 64 * 64 * n + 1 it is the one point of the last super-box."""
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    t = (p - lo) / (hi - lo) * np.float32(1023.0)
+    cell = np.where(t >= 0, np.minimum(t, np.float32(1023.0)), np.float32(0)).astype(np.uint32)
+
+    def spread(x):
+        x = (x | (x << np.uint32(16))) & np.uint32(0x030000FF)
+        x = (x | (x << np.uint32(8))) & np.uint32(0x0300F00F)
+        x = (x | (x << np.uint32(4))) & np.uint32(0x030C30C3)
+        return (x | (x << np.uint32(2))) & np.uint32(0x09249249)
+
+    code = spread(cell[:, 0]) | (spread(cell[:, 1]) << np.uint32(1)) | (spread(cell[:, 2]) << np.uint32(2))
+    return int(np.flatnonzero(code == code.max())[-1])
+
+
 def selection_mask(depth, alpha=None, rendered_z=None, stride=1, min_depth=0.2, max_depth=math.inf, alpha_below=0.5,
                    front_margin=0.05, dtype=np.float64):
     """[H,W] bool: the strided pixels gsr_unproject_rgbd selects, evaluated in `dtype`."""

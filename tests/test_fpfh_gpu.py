@@ -115,3 +115,40 @@ def test_empty_and_tiny_clouds():
     assert tuple(S.compute_fpfh_feature(z, z, 0.1).shape) == (0, 33)
     f, counts, count = S.compute_fpfh_feature(torch.rand(1, 3).cuda(), torch.rand(1, 3).cuda(), 0.5, 0, return_stats=True)
     assert f.tolist() == [[0.0] * 33] and count.tolist() == [1] and int(counts.sum()) == 0
+
+
+def test_staging_loop_second_round_counts():
+    """P = 64 * 4096 + 1: the smallest cloud with 65 super-boxes, so k_fpfh_spfh and k_fpfh_sum - one wave per workgroup - stage the
+    AABBs through LDS twice (knn_sweep<64>, csrc/knn_common.h).  The only super-box of round two holds ONE point, the row sorted
+    last, and only rows next to it depend on that round: besides 200 sampled rows, every row of the bounding box's top corner
+    (all coordinates > 15 / 16, some 64 rows), which that row lies in, is checked, and the row must be a member of other checked
+    rows' neighbourhoods.  count against the brute force of G.analyse on those rows alone: float32 differences promoted, d2 =
+    (dx dx + dy dy) + dz dz in float64, members d2 <= r2.  Exact, given the precondition asserted below: no d2 within 1e-6
+    (relative) of r2, five times what the float32 and the float64 d2 can differ by."""
+    import mapping_reference as MR
+    P, radius = 64 * 4096 + 1, 0.03                   # unit cube: 29.6 other rows within the radius on average
+    rng = np.random.default_rng(52)
+    pts = rng.random((P, 3), dtype=np.float32)
+    nrm = rng.standard_normal((P, 3)).astype(np.float32)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    last = MR.last_sorted_row(pts)
+    corner = np.flatnonzero((pts > 1 - 1 / 16).all(axis=1))
+    assert last in corner and corner.size < 200
+    rows = torch.from_numpy(np.union1d(rng.choice(P, 200, replace=False), corner)).cuda()
+    R = rows.numel()
+    d = dev(pts)
+    fpfh, _, count = S.compute_fpfh_feature(d, dev(nrm), radius, 0, return_stats=True)
+    r2 = G.NR.radius2(radius)
+    delta = (d[None, :, :] - d[rows, None, :]).double()                               # float32 differences, promoted
+    d2 = (delta[..., 0] * delta[..., 0] + delta[..., 1] * delta[..., 1]) + delta[..., 2] * delta[..., 2]
+    d2[torch.arange(R, device="cuda"), rows] = G.INF                                  # the row itself
+    assert float(((d2 - r2).abs() / r2).min()) > 1e-6
+    member = d2 <= r2
+    want = 1 + member.sum(dim=1)
+    users = int(member[:, last].sum())
+    print(f"fpfh 256k + 1: {R} rows, counts {int(want.min())} .. {int(want.max())}, mean {float(want.double().mean()):.1f}, the "
+          f"row sorted last is a member of {users} checked neighbourhoods")
+    assert users >= 1
+    assert 15 <= float(want.double().mean()) <= 40
+    assert torch.equal(count[rows].long(), want)
+    assert bool(torch.isfinite(fpfh[rows]).all())

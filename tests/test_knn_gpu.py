@@ -4,6 +4,7 @@ Tolerance: relative 1e-6 per entry, exactly 0 where the oracle gives 0.  Derived
 result differs from float64 only by the rounding of three differences, three squares, two adds, twice more for the mean - under
 8 * 2^-24 = 4.8e-7 relative - and the mean of the three smallest distances is continuous in which neighbour wins a tie.  A missed
 neighbour shows up orders of magnitude above that."""
+import functools
 import math
 
 import numpy as np
@@ -130,3 +131,63 @@ def test_non_finite_rows_do_not_disturb_the_finite_ones():
     ok[bad] = False
     want = MR.knn_dist2_bruteforce(pts[ok], device="cuda")
     assert float(((got[ok] - want).abs() / want).max()) <= REL
+
+
+# ---- the sweep's LDS staging loop in its second round (csrc/knn_common.h knn_sweep, 256 super-boxes per round) -----------------
+STAGED = 256 * BOX * BOX + 1      # the smallest cloud with 257 super-boxes (tests/test_registration_gpu.py uses it as a target)
+TAIL = 600
+
+
+@functools.lru_cache(maxsize=None)
+def staged_cloud():
+    """-> (points on the device, the row sorted last).  Super-box 257 - the only one staged in round two - holds ONE point, the
+    row sorted last, and only rows next to it depend on that round: the rows of the bounding box's top corner (every coordinate
+    > 15 / 16, some 256 of them), which it lies in, are moved to the END of the cloud, behind a random remainder, so that the
+    last TAIL rows are queries around it."""
+    pts = torch.rand(STAGED, 3, generator=gen(31))
+    corner = (pts > 1 - 1 / 16).all(dim=1)
+    assert 0 < int(corner.sum()) <= TAIL - 100
+    pts = torch.cat([pts[~corner], pts[corner]])
+    last = MR.last_sorted_row(pts.numpy())
+    assert last >= STAGED - int(corner.sum())
+    return pts.cuda(), last
+
+
+def held(got, want, label):
+    """`check`'s comparison on given rows: got float32, want float64, same shape"""
+    got = got.cpu().double()
+    zero = want == 0
+    err = ((got - want).abs() / want.clamp_min(1e-300))[~zero]
+    print(f"knn {label}: {tuple(got.shape)}, zeros {int(zero.sum())}, max rel err {float(err.max()) if err.numel() else 0.0:.3e}")
+    assert got.shape == want.shape and bool((got[zero] == 0).all())
+    assert err.numel() == 0 or float(err.max()) <= REL, float(err.max())
+
+
+def tail_bruteforce(pts, last):
+    """float64 [TAIL, 3]: the three smallest d2 of the last TAIL rows, as knn_dist2_bruteforce forms them; asserts that the row
+    sorted last is one of the three nearest of some OTHER queried row - an answer that only the second round can give"""
+    x = pts.double()
+    rows = torch.arange(STAGED - TAIL, STAGED, device="cuda")
+    d = torch.zeros((TAIL, STAGED), dtype=torch.float64, device="cuda")
+    for a in range(3):
+        d += (x[rows, a:a + 1] - x[None, :, a]) ** 2
+    d[torch.arange(TAIL, device="cuda"), rows] = math.inf                    # the row itself
+    top = torch.topk(d, 3, dim=1, largest=False, sorted=True)
+    users = int((top.indices == last).any(dim=1).sum())
+    print(f"knn 1M + 1: the row sorted last is among the three nearest of {users} queried rows")
+    assert users >= 1
+    return top.values.cpu()
+
+
+def test_dist2_staging_loop_second_round():
+    from simple_knn._C import knn_dist2
+    pts, last = staged_cloud()
+    got = knn_dist2(pts, first_query=STAGED - TAIL)
+    held(got, tail_bruteforce(pts, last).sum(dim=1) / 3, "dist2, 1M + 1, the last 600 rows")
+    held(got, MR.knn_dist2_bruteforce(pts, first_query=STAGED - TAIL, device="cuda"), "dist2, 1M + 1, the file's brute force")
+
+
+def test_knn_k_staging_loop_second_round():
+    from simple_knn._C import knn_k
+    pts, last = staged_cloud()
+    held(knn_k(pts, 3)[STAGED - TAIL:], tail_bruteforce(pts, last), "knn_k(3), 1M + 1, the last 600 rows")

@@ -122,3 +122,44 @@ def test_a_shuffled_cloud_gives_every_point_the_same_answer(kind, radius, nn):
     full = (count >= 3).cpu().numpy()
     diff = (m.cpu().numpy().astype(np.float64) - n.cpu().numpy()[perm].astype(np.float64))[full[perm]]
     assert np.abs(diff).max() <= 1e-6
+
+
+def test_staging_loop_second_round_counts():
+    """P = 256 * 4096 + 1: 257 super-boxes, so both sweeps of k_normals stage their AABBs through LDS twice (knn_sweep,
+    csrc/knn_common.h).  The only super-box of round two holds ONE point, the row sorted last, and only rows next to it depend on
+    that round: besides 200 sampled rows, every row of the bounding box's top corner (all coordinates > 15 / 16, some 256 rows),
+    which that row lies in, is checked, and the row must be a member of another checked row's neighbourhood.  count against the
+    brute force of NR.analyse on those rows alone: float32 differences promoted, d2 in float64, bound = min(r2, d_8), ties at
+    the bound all members.  Exact, given the precondition asserted below: what decides membership lies more than 1e-6 (relative)
+    apart, five times what the float32 and the float64 d2 can differ by (three roundings of 2^-24)."""
+    import mapping_reference as MR
+    P, nn = 256 * 4096 + 1, 9
+    radius = 0.0125                                   # unit cube: 8.6 other rows within it on average - both cuts decide
+    rng = np.random.default_rng(51)
+    pts = rng.random((P, 3), dtype=np.float32)
+    last = MR.last_sorted_row(pts)
+    corner = np.flatnonzero((pts > 1 - 1 / 16).all(axis=1))
+    assert last in corner and corner.size < 400
+    rows = torch.from_numpy(np.union1d(rng.choice(P, 200, replace=False), corner)).cuda()
+    R = rows.numel()
+    d = dev(pts)
+    _, count, _ = S.estimate_normals(d, radius, nn, return_stats=True)
+    r2 = NR.radius2(radius)
+    delta = (d[None, :, :] - d[rows, None, :]).double()                               # float32 differences, promoted
+    d2 = (delta[..., 0] * delta[..., 0] + delta[..., 1] * delta[..., 1]) + delta[..., 2] * delta[..., 2]
+    d2[torch.arange(R, device="cuda"), rows] = NR.INF                                 # the row itself
+    small = torch.topk(d2, nn, dim=1, largest=False, sorted=True).values              # d_1 .. d_9
+    bound = torch.clamp(small[:, nn - 2], max=r2)
+    member = d2 <= bound[:, None]
+    want = 1 + member.sum(dim=1)
+    inc = torch.where(member, d2, torch.full_like(d2, -NR.INF)).max(dim=1).values
+    exc = torch.where(~member, d2, torch.full_like(d2, NR.INF)).min(dim=1).values
+    margin = torch.minimum((exc - inc) / exc, torch.minimum((r2 - inc).abs() / r2, (exc - r2).abs() / r2))
+    assert float(margin.min()) > 1e-6
+    users = int(member[:, last].sum())
+    want = want.cpu().numpy()
+    print(f"normals 1M + 1: {R} rows, counts {np.bincount(want, minlength=nn + 1).tolist()}, the row sorted last is a member of "
+          f"{users} checked neighbourhoods")
+    assert users >= 1
+    assert want.min() < nn and (want == nn).sum() >= 20      # the radius cuts some neighbourhoods, max_nn others
+    assert np.array_equal(count[rows].cpu().numpy(), want)
