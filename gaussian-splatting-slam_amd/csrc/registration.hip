@@ -23,6 +23,10 @@
 //   eigenvalue of the symmetric 4 x 4 matrix built from the centred cross-covariance - a unit quaternion, so a reflection
 //   cannot come out - found by cyclic Jacobi with a fixed number of sweeps (horn_common.h, shared with features.hip).  T <- dT
 //   T.
+//
+// gsr_icp_update_plane / gsr_icp_update_colored: the same shift and summation structure over the point-to-plane residual - and,
+//   for the coloured update, the photometric residual in the target's tangent plane beside it (the gradient of colored.hip) -
+//   then one 6 x 6 LDL^T solve and dT = Tr(c) [Rz Ry Rx, t] Tr(-c), shared by both (icp_solve6_compose).
 #include "knn_common.h"
 #include "horn_common.h"
 #include "rigid_common.h"
@@ -30,7 +34,8 @@
 #define GSR_ICP_BLOCKS 256
 #define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
 #define GSR_ICP_PLANE_SUMS 30      // n, sum d2, sum r^2, J^T r [6], upper triangle of J^T J [21]
-#define GSR_ICP_PIVOT_MIN 1e-12    // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
+#define GSR_ICP_COLORED_SUMS 31    // n, sum d2, sum r_G^2, sum r_I^2 (both unweighted), J^T r [6], upper triangle of J^T J [21]
+#define GSR_ICP_PIVOT_MIN 1e-12   // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
 
 // (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
 
@@ -62,6 +67,15 @@ static inline GsrIcpLayout icp_layout() {
   L.shift = 0;
   L.part = 256;
   L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_PLANE_SUMS * 8);
+  return L;
+}
+// workspace of gsr_icp_update_colored: the same two parts, GSR_ICP_COLORED_SUMS per workgroup (a size of its own: the two entries
+// above keep theirs)
+static inline GsrIcpLayout icp_colored_layout() {
+  GsrIcpLayout L;
+  L.shift = 0;
+  L.part = 256;
+  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_COLORED_SUMS * 8);
   return L;
 }
 
@@ -316,43 +330,12 @@ __global__ __launch_bounds__(256) void k_icp_plane_partial(uint32_t Ps, const fl
   }
 }
 
-// one workgroup: the partials, then thread 0 solves and composes
-__global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
-                                                         const double* __restrict__ shift, double* __restrict__ T_dev,
-                                                         double* __restrict__ stats) {
-  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
-  double s[GSR_ICP_PLANE_SUMS];
-#pragma unroll
-  for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] = 0.0;
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_PLANE_SUMS + a];
-  }
-  gsr_block_sum(s);
-  if (threadIdx.x != 0) return;
-  const double n = s[0];
-  stats[0] = n;
-  stats[1] = n / (double)Ps;
-  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
-  stats[4] = s[1];
-  stats[5] = s[2];
-  stats[6] = stats[7] = 0.0;
-  if (n < 6.0) {
-    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
-    return;
-  }
-  {
-    int o = 9;
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      g[a] = -s[3 + a];
-#pragma unroll
-      for (int b = a; b < 6; b++) {
-        A[a][b] = A[b][a] = s[o];
-        o++;
-      }
-    }
-  }
+// thread 0 of a final kernel (the plane update's and the coloured one's): J^T J x = -J^T r on the matrix in A and the right-hand
+// side in g, both filled by the caller; then dR, dT and T <- dT T.  stats[3] = 0, or 2 with T as it was.  The arrays are LDS:
+// indexed at run time, which registers cannot be.
+__device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L)[6][6], double (&D)[6], double (&g)[6],
+                                                   double (&x)[6], const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                   double* __restrict__ stats) {
   // J^T J = L D L^T, L unit lower triangular; every pivot is held against its own diagonal entry (scale-free per unknown)
   for (int j = 0; j < 6; j++) {
     double d = A[j][j];
@@ -413,6 +396,152 @@ __global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t
   T_dev[12] = T_dev[13] = T_dev[14] = 0.0;
   T_dev[15] = 1.0;
   stats[3] = 0.0;
+}
+
+// one workgroup: the partials, then thread 0 solves and composes
+__global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
+                                                         const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                         double* __restrict__ stats) {
+  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
+  double s[GSR_ICP_PLANE_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] = 0.0;
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_PLANE_SUMS + a];
+  }
+  gsr_block_sum(s);
+  if (threadIdx.x != 0) return;
+  const double n = s[0];
+  stats[0] = n;
+  stats[1] = n / (double)Ps;
+  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
+  stats[4] = s[1];
+  stats[5] = s[2];
+  stats[6] = stats[7] = 0.0;
+  if (n < 6.0) {
+    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
+    return;
+  }
+  {
+    int o = 9;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      g[a] = -s[3 + a];
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        A[a][b] = A[b][a] = s[o];
+        o++;
+      }
+    }
+  }
+  icp_solve6_compose(A, L, D, g, x, shift, T_dev, stats);
+}
+
+// ---- one coloured update (Park, Zhou, Koltun 2017; Open3D's TransformationEstimationForColoredICP) -------------------------------------
+// I = (r + g + b) / 3 in float64, left to right (colored.hip forms the target's gradient from the same value)
+__device__ __forceinline__ double icp_intensity(const float* __restrict__ colors, size_t row) {
+  return (((double)colors[3 * row] + (double)colors[3 * row + 1]) + (double)colors[3 * row + 2]) / 3.0;
+}
+
+// per workgroup: s[0] = n, s[1] = sum |q - p|^2, s[2] = sum ((q - p).n)^2 (0 with lambda = 0), s[3] = sum (I_s - I_proj)^2 (0 with
+// lambda = 1), s[4..9] = J^T r, s[10..30] = J^T J rows 0 .. 5 from the diagonal on, r and J over both residuals
+__global__ __launch_bounds__(256) void k_icp_colored_partial(uint32_t Ps, const float* __restrict__ src,
+                                                             const float* __restrict__ scol, uint32_t Pt,
+                                                             const float* __restrict__ tgt, const float* __restrict__ nrm,
+                                                             const float* __restrict__ tcol, const float* __restrict__ grad,
+                                                             const int32_t* __restrict__ idx, double sqrt_g, double sqrt_i,
+                                                             const double* __restrict__ T_dev, const double* __restrict__ shift,
+                                                             double* __restrict__ part) {
+  const RegT T = reg_load(T_dev);
+  const double c0 = shift[0], c1 = shift[1], c2 = shift[2];
+  double s[GSR_ICP_COLORED_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) s[a] = 0.0;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < Ps; i += gridDim.x * 256u) {
+    float4 qf, pf;
+    if (!icp_pair(i, src, Pt, tgt, idx, T, qf, pf)) continue;
+    const size_t k = (size_t)idx[i];
+    const float n0 = nrm[3 * k], n1 = nrm[3 * k + 1], n2 = nrm[3 * k + 2];
+    const float g0 = grad[3 * k], g1 = grad[3 * k + 1], g2 = grad[3 * k + 2];
+    const double is = icp_intensity(scol, (size_t)i), it = icp_intensity(tcol, k);
+    if (!(knn_finite(n0) && knn_finite(n1) && knn_finite(n2) && knn_finite(g0) && knn_finite(g1) && knn_finite(g2) &&
+          fabs(is) < (double)KNN_INF && fabs(it) < (double)KNN_INF))
+      continue;
+    // (float32 values: the differences below are exact in float64)
+    const double q[3] = {(double)qf.x - c0, (double)qf.y - c1, (double)qf.z - c2};
+    const double e[3] = {(double)qf.x - (double)pf.x, (double)qf.y - (double)pf.y, (double)qf.z - (double)pf.z};
+    const double n[3] = {(double)n0, (double)n1, (double)n2};
+    const double d[3] = {(double)g0, (double)g1, (double)g2};
+    const double en = (e[0] * n[0] + e[1] * n[1]) + e[2] * n[2];
+    const double dn = (d[0] * n[0] + d[1] * n[1]) + d[2] * n[2];
+    // q_proj - p = e - (e.n) n;  I_proj = I_t + d.(q_proj - p);  m = -(I - n n^T) d
+    const double w[3] = {e[0] - en * n[0], e[1] - en * n[1], e[2] - en * n[2]};
+    const double ri = is - (it + ((d[0] * w[0] + d[1] * w[1]) + d[2] * w[2]));
+    const double m[3] = {dn * n[0] - d[0], dn * n[1] - d[1], dn * n[2] - d[2]};
+    const double rg = sqrt_g * en, rp = sqrt_i * ri;
+    const double JG[6] = {sqrt_g * (q[1] * n[2] - q[2] * n[1]), sqrt_g * (q[2] * n[0] - q[0] * n[2]),
+                          sqrt_g * (q[0] * n[1] - q[1] * n[0]), sqrt_g * n[0], sqrt_g * n[1], sqrt_g * n[2]};
+    const double JI[6] = {sqrt_i * (q[1] * m[2] - q[2] * m[1]), sqrt_i * (q[2] * m[0] - q[0] * m[2]),
+                          sqrt_i * (q[0] * m[1] - q[1] * m[0]), sqrt_i * m[0], sqrt_i * m[1], sqrt_i * m[2]};
+    s[0] += 1.0;
+    s[1] += (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    s[2] += sqrt_g > 0.0 ? en * en : 0.0;
+    s[3] += sqrt_i > 0.0 ? ri * ri : 0.0;
+    int o = 10;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      s[4 + a] += JG[a] * rg + JI[a] * rp;
+#pragma unroll
+      for (int b = a; b < 6; b++) s[o++] += JG[a] * JG[b] + JI[a] * JI[b];
+    }
+  }
+  gsr_block_sum(s);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_COLORED_SUMS + a] = s[a];
+  }
+}
+
+// one workgroup: the partials, then thread 0 solves and composes as the plane update does
+__global__ __launch_bounds__(256) void k_icp_colored_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
+                                                           const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                           double* __restrict__ stats) {
+  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
+  double s[GSR_ICP_COLORED_SUMS];
+#pragma unroll
+  for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) s[a] = 0.0;
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_COLORED_SUMS + a];
+  }
+  gsr_block_sum(s);
+  if (threadIdx.x != 0) return;
+  const double n = s[0];
+  stats[0] = n;
+  stats[1] = n / (double)Ps;
+  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
+  stats[4] = s[1];
+  stats[5] = s[2];
+  stats[6] = s[3];
+  stats[7] = 0.0;
+  if (n < 6.0) {
+    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
+    return;
+  }
+  {
+    int o = 10;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      g[a] = -s[4 + a];
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        A[a][b] = A[b][a] = s[o];
+        o++;
+      }
+    }
+  }
+  icp_solve6_compose(A, L, D, g, x, shift, T_dev, stats);
 }
 
 extern "C" {
@@ -542,6 +671,41 @@ int gsr_icp_update_plane(int64_t Ps, const float* source, int64_t Pt, const floa
   GSR_LAUNCH("icp_plane_final", k_icp_plane_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part,
              (const double*)shift, T_dev, stats_dev);
   return gsr_launch_status("icp_update_plane launch");
+}
+
+size_t gsr_icp_colored_workspace_bytes(int64_t Ps) {
+  (void)Ps;      // (as gsr_icp_workspace_bytes: at most GSR_ICP_BLOCKS rows of partial sums)
+  return icp_colored_layout().total;
+}
+
+int gsr_icp_update_colored(int64_t Ps, const float* source, const float* source_colors, int64_t Pt, const float* target,
+                           const float* target_normals, const float* target_colors, const float* target_gradient,
+                           const int32_t* idx, double lambda_geometric, double* T_dev, double* stats_dev, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (gsr_bad_size(Ps) || gsr_bad_size(Pt) || !source || !source_colors || !target || !target_normals || !target_colors ||
+      !target_gradient || !idx || !T_dev || !stats_dev || !workspace || !(lambda_geometric >= 0.0 && lambda_geometric <= 1.0)) {
+    gsr_set_error("icp_update_colored: bad arguments (Ps = %lld, Pt = %lld, lambda_geometric = %g: expected 0 .. 1)",
+                  (long long)Ps, (long long)Pt, lambda_geometric);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  const GsrIcpLayout L = icp_colored_layout();
+  if (workspace_bytes < L.total) {
+    gsr_set_error("icp_update_colored: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  double* shift = (double*)(ws + L.shift);
+  double* part = (double*)(ws + L.part);
+  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
+  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
+  const double sqrt_g = sqrt(lambda_geometric), sqrt_i = sqrt(1.0 - lambda_geometric);
+  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
+  GSR_LAUNCH("icp_colored_partial", k_icp_colored_partial, dim3(sblk), dim3(256), 0, st, ns, source, source_colors, nt, target,
+             target_normals, target_colors, target_gradient, idx, sqrt_g, sqrt_i, (const double*)T_dev, (const double*)shift, part);
+  GSR_LAUNCH("icp_colored_final", k_icp_colored_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part,
+             (const double*)shift, T_dev, stats_dev);
+  return gsr_launch_status("icp_update_colored launch");
 }
 
 }  // extern "C"

@@ -256,6 +256,16 @@ EXPORTS = {
     "gsr_normals_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_estimate_normals": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_int32, c_float_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, points, colors, normals, radius, max_nn, gradient, count_out, status_out, workspace + bytes, stream
+    "gsr_color_gradient_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_color_gradient": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # Ps, source, source_colors, Pt, target, target_normals, target_colors, target_gradient, idx, lambda_geometric, T_dev,
+    # stats_dev, workspace + bytes, stream
+    "gsr_icp_colored_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_icp_update_colored": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
     # P, points, normals, radius, max_nn, fpfh, spfh_counts, count, workspace + bytes, stream
     "gsr_fpfh_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_compute_fpfh": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

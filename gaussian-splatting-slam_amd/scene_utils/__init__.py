@@ -16,10 +16,11 @@ from .exposure import apply_exposure
 from .transform import transform_camera, correct_keyframes, validate_transforms
 from .frames import Frame, FramePyramid, undistort, build_pyramid
 from .pointcloud import voxel_down_sample, statistical_outlier_mask, remove_statistical_outliers, condition_point_cloud, \
-    estimate_normals
+    estimate_normals, estimate_color_gradients
 from .registration import NeighborIndex, RegistrationResult, nn_search, transform_points, icp_update, evaluate_registration, \
     registration_icp, register_and_merge, align_map, compute_fpfh_feature, feature_nn, match_features, \
-    registration_ransac_based_on_feature_matching, global_registration, ransac_trials
+    registration_ransac_based_on_feature_matching, global_registration, ransac_trials, registration_colored_icp, \
+    registration_multiscale
 from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, process_pointcloud, accumulate_pointclouds, \
     encode_pointcloud2, Image, CameraInfo, decode_image, encode_image, camera_info_intrinsics, pose_from_transform, register_depth, \
     frame_from_messages, frame_from_visual_merged

@@ -189,3 +189,63 @@ def estimate_normals(points, radius=0.1, max_nn=30, viewpoint=None, return_stats
             _C.check(lib.gsr_estimate_normals(P, _C.ptr(pts), r, nn, view, _C.ptr(normals), _C.ptr(count), _C.ptr(eig), _C.ptr(ws),
                                               ws.numel(), _C._stream()))
     return (normals, count, eig) if return_stats else normals
+
+
+GRADIENT_STATUS = ("solved", "fewer than four rows", "rejected pivot", "masked")      # status codes 0 .. 3 of gsr_color_gradient
+
+
+def _check_gradient(radius, max_nn, names=("radius", "max_nn")):
+    """the neighbourhood of estimate_color_gradients: _check_normals' rules with max_nn >= 4 (Open3D solves from four rows on)"""
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+        raise TypeError(f"{names[0]}={radius!r}: expected a number")
+    if math.isnan(radius) or not radius > 0:
+        raise ValueError(f"{names[0]}={radius}: expected a value > 0 (inf: limited by {names[1]} only)")
+    if isinstance(max_nn, bool) or not isinstance(max_nn, numbers.Integral):
+        raise TypeError(f"{names[1]}={max_nn!r}: expected an int")
+    if not 4 <= max_nn <= NB_NEIGHBORS_MAX:
+        raise ValueError(f"{names[1]}={max_nn}: expected 4 .. {NB_NEIGHBORS_MAX}")
+    return float(radius), int(max_nn)
+
+
+def _check_rows3_shape(t, name, rows=None):
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point() or t.dim() != 2 or t.shape[1] != 3 or \
+            (rows is not None and int(t.shape[0]) != rows):
+        raise ValueError(f"{name}: expected a floating-point tensor of shape ({'P' if rows is None else rows}, 3), one row per point")
+
+
+def _check_rows3(t, name, rows=None):
+    """a floating-point [rows,3] tensor on the HIP device -> contiguous float32; type and shape first"""
+    _check_rows3_shape(t, name, rows)
+    if not t.is_cuda:
+        raise _gsr().GsrError(f"{name} must live on the HIP device (no CPU path)")
+    return t.detach().float().contiguous()
+
+
+def estimate_color_gradients(points, colors, normals, radius, max_nn=30, return_stats=False):
+    """float32 [P,3] on the device: per row the gradient of the intensity (r + g + b) / 3 over the tangent plane of its normal -
+    what Open3D's registration_colored_icp prepares on the target (include/gsr.h gsr_color_gradient).  The neighbourhood is
+    estimate_normals' (radius, cut at the max_nn nearest, the point itself counted, ties all kept), max_nn 4 .. 33; the
+    least-squares fit of the members' intensity differences over their tangential offsets, with the constraint that the gradient
+    has no component along the normal, in float64 on the device.  Fewer than four rows, or a neighbourhood that does not fix the
+    gradient (collinear rows): 0.  A row with a non-finite point, colour or normal: NaN, and nobody's neighbour.
+    `return_stats`: also (count int32 [P], the neighbourhood's size; status uint8 [P]: 0 solved, 1 fewer than four rows, 2
+    rejected pivot, 3 masked).  No read-back."""
+    r, nn = _check_gradient(radius, max_nn)
+    rows = int(points.shape[0]) if isinstance(points, torch.Tensor) and points.dim() == 2 else None
+    if colors is None:
+        raise ValueError("colors: expected a floating-point tensor of shape (P, 3), one row per point")
+    nrm = _check_rows3(normals, "normals", rows)
+    pts, col = _check_cloud(points, colors, "estimate_color_gradients")
+    _C = _gsr()
+    P, dev = int(pts.shape[0]), pts.device
+    grad = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    count = torch.empty(P, dtype=torch.int32, device=dev) if return_stats else None
+    status = torch.empty(P, dtype=torch.uint8, device=dev) if return_stats else None
+    if P > 0:
+        lib = _C.lib()
+        nrm = nrm.to(dev)
+        with _C.on_device(dev):
+            ws = torch.empty(lib.gsr_color_gradient_workspace_bytes(P), dtype=torch.uint8, device=dev)
+            _C.check(lib.gsr_color_gradient(P, _C.ptr(pts), _C.ptr(col), _C.ptr(nrm), r, nn, _C.ptr(grad), _C.ptr(count),
+                                            _C.ptr(status), _C.ptr(ws), ws.numel(), _C._stream()))
+    return (grad, count, status) if return_stats else grad

@@ -1,5 +1,6 @@
 """Rigid registration of one point cloud to another: a nearest-neighbour index with row numbers and ICP, point-to-point (the
-default) or point-to-plane on the target's normals - what the
+default), point-to-plane on the target's normals, or coloured (the plane residual joined with a photometric one: Park, Zhou,
+Koltun 2017, Open3D's registration_colored_icp - for floors, walls and roads, where the texture stops the slide) - what the
 reference's pointcloud_registeration / pointcloud_registration_gpu (convert_visual_merged_msg.py:187-249, :393-432) do with Open3D
 before a message's cloud is merged into the accumulated one.  Everything runs in HIP (csrc/registration.hip over the structure of
 csrc/knn.hip); there is no CPU path.  Arguments are validated before any device work.
@@ -17,7 +18,8 @@ from typing import NamedTuple
 
 import torch
 
-from .pointcloud import _check_cloud, _check_normals, _check_voxel_size, estimate_normals, voxel_down_sample
+from .pointcloud import _check_cloud, _check_gradient, _check_normals, _check_rows3, _check_rows3_shape, _check_voxel_size, \
+    estimate_color_gradients, estimate_normals, voxel_down_sample
 
 USE_QUERY_ORDER = True      # registration_icp Morton-sorts the queries once (profiles/README.md, registration_bench: measured)
 
@@ -57,7 +59,8 @@ def _check_icp(relative_fitness, relative_rmse, max_iteration, check_every):
             raise ValueError(f"{n}={v}: expected >= {lo}")
 
 
-ESTIMATIONS = ("point_to_point", "point_to_plane")
+ESTIMATIONS = ("point_to_point", "point_to_plane", "colored")
+LAMBDA_GEOMETRIC = 0.968      # Open3D's default weight of the geometric residual in the coloured estimator
 
 
 def _check_estimation(estimation):
@@ -65,7 +68,15 @@ def _check_estimation(estimation):
         raise TypeError(f"estimation={estimation!r}: expected one of {ESTIMATIONS}")
     if estimation not in ESTIMATIONS:
         raise ValueError(f"estimation={estimation!r}: expected one of {ESTIMATIONS}")
-    return estimation == "point_to_plane"
+    return estimation
+
+
+def _check_lambda(lambda_geometric):
+    if isinstance(lambda_geometric, bool) or not isinstance(lambda_geometric, numbers.Real):
+        raise TypeError(f"lambda_geometric={lambda_geometric!r}: expected a number")
+    if not 0.0 <= lambda_geometric <= 1.0:      # (false for NaN)
+        raise ValueError(f"lambda_geometric={lambda_geometric}: expected 0 .. 1")
+    return float(lambda_geometric)
 
 
 def _rows(cloud):
@@ -200,17 +211,26 @@ def transform_points(points, transformation):
 
 
 class _Updater:
-    """gsr_icp_update - with the target's normals gsr_icp_update_plane - on fixed clouds: the workspace is allocated once"""
+    """gsr_icp_update - with the target's normals gsr_icp_update_plane, with `colored` = (source colours, target colours, target
+    gradients, lambda_geometric) besides them gsr_icp_update_colored - on fixed clouds: the workspace is allocated once"""
 
-    def __init__(self, src, tgt, normals=None):
+    def __init__(self, src, tgt, normals=None, colored=None):
         _C = _gsr()
-        self.src, self.tgt, self.normals = src, tgt, normals
+        self.src, self.tgt, self.normals, self.colored = src, tgt, normals, colored
+        size = _C.lib().gsr_icp_workspace_bytes if colored is None else _C.lib().gsr_icp_colored_workspace_bytes
         with _C.on_device(src.device):
-            self.ws = torch.empty(_C.lib().gsr_icp_workspace_bytes(int(src.shape[0])), dtype=torch.uint8, device=src.device)
+            self.ws = torch.empty(size(int(src.shape[0])), dtype=torch.uint8, device=src.device)
 
     def __call__(self, idx, Td, stats):
         _C = _gsr()
         with _C.on_device(self.src.device):
+            if self.colored is not None:
+                scol, tcol, grad, lam = self.colored
+                _C.check(_C.lib().gsr_icp_update_colored(int(self.src.shape[0]), _C.ptr(self.src), _C.ptr(scol),
+                                                         int(self.tgt.shape[0]), _C.ptr(self.tgt), _C.ptr(self.normals),
+                                                         _C.ptr(tcol), _C.ptr(grad), _C.ptr(idx), lam, _C.ptr(Td), _C.ptr(stats),
+                                                         _C.ptr(self.ws), self.ws.numel(), _C._stream()))
+                return
             if self.normals is not None:
                 _C.check(_C.lib().gsr_icp_update_plane(int(self.src.shape[0]), _C.ptr(self.src), int(self.tgt.shape[0]),
                                                        _C.ptr(self.tgt), _C.ptr(self.normals), _C.ptr(idx), _C.ptr(Td),
@@ -221,14 +241,32 @@ class _Updater:
                                              _C._stream()))
 
 
-def icp_update(source, target, correspondences, transformation, target_normals=None):
+def icp_update(source, target, correspondences, transformation, target_normals=None, source_colors=None, target_colors=None,
+               target_gradients=None, lambda_geometric=LAMBDA_GEOMETRIC):
     """One ICP update from given correspondences (int32 [Ps], -1 = none) -> (new transformation float64 [4,4] on the device,
     stats float64 [8] on the device: n, fitness, inlier_rmse, status, sum of squared distances, ...; include/gsr.h
     gsr_icp_update).  n, fitness and inlier_rmse describe the transformation that was passed in.  No read-back.
     target_normals ([Pt,3] float on the device): the point-to-plane update instead (gsr_icp_update_plane; stats[5] = the sum of
-    the squared point-to-plane residuals, status 1 below six correspondences, 2 when they do not fix all six unknowns)."""
+    the squared point-to-plane residuals, status 1 below six correspondences, 2 when they do not fix all six unknowns).
+    source_colors ([Ps,3]), target_colors and target_gradients ([Pt,3]; estimate_color_gradients of the target) besides the
+    normals: the coloured update (gsr_icp_update_colored; stats[5] and stats[6] = the sums of the squared geometric and
+    photometric residuals, unweighted).  Some of the four without the others is a ValueError."""
     T = _check_transform(transformation)
+    lam = _check_lambda(lambda_geometric)
+    given = [a is not None for a in (source_colors, target_colors, target_gradients)]
+    if any(given) and not (all(given) and target_normals is not None):
+        raise ValueError("icp_update: the coloured update needs target_normals, source_colors, target_colors and target_gradients "
+                         "together")
+    if all(given):      # (every shape before any device check)
+        for t, name, rows in ((source_colors, "source_colors", _rows(source)), (target_colors, "target_colors", _rows(target)),
+                              (target_gradients, "target_gradients", _rows(target))):
+            _check_rows3_shape(t, name, rows)
     nrm = _check_target_normals(target_normals, _rows(target))
+    colored = None
+    if all(given):
+        colored = (_check_rows3(source_colors, "source_colors", _rows(source)),
+                   _check_rows3(target_colors, "target_colors", _rows(target)),
+                   _check_rows3(target_gradients, "target_gradients", _rows(target)), lam)
     src, _ = _check_cloud(source, None, "icp_update")
     tgt, _ = _check_cloud(target, None, "icp_update")
     _nonempty(src, "icp_update", "source")
@@ -238,7 +276,10 @@ def icp_update(source, target, correspondences, transformation, target_normals=N
         raise ValueError(f"correspondences: expected an int32 tensor of shape ({int(src.shape[0])},)")
     Td = _device_T(T, src.device)
     stats = torch.zeros(8, dtype=torch.float64, device=src.device)
-    _Updater(src, tgt.to(src.device), None if nrm is None else nrm.to(src.device))(idx.to(src.device).contiguous(), Td, stats)
+    if colored is not None:
+        colored = tuple(c.to(src.device) for c in colored[:3]) + (lam,)
+    _Updater(src, tgt.to(src.device), None if nrm is None else nrm.to(src.device), colored)(idx.to(src.device).contiguous(), Td,
+                                                                                            stats)
     return Td, stats
 
 
@@ -282,7 +323,8 @@ def evaluate_registration(source, target, max_correspondence_distance, transform
 
 def registration_icp(source, target, max_correspondence_distance, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
                      max_iteration=30, check_every=1, index=None, use_order=None, estimation="point_to_point",
-                     target_normals=None, normal_radius=None, normal_max_nn=30):
+                     target_normals=None, normal_radius=None, normal_max_nn=30, source_colors=None, target_colors=None,
+                     lambda_geometric=LAMBDA_GEOMETRIC, target_gradients=None, gradient_radius=None, gradient_max_nn=30):
     """ICP of `source` onto `target` (both [P,3] float on the HIP device) from `init` (None = identity).
 
     Iteration k searches the neighbours under T_k, sums them and replaces T_k by T_{k+1} on the device; its fitness and RMSE
@@ -297,25 +339,62 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
     walls and road surfaces, where pairs slide along the plane, it needs far fewer iterations).  Point-to-plane takes
     `target_normals` ([Pt,3], one per target row) or estimates them once on the target with estimate_normals(normal_radius,
     normal_max_nn) - normal_radius is then required; both at once, or either with "point_to_point", is a ValueError.  An iteration with fewer than six correspondences, or with planes that do not
-    fix all six unknowns, leaves the transformation as it is.  Fitness and RMSE are the Euclidean ones for both estimators."""
+    fix all six unknowns, leaves the transformation as it is.  Fitness and RMSE are the Euclidean ones for every estimator.
+    "colored": the point-to-plane residual, weighted lambda_geometric, joined with a photometric one, weighted 1 -
+    lambda_geometric, measured in the target's tangent plane (include/gsr.h gsr_icp_update_colored) - on one plane, where
+    point-to-plane pairs slide, the texture fixes the remaining three unknowns.  It takes `source_colors` ([Ps,3]) and
+    `target_colors` ([Pt,3]), normals as point-to-plane does, and `target_gradients` ([Pt,3]) or `gradient_radius` to estimate
+    them once on the target with estimate_color_gradients(gradient_radius, gradient_max_nn) from those normals - the rules of
+    the normals: one of the two, and none of the colour arguments with another estimator."""
     _check_icp(relative_fitness, relative_rmse, max_iteration, check_every)
-    plane = _check_estimation(estimation)
+    est = _check_estimation(estimation)
+    plane, colored = est != "point_to_point", est == "colored"
     if not plane and (target_normals is not None or normal_radius is not None):
         raise ValueError('registration_icp: target_normals / normal_radius given, but estimation="point_to_point" uses no normals')
+    if not colored and (source_colors is not None or target_colors is not None or target_gradients is not None or
+                        gradient_radius is not None):
+        raise ValueError(f'registration_icp: colours / gradients given, but estimation="{est}" uses none')
     if target_normals is not None and normal_radius is not None:
         raise ValueError("registration_icp: target_normals and normal_radius both given - pass the normals or have them estimated")
-    nrm = _check_target_normals(target_normals, index.size if isinstance(index, NeighborIndex) else _rows(target))
+    target_rows = index.size if isinstance(index, NeighborIndex) else _rows(target)
+    if colored:      # (every shape before any device check)
+        for t, name, rows in ((source_colors, "source_colors", _rows(source)), (target_colors, "target_colors", target_rows),
+                              (target_gradients, "target_gradients", target_rows)):
+            if t is not None:
+                _check_rows3_shape(t, name, rows)
+    nrm = _check_target_normals(target_normals, target_rows)
     if plane and nrm is None:
         if normal_radius is None:
-            raise ValueError('registration_icp: estimation="point_to_plane" needs target_normals, or normal_radius to estimate them')
+            raise ValueError(f'registration_icp: estimation="{est}" needs target_normals, or normal_radius to estimate them')
         _check_normals(normal_radius, normal_max_nn)
+    lam = _check_lambda(lambda_geometric)
+    scol = tcol = grd = None
+    if colored:
+        if source_colors is None or target_colors is None:
+            raise ValueError('registration_icp: estimation="colored" needs source_colors and target_colors')
+        if target_gradients is not None and gradient_radius is not None:
+            raise ValueError("registration_icp: target_gradients and gradient_radius both given - pass the gradients or have "
+                             "them estimated")
+        if target_gradients is None:
+            if gradient_radius is None:
+                raise ValueError('registration_icp: estimation="colored" needs target_gradients, or gradient_radius to estimate '
+                                 'them')
+            _check_gradient(gradient_radius, gradient_max_nn, ("gradient_radius", "gradient_max_nn"))
+        scol = _check_rows3(source_colors, "source_colors", _rows(source))
+        tcol = _check_rows3(target_colors, "target_colors", target_rows)
+        grd = None if target_gradients is None else _check_rows3(target_gradients, "target_gradients", target_rows)
     src, index, md2, T = _prepare(source, target, max_correspondence_distance, init, index, "registration_icp")
     dev, P = src.device, int(src.shape[0])
     Td = _device_T(T, dev)
     order = index.query_order(src, Td) if (USE_QUERY_ORDER if use_order is None else use_order) else None
     if plane and nrm is None:
         nrm = estimate_normals(index.points, normal_radius, normal_max_nn)
-    updater = _Updater(src, index.points, nrm.to(dev) if plane else None)
+    if colored:
+        tcol = tcol.to(dev)
+        if grd is None:
+            grd = estimate_color_gradients(index.points, tcol, nrm.to(dev), gradient_radius, gradient_max_nn)
+    updater = _Updater(src, index.points, nrm.to(dev) if plane else None,
+                       (scol.to(dev), tcol, grd.to(dev), lam) if colored else None)
     idx = torch.empty(P, dtype=torch.int32, device=dev)
     stats = torch.zeros((max_iteration, 8), dtype=torch.float64, device=dev)
     iterations, converged = 0, False
@@ -594,6 +673,68 @@ def global_registration(source, target, voxel_size, seed=0, **ransac):
     return registration_ransac_based_on_feature_matching(src, tgt, feats[0], feats[1], True, 1.5 * v, **ransac)
 
 
+# what the drivers below decide themselves when they run the coloured (or the point-to-plane) estimator on clouds they down-sample
+_COLORED_OWN = ("target_normals", "normal_radius", "normal_max_nn", "source_colors", "target_colors", "target_gradients",
+                "gradient_radius", "gradient_max_nn")
+
+
+def registration_colored_icp(source, source_colors, target, target_colors, max_correspondence_distance, init=None,
+                             lambda_geometric=LAMBDA_GEOMETRIC, max_iteration=50, **icp):
+    """Open3D's call of the same name: registration_icp(estimation="colored") with Open3D's argument order and its 50
+    iterations.  The target's normals (`target_normals` or `normal_radius`) and colour gradients (`target_gradients` or
+    `gradient_radius`) and every other keyword go to registration_icp.  -> RegistrationResult."""
+    if "estimation" in icp:
+        raise TypeError('registration_colored_icp: the estimation is "colored" (registration_icp takes the others)')
+    return registration_icp(source, target, max_correspondence_distance, init=init, max_iteration=max_iteration,
+                            estimation="colored", source_colors=source_colors, target_colors=target_colors,
+                            lambda_geometric=lambda_geometric, **icp)
+
+
+def registration_multiscale(source, source_colors, target, target_colors, voxel_sizes, max_iterations, estimation="colored",
+                            init=None, lambda_geometric=LAMBDA_GEOMETRIC, **icp):
+    """Coarse-to-fine registration, Open3D's coloured-registration recipe: for every (voxel_size, max_iteration) of the two equally
+    long sequences, in the order given (coarse first), both clouds are down-sampled with voxel_down_sample (colours averaged),
+    normals and colour gradients of the down-sampled target are estimated with radius = 2 * voxel_size and max_nn = 30, and
+    registration_icp runs with max_correspondence_distance = voxel_size from the previous level's transformation (`init` for the
+    first).  estimation: "colored" (colours required), "point_to_plane" or "point_to_point" (colours may be None).  Further
+    keywords (relative_fitness, relative_rmse, check_every, use_order) go to every level.
+    -> (the last level's RegistrationResult - its correspondences number the rows of that level's down-sampled clouds -, the list of
+    every level's result)."""
+    est = _check_estimation(estimation)
+    lam = _check_lambda(lambda_geometric)
+    T = _check_transform(init, "init")
+    try:
+        voxels, iterations = list(voxel_sizes), list(max_iterations)
+    except TypeError:
+        raise TypeError("registration_multiscale: voxel_sizes and max_iterations are sequences, one entry per level") from None
+    if not voxels or len(voxels) != len(iterations):
+        raise ValueError(f"registration_multiscale: {len(voxels)} voxel sizes and {len(iterations)} iteration counts: expected "
+                         "as many of one as of the other, at least one")
+    voxels = [_check_voxel_size(v) for v in voxels]
+    iterations = [_check_int("max_iterations", n, 1) for n in iterations]
+    for k in ("index", "max_iteration", "estimation") + _COLORED_OWN:
+        if k in icp:
+            raise TypeError(f"registration_multiscale: {k} is decided per level, not accepted")
+    if (source_colors is None) != (target_colors is None):
+        raise ValueError("registration_multiscale: colours for both clouds or for neither")
+    if est == "colored" and source_colors is None:
+        raise ValueError('registration_multiscale: estimation="colored" needs the colours of both clouds')
+    src, scol = _check_cloud(source, source_colors, "registration_multiscale")
+    tgt, tcol = _check_cloud(target, target_colors, "registration_multiscale")
+    results = []
+    for v, n in zip(voxels, iterations):
+        sd, sc = voxel_down_sample(src, scol, v)
+        td, tc = voxel_down_sample(tgt, tcol, v)
+        level = dict(icp)
+        if est != "point_to_point":
+            level.update(normal_radius=2.0 * v, normal_max_nn=30)
+        if est == "colored":
+            level.update(gradient_radius=2.0 * v, gradient_max_nn=30, source_colors=sc, target_colors=tc, lambda_geometric=lam)
+        results.append(registration_icp(sd, td, v, init=T, max_iteration=n, estimation=est, **level))
+        T = results[-1].transformation
+    return results[-1], results
+
+
 def register_and_merge(source, source_colors, target, target_colors, voxel_size=0.05, max_correspondence_distance=None,
                        merge_voxel_size=None, estimation="point_to_point", global_init=False, global_seed=0, **icp):
     """The reference's pointcloud_registeration: down-sample both clouds (voxel_down_sample, voxel_size), ICP of the down-sampled
@@ -602,6 +743,9 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
     merge_voxel_size, down-sample the merged cloud.  Colours: both or neither.  -> (points, colors or None, result).
     estimation="point_to_plane": the down-sampled target's normals are estimated with radius = 2 * voxel_size, max_nn = 30 - the
     reference's estimate_normals calls at :193-196 - and the registration is point-to-plane.
+    estimation="colored": both clouds are down-sampled WITH their colours (averaged per voxel), normals and colour gradients of
+    the down-sampled target are estimated with radius = 2 * voxel_size, max_nn = 30, and the registration is the coloured one
+    (`lambda_geometric` may be passed on); colours are then required.
     global_init=True: ICP starts from a global registration of the down-sampled clouds instead of the identity - the reference's
     commented pipeline at :198-213: normals (radius 2 * voxel_size, max_nn 30, oriented towards the cloud's mean so that they
     turn with the cloud), compute_fpfh_feature (radius 5 * voxel_size, radius-only), mutual matching and
@@ -611,7 +755,8 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
         raise TypeError(f"global_init={global_init!r}: expected a bool")
     _check_seed(global_seed)
     v = _check_voxel_size(voxel_size)
-    plane = _check_estimation(estimation)
+    est = _check_estimation(estimation)
+    plane, colored = est == "point_to_plane", est == "colored"
     mv = None if merge_voxel_size is None else _check_voxel_size(merge_voxel_size)
     md = 5.0 * v if max_correspondence_distance is None else _check_distance("max_correspondence_distance",
                                                                              max_correspondence_distance, True)
@@ -621,10 +766,19 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
         raise TypeError("register_and_merge: starts from the identity and builds its own index (init / index not accepted)")
     if plane and ("target_normals" in icp or "normal_radius" in icp or "normal_max_nn" in icp):
         raise TypeError("register_and_merge: estimates the down-sampled target's normals itself (radius 2 * voxel_size, max_nn 30)")
+    if colored:
+        if any(k in icp for k in _COLORED_OWN):
+            raise TypeError("register_and_merge: the coloured registration takes the down-sampled clouds' colours and estimates "
+                            "normals and gradients itself (radius 2 * voxel_size, max_nn 30)")
+        if source_colors is None:
+            raise ValueError('register_and_merge: estimation="colored" needs the colours of both clouds')
     src, scol = _check_cloud(source, source_colors, "register_and_merge")
     tgt, tcol = _check_cloud(target, target_colors, "register_and_merge")
-    src_down, _ = voxel_down_sample(src, None, v)
-    tgt_down, _ = voxel_down_sample(tgt, None, v)
+    src_down, scol_down = voxel_down_sample(src, scol if colored else None, v)
+    tgt_down, tcol_down = voxel_down_sample(tgt, tcol if colored else None, v)
+    if colored:
+        icp = dict(icp, estimation="colored", normal_radius=2.0 * v, normal_max_nn=30, gradient_radius=2.0 * v, gradient_max_nn=30,
+                   source_colors=scol_down, target_colors=tcol_down)
     if plane:
         icp = dict(icp, estimation="point_to_plane", normal_radius=2.0 * v, normal_max_nn=30)
     if global_init:

@@ -3,7 +3,9 @@ the same search answered only for the rows from `first_query` on (new points aga
 the search for k = 1 .. 32 neighbours (every squared distance and / or the mean distance an outlier filter thresholds);
 `nn_search(query, target)`, the nearest row of ANOTHER cloud with its row number (csrc/registration.hip);
 `estimate_normals(points, radius, max_nn)`, the normal of every row from its hybrid neighbourhood (csrc/normals.hip);
-`compute_fpfh(points, normals, radius, max_nn)`, the 33-bin point feature histogram of every row (csrc/features.hip)."""
+`compute_fpfh(points, normals, radius, max_nn)`, the 33-bin point feature histogram of every row (csrc/features.hip);
+`estimate_color_gradients(points, colors, normals, radius, max_nn)`, the colour gradient of every row in its tangent plane
+(csrc/colored.hip)."""
 import math
 
 import torch
@@ -94,3 +96,10 @@ def compute_fpfh(points, normals, radius, max_nn=0, return_stats=False):
     `scene_utils.compute_fpfh_feature`."""
     from scene_utils.registration import compute_fpfh_feature as _compute_fpfh_feature
     return _compute_fpfh_feature(points, normals, radius, max_nn, return_stats)
+
+
+def estimate_color_gradients(points, colors, normals, radius, max_nn=30, return_stats=False):
+    """float32 [P,3]: per row the gradient of the intensity (r + g + b) / 3 over its tangent plane, from the neighbourhood of
+    `estimate_normals` - `scene_utils.estimate_color_gradients`."""
+    from scene_utils.pointcloud import estimate_color_gradients as _estimate_color_gradients
+    return _estimate_color_gradients(points, colors, normals, radius, max_nn, return_stats)

@@ -59,6 +59,8 @@ extern "C" {
  *    gsr_image_layout, gsr_image_decode, gsr_image_encode_rgb8, gsr_depth_register_workspace_bytes, gsr_depth_register: a
  *    sensor_msgs/Image byte buffer (colour, Bayer, depth) decoded on the device, its rgb8 inverse, and a depth image moved into
  *    the colour camera (additions only);
+ *    gsr_color_gradient_workspace_bytes, gsr_color_gradient, gsr_icp_colored_workspace_bytes, gsr_icp_update_colored: coloured
+ *    ICP - the colour gradient of a cloud and the joint geometric / photometric update (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -749,6 +751,58 @@ int gsr_estimate_normals(int64_t P, const float* points /*[P,3]*/, float radius,
                          const float* viewpoint /*HOST [3] or NULL*/, float* normals /*[P,3]*/, int32_t* count_out /*[P] or NULL*/,
                          float* eigenvalues_out /*[P,3] ascending, or NULL*/, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ---- coloured ICP (csrc/colored.hip, csrc/registration.hip) - Park, Zhou, Koltun 2017 as Open3D's
+ * registration_colored_icp states it: a colour gradient per target point, then updates that join the point-to-plane residual
+ * with a photometric one measured in the target's tangent plane.  Every result is a function of the input only, never of
+ * traversal, scheduling or launch shape; no float atomics, no allocation. ---- */
+
+/* Gradient of the intensity I = (((double)r + (double)g) + (double)b) / 3 over the tangent plane of every row.
+ * Neighbourhood: N_i of gsr_estimate_normals exactly (float32 d2, k = max_nn - 1, bound = min(r2, d_k), rows tied at the bound
+ * all belong - the departure from Open3D's hybrid search inherited from there - duplicates are members), max_nn in
+ * [4, GSR_KNN_K_MAX + 1].  A row whose point, normal or colour has a non-finite component is masked before the structure is built
+ * (it takes no part in the bounding box, the sort or the boxes, so no other row's bits depend on where it lies): gradient NaN,
+ * count 0, status 3, nobody's neighbour.
+ * Row i with normal n (taken as given: a unit vector is the caller's to provide) and n_i = |N_i|, all in float64: for every member
+ * j != i, in the order of the sorted structure (fixed for a given input: two runs give identical bits), delta = p_j - p_i per
+ * component in float32, promoted; u = delta - (delta.n) n with delta.n = (dx nx + dy ny) + dz nz; b = I_j - I_i.  M = sum u u^T
+ * (six sums), v = sum u b (three).  Then the constraint row (n_i - 1) n with right-hand side 0 (Open3D's
+ * InitializePointCloudForColoredICP): M += (n_i - 1)^2 n n^T.  M g = v is solved by LDL^T, g rounded to float32 once.
+ * status_out: 0 = solved; 1 = n_i < 4, gradient 0 (Open3D's rule); 2 = a pivot of the factorisation is not finite or is <= 1e-12 x
+ * its own diagonal entry of M (a collinear neighbourhood, say), gradient 0; 3 = masked.  count_out = n_i (0 for a masked row).
+ * Errors before any launch: P outside [1, 2^30 - 1], NULL points / colors / normals / gradient / workspace, radius <= 0 or NaN,
+ * max_nn outside [4, 33]: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_color_gradient_workspace_bytes(P):
+ * GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_color_gradient_workspace_bytes(int64_t P);
+int gsr_color_gradient(int64_t P, const float* points /*[P,3]*/, const float* colors /*[P,3]*/, const float* normals /*[P,3]*/,
+                       float radius, int32_t max_nn, float* gradient /*[P,3]*/, int32_t* count_out /*[P] or NULL*/,
+                       uint8_t* status_out /*[P] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One coloured ICP update on the device: gsr_icp_update_plane with a second residual per row.  With k = idx[i]: p =
+ * target[k], n = target_normals[k], d = target_gradient[k] (gsr_color_gradient of the target), I_s and I_t the intensities (as
+ * above) of source_colors[i] and target_colors[k].  Row i takes part iff 0 <= k < Pt and q = T s_i, p, n, d, I_s and I_t are all
+ * finite.  Everything is formed about the shift c of gsr_icp_update (the target point of the first row whose q and p are finite),
+ * q' = q - c, e = q - p, lambda = lambda_geometric, in float64:
+ *   geometric    r_G = sqrt(lambda) (e.n),                       J_G = sqrt(lambda) [q' x n, n];
+ *   photometric  q_proj - p = e - (e.n) n,  I_proj = I_t + d.(q_proj - p),  r_I = sqrt(1 - lambda) (I_s - I_proj),
+ *                m = -(I - n n^T) d = (d.n) n - d,              J_I = sqrt(1 - lambda) [q' x m, m]
+ * (Open3D's TransformationEstimationForColoredICP::ComputeTransformation; its default lambda is 0.968).  Over the n rows, with the
+ * summation structure of gsr_icp_update (deterministic, no float atomics), 31 sums per workgroup: the 21 entries of the upper
+ * triangle of J^T J and the 6 of J^T r over both residuals, n, sum |q - p|^2, sum (e.n)^2 and sum (I_s - I_proj)^2 - each of the
+ * last two 0 where its weight (lambda, 1 - lambda) is 0.  Solve and composition are the plane update's: LDL^T, x = (alpha, beta,
+ * gamma, t), dR = Rz(gamma) Ry(beta) Rx(alpha), dT = Tr(c) [dR, t] Tr(-c), T <- dT T (row 3 = 0 0 0 1).
+ * stats_dev[8] = n, fitness = n / Ps, inlier_rmse = sqrt(sum |q - p|^2 / n) (Euclidean; 0 with n = 0), status, sum |q - p|^2,
+ * sum r_G^2 / lambda, sum r_I^2 / (1 - lambda) (the unweighted residuals), 0 - all of the INCOMING T.  status: 0 = T updated; 1 = n
+ * < 6, T unchanged; 2 = a rejected pivot (gsr_icp_update_plane's rule: an untextured single plane, say), T unchanged.
+ * The workspace holds one sum more per workgroup than gsr_icp_workspace_bytes provides: it has its own query.
+ * Errors before any launch: sizes outside [1, 2^30 - 1], a NULL pointer, lambda_geometric outside [0, 1] or NaN:
+ * GSR_ERR_INVALID_ARGUMENT; workspace below gsr_icp_colored_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+size_t gsr_icp_colored_workspace_bytes(int64_t Ps);
+int gsr_icp_update_colored(int64_t Ps, const float* source /*[Ps,3]*/, const float* source_colors /*[Ps,3]*/, int64_t Pt,
+                           const float* target /*[Pt,3]*/, const float* target_normals /*[Pt,3]*/,
+                           const float* target_colors /*[Pt,3]*/, const float* target_gradient /*[Pt,3]*/,
+                           const int32_t* idx /*[Ps]*/, double lambda_geometric, double* T_dev /*[16] in/out*/,
+                           double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- global registration (csrc/features.hip) - what the reference's commented pipeline would take
  * from Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching.  Every result is a function of the input
