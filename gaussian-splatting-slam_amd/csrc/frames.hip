@@ -12,9 +12,14 @@
 //                       20 B read and 20 (1/4 + 1/16 + 1/64) B written per level-0 pixel.  Block origins are multiples of 32, so a
 //                       quad of any level never straddles two workgroups.
 //
-// Every result is a fixed sequence of float32 operations written with the __f*_rn intrinsics (the compiler may not contract
-// them): tests/frames_reference.py restates them in numpy, bit for bit for the pyramid.  No atomics, nothing read back.
+// Every result is a fixed sequence of separately rounded float32 operations, in the order include/gsr.h states:
+// tests/frames_reference.py restates them in numpy, bit for bit for both kernels.  No atomics, nothing read back.
 #include "gsr_common.h"
+
+// No implicit fma contraction in this file (as in preprocess.hip, exchange.hip and image.hip), and plain operators: the __f*_rn
+// intrinsics are inline functions of plain operators that carry the default contraction flags wherever they are called, so
+// "fx * xd + cx" built from them came out as one v_fma_f32 - under this pragma or not.
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -36,15 +41,13 @@ __global__ __launch_bounds__(256) void k_frame_undistort(GsrUndistortArgs a, con
     us = (float)u;
     vs = (float)v;
   } else {
-    const float x = __fdiv_rn(__fsub_rn((float)u, a.cxt), a.fxt), y = __fdiv_rn(__fsub_rn((float)v, a.cyt), a.fyt);
-    const float x2 = __fmul_rn(x, x), y2 = __fmul_rn(y, y), xy = __fmul_rn(x, y), r2 = __fadd_rn(x2, y2);
-    const float rho = __fadd_rn(1.0f, __fmul_rn(r2, __fadd_rn(a.k1, __fmul_rn(r2, __fadd_rn(a.k2, __fmul_rn(r2, a.k3))))));
-    const float xd = __fadd_rn(__fadd_rn(__fmul_rn(x, rho), __fmul_rn(__fmul_rn(2.0f, a.p1), xy)),
-                               __fmul_rn(a.p2, __fadd_rn(r2, __fmul_rn(2.0f, x2))));
-    const float yd = __fadd_rn(__fadd_rn(__fmul_rn(y, rho), __fmul_rn(a.p1, __fadd_rn(r2, __fmul_rn(2.0f, y2)))),
-                               __fmul_rn(__fmul_rn(2.0f, a.p2), xy));
-    us = __fadd_rn(__fmul_rn(a.fx, xd), a.cx);
-    vs = __fadd_rn(__fmul_rn(a.fy, yd), a.cy);
+    const float x = ((float)u - a.cxt) / a.fxt, y = ((float)v - a.cyt) / a.fyt;
+    const float x2 = x * x, y2 = y * y, xy = x * y, r2 = x2 + y2;
+    const float rho = 1.0f + r2 * (a.k1 + r2 * (a.k2 + r2 * a.k3));
+    const float xd = (x * rho + (2.0f * a.p1) * xy) + a.p2 * (r2 + 2.0f * x2);
+    const float yd = (y * rho + a.p1 * (r2 + 2.0f * y2)) + (2.0f * a.p2) * xy;
+    us = a.fx * xd + a.cx;
+    vs = a.fy * yd + a.cy;
   }
   const size_t plane = (size_t)a.H * a.W, pix = (size_t)v * a.W + u;
   // (a NaN coordinate fails every comparison: outside)
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(256) void k_frame_undistort(GsrUndistortArgs a, con
   }
   // 0 <= us <= Ws - 1 from here on: floor and ceil are pixel indices of the source, and so is floor(us + 0.5)
   const float x0f = floorf(us), y0f = floorf(vs);
-  const float ax = __fsub_rn(us, x0f), ay = __fsub_rn(vs, y0f);
+  const float ax = us - x0f, ay = vs - y0f;
   const int x0 = (int)x0f, y0 = (int)y0f;
   const int x1 = x0 + (ax > 0.0f ? 1 : 0), y1 = y0 + (ay > 0.0f ? 1 : 0);
   const size_t splane = (size_t)a.Hs * a.Ws;
@@ -68,12 +71,12 @@ __global__ __launch_bounds__(256) void k_frame_undistort(GsrUndistortArgs a, con
   for (int ch = 0; ch < 3; ch++) {
     const float* __restrict__ s = src_color + ch * splane;
     const float c00 = s[r0 + x0], c01 = s[r0 + x1], c10 = s[r1 + x0], c11 = s[r1 + x1];
-    const float top = __fadd_rn(c00, __fmul_rn(ax, __fsub_rn(c01, c00)));
-    const float bot = __fadd_rn(c10, __fmul_rn(ax, __fsub_rn(c11, c10)));
-    color[ch * plane + pix] = __fadd_rn(top, __fmul_rn(ay, __fsub_rn(bot, top)));
+    const float top = c00 + ax * (c01 - c00);
+    const float bot = c10 + ax * (c11 - c10);
+    color[ch * plane + pix] = top + ay * (bot - top);
   }
   if (DEPTH) {
-    const int xn = (int)floorf(__fadd_rn(us, 0.5f)), yn = (int)floorf(__fadd_rn(vs, 0.5f));
+    const int xn = (int)floorf(us + 0.5f), yn = (int)floorf(vs + 0.5f);
     depth[pix] = src_depth[(size_t)yn * a.Ws + xn];
   }
   mask[pix] = 1.0f;
@@ -95,21 +98,22 @@ struct GsrPyramidArgs {
 };
 
 __device__ __forceinline__ float pyr_color(float a, float b, float c, float d) {
-  return __fmul_rn(__fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d)), 0.25f);
+  return ((a + b) + (c + d)) * 0.25f;
 }
 
-// the mean of the valid (> 0) readings within the band of the smallest valid one, summed in the order a, b, c, d
+// the mean of the valid (> 0 and finite) readings within the band of the smallest valid one, summed in the order a, b, c, d
 __device__ __forceinline__ float pyr_depth(float a, float b, float c, float d, float band1) {
   const float big = __builtin_inff();
   const float m = fminf(fminf(a > 0.0f ? a : big, b > 0.0f ? b : big), fminf(c > 0.0f ? c : big, d > 0.0f ? d : big));
-  if (!(m < big)) return 0.0f;      // no valid reading (or only +inf ones)
-  const float lim = __fmul_rn(m, band1);
+  if (!(m < big)) return 0.0f;      // no valid reading: none > 0, or only +inf ones
+  // (a product that overflows takes every finite reading, and still no +inf one: +inf never enters a mean)
+  const float lim = fminf(m * band1, 3.402823466e+38f);
   float sum = 0.0f, n = 0.0f;
-  if (a > 0.0f && a <= lim) { sum = __fadd_rn(sum, a); n += 1.0f; }
-  if (b > 0.0f && b <= lim) { sum = __fadd_rn(sum, b); n += 1.0f; }
-  if (c > 0.0f && c <= lim) { sum = __fadd_rn(sum, c); n += 1.0f; }
-  if (d > 0.0f && d <= lim) { sum = __fadd_rn(sum, d); n += 1.0f; }
-  return __fdiv_rn(sum, n);          // (n >= 1: the smallest reading is within its own band)
+  if (a > 0.0f && a <= lim) { sum = sum + a; n += 1.0f; }
+  if (b > 0.0f && b <= lim) { sum = sum + b; n += 1.0f; }
+  if (c > 0.0f && c <= lim) { sum = sum + c; n += 1.0f; }
+  if (d > 0.0f && d <= lim) { sum = sum + d; n += 1.0f; }
+  return sum / n;                    // (n >= 1: the smallest reading is within its own band)
 }
 
 __device__ __forceinline__ float pyr_mask(float a, float b, float c, float d) {

@@ -1093,7 +1093,8 @@ int gsr_unproject_rgbd_k(const gsr_unproject_params_k* p, const float* depth, co
  *   us = fx xd + cx,  vs = fy yd + cy.
  * All-zero `dist` with a target K equal to the source K: the map is the identity, us = u, vs = v exactly.
  * mask = 1 iff 0 <= us <= src_w - 1 and 0 <= vs <= src_h - 1, i.e. the bilinear taps x0 = floor(us), x1 = ceil(us), y0 = floor(vs),
- * y1 = ceil(vs) all lie inside the source (on an integer coordinate the taps coincide); elsewhere mask, colour and depth are 0.
+ * y1 = ceil(vs) all lie inside the source (on an integer coordinate the taps coincide); elsewhere - a coordinate that overflowed
+ * to inf or NaN included - mask, colour and depth are 0.
  * colour: ax = us - x0, ay = vs - y0;  top = c(y0,x0) + ax (c(y0,x1) - c(y0,x0)),  bot = the same on row y1,  out = top + ay (bot - top)
  *   - at integer coordinates the source pixel, bit for bit.
  * depth: the source value at (floor(us + 0.5), floor(vs + 0.5)) - the nearest pixel, halves rounded up; never blended; z-depth is
@@ -1108,10 +1109,14 @@ int gsr_frame_undistort(int32_t src_w, int32_t src_h, const float* src_color, co
  * level l is w_l x h_l = (w_(l-1) / 2) x (h_(l-1) / 2), integer division - a trailing odd row or column is dropped - and its pixel
  * (X, Y) comes from the quad a = (2X, 2Y), b = (2X+1, 2Y), c = (2X, 2Y+1), d = (2X+1, 2Y+1) of the level below:
  *   colour  ((a + b) + (c + d)) 0.25, float32, in that order;
- *   depth   the valid readings are those > 0; m = the smallest; the result is the mean of the valid readings <= m (1 + depth_band)
- *           (the product rounded once), summed in the order a, b, c, d and divided by their count; 0 if none is valid: the near
- *           surface survives at a depth edge, a hole does not pull a reading towards 0;
- *   mask    1 iff all four are 1, else 0.
+ *   depth   the valid readings are those > 0 and < +inf (so NaN, -0.0, negative readings and +inf are not; a denormal is); m = the
+ *           smallest; the result is the mean of the valid readings <= m (1 + depth_band) (1 + depth_band rounded once, the
+ *           product rounded once; m itself always is one; a reading equal to the product is inside), summed in the order a, b,
+ *           c, d and divided by their count, every step in float32; 0 if none is valid: the near surface survives at a depth
+ *           edge, a hole does not pull a reading towards 0.  A quad whose only readings > 0 are +inf gives 0, as a quad without a
+ *           valid reading does, and +inf never enters a mean - not beside finite readings, and not when depth_band is so large
+ *           that the product overflows (then every finite valid reading is taken);
+ *   mask    1 iff all four are exactly 1, else 0 (0.5, 2 and NaN give 0).
  * A workgroup reads one 32 x 32 block of level 0 once and writes its part of every level (coarser levels reduced through LDS).
  * color_out / depth_out / mask_out: HOST arrays of `levels` device pointers (level 1 first); depth_out / mask_out may be NULL where
  * the input is.  Errors before the launch, GSR_ERR_INVALID_ARGUMENT: levels outside 1 .. 3, a level whose side would reach 0

@@ -297,3 +297,175 @@ def test_the_pyramid_reference_on_the_shared_scenes(size, levels):
         assert np.abs(c32 - c64).max() < 1e-6
         same = np.abs(d32 - d64) < 1e-5
         assert same.mean() > 0.98            # (a reading exactly at the band's edge may fall either way)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# what tests/test_frames_bits_gpu.py relies on, on the reference alone
+# ------------------------------------------------------------------------------------------------------------------------------
+def _ref32(case):
+    return FR.undistort_reference(case["color"], case["depth"], case["K"], case["D"], case["new_K"], case["W"], case["H"], np.float32)
+
+
+@pytest.mark.parametrize("dist", [FR.BARREL, FR.PINCUSHION], ids=["barrel", "pincushion"])
+def test_the_edge_size_undistort_cases_are_partly_inside(dist):
+    """W in {1, 63, 64, 65, 129} x H in {1, 3, 4, 5, 9}, k3, p1, p2 all non-zero: in the float32 restatement the inside share of
+    every target lies in 0.2 .. 0.98, so both mask values occur - except the 1 x 1 target, whose share can only be 0 or 1: its
+    one pixel is inside.  (With the shared scene's fixed new_K every one of these targets would lie wholly outside the source.)"""
+    assert dist[4] != 0 and dist[2] != 0 and dist[3] != 0
+    for W in FR.EDGE_W:
+        for H in FR.EDGE_H:
+            r = _ref32(FR.undistort_case(80, 60, W, H, dist))
+            share = float(r["mask"].mean())
+            if (W, H) == (1, 1):
+                assert share == 1.0
+                continue
+            assert 0.2 <= share <= 0.98, (W, H, share)
+            assert set(np.unique(r["mask"]).tolist()) == {0.0, 1.0}
+            assert (r["color"][:, r["mask"] == 0] == 0).all() and (r["depth"][r["mask"] == 0] == 0).all()
+    sc = FR.undistort_scene()
+    for W, H in ((1, 1), (63, 3), (64, 4), (65, 5)):
+        fixed = FR.undistort_reference(sc["color"], sc["depth"], sc["K"], sc["D"], sc["new_K"], W, H, np.float32)
+        assert fixed["mask"].sum() == 0
+
+
+def test_the_tiny_source_undistort_cases():
+    """1 x 1: the pixel (4, 4) alone is inside, at us = vs = 0 exactly, and carries the source pixel; 2 x 1 and 1 x 2: five pixels
+    of row / column 4, with fractional coordinates between the two source pixels."""
+    for Ws, Hs in FR.TINY_SOURCES:
+        case, n = FR.undistort_tiny_source_case(Ws, Hs)
+        r = _ref32(case)
+        assert int(r["mask"].sum()) == n and r["mask"][4, 4] == 1
+        if (Ws, Hs) == (1, 1):
+            assert r["us"][4, 4] == 0 and r["vs"][4, 4] == 0
+            assert np.array_equal(r["color"][:, 4, 4], case["color"][:, 0, 0]) and r["depth"][4, 4] == case["depth"][0, 0]
+        else:
+            line = r["us"][4, 2:7] if Ws == 2 else r["vs"][2:7, 4]
+            assert (r["mask"][4, 2:7] if Ws == 2 else r["mask"][2:7, 4]).all()
+            assert line[0] > 0 and line[-1] < 1 and len(set(line.tolist())) == 5
+            assert set(np.unique(r["depth"]).tolist()) == {0.0, float(case["depth"].flat[0]), float(case["depth"].flat[1])}
+
+
+@pytest.mark.parametrize("name", list(FR.EXACT_SHIFTS))
+def test_the_exact_coordinate_undistort_cases(name):
+    """undistort_map in float32 gives us = u + dx, vs = v + dy with no rounding at all, through the general path (not the identity:
+    K' differs), so every coordinate sits on the intended grid: all ties, all integers, the last column on src_w - 1.  The mask is
+    the one those coordinates give by hand, and on the integer grid the restatement copies the source."""
+    dx, dy, W, H = FR.EXACT_SHIFTS[name]
+    case = FR.undistort_exact_case(name)
+    assert all(v == 0 for v in case["D"]) and case["new_K"][:2] == case["K"][:2] and case["new_K"] != case["K"]
+    us, vs = FR.undistort_map(case["K"], case["D"], case["new_K"], W, H, np.float32)
+    u, v = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32))
+    assert us.dtype == np.float32 and np.array_equal(us, u + np.float32(dx)) and np.array_equal(vs, v + np.float32(dy))
+    inside = (u + dx >= 0) & (u + dx <= 15) & (v + dy >= 0) & (v + dy <= 11)
+    r = _ref32(case)
+    assert np.array_equal(r["mask"] == 1, inside) and inside.any()
+    if name.startswith("last"):
+        if "col" in name or "both" in name:
+            assert (us[:, -1] == case["Ws"] - 1).all() and inside[:, -1].any()
+        if "row" in name or "both" in name:
+            assert (vs[-1] == case["Hs"] - 1).all() and inside[-1].any()
+    if name in ("half_y", "half_x"):
+        assert (us[:, 0] == 0).all() if name == "half_y" else (vs[0] == 0).all()
+    if name == "minus_one":
+        assert not inside[:, 0].any() and not inside[0].any() and (us[:, 1] == 0).all() and (vs[1] == 0).all() and inside[1:, 1:].all()
+    if dx % 1 == 0 and dy % 1 == 0:            # the taps coincide: a copy, bit for bit
+        ys, xs = np.nonzero(inside)
+        sy, sx = ys + int(dy), xs + int(dx)
+        assert np.array_equal(r["color"][:, ys, xs], case["color"][:, sy, sx]) and np.array_equal(r["depth"][ys, xs], case["depth"][sy, sx])
+    else:                                      # ties: the nearest pixel is the one half a pixel UP (floor(us + 0.5))
+        ys, xs = np.nonzero(inside)
+        sy, sx = np.floor(ys + dy + 0.5).astype(int), np.floor(xs + dx + 0.5).astype(int)
+        assert np.array_equal(r["depth"][ys, xs], case["depth"][sy, sx])
+    assert len(np.unique(case["depth"])) == case["depth"].size          # a wrong nearest pixel is another value
+
+
+def test_the_overflow_undistort_case():
+    """Non-finite coordinates (inf and NaN) on part of the target, finite ones elsewhere; every non-finite pixel is outside and
+    exactly 0, and a large part of the rest is inside."""
+    case = FR.undistort_overflow_case()
+    assert all(np.isfinite(np.float32(v)) for v in case["D"] + case["K"] + case["new_K"])
+    r = _ref32(case)
+    bad = ~(np.isfinite(r["us"]) & np.isfinite(r["vs"]))
+    assert 0.1 < bad.mean() < 0.9 and np.isnan(r["us"]).any() and np.isinf(r["us"]).any() and np.isinf(r["vs"]).any()
+    assert (r["mask"][bad] == 0).all() and (r["color"][:, bad] == 0).all() and (r["depth"][bad] == 0).all()
+    assert 0.2 < r["mask"].mean() < 0.98 and r["mask"][~bad].mean() > 0.5
+
+
+def test_the_other_undistort_cases_have_both_mask_values():
+    cases = FR.undistort_named_cases()
+    for name in ("source_80x60", "source_80x60_pincushion", "upsample", "downsample", "special_values"):
+        r = _ref32(cases[name])
+        assert 0.2 <= r["mask"].mean() <= 0.98, (name, r["mask"].mean())
+    r = _ref32(cases["special_values"])
+    d = r["depth"]
+    assert np.isnan(r["color"]).any() and np.isinf(r["color"]).any()
+    assert np.isposinf(d).any() and np.isneginf(d).any() and (d == -1.5).any() and np.isnan(d).any() and (np.signbit(d) & (d == 0)).any()
+    full = FR.undistort_full_frame_case()
+    assert (full["W"], full["H"]) == (640, 480) and 0.5 < _ref32(full)["mask"].mean() < 0.99
+    # FR.differing: bits, with any NaN equal to a NaN
+    a = np.array([0.0, -0.0, np.nan, 1.0, np.inf], dtype=np.float32)
+    b = np.array([0.0, 0.0, -np.nan, np.nextafter(np.float32(1), np.float32(2)), np.inf], dtype=np.float32)
+    assert FR.differing(a, b).tolist() == [False, True, False, True, False]
+
+
+@pytest.mark.parametrize("band", [0.05, 0.0, 1e6, 3e38])
+def test_the_hand_built_pyramid_quads(band):
+    """depth_class_quads has the classes the GPU test is there for, and the reference treats each as include/gsr.h says - in both
+    dtypes, and at the stride of every level (the class sits in the level below the last)."""
+    q = FR.depth_class_quads(band)
+    nvalid = {k: sum(1 for r in v if 0 < r < np.inf) for k, v in q.items()}
+    assert [nvalid[f"valid{i}"] for i in range(5)] == [0, 1, 2, 3, 4]
+    assert all(np.isposinf(r) for r in q["inf_alone"]) and nvalid["inf_beside_finite"] == 1 and np.isposinf(q["inf_beside_finite"][0])
+    assert np.isnan(q["nan"][0]) and q["negative"][0] < 0 and np.signbit(q["minus_zero"][0]) and q["minus_zero"][0] == 0
+    assert 0 < q["denormal_alone"][0] < np.finfo(np.float32).tiny and len(set(q["equal4"])) == 1
+    one = np.float32(1) + np.float32(band)
+    with np.errstate(over="ignore"):
+        edge = np.float32(np.float32(2) * one)
+    assert q["at_edge"][1] == edge and (q["above_edge"][1] == np.nextafter(edge, np.float32(np.inf)) or np.isinf(edge))
+    for dtype in (np.float32, np.float64):
+        for level in (1, 2, 3):
+            color, depth, mask, where = FR.depth_class_scene(band, level)
+            assert depth.shape == (4 << level, 6 << level) and set(where) == set(q)
+            out = FR.pyramid_reference(color, depth, mask, level, band, dtype)[-1]
+            got = {k: out[1][rc] for k, rc in where.items()}
+            assert np.isfinite(out[1]).all()                                  # +inf (and NaN) never enter a mean
+            for k in ("valid0", "inf_alone", "inf_and_holes", "nan_alone", "negative_alone", "minus_zero_alone"):
+                assert got[k] == 0 and not np.signbit(got[k]), (k, got[k])
+            assert got["valid1"] == 2 and got["inf_beside_finite"] == 2 and got["equal4"] == 2.5
+            assert got["denormal_alone"] == q["denormal_alone"][0] and got["denormal_beside_finite"] == q["denormal_alone"][0]
+            if level == 1 and dtype == np.float32:                           # (deeper, an invalid square has become 0: still invalid)
+                if band == 0.05:
+                    assert got["at_edge"] == (np.float32(2) + edge) / np.float32(2) and got["above_edge"] == 2
+                    assert got["far"] == 2 and got["inf_beside_three"] == (np.float32(2) + np.float32(2.05)) / np.float32(2)
+                if band == 0.0:
+                    assert got["valid4"] == 2 and got["at_edge"] == 2 and got["denormals"] == q["denormals"][0]
+                if band >= 1e6:                                              # every finite valid reading is taken, +inf still not
+                    assert got["far"] == 2.75 and got["inf_beside_three"] == np.float32(7.55) / np.float32(3)
+            # mask values other than 1 give 0
+            m0 = np.stack(FR._quads(mask)) if level == 1 else None
+            if m0 is not None:
+                assert {0.5, 2.0}.issubset(set(np.unique(mask[~np.isnan(mask)]).tolist())) and np.isnan(mask).any()
+                assert np.array_equal(out[2] == 1, (m0 == 1).all(0)) and (out[2] == 1).any() and (out[2] == 0).any()
+
+
+@pytest.mark.parametrize("size", [(66, 65), (33, 33), (64, 32), (31, 3)])
+def test_the_float32_and_float64_pyramid_chains_agree(size):
+    """Colour and depth of the two chains within 1e-6 at every level, apart from quads with a reading within 1e-5 (relative) of
+    the band's edge in the float64 chain, and whatever such a quad feeds further up."""
+    Wp, Hp = size
+    color, depth, mask = FR.pyramid_scene(Wp, Hp, seed=Wp)
+    levels = FR.max_levels(Wp, Hp)
+    l32 = FR.pyramid_reference(color, depth, mask, levels)
+    l64 = FR.pyramid_reference(color, depth, mask, levels, dtype=np.float64)
+    below, tainted = depth.astype(np.float64), np.zeros(depth.shape, dtype=bool)
+    for (c32, d32, m32), (c64, d64, m64) in zip(l32, l64):
+        assert np.abs(c32 - c64).max() <= 1e-6 and np.array_equal(m32, m64)
+        q = np.stack(FR._quads(below))
+        m = np.where(q > 0, q, np.inf).min(0)
+        lim = m * 1.05
+        with np.errstate(invalid="ignore"):
+            near = ((q > 0) & (np.abs(q - lim) <= 1e-5 * lim)).any(0)
+        tainted = near | np.stack(FR._quads(tainted)).any(0)
+        assert tainted.mean() < 0.02
+        assert np.abs(d32 - d64)[~tainted].max() <= 1e-6, np.abs(d32 - d64)[~tainted].max()
+        below = d64

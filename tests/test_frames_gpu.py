@@ -179,9 +179,11 @@ def test_off_centre_camera_gradients_through_device_pose_camera():
 def test_undistort_matches_the_reference():
     """The shared scene (80 x 60 source, D = (-0.28, 0.07, 1e-3, -5e-4, 0), 72 x 56 target with its own K) through Frame.from_sensor.
     Colour where the mask is 1: within max(1e-6, 4 x the float32 restatement's own error against float64 on this input) of the
-    float64 reference (4: contraction differences between the compiler and numpy).  Mask: the reference's, except where a tap lies
-    within 1e-3 px of the source border.  Depth: the reference's exactly, target pixels within 1e-3 px of a nearest-pixel tie left
-    out (under 1 % of the image: tests/test_frames_cpu.py).
+    float64 reference (the factor 4 dates from when the compiler contracted the kernel's arithmetic to fma; frames.hip is now
+    compiled without contraction and equals the restatement bit for bit, so 1 would do: tests/test_frames_bits_gpu.py holds it
+    to that, with no pixel left out).  Mask: the float64 reference's, except where a tap lies within 1e-3 px of the source
+    border.  Depth: the float64 reference's exactly, target pixels within 1e-3 px of a nearest-pixel tie left out (under 1 % of
+    the image: tests/test_frames_cpu.py) - float32 and float64 coordinates may round to different sides there.
     Measured on an MI355X: see profiles/frames.txt."""
     sc = FR.undistort_scene()
     args = (sc["color"], sc["depth"], sc["K"], sc["D"], sc["new_K"], sc["W"], sc["H"])
