@@ -128,6 +128,9 @@ IMG_TILE_W = 256             # GSR_IMG_TILE_W: pixels of one row per workgroup o
 IMG_TILE_H = 1               # rows per workgroup: rows are not tiled (Bayer stages the rows above and below as halo)
 DEPTH_REGISTER_CAP = 8       # columns / rows of a footprint of gsr_depth_register before it is cut
 
+ODOMETRY_TILE_W = 32         # GSR_ODO_TILE_W x GSR_ODO_TILE_H: pixels per workgroup of gsr_odometry_prepare (csrc/odometry.hip)
+ODOMETRY_TILE_H = 8
+
 FPFH_WIDTH = 33              # GSR_FPFH_WIDTH
 FEATURE_NN_TILE = 128        # GSR_FEATURE_NN_TILE
 RANSAC_N_MAX = 8             # GSR_RANSAC_N_MAX
@@ -266,6 +269,14 @@ EXPORTS = {
     "gsr_icp_update_colored": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
+    # w, h, color, depth, mask, depth_min, depth_max, intensity_out, depth_out, grad_out, stream
+    "gsr_odometry_prepare": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    # w, h, K (host float64[4]), src_intensity, src_depth, tgt_intensity, tgt_depth, tgt_grad, lambda_geometric, depth_diff_max,
+    # apply, T_dev, stats_dev, workspace + bytes, stream
+    "gsr_odometry_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_odometry_update": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double)] + [C.c_void_p] * 5 +
+                            [C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # P, points, normals, radius, max_nn, fpfh, spfh_counts, count, workspace + bytes, stream
     "gsr_fpfh_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_compute_fpfh": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

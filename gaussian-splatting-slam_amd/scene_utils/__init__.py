@@ -24,3 +24,5 @@ from .registration import NeighborIndex, RegistrationResult, nn_search, transfor
 from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, process_pointcloud, accumulate_pointclouds, \
     encode_pointcloud2, Image, CameraInfo, decode_image, encode_image, camera_info_intrinsics, pose_from_transform, register_depth, \
     frame_from_messages, frame_from_visual_merged
+from .odometry import OdometryLevel, OdometryResult, prepare_odometry_level, odometry_update, rgbd_odometry, \
+    camera_after_odometry

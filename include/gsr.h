@@ -61,6 +61,8 @@ extern "C" {
  *    the colour camera (additions only);
  *    gsr_color_gradient_workspace_bytes, gsr_color_gradient, gsr_icp_colored_workspace_bytes, gsr_icp_update_colored: coloured
  *    ICP - the colour gradient of a cloud and the joint geometric / photometric update (additions only);
+ *    gsr_odometry_prepare, gsr_odometry_workspace_bytes, gsr_odometry_update: dense frame-to-frame RGB-D odometry on the pixel
+ *    grid - intensity / depth / Sobel planes and the hybrid photometric + depth Gauss-Newton update (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -803,6 +805,63 @@ int gsr_icp_update_colored(int64_t Ps, const float* source /*[Ps,3]*/, const flo
                            const float* target_colors /*[Pt,3]*/, const float* target_gradient /*[Pt,3]*/,
                            const int32_t* idx /*[Ps]*/, double lambda_geometric, double* T_dev /*[16] in/out*/,
                            double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- dense RGB-D odometry (csrc/odometry.hip) - the hybrid photometric + depth term of
+ * Steinbruecker et al. 2011 / Park et al. 2017, Open3D's compute_rgbd_odometry with the hybrid Jacobian: the coloured ICP above on
+ * the pixel grid, where the association is a projection instead of a search.  Every result is a function of the input only, never
+ * of scheduling or launch shape; no float atomics, no allocation, nothing read back. ---- */
+
+/* The planes one frame contributes, ONE launch, all float32, every operation rounded on its own (no contraction).
+ * seen(x,y) = mask is NULL or mask(x,y) == 1 exactly; ok(x,y) = seen and depth finite and depth_min < depth <= depth_max.
+ *   depth_out     = depth where ok, NaN elsewhere;
+ *   intensity_out = ((r + g) + b) / 3.0f where seen, NaN elsewhere (gsr_frame_undistort writes colour 0 outside the mask: that must
+ *                   not become an edge); a non-finite colour component gives what IEEE arithmetic gives;
+ *   grad_out      = four planes dI/dx, dI/dy, dD/dx, dD/dy: the 3 x 3 Sobel operator on intensity_out resp. depth_out times 0.125.
+ *                   With P = the plane:  d/dx = (((P(x+1,y-1) - P(x-1,y-1)) + 2.0f (P(x+1,y) - P(x-1,y))) + (P(x+1,y+1) - P(x-1,y+1)))
+ *                   * 0.125f, and d/dy its transpose: (((P(x-1,y+1) - P(x-1,y-1)) + 2.0f (P(x,y+1) - P(x,y-1))) + (P(x+1,y+1) -
+ *                   P(x+1,y-1))) * 0.125f.  Pixels on the image border (x = 0, y = 0, x = w - 1, y = h - 1) get NaN in all four;
+ *                   inside, an invalid tap spreads by IEEE NaN arithmetic alone.  NULL: not wanted (the source frame of
+ *                   gsr_odometry_update needs only the first two outputs).
+ * Errors before the launch: NULL color / depth / intensity_out / depth_out, a side < 1 or more than 2^30 - 1 pixels, depth_min or
+ * depth_max NaN, depth_max <= depth_min: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_odometry_prepare(int32_t w, int32_t h, const float* color /*[3,h,w]*/, const float* depth /*[h,w]*/,
+                         const float* mask /*[h,w] or NULL*/, float depth_min, float depth_max, float* intensity_out /*[h,w]*/,
+                         float* depth_out /*[h,w]*/, float* grad_out /*[4,h,w] or NULL*/, void* stream);
+
+/* One Gauss-Newton step for T (float64 row-major 4 x 4, source-camera to target-camera coordinates), both images w x h with
+ * K = (fx, fy, cx, cy) (HOST float64[4], pixel centres at integer coordinates), planes from gsr_odometry_prepare.  For the source
+ * pixel (x, y), everything in float64 from the float32 planes, every operation rounded on its own, in this order:
+ *   1. d = src_depth, I_s = src_intensity: both finite;
+ *   2. P = (d ((x - cx) / fx), d ((y - cy) / fy), d);
+ *   3. Q = R P + t, component k = ((T[k,0] Px + T[k,1] Py) + T[k,2] Pz) + T[k,3];
+ *   4. Qz finite and > 0;
+ *   5. u = fx (Qx / Qz) + cx, v = fy (Qy / Qz) + cy;
+ *   6. ui = floor(u + 0.5), vi = floor(v + 0.5), 0 <= ui <= w - 1 and 0 <= vi <= h - 1 compared as doubles (a NaN, an infinity or
+ *      a value beyond an int drops out here, before any conversion);
+ *   7. at (vi, ui): d_t = tgt_depth, I_t = tgt_intensity and the four components gIx, gIy, gDx, gDy of tgt_grad all finite;
+ *   8. |d_t - Qz| <= depth_diff_max.
+ * The pixels that pass are the n participants.  With a = fx / Qz, b = fy / Qz, lambda = lambda_geometric:
+ *   depth        r_D = d_t - Qz,   c_D = (gDx a, gDy b, -(((gDx a) Qx + (gDy b) Qy) / Qz) - 1),   J_D = sqrt(lambda) [Q x c_D, c_D];
+ *   photometric  r_I = I_t - I_s,  c_I = (gIx a, gIy b, -(((gIx a) Qx + (gIy b) Qy) / Qz)),       J_I = sqrt(1 - lambda) [Q x c_I, c_I]
+ * (Q x c = (Qy c2 - Qz c1, Qz c0 - Qx c2, Qx c1 - Qy c0), each entry then times the weight), the residuals weighted by the same
+ * factors.  Over the participants, with the summation structure of gsr_icp_update (at most 256 workgroups over fixed slices of
+ * the row-major pixel index, a fixed in-wave butterfly, wave and workgroup sums added in order), 30 sums: the 21 entries of the
+ * upper triangle of J^T J (J_D[p] J_D[q] + J_I[p] J_I[q]) and the 6 of J^T r (J_D[p] r_D' + J_I[p] r_I', the weighted residuals), n,
+ * sum r_D^2 and sum r_I^2 - the last two unweighted, each 0 where its weight (lambda, 1 - lambda) is 0.  One thread solves J^T J x =
+ * -J^T r by LDL^T with the pivot rule of gsr_icp_update_plane; x = (alpha, beta, gamma, t), dR = Rz(gamma) Ry(beta) Rx(alpha),
+ * T <- [dR, t] T (row 3 = 0 0 0 1; no shift: camera coordinates lie near the origin).
+ * stats_dev[8] = n, fitness = n / (w h), inlier_rmse = sqrt(sum r_D^2 / n) (0 with n = 0), status, sum r_D^2, sum r_I^2, 0, 0 - all
+ * of the INCOMING T.  status: 0 = T updated; 1 = n < 6; 2 = a rejected pivot (a fronto-parallel untextured wall, say).  With
+ * status != 0, or with apply == 0 (stats and status only), T_dev is left bit for bit as it was.
+ * Errors before any launch: a NULL pointer, a side < 1 or more than 2^30 - 1 pixels, K not finite or fx, fy not > 0,
+ * lambda_geometric outside [0, 1] or NaN, depth_diff_max not > 0: GSR_ERR_INVALID_ARGUMENT; workspace below
+ * gsr_odometry_workspace_bytes(w, h): GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_odometry_workspace_bytes(int32_t w, int32_t h);
+int gsr_odometry_update(int32_t w, int32_t h, const double* K /*HOST [4]*/, const float* src_intensity /*[h,w]*/,
+                        const float* src_depth /*[h,w]*/, const float* tgt_intensity /*[h,w]*/, const float* tgt_depth /*[h,w]*/,
+                        const float* tgt_grad /*[4,h,w]*/, double lambda_geometric, double depth_diff_max, int32_t apply,
+                        double* T_dev /*[16] in/out*/, double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ---- global registration (csrc/features.hip) - what the reference's commented pipeline would take
  * from Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching.  Every result is a function of the input
