@@ -330,6 +330,26 @@ __device__ __forceinline__ void gsr_block_sum(double (&s)[N]) {
 #pragma unroll
   for (int a = 0; a < N; a++) s[a] = ((sh[0][a] + sh[1][a]) + sh[2][a]) + sh[3][a];
 }
+// The two ends of a sum over a whole launch: every workgroup leaves its block sum as row blockIdx.x of `part` ...
+template <int N>
+__device__ __forceinline__ void gsr_block_sum_store(double (&s)[N], double* __restrict__ part) {
+  gsr_block_sum(s);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int a = 0; a < N; a++) part[(size_t)blockIdx.x * N + a] = s[a];
+  }
+}
+// ... and one workgroup adds the `rows` rows: thread t takes rows t, t + 256, ... in order, then the block sum (valid in thread 0)
+template <int N>
+__device__ __forceinline__ void gsr_block_sum_rows(double (&s)[N], const double* __restrict__ part, uint32_t rows) {
+#pragma unroll
+  for (int a = 0; a < N; a++) s[a] = 0.0;
+  for (uint32_t b = threadIdx.x; b < rows; b += 256u) {
+#pragma unroll
+    for (int a = 0; a < N; a++) s[a] += part[(size_t)b * N + a];
+  }
+  gsr_block_sum(s);
+}
 
 // Number of instances the binning / compositing stages work on: min(num_rendered, capacity).  num_rendered lives on the
 // DEVICE (geometry state `meta[2..3]`, 64-bit, written by k_sum_tiles); `cap` is what the caller's binning state was sized

@@ -1,7 +1,7 @@
 // odometry.hip - dense frame-to-frame RGB-D odometry on the pixel grid: the hybrid photometric + depth term of Steinbruecker et
 // al. 2011 / Park et al. 2017 (what Open3D offers as compute_rgbd_odometry with the hybrid Jacobian).  The image-grid sibling of
-// the coloured ICP of registration.hip: the same 6-unknown Gauss-Newton step, the same summation and solve
-// (gsr_block_sum, icp_solve6_compose), and the association by projection instead of by search.
+// the coloured ICP of registration.hip: the same 6-unknown Gauss-Newton step, the same summation and the same final kernel
+// (gsr_block_sum_store, k_gn6_final of solve6_common.h), and the association by projection instead of by search.
 //
 // gsr_odometry_prepare: ONE launch, a workgroup = a 32 x 8 tile of pixels.  Every thread forms the intensity and the validated
 //   depth of its pixel (and, 340 cells over 256 threads, of the one-pixel halo) into two LDS planes; the centre cells are written
@@ -11,8 +11,8 @@
 //
 // gsr_odometry_update: <= 256 workgroups over fixed slices of the row-major pixel index; per source pixel the warp, the tests, the
 //   two residuals and their Jacobians in float64 in the order include/gsr.h states, 30 float64 sums per thread, gsr_block_sum
-//   (a fixed butterfly, the wave sums in order), one row of partials per workgroup; then one workgroup adds the rows and one thread
-//   solves and composes.  No float atomics, nothing read back, no allocation.  Two source planes are streamed and six target
+//   (a fixed butterfly, the wave sums in order), one row of partials per workgroup; then the shared final kernel: one workgroup adds
+//   the rows and one thread solves and composes, into a copy that reaches T only with status 0 and `apply`.  No float atomics, nothing read back, no allocation.  Two source planes are streamed and six target
 //   planes gathered per pixel; the gather is smooth (neighbouring lanes read neighbouring target pixels).
 #include "gsr_common.h"
 #include "solve6_common.h"
@@ -23,21 +23,11 @@
 
 #define GSR_ODO_TILE_W 32
 #define GSR_ODO_TILE_H 8
-#define GSR_ODO_BLOCKS 256
-#define GSR_ODO_SUMS 30      // n, sum r_D^2, sum r_I^2 (both unweighted), J^T r [6], upper triangle of J^T J [21]
+#define GSR_ODO_H 3                                // n, sum r_D^2, sum r_I^2 (both unweighted)
+#define GSR_ODO_SUMS (GSR_ODO_H + GSR_GN6_TERMS)   // ... J^T r [6], upper triangle of J^T J [21]
+// (the workspace: gn_layout(GSR_ODO_SUMS, false) of solve6_common.h - the rows of partial sums, no shift)
 
 namespace {
-
-struct GsrOdoLayout {
-  size_t part;       // double[GSR_ODO_BLOCKS][GSR_ODO_SUMS]
-  size_t total;
-};
-inline GsrOdoLayout odo_layout() {
-  GsrOdoLayout L;
-  L.part = 0;
-  L.total = gsr_align((size_t)GSR_ODO_BLOCKS * GSR_ODO_SUMS * 8);
-  return L;
-}
 
 inline bool odo_bad_image(int32_t w, int32_t h) { return w < 1 || h < 1 || (int64_t)w * h > 0x3FFFFFFF; }
 
@@ -163,58 +153,10 @@ __global__ __launch_bounds__(256) void k_odometry_partial(GsrOdoArgs A, const fl
       for (int q = p; q < 6; q++) s[o++] += JD[p] * JD[q] + JI[p] * JI[q];
     }
   }
-  gsr_block_sum(s);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int a = 0; a < GSR_ODO_SUMS; a++) part[(size_t)blockIdx.x * GSR_ODO_SUMS + a] = s[a];
-  }
+  gsr_block_sum_store(s, part);
 }
 
-// one workgroup: the partials, then thread 0 solves and composes as the plane update does (about the origin: camera coordinates)
-__global__ __launch_bounds__(256) void k_odometry_final(uint32_t nblk, double pixels, int apply, const double* __restrict__ part,
-                                                        double* __restrict__ T_dev, double* __restrict__ stats) {
-  // thread 0 only: indexed at run time, which registers cannot be.  Tn: the copy the step is composed into (T_dev itself is
-  // written only when the step is taken)
-  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6], zero[3], Tn[16];
-  double s[GSR_ODO_SUMS];
-#pragma unroll
-  for (int a = 0; a < GSR_ODO_SUMS; a++) s[a] = 0.0;
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-#pragma unroll
-    for (int a = 0; a < GSR_ODO_SUMS; a++) s[a] += part[(size_t)b * GSR_ODO_SUMS + a];
-  }
-  gsr_block_sum(s);
-  if (threadIdx.x != 0) return;
-  const double n = s[0];
-  stats[0] = n;
-  stats[1] = n / pixels;
-  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
-  stats[4] = s[1];
-  stats[5] = s[2];
-  stats[6] = stats[7] = 0.0;
-  if (n < 6.0) {
-    stats[3] = 1.0;      // fewer participants than unknowns: T stays
-    return;
-  }
-  {
-    int o = 9;
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      g[a] = -s[3 + a];
-#pragma unroll
-      for (int b = a; b < 6; b++) {
-        A[a][b] = A[b][a] = s[o];
-        o++;
-      }
-    }
-  }
-  zero[0] = zero[1] = zero[2] = 0.0;
-  for (int i = 0; i < 16; i++) Tn[i] = T_dev[i];
-  icp_solve6_compose(A, L, D, g, x, zero, Tn, stats);      // (sets stats[3])
-  if (apply && stats[3] == 0.0) {
-    for (int i = 0; i < 16; i++) T_dev[i] = Tn[i];
-  }
-}
+// (the final kernel: k_gn6_final of solve6_common.h, about the origin - camera coordinates - and with the caller's `apply`)
 
 inline bool finite_d(double v) { return fabs(v) <= 1.7e308; }      // false for NaN and +-inf
 
@@ -239,8 +181,8 @@ extern "C" int gsr_odometry_prepare(int32_t w, int32_t h, const float* color, co
 
 extern "C" size_t gsr_odometry_workspace_bytes(int32_t w, int32_t h) {
   (void)w;
-  (void)h;      // (the partial sums of at most GSR_ODO_BLOCKS workgroups: the size does not grow with the image)
-  return odo_layout().total;
+  (void)h;      // (the partial sums of at most GSR_GN_BLOCKS workgroups: the size does not grow with the image)
+  return gn_layout(GSR_ODO_SUMS, false).total;
 }
 
 extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const float* src_intensity, const float* src_depth,
@@ -258,7 +200,7 @@ extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const 
                   "0 .. 1; depth_diff_max = %g: expected > 0)", K[0], K[1], K[2], K[3], lambda_geometric, depth_diff_max);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrOdoLayout L = odo_layout();
+  const GsrGnLayout L = gn_layout(GSR_ODO_SUMS, false);
   if (workspace_bytes < L.total) {
     gsr_set_error("odometry_update: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
     return GSR_ERR_STATE_TOO_SMALL;
@@ -271,11 +213,10 @@ extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const 
   A.depth_diff_max = depth_diff_max;
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)((char*)workspace + L.part);
-  const uint32_t N = (uint32_t)w * (uint32_t)h, nblk = (N + 255u) / 256u;
-  const uint32_t sblk = nblk < (uint32_t)GSR_ODO_BLOCKS ? nblk : (uint32_t)GSR_ODO_BLOCKS;
+  const uint32_t N = (uint32_t)w * (uint32_t)h, sblk = gn_partial_blocks(N);
   GSR_LAUNCH("odometry_partial", k_odometry_partial, dim3(sblk), dim3(256), 0, st, A, src_intensity, src_depth, tgt_intensity,
              tgt_depth, tgt_grad, (const double*)T_dev, part);
-  GSR_LAUNCH("odometry_final", k_odometry_final, dim3(1), dim3(256), 0, st, sblk, (double)N, (int)apply, (const double*)part, T_dev,
-             stats_dev);
+  GSR_LAUNCH("odometry_final", k_gn6_final<GSR_ODO_H>, dim3(1), dim3(256), 0, st, sblk, (double)N, (int)apply, (const double*)part,
+             (const double*)nullptr, T_dev, stats_dev);
   return gsr_launch_status("odometry_update launch");
 }

@@ -231,23 +231,15 @@ __global__ __launch_bounds__(256) void k_outlier_partial(uint32_t P, const float
       }
     }
   }
-  gsr_block_sum(s);
-  if (threadIdx.x == 0) {
-    part[2 * (size_t)blockIdx.x] = s[0];
-    part[2 * (size_t)blockIdx.x + 1] = s[1];
-  }
+  gsr_block_sum_store(s, part);
 }
 
 // one workgroup: MODE 0 -> stats[0] = n_valid, stats[1] = mu; MODE 1 -> stats[2] = sigma, stats[3] = threshold
 template <int MODE>
 __global__ __launch_bounds__(256) void k_outlier_final(uint32_t nblk, const double* __restrict__ part, double std_ratio,
                                                        double* __restrict__ stats) {
-  double s[2] = {0.0, 0.0};      // the sum, the count
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-    s[0] += part[2 * (size_t)b];
-    s[1] += part[2 * (size_t)b + 1];
-  }
-  gsr_block_sum(s);
+  double s[2];      // the sum, the count
+  gsr_block_sum_rows(s, part, nblk);
   if (threadIdx.x != 0) return;
   if (MODE == 0) {
     stats[0] = s[1];

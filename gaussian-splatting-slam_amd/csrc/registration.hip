@@ -26,16 +26,19 @@
 //
 // gsr_icp_update_plane / gsr_icp_update_colored: the same shift and summation structure over the point-to-plane residual - and,
 //   for the coloured update, the photometric residual in the target's tangent plane beside it (the gradient of colored.hip) -
-//   then one 6 x 6 LDL^T solve and dT = Tr(c) [Rz Ry Rx, t] Tr(-c), shared by both (icp_solve6_compose).
+//   then the final kernel all 6-unknown updates share (k_gn6_final, solve6_common.h: the rows of partial sums, the stats, the
+//   n < 6 rule, one 6 x 6 LDL^T solve and dT = Tr(c) [Rz Ry Rx, t] Tr(-c)).  The three entries share their host prelude too
+//   (icp_begin: the workspace check, the shift launch).
 #include "knn_common.h"
 #include "horn_common.h"
 #include "rigid_common.h"
 #include "solve6_common.h"
 
-#define GSR_ICP_BLOCKS 256
-#define GSR_ICP_SUMS 17            // n, sum d2, q[3], p[3], q p^T [9]
-#define GSR_ICP_PLANE_SUMS 30      // n, sum d2, sum r^2, J^T r [6], upper triangle of J^T J [21]
-#define GSR_ICP_COLORED_SUMS 31    // n, sum d2, sum r_G^2, sum r_I^2 (both unweighted), J^T r [6], upper triangle of J^T J [21]
+#define GSR_ICP_SUMS 17                                  // n, sum d2, q[3], p[3], q p^T [9]
+#define GSR_ICP_PLANE_H 3                                // n, sum d2, sum r^2
+#define GSR_ICP_COLORED_H 4                              // n, sum d2, sum r_G^2, sum r_I^2 (both unweighted)
+#define GSR_ICP_PLANE_SUMS (GSR_ICP_PLANE_H + GSR_GN6_TERMS)          // ... J^T r [6], upper triangle of J^T J [21]
+#define GSR_ICP_COLORED_SUMS (GSR_ICP_COLORED_H + GSR_GN6_TERMS)
 
 // (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
 
@@ -56,28 +59,8 @@ static inline GsrNnOrderLayout nn_order_layout(size_t P) {
   return L;
 }
 
-// workspace of gsr_icp_update
-struct GsrIcpLayout {
-  size_t shift;      // double[4]: the shift, [3] = 1 when a valid row exists
-  size_t part;       // double[GSR_ICP_BLOCKS][GSR_ICP_PLANE_SUMS] (the point-to-point update uses GSR_ICP_SUMS of each row's)
-  size_t total;
-};
-static inline GsrIcpLayout icp_layout() {
-  GsrIcpLayout L;
-  L.shift = 0;
-  L.part = 256;
-  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_PLANE_SUMS * 8);
-  return L;
-}
-// workspace of gsr_icp_update_colored: the same two parts, GSR_ICP_COLORED_SUMS per workgroup (a size of its own: the two entries
-// above keep theirs)
-static inline GsrIcpLayout icp_colored_layout() {
-  GsrIcpLayout L;
-  L.shift = 0;
-  L.part = 256;
-  L.total = 256 + gsr_align((size_t)GSR_ICP_BLOCKS * GSR_ICP_COLORED_SUMS * 8);
-  return L;
-}
+// workspace of gsr_icp_update and gsr_icp_update_plane: gn_layout(GSR_ICP_PLANE_SUMS, true) (solve6_common.h; the point-to-point
+// update uses GSR_ICP_SUMS of each row's); of gsr_icp_update_colored: gn_layout(GSR_ICP_COLORED_SUMS, true), a size of its own
 
 // ---- q = (float)(R s + t): RegT, reg_load, reg_apply (rigid_common.h, shared with pointcloud2.hip) -----------------------------
 
@@ -219,11 +202,7 @@ __global__ __launch_bounds__(256) void k_icp_partial(uint32_t Ps, const float* _
       for (int b = 0; b < 3; b++) s[8 + 3 * a + b] += q[a] * p[b];
     }
   }
-  gsr_block_sum(s);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_SUMS + a] = s[a];
-  }
+  gsr_block_sum_store(s, part);
 }
 
 // one workgroup: the partials, then thread 0 solves and composes
@@ -232,20 +211,10 @@ __global__ __launch_bounds__(256) void k_icp_final(uint32_t nblk, uint32_t Ps, c
                                                    double* __restrict__ stats) {
   __shared__ double A[4][4], V[4][4];      // thread 0 only: indexed at run time, which registers cannot be
   double s[GSR_ICP_SUMS];
-#pragma unroll
-  for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] = 0.0;
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_SUMS + a];
-  }
-  gsr_block_sum(s);
+  gsr_block_sum_rows(s, part, nblk);
   if (threadIdx.x != 0) return;
+  gn_stats_header<2>(s, (double)Ps, stats);      // (n, sum d2)
   const double n = s[0];
-  stats[0] = n;
-  stats[1] = n / (double)Ps;
-  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
-  stats[4] = s[1];
-  stats[5] = stats[6] = stats[7] = 0.0;
   if (n < 3.0) {
     stats[3] = 1.0;      // too few correspondences: T stays
     return;
@@ -323,54 +292,10 @@ __global__ __launch_bounds__(256) void k_icp_plane_partial(uint32_t Ps, const fl
       for (int b = a; b < 6; b++) s[o++] += J[a] * J[b];
     }
   }
-  gsr_block_sum(s);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_PLANE_SUMS + a] = s[a];
-  }
+  gsr_block_sum_store(s, part);
 }
 
-// (the solve and the composition shared by the plane update, the coloured one and odometry.hip: icp_solve6_compose, solve6_common.h)
-
-// one workgroup: the partials, then thread 0 solves and composes
-__global__ __launch_bounds__(256) void k_icp_plane_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
-                                                         const double* __restrict__ shift, double* __restrict__ T_dev,
-                                                         double* __restrict__ stats) {
-  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
-  double s[GSR_ICP_PLANE_SUMS];
-#pragma unroll
-  for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] = 0.0;
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_PLANE_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_PLANE_SUMS + a];
-  }
-  gsr_block_sum(s);
-  if (threadIdx.x != 0) return;
-  const double n = s[0];
-  stats[0] = n;
-  stats[1] = n / (double)Ps;
-  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
-  stats[4] = s[1];
-  stats[5] = s[2];
-  stats[6] = stats[7] = 0.0;
-  if (n < 6.0) {
-    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
-    return;
-  }
-  {
-    int o = 9;
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      g[a] = -s[3 + a];
-#pragma unroll
-      for (int b = a; b < 6; b++) {
-        A[a][b] = A[b][a] = s[o];
-        o++;
-      }
-    }
-  }
-  icp_solve6_compose(A, L, D, g, x, shift, T_dev, stats);
-}
+// (the final kernel shared by the plane update, the coloured one and odometry.hip: k_gn6_final, solve6_common.h)
 
 // ---- one coloured update (Park, Zhou, Koltun 2017; Open3D's TransformationEstimationForColoredICP) -------------------------------------
 // I = (r + g + b) / 3 in float64, left to right (colored.hip forms the target's gradient from the same value)
@@ -430,52 +355,32 @@ __global__ __launch_bounds__(256) void k_icp_colored_partial(uint32_t Ps, const 
       for (int b = a; b < 6; b++) s[o++] += JG[a] * JG[b] + JI[a] * JI[b];
     }
   }
-  gsr_block_sum(s);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) part[(size_t)blockIdx.x * GSR_ICP_COLORED_SUMS + a] = s[a];
-  }
+  gsr_block_sum_store(s, part);
 }
 
-// one workgroup: the partials, then thread 0 solves and composes as the plane update does
-__global__ __launch_bounds__(256) void k_icp_colored_final(uint32_t nblk, uint32_t Ps, const double* __restrict__ part,
-                                                           const double* __restrict__ shift, double* __restrict__ T_dev,
-                                                           double* __restrict__ stats) {
-  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6];      // thread 0 only: indexed at run time, which registers cannot be
-  double s[GSR_ICP_COLORED_SUMS];
-#pragma unroll
-  for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) s[a] = 0.0;
-  for (uint32_t b = threadIdx.x; b < nblk; b += 256u) {
-#pragma unroll
-    for (int a = 0; a < GSR_ICP_COLORED_SUMS; a++) s[a] += part[(size_t)b * GSR_ICP_COLORED_SUMS + a];
+// ---- host: what the three update entries do alike -------------------------------------------------------------------------------------
+struct IcpRun {
+  hipStream_t st;
+  uint32_t ns, nt, sblk;
+  double *shift, *part;
+};
+// after the entry's own argument check: the workspace check in the entry's name, the two parts of the workspace, the grid of the
+// partial kernel, and the shift launch.  GSR_OK, or the error to return
+static int icp_begin(const char* entry, int sums, int64_t Ps, const float* source, int64_t Pt, const float* target,
+                     const int32_t* idx, const double* T_dev, void* workspace, size_t workspace_bytes, void* stream, IcpRun& r) {
+  const GsrGnLayout L = gn_layout(sums, true);
+  if (workspace_bytes < L.total) {
+    gsr_set_error("%s: workspace of %zu bytes, %zu needed", entry, workspace_bytes, L.total);
+    return GSR_ERR_STATE_TOO_SMALL;
   }
-  gsr_block_sum(s);
-  if (threadIdx.x != 0) return;
-  const double n = s[0];
-  stats[0] = n;
-  stats[1] = n / (double)Ps;
-  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
-  stats[4] = s[1];
-  stats[5] = s[2];
-  stats[6] = s[3];
-  stats[7] = 0.0;
-  if (n < 6.0) {
-    stats[3] = 1.0;      // fewer correspondences than unknowns: T stays
-    return;
-  }
-  {
-    int o = 10;
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      g[a] = -s[4 + a];
-#pragma unroll
-      for (int b = a; b < 6; b++) {
-        A[a][b] = A[b][a] = s[o];
-        o++;
-      }
-    }
-  }
-  icp_solve6_compose(A, L, D, g, x, shift, T_dev, stats);
+  r.st = (hipStream_t)stream;
+  r.shift = (double*)((char*)workspace + L.shift);
+  r.part = (double*)((char*)workspace + L.part);
+  r.ns = (uint32_t)Ps;
+  r.nt = (uint32_t)Pt;
+  r.sblk = gn_partial_blocks(r.ns);
+  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, r.st, r.ns, source, r.nt, target, idx, T_dev, r.shift);
+  return GSR_OK;
 }
 
 extern "C" {
@@ -551,8 +456,8 @@ int gsr_transform_points(int64_t P, const float* points, const double* T_dev, fl
 }
 
 size_t gsr_icp_workspace_bytes(int64_t Ps) {
-  (void)Ps;      // (the partial sums of at most GSR_ICP_BLOCKS workgroups: the size does not grow with the cloud)
-  return icp_layout().total;
+  (void)Ps;      // (the partial sums of at most GSR_GN_BLOCKS workgroups: the size does not grow with the cloud)
+  return gn_layout(GSR_ICP_PLANE_SUMS, true).total;
 }
 
 int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* target, const int32_t* idx, double* T_dev,
@@ -561,22 +466,14 @@ int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* tar
     gsr_set_error("icp_update: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrIcpLayout L = icp_layout();
-  if (workspace_bytes < L.total) {
-    gsr_set_error("icp_update: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  double* shift = (double*)(ws + L.shift);
-  double* part = (double*)(ws + L.part);
-  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
-  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
-  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
-  GSR_LAUNCH("icp_partial", k_icp_partial, dim3(sblk), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev,
-             (const double*)shift, part);
-  GSR_LAUNCH("icp_final", k_icp_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part, (const double*)shift, T_dev,
-             stats_dev);
+  IcpRun r;
+  if (const int rc = icp_begin("icp_update", GSR_ICP_PLANE_SUMS, Ps, source, Pt, target, idx, T_dev, workspace, workspace_bytes,
+                               stream, r))
+    return rc;
+  GSR_LAUNCH("icp_partial", k_icp_partial, dim3(r.sblk), dim3(256), 0, r.st, r.ns, source, r.nt, target, idx, (const double*)T_dev,
+             (const double*)r.shift, r.part);
+  GSR_LAUNCH("icp_final", k_icp_final, dim3(1), dim3(256), 0, r.st, r.sblk, r.ns, (const double*)r.part, (const double*)r.shift,
+             T_dev, stats_dev);
   return gsr_launch_status("icp_update launch");
 }
 
@@ -588,28 +485,20 @@ int gsr_icp_update_plane(int64_t Ps, const float* source, int64_t Pt, const floa
     gsr_set_error("icp_update_plane: bad arguments (Ps = %lld, Pt = %lld)", (long long)Ps, (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrIcpLayout L = icp_layout();
-  if (workspace_bytes < L.total) {
-    gsr_set_error("icp_update_plane: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  double* shift = (double*)(ws + L.shift);
-  double* part = (double*)(ws + L.part);
-  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
-  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
-  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
-  GSR_LAUNCH("icp_plane_partial", k_icp_plane_partial, dim3(sblk), dim3(256), 0, st, ns, source, nt, target, target_normals, idx,
-             (const double*)T_dev, (const double*)shift, part);
-  GSR_LAUNCH("icp_plane_final", k_icp_plane_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part,
-             (const double*)shift, T_dev, stats_dev);
+  IcpRun r;
+  if (const int rc = icp_begin("icp_update_plane", GSR_ICP_PLANE_SUMS, Ps, source, Pt, target, idx, T_dev, workspace,
+                               workspace_bytes, stream, r))
+    return rc;
+  GSR_LAUNCH("icp_plane_partial", k_icp_plane_partial, dim3(r.sblk), dim3(256), 0, r.st, r.ns, source, r.nt, target, target_normals,
+             idx, (const double*)T_dev, (const double*)r.shift, r.part);
+  GSR_LAUNCH("icp_plane_final", k_gn6_final<GSR_ICP_PLANE_H>, dim3(1), dim3(256), 0, r.st, r.sblk, (double)r.ns, 1,
+             (const double*)r.part, (const double*)r.shift, T_dev, stats_dev);
   return gsr_launch_status("icp_update_plane launch");
 }
 
 size_t gsr_icp_colored_workspace_bytes(int64_t Ps) {
-  (void)Ps;      // (as gsr_icp_workspace_bytes: at most GSR_ICP_BLOCKS rows of partial sums)
-  return icp_colored_layout().total;
+  (void)Ps;      // (as gsr_icp_workspace_bytes: at most GSR_GN_BLOCKS rows of partial sums)
+  return gn_layout(GSR_ICP_COLORED_SUMS, true).total;
 }
 
 int gsr_icp_update_colored(int64_t Ps, const float* source, const float* source_colors, int64_t Pt, const float* target,
@@ -622,23 +511,16 @@ int gsr_icp_update_colored(int64_t Ps, const float* source, const float* source_
                   (long long)Ps, (long long)Pt, lambda_geometric);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrIcpLayout L = icp_colored_layout();
-  if (workspace_bytes < L.total) {
-    gsr_set_error("icp_update_colored: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  double* shift = (double*)(ws + L.shift);
-  double* part = (double*)(ws + L.part);
-  const uint32_t ns = (uint32_t)Ps, nt = (uint32_t)Pt, nblk = (ns + 255u) / 256u;
-  const uint32_t sblk = nblk < (uint32_t)GSR_ICP_BLOCKS ? nblk : (uint32_t)GSR_ICP_BLOCKS;
+  IcpRun r;
+  if (const int rc = icp_begin("icp_update_colored", GSR_ICP_COLORED_SUMS, Ps, source, Pt, target, idx, T_dev, workspace,
+                               workspace_bytes, stream, r))
+    return rc;
   const double sqrt_g = sqrt(lambda_geometric), sqrt_i = sqrt(1.0 - lambda_geometric);
-  GSR_LAUNCH("icp_shift", k_icp_shift, dim3(1), dim3(256), 0, st, ns, source, nt, target, idx, (const double*)T_dev, shift);
-  GSR_LAUNCH("icp_colored_partial", k_icp_colored_partial, dim3(sblk), dim3(256), 0, st, ns, source, source_colors, nt, target,
-             target_normals, target_colors, target_gradient, idx, sqrt_g, sqrt_i, (const double*)T_dev, (const double*)shift, part);
-  GSR_LAUNCH("icp_colored_final", k_icp_colored_final, dim3(1), dim3(256), 0, st, sblk, ns, (const double*)part,
-             (const double*)shift, T_dev, stats_dev);
+  GSR_LAUNCH("icp_colored_partial", k_icp_colored_partial, dim3(r.sblk), dim3(256), 0, r.st, r.ns, source, source_colors, r.nt,
+             target, target_normals, target_colors, target_gradient, idx, sqrt_g, sqrt_i, (const double*)T_dev,
+             (const double*)r.shift, r.part);
+  GSR_LAUNCH("icp_colored_final", k_gn6_final<GSR_ICP_COLORED_H>, dim3(1), dim3(256), 0, r.st, r.sblk, (double)r.ns, 1,
+             (const double*)r.part, (const double*)r.shift, T_dev, stats_dev);
   return gsr_launch_status("icp_update_colored launch");
 }
 

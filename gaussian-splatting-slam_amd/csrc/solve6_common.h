@@ -1,15 +1,52 @@
 // solve6_common.h - the 6-unknown Gauss-Newton step of include/gsr.h, shared by registration.hip (gsr_icp_update_plane,
-// gsr_icp_update_colored) and odometry.hip (gsr_odometry_update): ONE body for the LDL^T solve, the vector-to-matrix composition
-// and T <- dT T, so the pivot rule and the order of operations agree by construction.
+// gsr_icp_update_colored) and odometry.hip (gsr_odometry_update): ONE workspace layout, ONE final kernel (the rows of partial sums,
+// the stats header, the n < 6 rule, the unpacking of the triangle) and ONE body for the LDL^T solve, the vector-to-matrix
+// composition and T <- dT T, so the thresholds, the stats layout, the pivot rule and the order of operations agree by
+// construction.  What differs between the updates stays in their files: the partial kernel that forms a workgroup's row
+//   s[0] = n, s[1 .. H-1] = sums of squared residuals, s[H .. H+5] = J^T r, s[H+6 .. H+26] = J^T J rows 0 .. 5 from the diagonal on.
+// (Everything here is defined above odometry.hip's `fp contract(off)`: both files compile these bodies alike.)
 #pragma once
+#include "gsr_common.h"
 
 #define GSR_ICP_PIVOT_MIN 1e-12   // LDL^T: a pivot at or below this share of its diagonal entry is no pivot
+#define GSR_GN_BLOCKS 256         // workgroups of a partial kernel at most = rows of partial sums
+#define GSR_GN6_TERMS 27          // J^T r [6], upper triangle of J^T J [21]: what follows the H header sums of a row
+
+// workspace of an update: the rows of partial sums do not grow with the cloud or the image
+struct GsrGnLayout {
+  size_t shift;      // double[4]: the shift, [3] = 1 when a valid row exists (with_shift only)
+  size_t part;       // double[GSR_GN_BLOCKS][sums]
+  size_t total;
+};
+static inline GsrGnLayout gn_layout(int sums, bool with_shift) {
+  GsrGnLayout L;
+  L.shift = 0;
+  L.part = with_shift ? 256 : 0;
+  L.total = L.part + gsr_align((size_t)GSR_GN_BLOCKS * sums * 8);
+  return L;
+}
+// workgroups of a partial kernel over n rows or pixels: 256 each, the rest by the grid-stride loop
+static inline uint32_t gn_partial_blocks(uint32_t n) {
+  const uint32_t nblk = (n + 255u) / 256u;
+  return nblk < (uint32_t)GSR_GN_BLOCKS ? nblk : (uint32_t)GSR_GN_BLOCKS;
+}
 
 #ifdef __HIPCC__
-// thread 0 of a final kernel (the plane update's, the coloured one's and the odometry's): J^T J x = -J^T r on the matrix in A and
-// the right-hand side in g, both filled by the caller; then dR, dT and T <- dT T.  stats[3] = 0, or 2 with T as it was.  The
-// arrays are LDS: indexed at run time, which registers cannot be.  `shift`: the point dT is formed about (three zeros: about the
-// origin).
+// thread 0 of a final kernel: stats[0..2] and [4..7] of include/gsr.h from a summed row with H header sums (s[0] = n, s[1] = the
+// sum the RMSE is taken from); stats[3] is the caller's
+template <int H, int N>
+__device__ __forceinline__ void gn_stats_header(const double (&s)[N], double denom, double* __restrict__ stats) {
+  const double n = s[0];
+  stats[0] = n;
+  stats[1] = n / denom;
+  stats[2] = n > 0.0 ? sqrt(s[1] / n) : 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) stats[4 + k] = k < H - 1 ? s[1 + k] : 0.0;
+}
+
+// thread 0 of the final kernel: J^T J x = -J^T r on the matrix in A and the right-hand side in g, both filled by the caller; then
+// dR, dT and T <- dT T.  stats[3] = 0, or 2 with T as it was.  The arrays are LDS: indexed at run time, which registers cannot
+// be.  `shift`: the point dT is formed about (three zeros: about the origin).
 __device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L)[6][6], double (&D)[6], double (&g)[6],
                                                    double (&x)[6], const double* __restrict__ shift, double* __restrict__ T_dev,
                                                    double* __restrict__ stats) {
@@ -73,5 +110,43 @@ __device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L
   T_dev[12] = T_dev[13] = T_dev[14] = 0.0;
   T_dev[15] = 1.0;
   stats[3] = 0.0;
+}
+
+// one workgroup: the `nblk` rows of partial sums, then thread 0 writes the stats, solves and composes.  H: the header sums of a
+// row (3: plane and odometry, 4: coloured).  denom: what fitness = n / denom is taken over (source rows, pixels).  shift: the
+// point the unknowns are formed about, NULL = the origin (camera coordinates).  T_dev is written only with status 0 and `apply`:
+// status 1 (n < 6), status 2 (a rejected pivot) and apply = 0 leave it bit for bit.  (static: each file launches its own copy)
+template <int H>
+static __global__ __launch_bounds__(256) void k_gn6_final(uint32_t nblk, double denom, int apply, const double* __restrict__ part,
+                                                          const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                          double* __restrict__ stats) {
+  // thread 0 only: indexed at run time, which registers cannot be.  Tn: the copy the step is composed into
+  __shared__ double A[6][6], L[6][6], D[6], g[6], x[6], c[3], Tn[16];
+  double s[H + GSR_GN6_TERMS];
+  gsr_block_sum_rows(s, part, nblk);
+  if (threadIdx.x != 0) return;
+  gn_stats_header<H>(s, denom, stats);
+  if (s[0] < 6.0) {
+    stats[3] = 1.0;      // fewer rows than unknowns: T stays
+    return;
+  }
+  {
+    int o = H + 6;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      g[a] = -s[H + a];
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        A[a][b] = A[b][a] = s[o];
+        o++;
+      }
+    }
+  }
+  for (int a = 0; a < 3; a++) c[a] = shift ? shift[a] : 0.0;
+  for (int i = 0; i < 16; i++) Tn[i] = T_dev[i];
+  icp_solve6_compose(A, L, D, g, x, c, Tn, stats);      // (sets stats[3])
+  if (apply && stats[3] == 0.0) {
+    for (int i = 0; i < 16; i++) T_dev[i] = Tn[i];
+  }
 }
 #endif
