@@ -6,41 +6,13 @@
 #include <string.h>
 #include <time.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include <atomic>
-
 #include "gsr_common.h"
-
-// launchers defined in the kernel files
-void gsr_launch_preprocess_fwd(const gsr_settings*, const gsr_gaussians*, int32_t*, char*, const GsrGeomLayout&, bool, bool, uint32_t*, int,
-                               const uint32_t*, uint32_t*, uint32_t, bool, hipStream_t);
-void gsr_launch_shade(const gsr_settings*, const gsr_gaussians*, char*, const GsrGeomLayout&, bool, hipStream_t);
-void gsr_launch_adam_culled_rows(int, int, const char*, const GsrGeomLayout&, const GsrAdamArgs&, uint32_t, hipStream_t);
-int gsr_launch_preprocess_bwd(const gsr_settings*, const gsr_gaussians*, const int32_t*, const char*,
-                              const GsrGeomLayout&, const float4*, uint32_t, const gsr_grads*, const GsrAdamArgs*, int,
-                              float*, bool, bool, hipStream_t);
-size_t gsr_cam_scratch_floats(int);
-void gsr_launch_cam_reduce(int, float*, float*, float*, float*, hipStream_t);
-void gsr_launch_mark_visible(int, const float*, const float*, uint8_t*, hipStream_t);
-void gsr_launch_emit(int, int, int, char*, const GsrGeomLayout&, char*, const GsrBinLayout&, uint32_t, bool, unsigned long long*,
-                     int, const uint32_t*, hipStream_t);
-void gsr_launch_tile_depth_sort(int, bool, uint2*, const uint2*, uint32_t*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*,
-                                uint32_t*, uint32_t*, uint32_t*, hipStream_t);
-void gsr_launch_finalize(uint32_t, const uint32_t*, const uint32_t*, char*, const GsrBinLayout&, hipStream_t);
-void gsr_launch_sum_tiles(int, const char*, const GsrGeomLayout&, uint32_t*, hipStream_t);
-void gsr_launch_render_fwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, float*,
-                           float*, float*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
-                           uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, float*, uint32_t*, float, uint32_t, hipStream_t);
-void gsr_launch_count_pairs(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*, uint32_t*,
-                            hipStream_t);
-void gsr_launch_render_bwd(const gsr_settings*, int, int, const uint2*, const uint32_t*, const float4*,
-                           const float*, const uint32_t*, const float*, const float*, const uint32_t*, float4*,
-                           const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, const float*,
-                           hipStream_t);
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -80,7 +52,7 @@ int gsr_launch_status(const char* what) {
 
 // status0: the frame's first status word on the device (meta[0]); with debug = 1 a stage that left GSR_STATUS_SORT_TIMEOUT there
 // fails the call (reference README.md:168-171: with --debug a failing rasterizer call raises and dumps its inputs).
-static int debug_sync(const gsr_settings* s, hipStream_t st, const char* stage, const uint32_t* status0 = nullptr) {
+static int debug_sync_status(const gsr_settings* s, hipStream_t st, const char* stage, const uint32_t* status0) {
   static const bool trace = getenv("GSR_TRACE") != nullptr;   // GSR_TRACE=1: name every stage on stderr as it completes
   if (trace) {
     fprintf(stderr, "[gsr] launched: %s\n", stage);
@@ -106,6 +78,7 @@ static int debug_sync(const gsr_settings* s, hipStream_t st, const char* stage, 
   }
   return 0;
 }
+static int debug_sync(const gsr_settings* s, hipStream_t st, const char* stage) { return debug_sync_status(s, st, stage, nullptr); }
 
 // ---------------------------------------------------------------------------------------------------
 // per-kernel profiling (HIP events on the launch stream)
@@ -207,18 +180,6 @@ static hipEvent_t readback_event() {
   return d->readback;
 }
 
-static int tile_bits(int tiles) {
-  int b = 1;
-  while ((1 << b) < tiles) b++;
-  return b;
-}
-// which ping-pong buffer holds the tile-sorted (key, slot) arrays: one swap per 8-bit pass
-static int tile_sort_result_buffer(int tiles) { return gsr_radix_passes(tile_bits(tiles)) & 1; }
-// the Gaussian-id list rides through the tile sort as a second payload, ping-ponging gauss_of_slot <-> point_list
-static size_t point_list_offset(const GsrBinLayout& BL, int tiles) {
-  return tile_sort_result_buffer(tiles) ? BL.point_list : BL.gauss_of_slot;
-}
-
 static int validate(const gsr_settings* s, const gsr_gaussians* g) {
   if (!s || !g) { gsr_set_error("null settings/gaussians"); return GSR_ERR_INVALID_ARGUMENT; }
   if (g->P < 0 || s->image_width <= 0 || s->image_height <= 0) {
@@ -248,10 +209,38 @@ static int validate(const gsr_settings* s, const gsr_gaussians* g) {
     }
   }
   // tile ids are sort keys and 16-bit rect coordinates: at most 65535 tiles per side and 2^24 tiles in all
-  const long long gx = ((long long)s->image_width + GSR_TILE - 1) / GSR_TILE, gy = ((long long)s->image_height + GSR_TILE - 1) / GSR_TILE;
-  if (gx > 65535 || gy > 65535 || gx * gy > (1ll << 24)) {
-    gsr_set_error("image too large: %lld x %lld tiles (limit 65535 per side, 2^24 in all)", gx, gy);
+  const GsrTileGrid grid = gsr_tile_grid(s->image_width, s->image_height);
+  if (grid.gx > 65535 || grid.gy > 65535 || grid.gx * grid.gy > (1ll << 24)) {
+    gsr_set_error("image too large: %lld x %lld tiles (limit 65535 per side, 2^24 in all)", grid.gx, grid.gy);
     return GSR_ERR_INVALID_ARGUMENT;
+  }
+  return 0;
+}
+
+// The frame of a call on validated settings: `capacity` instances (num_rendered on the blocking path) lay out the binning state.
+// A blob whose size the entry point is told must be there and hold its layout; the backward and the debug hooks, which are not told,
+// pass GSR_UNSIZED.
+static const size_t GSR_UNSIZED = ~(size_t)0;
+static int frame_view(GsrFrame& F, const gsr_settings* s, int P, int64_t capacity, const void* geometry_state,
+                      const void* binning_state, size_t binning_bytes, const void* image_state, size_t image_bytes) {
+  if (capacity < 0 || capacity > 0x3FFFFFFFll) {   // the tile sort counts keys in 30-bit fields (sort_scan.hip)
+    gsr_set_error("num_rendered / capacity %lld out of range (limit 2^30 - 1)", (long long)capacity);
+    return capacity < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_ERR_TOO_MANY_INSTANCES;
+  }
+  const GsrTileGrid grid = gsr_tile_grid(s->image_width, s->image_height);
+  F.P = P;
+  F.gx = (int)grid.gx;
+  F.tiles = (int)grid.tiles;
+  F.R = (size_t)capacity;
+  F.GL = gsr_geom_layout(P);
+  F.BL = gsr_bin_layout(F.R, grid.tiles);
+  F.IL = gsr_img_layout(s->image_width, s->image_height);
+  // (a backward only reads the three blobs: its entry points take them as const)
+  F.geom = (char*)geometry_state; F.bin = (char*)binning_state; F.img = (char*)image_state;
+  if ((binning_bytes != GSR_UNSIZED && (!binning_state || binning_bytes < F.BL.total)) ||
+      (image_bytes != GSR_UNSIZED && (!image_state || image_bytes < F.IL.total))) {
+    gsr_set_error("binning/image state too small: %zu < %zu or %zu < %zu", binning_bytes, F.BL.total, image_bytes, F.IL.total);
+    return GSR_ERR_STATE_TOO_SMALL;
   }
   return 0;
 }
@@ -265,8 +254,7 @@ size_t gsr_geometry_state_bytes(int32_t P) { return gsr_geom_layout((size_t)(P <
 size_t gsr_image_state_bytes(int32_t W, int32_t H) { return gsr_img_layout(W, H).total; }
 size_t gsr_binning_state_bytes(int32_t P, int32_t W, int32_t H, int64_t R) {
   (void)P;
-  const size_t tiles = (size_t)((W + GSR_TILE - 1) / GSR_TILE) * (size_t)((H + GSR_TILE - 1) / GSR_TILE);
-  return gsr_bin_layout((size_t)(R < 0 ? 0 : R), tiles).total;
+  return gsr_bin_layout((size_t)(R < 0 ? 0 : R), gsr_tile_grid(W, H).tiles).total;
 }
 size_t gsr_backward_scratch_bytes(int32_t P, int64_t R) {
   (void)P;
@@ -302,17 +290,53 @@ static uint32_t* device_alias_of_pinned(uint32_t* host) {
   return nullptr;
 }
 
-// Geometry stages of the forward: projection, num_rendered (kept on the device in meta[2..3] and copied to `host_status`),
+// gsr_render_extras: NULL = the inverse-depth channel and no opacity plane (every entry point without `_ex`)
+static int check_extras(const gsr_render_extras* ex) {
+  if (ex && ex->depth_kind != GSR_DEPTH_INVERSE && ex->depth_kind != GSR_DEPTH_Z) {
+    gsr_set_error("gsr_render_extras.depth_kind %d: expected GSR_DEPTH_INVERSE (0) or GSR_DEPTH_Z (1)", (int)ex->depth_kind);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  // (written so that a NaN fails it too)
+  if (ex && ex->n_touched && !(ex->touched_T_min >= 0.0f && ex->touched_T_min < 1.0f)) {
+    gsr_set_error("gsr_render_extras.touched_T_min %g: expected a transmittance threshold in [0, 1)", (double)ex->touched_T_min);
+    return GSR_ERR_INVALID_ARGUMENT;
+  }
+  return 0;
+}
+static bool ex_depth_z(const gsr_render_extras* ex) { return ex && ex->depth_kind == GSR_DEPTH_Z; }
+
+// What one forward call asks for beyond its frame and its outputs: the defaults are the plain blocking forward
+// (gsr_forward_prepare + gsr_forward_render), every entry point names the fields in which it differs.  A new per-call option is
+// one field here and its use in forward_geometry / forward_render_impl.
+struct ForwardCall {
+  bool for_backward = false;           // record what gsr_backward needs (emission slots through the tile sort, walk classes)
+  bool defer_color = false;            // the projection kernel leaves SH -> RGB to a later pass
+  bool shade_late = false;             // ... which phase 2 runs as the LAST thing in front of the compositing
+  hipEvent_t sh_ready = nullptr;       // phase 2 waits for it before it needs the colours (the caller's SH update, or the side stream's join)
+  SideShade* shade_aside = nullptr;    // the colour pass runs on the library's side stream
+  bool tile_local = false;             // second binning form: emission in index order, every tile orders its own list
+  uint32_t* host_status = nullptr;     // the caller's 8 status words, delivered at the END of the frame
+  uint32_t* count_slot = nullptr;      // this thread's pinned slot, where a waiting caller finds the count ...
+  hipEvent_t count_event = nullptr;    // ... recorded right behind the copy that delivers it
+  unsigned long long* early = nullptr; // ... or the slot's device alias (tile-local form, armed by forward_geometry)
+  uint32_t* sort_head = nullptr;       // tile-local form: head of the tile sort's scratch, cleared by the projection kernel
+  uint32_t* tile_cutoff = nullptr;     // per-tile depth cut-off (gsr_forward_async_culled): updated by the compositing kernel ...
+  uint32_t* culled_any = nullptr;      // ... per-tile "lost an instance" tags in the binning state ...
+  bool cull_applied = false;           // ... and the lists are counted and emitted with the cut-off
+  uint32_t frame_tag = 0;
+  const gsr_render_extras* extras = nullptr;   // depth kind, out_alpha, n_touched
+};
+
+// gsr_radix_sort_pairs without its optional pieces: no second payload riding along; the number of keys is `n` itself, not a word on
+// the device
+static uint32_t* const NO_PAYLOAD = nullptr;
+static const uint32_t* const COUNT_IS_N = nullptr;
+
+// Geometry stages of the forward: projection, num_rendered (kept on the device in meta[2..3] and copied to `c.count_slot`),
 // depth order, tile-count prefix sum.  Never waits for the device.
 static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
-                            int32_t* radii, hipStream_t st, bool defer_color, uint32_t* host_status,
-                            hipEvent_t copied /* recorded right behind the status copy, or nullptr */,
-                            SideShade* shade_aside = nullptr, bool tile_local = false,
-                            unsigned long long** early_word = nullptr,
-                            uint32_t* tile_sort_head = nullptr /* tile-local form: cleared by the projection kernel */,
-                            const uint32_t* tile_cutoff = nullptr /* lists truncated by depth (gsr_forward_async_culled) */,
-                            uint32_t* culled_any = nullptr, uint32_t frame_tag = 0,
-                            bool depth_z = false /* gsr_render_extras.depth_kind = GSR_DEPTH_Z */) {
+                            int32_t* radii, ForwardCall& c, hipStream_t st) {
+  const bool tile_local = c.tile_local;
   const int P = g->P;
   const GsrGeomLayout L = gsr_geom_layout(P);
   if (!geometry_state || geometry_bytes < L.total) {
@@ -328,17 +352,18 @@ static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void*
   static_assert(sizeof(uint32_t) == 4, "");
   if (!tile_local && (rc = gsr_check(hipMemsetAsync(meta, 0, 256 + GSR_RADIX_HEAD_WORDS * 4, st), "memset meta"))) return rc;
 
-  gsr_launch_preprocess_fwd(s, g, radii, geom, L, defer_color, /*block_sums=*/tile_local, tile_local ? tile_sort_head : nullptr,
-                            GSR_RADIX_HEAD_WORDS, tile_cutoff, culled_any, frame_tag, depth_z, st);
+  gsr_launch_preprocess_fwd(s, g, radii, geom, L, c.defer_color, /*block_sums=*/tile_local, tile_local ? c.sort_head : nullptr,
+                            GSR_RADIX_HEAD_WORDS, c.cull_applied ? c.tile_cutoff : nullptr,
+                            c.cull_applied ? c.culled_any : nullptr, c.frame_tag, ex_depth_z(c.extras), st);
   if ((rc = debug_sync(s, st, "preprocess"))) return rc;
   // (tile-local binning form: the colour pass is forked behind the emission instead - forward_render_impl - because the
   // two are both HBM-bound and slowed each other down (emission 36 -> 55 us); the tile sort and the per-tile ordering that
   // follow are latency- / issue-bound and share the machine well: -12 us per frame at C3)
-  if (shade_aside && !tile_local) {
-    if ((rc = gsr_check(hipEventRecord(shade_aside->fork, st), "fork shade"))) return rc;
-    if ((rc = gsr_check(hipStreamWaitEvent(shade_aside->stream, shade_aside->fork, 0), "fork shade"))) return rc;
-    gsr_launch_shade(s, g, geom, L, /*beside_other_work=*/true, shade_aside->stream);
-    if ((rc = gsr_check(hipEventRecord(shade_aside->join, shade_aside->stream), "join shade"))) return rc;
+  if (SideShade* aside = tile_local ? nullptr : c.shade_aside) {
+    if ((rc = gsr_check(hipEventRecord(aside->fork, st), "fork shade"))) return rc;
+    if ((rc = gsr_check(hipStreamWaitEvent(aside->stream, aside->fork, 0), "fork shade"))) return rc;
+    gsr_launch_shade(s, g, geom, L, /*beside_other_work=*/true, aside->stream);
+    if ((rc = gsr_check(hipEventRecord(aside->join, aside->stream), "join shade"))) return rc;
   }
 
   // num_rendered (meta[2..3]) and the error flags go back to the host NOW, ahead of the depth sort and the offset scan:
@@ -350,30 +375,29 @@ static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void*
     // takes the prefix sum and num_rendered from them itself.  A caller that waits for the count - gsr_forward_async(
     // num_rendered_out) - gets it from that kernel: one 8-byte store into this thread's pinned slot, word pair [8..9],
     // GSR_COUNT_VALID | flag << 62 | count; here only the slot is armed.
-    unsigned long long* early = nullptr;
-    if (host_status) {
+    c.early = nullptr;
+    if (c.count_slot) {
       DeviceLocal* d = device_local();
-      if (d && d->pinned == host_status && d->pinned_dev) {
-        ((volatile unsigned long long*)(host_status + 8))[0] = 0ull;
-        early = (unsigned long long*)(d->pinned_dev + 8);
+      if (d && d->pinned == c.count_slot && d->pinned_dev) {
+        ((volatile unsigned long long*)(c.count_slot + 8))[0] = 0ull;
+        c.early = (unsigned long long*)(d->pinned_dev + 8);
       }
     }
-    if (early_word) *early_word = early;
     return debug_sync(s, st, "projection");
   }
   gsr_launch_sum_tiles(P, geom, L, meta, st);
-  if (host_status &&
-      (rc = gsr_check(hipMemcpyAsync(host_status, meta, 16, hipMemcpyDeviceToHost, st), "read num_rendered")))
+  if (c.count_slot &&
+      (rc = gsr_check(hipMemcpyAsync(c.count_slot, meta, 16, hipMemcpyDeviceToHost, st), "read num_rendered")))
     return rc;
-  if (copied && (rc = gsr_check(hipEventRecord(copied, st), "record read-back event"))) return rc;
+  if (c.count_event && (rc = gsr_check(hipEventRecord(c.count_event, st), "record read-back event"))) return rc;
 
   // depth order of the Gaussians (stable, so equal depths keep ascending id); 4 passes -> result in (depth_key, order)
   const int where = gsr_radix_sort_pairs((uint32_t*)(geom + L.depth_key), (uint32_t*)(geom + L.order),
                                          (uint32_t*)(geom + L.key_tmp), (uint32_t*)(geom + L.val_tmp),
-                                         /*vals_iota=*/true, (size_t)P, 32, (uint32_t*)(geom + L.radix_tmp), st, nullptr,
-                                         nullptr, nullptr, /*head_zeroed=*/true, /*fail_flags=*/meta);
+                                         /*vals_iota=*/true, (size_t)P, 32, (uint32_t*)(geom + L.radix_tmp), st, NO_PAYLOAD,
+                                         NO_PAYLOAD, COUNT_IS_N, /*head_zeroed=*/true, /*fail_flags=*/meta);
   if (where != 0) { gsr_set_error("internal: depth sort ended in the wrong buffer"); return GSR_ERR_HIP; }
-  if ((rc = debug_sync(s, st, "depth sort", meta))) return rc;
+  if ((rc = debug_sync_status(s, st, "depth sort", meta))) return rc;
 
   // inclusive prefix sum of tiles_touched in depth order (its last element equals num_rendered)
   gsr_scan_u32((const uint32_t*)(geom + L.tiles_touched), (const uint32_t*)(geom + L.order),
@@ -438,60 +462,45 @@ static int64_t wait_for_count(uint32_t* host, hipEvent_t ev, bool early_word) {
   return (int64_t)total;
 }
 
-// gsr_render_extras: NULL = the inverse-depth channel and no opacity plane (every entry point without `_ex`)
-static int check_extras(const gsr_render_extras* ex) {
-  if (ex && ex->depth_kind != GSR_DEPTH_INVERSE && ex->depth_kind != GSR_DEPTH_Z) {
-    gsr_set_error("gsr_render_extras.depth_kind %d: expected GSR_DEPTH_INVERSE (0) or GSR_DEPTH_Z (1)", (int)ex->depth_kind);
-    return GSR_ERR_INVALID_ARGUMENT;
-  }
-  // (written so that a NaN fails it too)
-  if (ex && ex->n_touched && !(ex->touched_T_min >= 0.0f && ex->touched_T_min < 1.0f)) {
-    gsr_set_error("gsr_render_extras.touched_T_min %g: expected a transmittance threshold in [0, 1)", (double)ex->touched_T_min);
-    return GSR_ERR_INVALID_ARGUMENT;
-  }
-  return 0;
-}
-static bool ex_depth_z(const gsr_render_extras* ex) { return ex && ex->depth_kind == GSR_DEPTH_Z; }
-static float* ex_alpha(const gsr_render_extras* ex) { return ex ? ex->out_alpha : nullptr; }
-static const float* ex_dalpha(const gsr_render_extras* ex) { return ex ? ex->dL_dalpha : nullptr; }
-
+// phase 1 for a caller that sizes its binning state from the count: c.defer_color, c.extras
 static int64_t forward_prepare_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
-                                    size_t geometry_bytes, int32_t* radii, void* stream, bool defer_color,
-                                    const gsr_render_extras* ex = nullptr) {
+                                    size_t geometry_bytes, int32_t* radii, ForwardCall c, void* stream) {
   int rc = validate(s, g);
   if (rc) return rc;
-  if ((rc = check_extras(ex))) return rc;
+  if ((rc = check_extras(c.extras))) return rc;
   if (g->P == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t* host = pinned_slot();
-  hipEvent_t ev = readback_event();
-  if (!host || !ev) { gsr_set_error("hipHostMalloc / hipEventCreate failed"); return GSR_ERR_HIP; }
+  c.count_slot = pinned_slot();
+  c.count_event = readback_event();
+  if (!c.count_slot || !c.count_event) { gsr_set_error("hipHostMalloc / hipEventCreate failed"); return GSR_ERR_HIP; }
   // the host waits on an event recorded right behind the 16-byte copy, i.e. while the depth sort and the offset scan are still
   // queued: the GPU has ~0.1 ms of work left when the host goes on to size the binning state and enqueue the rest
-  if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, st, defer_color, host, ev, nullptr, false, nullptr,
-                             nullptr, nullptr, nullptr, 0, ex_depth_z(ex))))
-    return rc;
-  return wait_for_count(host, ev, false);
+  if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, c, (hipStream_t)stream))) return rc;
+  return wait_for_count(c.count_slot, c.count_event, false);
 }
 
 int64_t gsr_forward_prepare(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
                             size_t geometry_bytes, int32_t* radii, void* stream) {
-  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, false);
+  return gsr_forward_prepare_ex(s, g, geometry_state, geometry_bytes, radii, stream, /*extras=*/nullptr);
 }
 
 int64_t gsr_forward_prepare_geometry(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
                                      size_t geometry_bytes, int32_t* radii, void* stream) {
-  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, true);
+  return gsr_forward_prepare_geometry_ex(s, g, geometry_state, geometry_bytes, radii, stream, /*extras=*/nullptr);
 }
 
 int64_t gsr_forward_prepare_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
                                int32_t* radii, void* stream, const gsr_render_extras* extras) {
-  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, false, extras);
+  ForwardCall c;
+  c.extras = extras;
+  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, c, stream);
 }
 
 int64_t gsr_forward_prepare_geometry_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state,
                                         size_t geometry_bytes, int32_t* radii, void* stream, const gsr_render_extras* extras) {
-  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, stream, true, extras);
+  ForwardCall c;
+  c.defer_color = true;
+  c.extras = extras;
+  return forward_prepare_impl(s, g, geometry_state, geometry_bytes, radii, c, stream);
 }
 
 int gsr_forward_shade(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* stream) {
@@ -508,43 +517,27 @@ int gsr_forward_shade(const gsr_settings* s, const gsr_gaussians* g, void* geome
 // kernels from the geometry state (min(meta num_rendered, capacity), gsr_eff_n).  On the blocking path the two are equal.
 static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                                size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
-                               float* out_color, float* out_invdepth, bool for_backward, bool shade_late,
-                               hipEvent_t sh_ready, void* stream, bool tile_local = false,
-                               uint32_t* host_status_late = nullptr, unsigned long long* early = nullptr,
-                               uint32_t* host_count = nullptr, hipEvent_t count_copied = nullptr,
-                               bool sort_head_clean = false /* this call's projection kernel cleared the tile sort's head */,
-                               uint32_t* tile_cutoff = nullptr /* per-tile depth cut-off: updated by the compositing kernel */,
-                               bool cull_applied = false /* ... and the projection counted with it: emit with it too */,
-                               uint32_t frame_tag = 0, const gsr_render_extras* ex = nullptr /* out_alpha, n_touched */) {
-  float* out_alpha = ex_alpha(ex);
-  uint32_t* n_touched = (ex && g && g->P > 0) ? ex->n_touched : nullptr;
+                               float* out_color, float* out_invdepth, const ForwardCall& c, void* stream) {
+  const gsr_render_extras* ex = c.extras;
   int rc = validate(s, g);
   if (rc) return rc;
-  if (num_rendered < 0 || num_rendered > 0x3FFFFFFFll) {   // the tile sort counts keys in 30-bit fields (sort_scan.hip)
-    gsr_set_error("num_rendered / capacity %lld out of range (limit 2^30 - 1)", (long long)num_rendered);
-    return num_rendered < 0 ? GSR_ERR_INVALID_ARGUMENT : GSR_ERR_TOO_MANY_INSTANCES;
-  }
+  if ((rc = check_extras(ex))) return rc;
+  GsrFrame F;
+  if ((rc = frame_view(F, s, g->P, num_rendered, geometry_state, binning_state, binning_bytes, image_state, image_bytes))) return rc;
+  uint32_t* n_touched = (ex && g->P > 0) ? ex->n_touched : nullptr;
+  const bool for_backward = c.for_backward, tile_local = c.tile_local, shade_late = c.shade_late;
+  const hipEvent_t sh_ready = c.sh_ready;
   hipStream_t st = (hipStream_t)stream;
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
-  const int tiles = gx * gy;
-  const size_t R = (size_t)num_rendered;
-  const GsrGeomLayout GL = gsr_geom_layout(g->P);
-  const GsrBinLayout BL = gsr_bin_layout(R, tiles);
-  const GsrImgLayout IL = gsr_img_layout(W, H);
-  if (!binning_state || binning_bytes < BL.total || !image_state || image_bytes < IL.total) {
-    gsr_set_error("binning/image state too small: %zu < %zu or %zu < %zu", binning_bytes, BL.total, image_bytes,
-                  IL.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
-  char* geom = (char*)geometry_state;
-  char* bin = (char*)binning_state;
-  char* img = (char*)image_state;
-  const uint32_t* n_dev = g->P > 0 ? (const uint32_t*)(geom + GL.meta) + 2 : nullptr;
+  const int tiles = F.tiles;
+  const size_t R = F.R;
+  const GsrGeomLayout& GL = F.GL;
+  const GsrBinLayout& BL = F.BL;
+  char *geom = F.geom, *bin = F.bin;
+  const uint32_t* n_dev = g->P > 0 ? F.n_dev() : nullptr;
   // (round 4) walk classes: with a backward to follow, the compositing kernel files every tile under the class of its walk length
   // (image state), and the backward takes the classes longest first.  The 64 counters are cleared by the first workgroup of the
   // kernel in front of the compositing (tile-local form: the per-tile ordering), by a memset where there is none.
-  uint32_t* walk_cnt = for_backward ? (uint32_t*)(img + IL.walk_cnt) : nullptr;
+  uint32_t* walk_cnt = for_backward ? F.walk_cnt() : nullptr;
   bool walk_cnt_clear = false;
   if (R == 0 || g->P == 0) {   // nothing to emit: every tile range is empty (otherwise the emit kernel clears them on its way)
     if ((rc = gsr_check(hipMemsetAsync(bin + BL.ranges, 0, (size_t)tiles * 8, st), "memset ranges"))) return rc;
@@ -555,62 +548,50 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
     // to it: the projection kernel of this call did that, or (re-render on another binning state) a memset here.
     const char* th = getenv("GSR_TILE_HIST");
     // (the emission kernel's LDS histograms cover two passes = 16 tile bits: a frame of more than 65536 tiles takes the chain)
-    const bool fused_bins = tile_local && !(th && th[0] == '0') && tile_bits(tiles) <= 2 * GSR_RADIX_BITS;
-    if (fused_bins && !sort_head_clean &&
+    const bool fused_bins = tile_local && !(th && th[0] == '0') && gsr_tile_bits(tiles) <= 2 * GSR_RADIX_BITS;
+    if (fused_bins && !c.sort_head &&
         (rc = gsr_check(hipMemsetAsync(bin + BL.radix_tmp, 0, GSR_RADIX_HEAD_WORDS * 4, st), "memset sort head")))
       return rc;
-    gsr_launch_emit(g->P, gx, tiles, geom, GL, bin, BL, (uint32_t)R, tile_local, early, fused_bins ? tile_bits(tiles) : 0,
-                    cull_applied ? tile_cutoff : nullptr, st);
+    gsr_launch_emit(g->P, F.gx, tiles, geom, GL, bin, BL, (uint32_t)R, tile_local, c.early, fused_bins ? gsr_tile_bits(tiles) : 0,
+                    c.cull_applied ? c.tile_cutoff : nullptr, st);
     // tile-local form: the emission kernel is where num_rendered comes into being.  A waiting caller whose pinned slot has no
-    // device alias (early == nullptr) gets the status words by a copy, marked by an event
-    if (tile_local && host_count && !early) {
-      if ((rc = gsr_check(hipMemcpyAsync(host_count, geom + GL.meta, 16, hipMemcpyDeviceToHost, st), "read num_rendered"))) return rc;
-      if (count_copied && (rc = gsr_check(hipEventRecord(count_copied, st), "record read-back event"))) return rc;
+    // device alias (c.early == nullptr) gets the status words by a copy, marked by an event
+    if (tile_local && c.count_slot && !c.early) {
+      if ((rc = gsr_check(hipMemcpyAsync(c.count_slot, F.meta(), 16, hipMemcpyDeviceToHost, st), "read num_rendered"))) return rc;
+      if (c.count_event && (rc = gsr_check(hipEventRecord(c.count_event, st), "record read-back event"))) return rc;
     }
-    {
-      SideShade* a = (tile_local && !shade_late && sh_ready) ? side_shade() : nullptr;
-      if (a && sh_ready == a->join) {      // colour pass on the side stream, beside the tile sort (see forward_geometry)
-        if ((rc = gsr_check(hipEventRecord(a->fork, st), "fork shade"))) return rc;
-        if ((rc = gsr_check(hipStreamWaitEvent(a->stream, a->fork, 0), "fork shade"))) return rc;
-        gsr_launch_shade(s, g, (char*)geom, GL, /*beside_other_work=*/true, a->stream);
-        if ((rc = gsr_check(hipEventRecord(a->join, a->stream), "join shade"))) return rc;
-      }
+    SideShade* a = (tile_local && !shade_late && sh_ready) ? side_shade() : nullptr;
+    if (a && sh_ready == a->join) {      // colour pass on the side stream, beside the tile sort (see forward_geometry)
+      if ((rc = gsr_check(hipEventRecord(a->fork, st), "fork shade"))) return rc;
+      if ((rc = gsr_check(hipStreamWaitEvent(a->stream, a->fork, 0), "fork shade"))) return rc;
+      gsr_launch_shade(s, g, geom, GL, /*beside_other_work=*/true, a->stream);
+      if ((rc = gsr_check(hipEventRecord(a->join, a->stream), "join shade"))) return rc;
     }
     if ((rc = debug_sync(s, st, "emit instances"))) return rc;
     // With a backward to follow, the sort carries (emission slot, Gaussian id): the slot of every list position is where the
     // backward stores that instance's gradient record.  A forward-only render (torch.no_grad) needs the ids alone: they
     // become the one sorted value (same ping-pong parity, so the list ends up in the same place), 8 B less per key and pass.
+    uint2* ranges_enc = fused_bins ? (uint2*)(bin + BL.ranges_enc) : nullptr;
     const int where =
         for_backward
             ? gsr_radix_sort_pairs((uint32_t*)(bin + BL.key_a), (uint32_t*)(bin + BL.val_a), (uint32_t*)(bin + BL.key_b),
-                                   (uint32_t*)(bin + BL.val_b), /*vals_iota=*/true, R, tile_bits(tiles),
+                                   (uint32_t*)(bin + BL.val_b), /*vals_iota=*/true, R, gsr_tile_bits(tiles),
                                    (uint32_t*)(bin + BL.radix_tmp), st, (uint32_t*)(bin + BL.gauss_of_slot),
                                    (uint32_t*)(bin + BL.point_list), n_dev, /*head_zeroed (by the emit kernel)=*/true,
-                                   /*fail_flags=*/(uint32_t*)(geom + GL.meta), /*hist_counted=*/fused_bins,
-                                   fused_bins ? (uint2*)(bin + BL.ranges_enc) : nullptr)
+                                   /*fail_flags=*/F.meta(), /*hist_counted=*/fused_bins, ranges_enc)
             : gsr_radix_sort_pairs((uint32_t*)(bin + BL.key_a), (uint32_t*)(bin + BL.gauss_of_slot),
                                    (uint32_t*)(bin + BL.key_b), (uint32_t*)(bin + BL.point_list), /*vals_iota=*/false, R,
-                                   tile_bits(tiles), (uint32_t*)(bin + BL.radix_tmp), st, nullptr, nullptr, n_dev, true,
-                                   (uint32_t*)(geom + GL.meta), fused_bins, fused_bins ? (uint2*)(bin + BL.ranges_enc) : nullptr);
-    if (where != tile_sort_result_buffer(tiles)) { gsr_set_error("internal: tile sort buffer parity"); return GSR_ERR_HIP; }
-    if ((rc = debug_sync(s, st, "tile sort", (const uint32_t*)(geom + GL.meta)))) return rc;
+                                   gsr_tile_bits(tiles), (uint32_t*)(bin + BL.radix_tmp), st, NO_PAYLOAD, NO_PAYLOAD, n_dev,
+                                   /*head_zeroed=*/true, /*fail_flags=*/F.meta(), /*hist_counted=*/fused_bins, ranges_enc);
+    if (where != gsr_tile_sort_result_buffer(tiles)) { gsr_set_error("internal: tile sort buffer parity"); return GSR_ERR_HIP; }
+    if ((rc = debug_sync_status(s, st, "tile sort", F.meta()))) return rc;
     if (!fused_bins) {
       const uint32_t* ks = (const uint32_t*)(bin + (where ? BL.key_b : BL.key_a));
       gsr_launch_finalize((uint32_t)R, n_dev, ks, bin, BL, st);
       if ((rc = debug_sync(s, st, "finalize bins"))) return rc;
     }
     if (tile_local) {
-      // every tile orders its own list by (depth bits, id); the free halves of the tile sort's ping-pong buffers serve the
-      // (slow) path for lists beyond the LDS capacity
-      uint32_t* free_k = (uint32_t*)(bin + (where ? BL.key_a : BL.key_b));
-      uint32_t* free_w = (uint32_t*)(bin + (where ? BL.gauss_of_slot : BL.point_list));
-      uint32_t* free_v = (uint32_t*)(bin + (for_backward ? (where ? BL.val_a : BL.val_b) : BL.val_a));
-      uint32_t* slots = for_backward ? (uint32_t*)(bin + (where ? BL.val_b : BL.val_a)) : nullptr;
-      gsr_launch_tile_depth_sort(tiles, for_backward, (uint2*)(bin + BL.ranges),
-                                 fused_bins ? (const uint2*)(bin + BL.ranges_enc) : nullptr,
-                                 (uint32_t*)(bin + point_list_offset(BL, tiles)), slots,
-                                 (const uint32_t*)(geom + GL.depth_key), free_k, free_v, free_w,
-                                 (uint32_t*)(geom + GL.meta), walk_cnt, st);
+      gsr_launch_tile_depth_sort(F, for_backward, /*ranges_encoded=*/fused_bins, st);   // (binning.hip: every tile orders its own list)
       walk_cnt_clear = true;
       if ((rc = debug_sync(s, st, "tile depth sort"))) return rc;
     }
@@ -620,9 +601,9 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
     return rc;
   // status words of the non-blocking forward: written by the compositing kernel itself when the caller's slot is pinned
   // host memory (it is mapped into the device's address space), copied otherwise
-  uint32_t* status_dev = (host_status_late && g->P > 0) ? device_alias_of_pinned(host_status_late) : nullptr;
-  if (host_status_late && g->P > 0 && !status_dev &&
-      (rc = gsr_check(hipMemcpyAsync(host_status_late, geom + GL.meta, 32, hipMemcpyDeviceToHost, st), "read status")))
+  uint32_t* status_dev = (c.host_status && g->P > 0) ? device_alias_of_pinned(c.host_status) : nullptr;
+  if (c.host_status && g->P > 0 && !status_dev &&
+      (rc = gsr_check(hipMemcpyAsync(c.host_status, F.meta(), 32, hipMemcpyDeviceToHost, st), "read status")))
     return rc;
   if (!shade_late && sh_ready && g->P > 0) {   // colours were evaluated on a side stream: join it
     if ((rc = gsr_check(hipStreamWaitEvent(st, sh_ready, 0), "join shade"))) return rc;
@@ -638,14 +619,8 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
   // all forward paths share, so a frame whose phase 2 is repeated (capacity did not hold, culled frame flagged, re-render) starts
   // from zero again and nothing is counted twice
   if (n_touched && (rc = gsr_check(hipMemsetAsync(n_touched, 0, (size_t)g->P * 4, st), "memset n_touched"))) return rc;
-  gsr_launch_render_fwd(s, tiles, gx, (const uint2*)(bin + BL.ranges), (const uint32_t*)(bin + point_list_offset(BL, tiles)),
-                        (const float4*)(geom + GL.rec), out_color, out_invdepth, (float*)(img + IL.final_T),
-                        (uint32_t*)(img + IL.n_contrib), status_dev ? (const uint32_t*)(geom + GL.meta) : nullptr, status_dev,
-                        (g->P > 0 && R > 0) ? tile_cutoff : nullptr, (const uint32_t*)(geom + GL.depth_key),
-                        cull_applied ? (const uint32_t*)(bin + BL.culled_any) : nullptr, frame_tag, (uint32_t*)(geom + GL.meta),
-                        walk_cnt, walk_cnt ? (uint32_t*)(img + IL.walk_list) : nullptr,
-                        walk_cnt ? (uint32_t*)(img + IL.walk_of_tile) : nullptr, out_alpha, n_touched,
-                        n_touched ? ex->touched_T_min : 0.f, (uint32_t)R, st);
+  gsr_launch_render_fwd(s, F, out_color, out_invdepth, ex ? ex->out_alpha : nullptr, n_touched, n_touched ? ex->touched_T_min : 0.f,
+                        /*walk_classes=*/for_backward, status_dev, c.tile_cutoff, c.cull_applied, c.frame_tag, st);
   if ((rc = debug_sync(s, st, "render forward"))) return rc;
   return gsr_launch_status("forward");
 }
@@ -653,107 +628,114 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
 int gsr_forward_render(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                        size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
                        float* out_color, float* out_invdepth, int32_t for_backward, void* stream) {
-  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream);
+  return gsr_forward_render_ex(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
+                               out_color, out_invdepth, for_backward, stream, /*extras=*/nullptr);
 }
 
 int gsr_forward_render_shade(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                              size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
                              float* out_color, float* out_invdepth, int32_t for_backward, void* sh_ready_event,
                              void* stream) {
-  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, true, (hipEvent_t)sh_ready_event, stream);
+  return gsr_forward_render_shade_ex(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
+                                     out_color, out_invdepth, for_backward, sh_ready_event, stream, /*extras=*/nullptr);
 }
 
 // (the depth kind was applied by the gsr_forward_prepare*_ex call that filled the geometry state: phase 2 takes the opacity plane)
 int gsr_forward_render_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                           size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes, float* out_color,
                           float* out_invdepth, int32_t for_backward, void* stream, const gsr_render_extras* extras) {
-  int rc = check_extras(extras);
-  if (rc) return rc;
+  ForwardCall c;
+  c.for_backward = for_backward != 0;
+  c.extras = extras;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr,
-                             nullptr, false, nullptr, false, 0, extras);
+                             out_color, out_invdepth, c, stream);
 }
 
 int gsr_forward_render_shade_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                                 size_t binning_bytes, int64_t num_rendered, void* image_state, size_t image_bytes,
                                 float* out_color, float* out_invdepth, int32_t for_backward, void* sh_ready_event,
                                 void* stream, const gsr_render_extras* extras) {
-  int rc = check_extras(extras);
-  if (rc) return rc;
+  ForwardCall c;
+  c.for_backward = for_backward != 0;
+  c.shade_late = true;
+  c.sh_ready = (hipEvent_t)sh_ready_event;
+  c.extras = extras;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, num_rendered, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, true, (hipEvent_t)sh_ready_event, stream, false, nullptr,
-                             nullptr, nullptr, nullptr, false, nullptr, false, 0, extras);
+                             out_color, out_invdepth, c, stream);
 }
 
+// `c` as the caller states it: for_backward, defer_color, sh_ready, host_status, tile_local, tile_cutoff + cull_applied (= asked
+// for), extras; what the frame needs on top of that is worked out here.
 static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
-                      int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
-                      size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
-                      int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
-                      void* stream, int64_t* num_rendered_out, uint32_t* tile_cutoff, bool cull_apply,
-                      const gsr_render_extras* ex = nullptr) {
+                              int32_t* radii, void* binning_state, size_t binning_bytes, int64_t capacity, void* image_state,
+                              size_t image_bytes, float* out_color, float* out_invdepth, ForwardCall c,
+                              int64_t* num_rendered_out, void* stream) {
   int rc = validate(s, g);
   if (rc) return rc;
-  if ((rc = check_extras(ex))) return rc;
-  const bool tlo = tile_local_sort != 0;
+  if ((rc = check_extras(c.extras))) return rc;
   if (num_rendered_out) *num_rendered_out = 0;
-  if (g->P > 0) {
-    const bool late = defer_color != 0 && !g->colors_precomp;
-    const char* aside_str = getenv("GSR_SHADE_STREAM");      // (read per call: tests switch it inside one process)
-    const int aside_env = aside_str ? atoi(aside_str) : -1;
-    const bool want_aside = aside_env < 0 ? g->P >= 200000 : aside_env != 0;
-    SideShade* aside = (want_aside && !late && !g->colors_precomp && (g->shs || g->dc) && !s->debug) ? side_shade() : nullptr;
-    // verified speculation (num_rendered_out): the count goes to this thread's pinned slot as EARLY as the kernels know it,
-    // the whole frame is enqueued for `capacity`, and only then does the host wait for the count - the device still has the
-    // binning and compositing stages queued, so it never idles while the host looks
-    uint32_t* host = nullptr;
-    hipEvent_t ev = nullptr;
-    unsigned long long* early = nullptr;
-    if (num_rendered_out) {
-      host = pinned_slot();
-      ev = readback_event();
-      if (!host || !ev) { gsr_set_error("hipHostMalloc / hipEventCreate failed"); return GSR_ERR_HIP; }
-    }
-    // (tile-local form: the projection kernel clears the head of the tile sort's scratch in the caller's binning state, so that
-    // the emission's workgroups can add their digit counts to it)
-    uint32_t* sort_head = nullptr;
-    uint32_t* culled_any = nullptr;
-    static std::atomic<uint32_t> frame_counter{0};
-    const uint32_t frame_tag = ++frame_counter | 0x40000000u;     // (never 0: what a cleared buffer holds)
-    // lists truncated by the per-tile depth cut-off: only on the path whose frames are looked at AFTERWARDS (unverified: a frame
-    // whose truncation turns out too tight flags itself, its backward is a no-op, the caller renders it again), in the tile-local
-    // binning form (the projection kernel clears the per-tile "lost an instance" flags next to the sort's head)
-    bool cull = cull_apply && tile_cutoff != nullptr && tlo && num_rendered_out == nullptr && !s->debug;
-    if (tlo && binning_state && capacity > 0) {
-      const int gx0 = (s->image_width + GSR_TILE - 1) / GSR_TILE, gy0 = (s->image_height + GSR_TILE - 1) / GSR_TILE;
-      const GsrBinLayout BL0 = gsr_bin_layout((size_t)capacity, (size_t)gx0 * gy0);
-      if (binning_bytes >= BL0.total) {
-        sort_head = (uint32_t*)((char*)binning_state + BL0.radix_tmp);
-        culled_any = (uint32_t*)((char*)binning_state + BL0.culled_any);
-      }
-    }
-    if (!culled_any) cull = false;
-    if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, (hipStream_t)stream, late || aside != nullptr,
-                               host, ev, aside, tlo, &early, sort_head, cull ? tile_cutoff : nullptr, cull ? culled_any : nullptr,
-                               frame_tag, ex_depth_z(ex))))
-      return rc;
-    // (the caller's status words - flags, num_rendered and, in the tile-local form, the longest tile list meta[4] - leave at the END)
-    rc = forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, aside ? false : late,
-                             aside ? aside->join : (hipEvent_t)sh_ready_event, stream, tlo, host_status, early, tlo ? host : nullptr,
-                             ev, /*sort_head_clean=*/sort_head != nullptr, tile_cutoff, cull, frame_tag, ex);
-    if (rc) return rc;
-    if (num_rendered_out) {
-      const int64_t n = wait_for_count(host, ev, early != nullptr);
-      if (n < 0) return (int)n;
-      *num_rendered_out = n;
-    }
-    return 0;
+  if (g->P == 0) {      // background only: phase 2 on an empty frame
+    ForwardCall empty;
+    empty.for_backward = c.for_backward;
+    empty.extras = c.extras;
+    return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, 0, image_state, image_bytes, out_color,
+                               out_invdepth, empty, stream);
   }
-  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, 0, image_state, image_bytes, out_color,
-                             out_invdepth, for_backward != 0, false, nullptr, stream, false, nullptr, nullptr, nullptr, nullptr,
-                             false, nullptr, false, 0, ex);
+  const bool late = c.defer_color && !g->colors_precomp;
+  const char* aside_str = getenv("GSR_SHADE_STREAM");      // (read per call: tests switch it inside one process)
+  const int aside_env = aside_str ? atoi(aside_str) : -1;
+  const bool want_aside = aside_env < 0 ? g->P >= 200000 : aside_env != 0;
+  c.shade_aside = (want_aside && !late && !g->colors_precomp && (g->shs || g->dc) && !s->debug) ? side_shade() : nullptr;
+  c.defer_color = late || c.shade_aside != nullptr;
+  c.shade_late = c.shade_aside ? false : late;
+  if (c.shade_aside) c.sh_ready = c.shade_aside->join;
+  // verified speculation (num_rendered_out): the count goes to this thread's pinned slot as EARLY as the kernels know it,
+  // the whole frame is enqueued for `capacity`, and only then does the host wait for the count - the device still has the
+  // binning and compositing stages queued, so it never idles while the host looks
+  if (num_rendered_out) {
+    c.count_slot = pinned_slot();
+    c.count_event = readback_event();
+    if (!c.count_slot || !c.count_event) { gsr_set_error("hipHostMalloc / hipEventCreate failed"); return GSR_ERR_HIP; }
+  }
+  static std::atomic<uint32_t> frame_counter{0};
+  c.frame_tag = ++frame_counter | 0x40000000u;     // (never 0: what a cleared buffer holds)
+  // (tile-local form: the projection kernel clears the head of the tile sort's scratch in the caller's binning state, so that
+  // the emission's workgroups can add their digit counts to it.  A state too small for the frame is phase 2's error, below.)
+  GsrFrame F;
+  if (c.tile_local && capacity > 0 &&
+      frame_view(F, s, g->P, capacity, geometry_state, binning_state, binning_bytes, image_state, image_bytes) == 0) {
+    c.sort_head = (uint32_t*)(F.bin + F.BL.radix_tmp);
+    c.culled_any = (uint32_t*)(F.bin + F.BL.culled_any);
+  }
+  // lists truncated by the per-tile depth cut-off: only on the path whose frames are looked at AFTERWARDS (unverified: a frame
+  // whose truncation turns out too tight flags itself, its backward is a no-op, the caller renders it again), in the tile-local
+  // binning form (the projection kernel clears the per-tile "lost an instance" flags next to the sort's head)
+  c.cull_applied = c.cull_applied && c.tile_cutoff != nullptr && c.tile_local && num_rendered_out == nullptr && !s->debug &&
+                   c.culled_any != nullptr;
+  if ((rc = forward_geometry(s, g, geometry_state, geometry_bytes, radii, c, (hipStream_t)stream))) return rc;
+  // (the caller's status words - flags, num_rendered and, in the tile-local form, the longest tile list meta[4] - leave at the END)
+  if ((rc = forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes, out_color,
+                                out_invdepth, c, stream)))
+    return rc;
+  if (num_rendered_out) {
+    const int64_t n = wait_for_count(c.count_slot, c.count_event, c.early != nullptr);
+    if (n < 0) return (int)n;
+    *num_rendered_out = n;
+  }
+  return 0;
+}
+
+// the fields every gsr_forward_async* entry point states
+static ForwardCall async_call(int32_t for_backward, int32_t defer_color, void* sh_ready_event, uint32_t* host_status,
+                              int32_t tile_local_sort, const gsr_render_extras* extras) {
+  ForwardCall c;
+  c.for_backward = for_backward != 0;
+  c.defer_color = defer_color != 0;
+  c.sh_ready = (hipEvent_t)sh_ready_event;
+  c.host_status = host_status;
+  c.tile_local = tile_local_sort != 0;
+  c.extras = extras;
+  return c;
 }
 
 int gsr_forward_async(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -761,9 +743,9 @@ int gsr_forward_async(const gsr_settings* s, const gsr_gaussians* g, void* geome
                       size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
                       int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
                       void* stream, int64_t* num_rendered_out) {
-  return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
-                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
-                            tile_local_sort, stream, num_rendered_out, nullptr, false);
+  return gsr_forward_async_ex(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
+                              image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
+                              tile_local_sort, stream, num_rendered_out, /*extras=*/nullptr);
 }
 
 int gsr_forward_async_culled(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -771,9 +753,10 @@ int gsr_forward_async_culled(const gsr_settings* s, const gsr_gaussians* g, void
                              size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
                              int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
                              void* stream, int64_t* num_rendered_out, uint32_t* tile_depth_cutoff, int32_t apply) {
-  return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
-                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
-                            tile_local_sort, stream, num_rendered_out, tile_depth_cutoff, apply != 0);
+  return gsr_forward_async_culled_ex(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity,
+                                     image_state, image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event,
+                                     host_status, tile_local_sort, stream, num_rendered_out, tile_depth_cutoff, apply,
+                                     /*extras=*/nullptr);
 }
 
 int gsr_forward_async_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -781,9 +764,9 @@ int gsr_forward_async_ex(const gsr_settings* s, const gsr_gaussians* g, void* ge
                          size_t image_bytes, float* out_color, float* out_invdepth, int32_t for_backward,
                          int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
                          void* stream, int64_t* num_rendered_out, const gsr_render_extras* extras) {
+  const ForwardCall c = async_call(for_backward, defer_color, sh_ready_event, host_status, tile_local_sort, extras);
   return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
-                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
-                            tile_local_sort, stream, num_rendered_out, nullptr, false, extras);
+                            image_bytes, out_color, out_invdepth, c, num_rendered_out, stream);
 }
 
 int gsr_forward_async_culled_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, size_t geometry_bytes,
@@ -792,31 +775,44 @@ int gsr_forward_async_culled_ex(const gsr_settings* s, const gsr_gaussians* g, v
                                 int32_t defer_color, void* sh_ready_event, uint32_t* host_status, int32_t tile_local_sort,
                                 void* stream, int64_t* num_rendered_out, uint32_t* tile_depth_cutoff, int32_t apply,
                                 const gsr_render_extras* extras) {
+  ForwardCall c = async_call(for_backward, defer_color, sh_ready_event, host_status, tile_local_sort, extras);
+  c.tile_cutoff = tile_depth_cutoff;
+  c.cull_applied = apply != 0;
   return forward_async_impl(s, g, geometry_state, geometry_bytes, radii, binning_state, binning_bytes, capacity, image_state,
-                            image_bytes, out_color, out_invdepth, for_backward, defer_color, sh_ready_event, host_status,
-                            tile_local_sort, stream, num_rendered_out, tile_depth_cutoff, apply != 0, extras);
+                            image_bytes, out_color, out_invdepth, c, num_rendered_out, stream);
+}
+
+// everything phase 2 reads of the geometry state - records with their colours, tile counts, the count itself, depth order
+// or per-workgroup start slots - was left complete by the gsr_forward_async call this one repairs
+int gsr_forward_rerender(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
+                         size_t binning_bytes, int64_t capacity, void* image_state, size_t image_bytes, float* out_color,
+                         float* out_invdepth, int32_t for_backward, int32_t tile_local_sort, uint32_t* host_status,
+                         void* stream) {
+  return gsr_forward_rerender_ex(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
+                                 out_color, out_invdepth, for_backward, tile_local_sort, host_status, stream, /*extras=*/nullptr);
 }
 
 int gsr_forward_rerender_ex(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
                             size_t binning_bytes, int64_t capacity, void* image_state, size_t image_bytes, float* out_color,
                             float* out_invdepth, int32_t for_backward, int32_t tile_local_sort, uint32_t* host_status,
                             void* stream, const gsr_render_extras* extras) {
-  int rc = check_extras(extras);
-  if (rc) return rc;
+  ForwardCall c;
+  c.for_backward = for_backward != 0;
+  c.tile_local = tile_local_sort != 0;
+  c.host_status = host_status;
+  c.extras = extras;
   return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream, tile_local_sort != 0,
-                             host_status, nullptr, nullptr, nullptr, false, nullptr, false, 0, extras);
+                             out_color, out_invdepth, c, stream);
 }
 
-int gsr_forward_rerender(const gsr_settings* s, const gsr_gaussians* g, void* geometry_state, void* binning_state,
-                         size_t binning_bytes, int64_t capacity, void* image_state, size_t image_bytes, float* out_color,
-                         float* out_invdepth, int32_t for_backward, int32_t tile_local_sort, uint32_t* host_status,
-                         void* stream) {
-  // everything phase 2 reads of the geometry state - records with their colours, tile counts, the count itself, depth order
-  // or per-workgroup start slots - was left complete by the gsr_forward_async call this one repairs
-  return forward_render_impl(s, g, geometry_state, binning_state, binning_bytes, capacity, image_state, image_bytes,
-                             out_color, out_invdepth, for_backward != 0, false, nullptr, stream, tile_local_sort != 0,
-                             host_status);
+// the per-step factors of parameter group i: lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step), formed in double (sparse = 1: no
+// bias correction, the kernel uses lr itself)
+static void adam_step_factors(const gsr_fused_adam* opt, int i, GsrAdamArgs& A) {
+  A.lr[i] = opt->lr[i];
+  const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step[i]);
+  const double bc2 = 1.0 - pow(opt->beta2, (double)opt->step[i]);
+  A.step_size[i] = opt->sparse == 1 ? 0.f : (float)((double)opt->lr[i] / bc1);
+  A.inv_bc2_sqrt[i] = opt->sparse == 1 ? 0.f : (float)(1.0 / sqrt(bc2));
 }
 
 static int adam_args(const gsr_gaussians* g, const gsr_fused_adam* opt, GsrAdamArgs& A) {
@@ -829,11 +825,7 @@ static int adam_args(const gsr_gaussians* g, const gsr_fused_adam* opt, GsrAdamA
       return GSR_ERR_INVALID_ARGUMENT;
     }
     A.p[i] = params[i]; A.m[i] = opt->exp_avg[i]; A.v[i] = opt->exp_avg_sq[i];
-    A.lr[i] = opt->lr[i];
-    const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step[i]);
-    const double bc2 = 1.0 - pow(opt->beta2, (double)opt->step[i]);
-    A.step_size[i] = opt->sparse == 1 ? 0.f : (float)((double)opt->lr[i] / bc1);
-    A.inv_bc2_sqrt[i] = opt->sparse == 1 ? 0.f : (float)(1.0 / sqrt(bc2));
+    adam_step_factors(opt, i, A);
   }
   A.beta1 = (float)opt->beta1; A.beta2 = (float)opt->beta2;
   A.omb1 = (float)(1.0 - opt->beta1); A.omb2 = (float)(1.0 - opt->beta2);
@@ -856,15 +848,10 @@ extern "C" int gsr_adam_set_dynamic(const gsr_fused_adam* opt, float* dynamic_de
     gsr_set_error("adam_set_dynamic: bad arguments");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  // (the same arithmetic as adam_args: lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step) formed in double)
   GsrAdamArgs A;
   for (int i = 0; i < 6; i++) {
     A.p[i] = A.m[i] = A.v[i] = nullptr;
-    A.lr[i] = opt->lr[i];
-    const double bc1 = 1.0 - pow(opt->beta1, (double)opt->step[i]);
-    const double bc2 = 1.0 - pow(opt->beta2, (double)opt->step[i]);
-    A.step_size[i] = opt->sparse == 1 ? 0.f : (float)((double)opt->lr[i] / bc1);
-    A.inv_bc2_sqrt[i] = opt->sparse == 1 ? 0.f : (float)(1.0 / sqrt(bc2));
+    adam_step_factors(opt, i, A);
   }
   A.beta1 = A.beta2 = A.omb1 = A.omb2 = A.eps = 0.f;
   A.dyn = nullptr;
@@ -872,29 +859,41 @@ extern "C" int gsr_adam_set_dynamic(const gsr_fused_adam* opt, float* dynamic_de
   return gsr_launch_status("adam set dynamic");
 }
 
+// what a backward call asks for beyond the plain gsr_backward (the defaults)
+struct BackwardCall {
+  const gsr_fused_adam* opt = nullptr;       // the optimizer step folded into the projection backward
+  const gsr_camera_grads* cam = nullptr;     // gradients of the camera, summed through cam_scratch
+  void* cam_scratch = nullptr;
+  size_t cam_scratch_bytes = 0;
+  const gsr_render_extras* extras = nullptr; // depth kind, dL_dalpha
+  bool cam_only = false;                     // no per-Gaussian output at all: `grads` is not looked at
+};
+
 static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
                          const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
-                         const gsr_fused_adam* opt, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
-                         void* stream, const gsr_render_extras* ex = nullptr, bool cam_only = false) {
+                         const BackwardCall& c, void* stream) {
+  const gsr_fused_adam* opt = c.opt;
+  const gsr_camera_grads* cam = c.cam;
+  const gsr_render_extras* ex = c.extras;
   int rc = validate(s, g);
   if (rc) return rc;
   if ((rc = check_extras(ex))) return rc;
   if (cam && !cam->dL_dviewmatrix && !cam->dL_dprojmatrix && !cam->dL_dcampos) cam = nullptr;   // nothing asked for: plain
   // camera-only form (gsr_backward_camera_only): no per-Gaussian output at all - `grads` is not looked at
   static const gsr_grads no_grads = {};
-  if (cam_only) {
+  if (c.cam_only) {
     if (!cam || !dL_dcolor) {
       gsr_set_error("backward_camera_only: no camera gradient asked for (or dL_dcolor missing)");
       return GSR_ERR_INVALID_ARGUMENT;
     }
     grads = &no_grads;
   }
-  if (cam && (!cam_scratch || cam_scratch_bytes < gsr_camera_grad_scratch_bytes(g->P))) {
+  if (cam && (!c.cam_scratch || c.cam_scratch_bytes < gsr_camera_grad_scratch_bytes(g->P))) {
     gsr_set_error("backward_camera: camera scratch too small (gsr_camera_grad_scratch_bytes)");
     return GSR_ERR_STATE_TOO_SMALL;
   }
-  if (!cam_only &&
+  if (!c.cam_only &&
       (!grads || !grads->dL_dmeans2D || !dL_dcolor || (!opt && (!grads->dL_dmeans3D || !grads->dL_dopacities)))) {
     gsr_set_error("backward: missing mandatory gradient buffers");
     return GSR_ERR_INVALID_ARGUMENT;
@@ -905,42 +904,29 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
     return GSR_ERR_INVALID_ARGUMENT;
   }
   hipStream_t st = (hipStream_t)stream;
+  float* cam_rows = cam ? (float*)c.cam_scratch : nullptr;
   if (g->P == 0) {
     if (!cam) return 0;
-    gsr_launch_cam_reduce(0, (float*)cam_scratch, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, st);   // zeros
+    gsr_launch_cam_reduce(0, cam_rows, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, st);   // zeros
     return gsr_launch_status("backward camera");
   }
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
-  const int tiles = gx * gy;
-  const size_t R = (size_t)num_rendered;
   if (scratch_bytes < gsr_backward_scratch_bytes(g->P, num_rendered) || !scratch) {
     gsr_set_error("backward scratch too small");
     return GSR_ERR_STATE_TOO_SMALL;
   }
-  const GsrGeomLayout GL = gsr_geom_layout(g->P);
-  const GsrBinLayout BL = gsr_bin_layout(R, tiles);
-  const GsrImgLayout IL = gsr_img_layout(W, H);
-  const char* geom = (const char*)geometry_state;
-  const char* bin = (const char*)binning_state;
-  const char* img = (const char*)image_state;
+  GsrFrame F;
+  if ((rc = frame_view(F, s, g->P, num_rendered, geometry_state, binning_state, GSR_UNSIZED, image_state, GSR_UNSIZED))) return rc;
   float4* igrad = (float4*)scratch;
-  if (R > 0) {
-    gsr_launch_render_bwd(s, tiles, gx, (const uint2*)(bin + BL.ranges), (const uint32_t*)(bin + point_list_offset(BL, tiles)),
-                          (const float4*)(geom + GL.rec), (const float*)(img + IL.final_T),
-                          (const uint32_t*)(img + IL.n_contrib), dL_dcolor, dL_dinvdepth,
-                          (const uint32_t*)(bin + (tile_sort_result_buffer(tiles) ? BL.val_b : BL.val_a)), igrad,
-                          (const uint32_t*)(geom + GL.meta) + 2, (uint32_t)R, (const uint32_t*)(img + IL.walk_cnt),
-                          (const uint32_t*)(img + IL.walk_list), (const uint32_t*)(img + IL.walk_of_tile), ex_dalpha(ex), st);
+  if (F.R > 0) {
+    gsr_launch_render_bwd(s, F, dL_dcolor, dL_dinvdepth, ex ? ex->dL_dalpha : nullptr, igrad, st);
     if ((rc = debug_sync(s, st, "render backward"))) return rc;
   }
   GsrAdamArgs A;
   if (opt && (rc = adam_args(g, opt, A))) return rc;
   // rows: 0 every row (dense) / 1 rows with radii > 0, no bias correction (sparse) / 2 dense, rows with instances only
   const int mode = !opt ? 0 : (opt->sparse == 1 ? 2 : (opt->sparse == 2 ? 3 : 1));
-  float* cam_rows = cam ? (float*)cam_scratch : nullptr;
-  const int groups = gsr_launch_preprocess_bwd(s, g, radii, geom, GL, igrad, (uint32_t)R, grads, opt ? &A : nullptr, mode,
-                                               cam_rows, ex_depth_z(ex), cam_only, st);
+  const int groups = gsr_launch_preprocess_bwd(s, g, radii, F.geom, F.GL, igrad, (uint32_t)F.R, grads, opt ? &A : nullptr, mode,
+                                               cam_rows, ex_depth_z(ex), c.cam_only, st);
   if (groups < 0) {
     gsr_set_error("backward_adam needs the raw-parameter call form with dc / shs passed separately (raw_activations = 1, "
                   "dc != NULL, no colors_precomp / cov3D_precomp, every stored SH coefficient active)");
@@ -954,46 +940,32 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   return gsr_launch_status("backward");
 }
 
-int gsr_backward(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
-                 const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
-                 const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
-                 void* stream) {
-  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, nullptr, nullptr, nullptr, 0, stream);
-}
-
-int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
-                        const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
-                        const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
-                        const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream) {
-  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream);
-}
-
-int gsr_backward_camera_only(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
-                             const void* geometry_state, const void* binning_state, const void* image_state,
-                             int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
-                             size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
-                             void* stream) {
-  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, nullptr, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, nullptr, true);
-}
-
-int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
-                      const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
-                      const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
-                      const gsr_fused_adam* opt, void* stream) {
-  if (!opt) { gsr_set_error("backward_adam: null optimizer arguments"); return GSR_ERR_INVALID_ARGUMENT; }
-  return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, opt, nullptr, nullptr, 0, stream);
-}
-
 int gsr_backward_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
                     const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
                     const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads, void* stream,
                     const gsr_render_extras* extras) {
+  BackwardCall c;
+  c.extras = extras;
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, nullptr, nullptr, nullptr, 0, stream, extras);
+                       scratch, scratch_bytes, grads, c, stream);
+}
+
+int gsr_backward(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                 const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                 const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                 void* stream) {
+  return gsr_backward_ex(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth, scratch,
+                         scratch_bytes, grads, stream, /*extras=*/nullptr);
+}
+
+static BackwardCall camera_call(const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
+                                const gsr_render_extras* extras) {
+  BackwardCall c;
+  c.cam = cam;
+  c.cam_scratch = cam_scratch;
+  c.cam_scratch_bytes = cam_scratch_bytes;
+  c.extras = extras;
+  return c;
 }
 
 int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
@@ -1002,7 +974,15 @@ int gsr_backward_camera_ex(const gsr_settings* s, const gsr_gaussians* g, const 
                            const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream,
                            const gsr_render_extras* extras) {
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, extras);
+                       scratch, scratch_bytes, grads, camera_call(cam, cam_scratch, cam_scratch_bytes, extras), stream);
+}
+
+int gsr_backward_camera(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                        const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                        const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                        const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes, void* stream) {
+  return gsr_backward_camera_ex(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                                scratch, scratch_bytes, grads, cam, cam_scratch, cam_scratch_bytes, stream, /*extras=*/nullptr);
 }
 
 int gsr_backward_camera_only_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
@@ -1010,8 +990,20 @@ int gsr_backward_camera_only_ex(const gsr_settings* s, const gsr_gaussians* g, c
                                 int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
                                 size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch,
                                 size_t cam_scratch_bytes, void* stream, const gsr_render_extras* extras) {
+  BackwardCall c = camera_call(cam, cam_scratch, cam_scratch_bytes, extras);
+  c.cam_only = true;
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, nullptr, nullptr, cam, cam_scratch, cam_scratch_bytes, stream, extras, true);
+                       scratch, scratch_bytes, /*grads=*/nullptr, c, stream);
+}
+
+int gsr_backward_camera_only(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
+                             const void* geometry_state, const void* binning_state, const void* image_state,
+                             int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, void* scratch,
+                             size_t scratch_bytes, const gsr_camera_grads* cam, void* cam_scratch, size_t cam_scratch_bytes,
+                             void* stream) {
+  return gsr_backward_camera_only_ex(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor,
+                                     dL_dinvdepth, scratch, scratch_bytes, cam, cam_scratch, cam_scratch_bytes, stream,
+                                     /*extras=*/nullptr);
 }
 
 int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
@@ -1019,8 +1011,19 @@ int gsr_backward_adam_ex(const gsr_settings* s, const gsr_gaussians* g, const in
                          const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
                          const gsr_fused_adam* opt, void* stream, const gsr_render_extras* extras) {
   if (!opt) { gsr_set_error("backward_adam: null optimizer arguments"); return GSR_ERR_INVALID_ARGUMENT; }
+  BackwardCall c;
+  c.opt = opt;
+  c.extras = extras;
   return backward_impl(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
-                       scratch, scratch_bytes, grads, opt, nullptr, nullptr, 0, stream, extras);
+                       scratch, scratch_bytes, grads, c, stream);
+}
+
+int gsr_backward_adam(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const void* geometry_state,
+                      const void* binning_state, const void* image_state, int64_t num_rendered, const float* dL_dcolor,
+                      const float* dL_dinvdepth, void* scratch, size_t scratch_bytes, const gsr_grads* grads,
+                      const gsr_fused_adam* opt, void* stream) {
+  return gsr_backward_adam_ex(s, g, radii, geometry_state, binning_state, image_state, num_rendered, dL_dcolor, dL_dinvdepth,
+                              scratch, scratch_bytes, grads, opt, stream, /*extras=*/nullptr);
 }
 
 int gsr_adam_step_culled_rows(const gsr_gaussians* g, const void* geometry_state, int64_t num_rendered,
@@ -1070,10 +1073,10 @@ int gsr_debug_geometry_views(const void* geometry_state, int32_t P, const float*
 
 int gsr_debug_binning_views(const void* binning_state, int32_t W, int32_t H, int64_t R, const uint32_t** point_list,
                             const uint32_t** ranges) {
-  const size_t tiles = (size_t)((W + GSR_TILE - 1) / GSR_TILE) * (size_t)((H + GSR_TILE - 1) / GSR_TILE);
+  const size_t tiles = gsr_tile_grid(W, H).tiles;
   const GsrBinLayout BL = gsr_bin_layout((size_t)R, tiles);
   const char* bin = (const char*)binning_state;
-  if (point_list) *point_list = (const uint32_t*)(bin + point_list_offset(BL, tiles));
+  if (point_list) *point_list = (const uint32_t*)(bin + gsr_point_list_offset(BL, (int)tiles));
   if (ranges) *ranges = (const uint32_t*)(bin + BL.ranges);
   return 0;
 }
@@ -1084,15 +1087,10 @@ int gsr_debug_count_pairs(const gsr_settings* s, int32_t P, const void* geometry
     gsr_set_error("count_pairs: bad arguments");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
-  const int tiles = gx * gy;
-  const GsrGeomLayout GL = gsr_geom_layout(P);
-  const GsrBinLayout BL = gsr_bin_layout((size_t)num_rendered, tiles);
-  const char* geom = (const char*)geometry_state;
-  const char* bin = (const char*)binning_state;
-  gsr_launch_count_pairs(s, tiles, gx, (const uint2*)(bin + BL.ranges), (const uint32_t*)(bin + point_list_offset(BL, tiles)),
-                         (const float4*)(geom + GL.rec), pairs, (hipStream_t)stream);
+  GsrFrame F;
+  const int rc = frame_view(F, s, P, num_rendered, geometry_state, binning_state, GSR_UNSIZED, /*image_state=*/nullptr, GSR_UNSIZED);
+  if (rc) return rc;
+  gsr_launch_count_pairs(s, F, pairs, (hipStream_t)stream);
   return gsr_launch_status("count_pairs");
 }
 

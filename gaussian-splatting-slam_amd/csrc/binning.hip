@@ -437,9 +437,9 @@ __global__ __launch_bounds__(256) void k_tile_depth_sort(const uint2* __restrict
 
 // ranges_enc: nullptr (ranges hold [start, end) already: k_finalize_bins ran) or the encoded pairs of the sort's last pass, which
 // the first launch decodes into `ranges`
-void gsr_launch_tile_depth_sort(int tiles, bool dual, uint2* ranges, const uint2* ranges_enc, uint32_t* point_list,
-                                uint32_t* slot_of_pos, const uint32_t* depth_key, uint32_t* free_a, uint32_t* free_b,
-                                uint32_t* free_c, uint32_t* meta, uint32_t* walk_cnt, hipStream_t st) {
+static void launch_tile_depth_sort(int tiles, bool dual, uint2* ranges, const uint2* ranges_enc, uint32_t* point_list,
+                                   uint32_t* slot_of_pos, const uint32_t* depth_key, uint32_t* free_a, uint32_t* free_b,
+                                   uint32_t* free_c, uint32_t* meta, uint32_t* walk_cnt, hipStream_t st) {
   const uint2* rin = ranges_enc ? ranges_enc : (const uint2*)ranges;
   // (ABOVEV == 0: the first launch over the tiles - the one that clears the walk-class counters)
 #define GSR_TLO(NAME, D, CAPV, ABOVEV, DEC, RIN)                                                                         \
@@ -467,6 +467,20 @@ void gsr_launch_tile_depth_sort(int tiles, bool dual, uint2* ranges, const uint2
 #undef GSR_TLO
 }
 
+// Every tile of a frame orders its own list by (depth bits, id); the free halves of the tile sort's ping-pong buffers serve the
+// (slow) path for lists beyond the LDS capacity.
+void gsr_launch_tile_depth_sort(const GsrFrame& F, bool for_backward, bool ranges_encoded, hipStream_t st) {
+  const GsrBinLayout& BL = F.BL;
+  const int where = gsr_tile_sort_result_buffer(F.tiles);
+  uint32_t* free_k = (uint32_t*)(F.bin + (where ? BL.key_a : BL.key_b));
+  uint32_t* free_w = (uint32_t*)(F.bin + (where ? BL.gauss_of_slot : BL.point_list));
+  uint32_t* free_v = (uint32_t*)(F.bin + (for_backward ? (where ? BL.val_a : BL.val_b) : BL.val_a));
+  uint32_t* slots = for_backward ? (uint32_t*)(F.bin + (where ? BL.val_b : BL.val_a)) : nullptr;
+  launch_tile_depth_sort(F.tiles, for_backward, F.ranges(), ranges_encoded ? (const uint2*)(F.bin + BL.ranges_enc) : nullptr,
+                         F.point_list(), slots, F.depth_key(), free_k, free_v, free_w, F.meta(),
+                         for_backward ? F.walk_cnt() : nullptr, st);
+}
+
 // test hook (include/gsr.h): the per-tile ordering on caller-made lists, without the walk-class counters
 extern "C" int gsr_debug_tile_depth_sort(int32_t tiles, int32_t dual, uint32_t* ranges, const uint32_t* ranges_enc,
                                          uint32_t* point_list, uint32_t* slot_of_pos, const uint32_t* depth_key,
@@ -475,8 +489,8 @@ extern "C" int gsr_debug_tile_depth_sort(int32_t tiles, int32_t dual, uint32_t* 
     gsr_set_error("debug_tile_depth_sort: bad arguments");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  gsr_launch_tile_depth_sort(tiles, dual != 0, (uint2*)ranges, (const uint2*)ranges_enc, point_list, dual ? slot_of_pos : nullptr,
-                             depth_key, free_a, free_b, free_c, meta, nullptr, (hipStream_t)stream);
+  launch_tile_depth_sort(tiles, dual != 0, (uint2*)ranges, (const uint2*)ranges_enc, point_list, dual ? slot_of_pos : nullptr,
+                         depth_key, free_a, free_b, free_c, meta, nullptr, (hipStream_t)stream);
   return gsr_launch_status("debug tile depth sort");
 }
 

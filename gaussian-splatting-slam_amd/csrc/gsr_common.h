@@ -186,10 +186,17 @@ static inline GsrBinLayout gsr_bin_layout(size_t R, size_t tiles) {
   return L;
 }
 
+// the tile grid of a W x H image: tiles per row and per column (64-bit: api.hip's validate() holds them to their limits), and in all
+struct GsrTileGrid { long long gx, gy; size_t tiles; };
+static inline GsrTileGrid gsr_tile_grid(int W, int H) {
+  const long long gx = ((long long)W + GSR_TILE - 1) / GSR_TILE, gy = ((long long)H + GSR_TILE - 1) / GSR_TILE;
+  return {gx, gy, (size_t)gx * (size_t)gy};
+}
+
 static inline GsrImgLayout gsr_img_layout(int W, int H) {
   GsrImgLayout L;
   const size_t N = (size_t)W * (size_t)H;
-  const size_t tiles = (size_t)((W + GSR_TILE - 1) / GSR_TILE) * (size_t)((H + GSR_TILE - 1) / GSR_TILE);
+  const size_t tiles = gsr_tile_grid(W, H).tiles;
   size_t o = 0;
   L.final_T = o;   o += gsr_align(N * 4);
   L.n_contrib = o; o += gsr_align(N * 4);
@@ -240,6 +247,41 @@ __device__ __forceinline__ GsrAdamArgs gsr_adam_resolve(const GsrAdamArgs& in) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// One frame as the host path sees it (api.hip frame_view fills it): the three caller-owned state blobs, their layouts, the tile
+// grid and the capacity the binning state is laid out for.  The launchers below take it and slice their own pointers out of it.
+// -------------------------------------------------------------------------------------------------
+static inline int gsr_tile_bits(int tiles) {
+  int b = 1;
+  while ((1 << b) < tiles) b++;
+  return b;
+}
+// which ping-pong buffer holds the tile-sorted (key, slot) arrays: one swap per 8-bit pass
+static inline int gsr_tile_sort_result_buffer(int tiles) { return gsr_radix_passes(gsr_tile_bits(tiles)) & 1; }
+// the Gaussian-id list rides through the tile sort as a second payload, ping-ponging gauss_of_slot <-> point_list
+static inline size_t gsr_point_list_offset(const GsrBinLayout& BL, int tiles) {
+  return gsr_tile_sort_result_buffer(tiles) ? BL.point_list : BL.gauss_of_slot;
+}
+
+struct GsrFrame {
+  char* geom;            // geometry state (per Gaussian; a backward only reads the three blobs)
+  char* bin;             // binning state (per instance and per tile), laid out for R instances
+  char* img;             // image state (per pixel, walk classes)
+  GsrGeomLayout GL;
+  GsrBinLayout BL;
+  GsrImgLayout IL;
+  int P, gx, tiles;
+  size_t R;              // the CAPACITY: the instances really present are min(meta num_rendered, R), read on the device (gsr_eff_n)
+
+  uint32_t* meta() const { return (uint32_t*)(geom + GL.meta); }
+  const uint32_t* n_dev() const { return (const uint32_t*)(geom + GL.meta) + 2; }      // the 64-bit count, meta[2..3]
+  const float4* rec() const { return (const float4*)(geom + GL.rec); }
+  const uint32_t* depth_key() const { return (const uint32_t*)(geom + GL.depth_key); }
+  uint2* ranges() const { return (uint2*)(bin + BL.ranges); }
+  uint32_t* point_list() const { return (uint32_t*)(bin + gsr_point_list_offset(BL, tiles)); }
+  uint32_t* walk_cnt() const { return (uint32_t*)(img + IL.walk_cnt); }
+};
+
+// -------------------------------------------------------------------------------------------------
 // host-side launch helpers (api.hip owns the definitions)
 // -------------------------------------------------------------------------------------------------
 void gsr_set_error(const char* fmt, ...);
@@ -262,6 +304,41 @@ int gsr_launch_status(const char* what);
       if (gsr_e_ != hipSuccess) gsr_note_launch_failure(name, gsr_e_);         \
     }                                                                          \
   } while (0)
+
+// The launchers of the kernel files, declared ONCE and with parameter names: the kernel files and api.hip see the same prototype.
+// preprocess.hip
+void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, int32_t* radii, char* geom, const GsrGeomLayout& L,
+                               bool defer_color, bool block_sums, uint32_t* zero_words, int n_zero_words,
+                               const uint32_t* tile_cutoff, uint32_t* culled_any, uint32_t frame_tag, bool depth_z, hipStream_t st);
+void gsr_launch_shade(const gsr_settings* s, const gsr_gaussians* g, char* geom, const GsrGeomLayout& L, bool beside_other_work,
+                      hipStream_t st);
+void gsr_launch_sum_tiles(int P, const char* geom, const GsrGeomLayout& L, uint32_t* meta, hipStream_t st);
+int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const char* geom,
+                              const GsrGeomLayout& L, const float4* igrad, uint32_t cap, const gsr_grads* gr,
+                              const GsrAdamArgs* adam, int adam_mode, float* cam_rows, bool depth_z, bool cam_only, hipStream_t st);
+void gsr_launch_adam_culled_rows(int P, int sh_stride, const char* geom, const GsrGeomLayout& L, const GsrAdamArgs& A, uint32_t cap,
+                                 hipStream_t st);
+size_t gsr_cam_scratch_floats(int P);
+void gsr_launch_cam_reduce(int n, float* rows, float* dV, float* dPV, float* dcam, hipStream_t st);
+void gsr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t st);
+// binning.hip
+void gsr_launch_emit(int P, int grid_x, int tiles, char* geom, const GsrGeomLayout& GL, char* bin, const GsrBinLayout& BL,
+                     uint32_t cap, bool index_order, unsigned long long* early, int count_hist_bits, const uint32_t* tile_cutoff,
+                     hipStream_t st);
+void gsr_launch_finalize(uint32_t cap, const uint32_t* n_dev, const uint32_t* tile_sorted, char* bin, const GsrBinLayout& BL,
+                         hipStream_t st);
+// for_backward: the emission slots are permuted along, and the walk-class counters cleared; ranges_encoded: the tile sort's last
+// pass left the ranges (no k_finalize_bins ran)
+void gsr_launch_tile_depth_sort(const GsrFrame& F, bool for_backward, bool ranges_encoded, hipStream_t st);
+// render.hip
+// walk_classes: file every tile under its walk class (a backward follows); status_dst: the caller's pinned status slot as the device
+// sees it, or nullptr; tile_cutoff: updated per tile, and with cull_applied the frame was counted and emitted with it
+void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_color, float* out_invdepth, float* out_alpha,
+                           uint32_t* n_touched, float touch_T_min, bool walk_classes, uint32_t* status_dst, uint32_t* tile_cutoff,
+                           bool cull_applied, uint32_t frame_tag, hipStream_t st);
+void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* pairs, hipStream_t st);
+void gsr_launch_render_bwd(const gsr_settings* s, const GsrFrame& F, const float* dL_dpix, const float* dL_dinvdepth,
+                           const float* dL_dalpha, float4* igrad, hipStream_t st);
 
 // sort_scan.hip
 // Exclusive (inclusive=0) or inclusive scan of n u32 values: out[i] = scan(src[idx ? idx[i] : i]).

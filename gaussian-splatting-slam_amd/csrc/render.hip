@@ -1480,12 +1480,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
   }
 }
 
-void gsr_launch_render_fwd(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges,
-                           const uint32_t* point_list, const float4* rec, float* out_color, float* out_invdepth,
-                           float* final_T, uint32_t* n_contrib, const uint32_t* status_src, uint32_t* status_dst,
-                           uint32_t* tile_cutoff, const uint32_t* depth_key, const uint32_t* culled_any, uint32_t frame_tag,
-                           uint32_t* meta, uint32_t* walk_cnt, uint32_t* walk_list, uint32_t* walk_of_tile, float* out_alpha,
-                           uint32_t* n_touched, float touch_T_min, uint32_t touch_cap, hipStream_t st) {
+void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_color, float* out_invdepth, float* out_alpha,
+                           uint32_t* n_touched, float touch_T_min, bool walk_classes, uint32_t* status_dst, uint32_t* tile_cutoff,
+                           bool cull_applied, uint32_t frame_tag, hipStream_t st) {
+  const int tiles = F.tiles, grid_x = F.gx;
+  const uint2* ranges = F.ranges();
+  const uint32_t* point_list = F.point_list();
+  const float4* rec = F.rec();
+  float* final_T = (float*)(F.img + F.IL.final_T);
+  uint32_t* n_contrib = (uint32_t*)(F.img + F.IL.n_contrib);
+  // status words of the non-blocking forward: stored by the kernel itself where the caller's slot is mapped into the device
+  const uint32_t* status_src = status_dst ? (const uint32_t*)F.meta() : nullptr;
+  if (!(F.P > 0 && F.R > 0)) tile_cutoff = nullptr;                         // (no list was emitted: nothing to learn a cut-off from)
+  const uint32_t* depth_key = F.depth_key();
+  const uint32_t* culled_any = cull_applied ? (const uint32_t*)(F.bin + F.BL.culled_any) : nullptr;
+  uint32_t* meta = F.meta();
+  uint32_t* walk_cnt = walk_classes ? F.walk_cnt() : nullptr;
+  uint32_t* walk_list = walk_cnt ? (uint32_t*)(F.img + F.IL.walk_list) : nullptr;
+  uint32_t* walk_of_tile = walk_cnt ? (uint32_t*)(F.img + F.IL.walk_of_tile) : nullptr;
+  const uint32_t touch_cap = (uint32_t)F.R;
   // cut-off margin of the depth-truncated lists: 1.75 x the entries a tile needed + 48 (measured, profiles/r04_tile_cull.txt: 1.25 x + 16
   // flags 54 % of the frames of a run that trains from scratch, 1.5 x + 32 1 %, 1.75 x + 48 none; C3 and the 2 x splats scene)
   unsigned mq8 = 448, madd = 48;
@@ -1510,8 +1523,11 @@ void gsr_launch_render_fwd(const gsr_settings* s, int tiles, int grid_x, const u
 #undef GSR_FWD_LAUNCH
 }
 
-void gsr_launch_count_pairs(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges, const uint32_t* point_list,
-                            const float4* rec, uint32_t* pairs, hipStream_t st) {
+void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* pairs, hipStream_t st) {
+  const int tiles = F.tiles, grid_x = F.gx;
+  const uint2* ranges = F.ranges();
+  const uint32_t* point_list = F.point_list();
+  const float4* rec = F.rec();
   // (the instrumented build counts the entries the PUBLISHED loop evaluates per pixel - the unit of SURVEY 8(d)'s FLOP model -
   // i.e. the unmasked walk; the masked production kernel evaluates fewer)
   hipLaunchKernelGGL((k_render_fwd<true, false>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, ranges,
@@ -1521,12 +1537,21 @@ void gsr_launch_count_pairs(const gsr_settings* s, int tiles, int grid_x, const 
                      (float*)nullptr, (uint32_t*)nullptr, 0.f, 0u);
 }
 
-void gsr_launch_render_bwd(const gsr_settings* s, int tiles, int grid_x, const uint2* ranges,
-                           const uint32_t* point_list, const float4* rec, const float* final_T,
-                           const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dinvdepth,
-                           const uint32_t* slot_of_pos, float4* igrad, const uint32_t* n_dev, uint32_t cap,
-                           const uint32_t* walk_cnt, const uint32_t* walk_list, const uint32_t* walk_of_tile,
-                           const float* dL_dalpha, hipStream_t st) {
+void gsr_launch_render_bwd(const gsr_settings* s, const GsrFrame& F, const float* dL_dpix, const float* dL_dinvdepth,
+                           const float* dL_dalpha, float4* igrad, hipStream_t st) {
+  const int tiles = F.tiles, grid_x = F.gx;
+  const uint2* ranges = F.ranges();
+  const uint32_t* point_list = F.point_list();
+  const float4* rec = F.rec();
+  const float* final_T = (const float*)(F.img + F.IL.final_T);
+  const uint32_t* n_contrib = (const uint32_t*)(F.img + F.IL.n_contrib);
+  // the emission slot of every list position: the value the tile sort carried, in the buffer its last pass wrote
+  const uint32_t* slot_of_pos = (const uint32_t*)(F.bin + (gsr_tile_sort_result_buffer(tiles) ? F.BL.val_b : F.BL.val_a));
+  const uint32_t* n_dev = F.n_dev();
+  const uint32_t cap = (uint32_t)F.R;
+  const uint32_t* walk_cnt = F.walk_cnt();
+  const uint32_t* walk_list = (const uint32_t*)(F.img + F.IL.walk_list);
+  const uint32_t* walk_of_tile = (const uint32_t*)(F.img + F.IL.walk_of_tile);
   // GSR_BWD_LPT=0: tiles in index order (the A/B of the walk classes, profiles/r04_bwd_lpt_ab.txt)
   if (const char* lp = getenv("GSR_BWD_LPT")) {
     if (lp[0] == '0') walk_cnt = nullptr;
