@@ -1,8 +1,8 @@
 // solve6_common.h - the 6-unknown Gauss-Newton step of include/gsr.h, shared by registration.hip (gsr_icp_update_plane,
 // gsr_icp_update_colored) and odometry.hip (gsr_odometry_update): ONE workspace layout, ONE final kernel (the rows of partial sums,
 // the stats header, the n < 6 rule, the unpacking of the triangle) and ONE body for the LDL^T solve, the vector-to-matrix
-// composition and T <- dT T, so the thresholds, the stats layout, the pivot rule and the order of operations agree by
-// construction.  What differs between the updates stays in their files: the partial kernel that forms a workgroup's row
+// composition and T <- dT T (posegraph.hip takes the same three for its 6 x 6 node blocks and its pose update), so the
+// thresholds, the stats layout, the pivot rule and the order of operations agree by construction.  What differs between the updates stays in their files: the partial kernel that forms a workgroup's row
 //   s[0] = n, s[1 .. H-1] = sums of squared residuals, s[H .. H+5] = J^T r, s[H+6 .. H+26] = J^T J rows 0 .. 5 from the diagonal on.
 // (Everything here is defined above odometry.hip's `fp contract(off)`: both files compile these bodies alike.)
 #pragma once
@@ -44,20 +44,16 @@ __device__ __forceinline__ void gn_stats_header(const double (&s)[N], double den
   for (int k = 0; k < 4; k++) stats[4 + k] = k < H - 1 ? s[1 + k] : 0.0;
 }
 
-// thread 0 of the final kernel: J^T J x = -J^T r on the matrix in A and the right-hand side in g, both filled by the caller; then
-// dR, dT and T <- dT T.  stats[3] = 0, or 2 with T as it was.  The arrays are LDS: indexed at run time, which registers cannot
-// be.  `shift`: the point dT is formed about (three zeros: about the origin).
-__device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L)[6][6], double (&D)[6], double (&g)[6],
-                                                   double (&x)[6], const double* __restrict__ shift, double* __restrict__ T_dev,
-                                                   double* __restrict__ stats) {
-  // J^T J = L D L^T, L unit lower triangular; every pivot is held against its own diagonal entry (scale-free per unknown)
+// The three bodies of the step, shared with posegraph.hip (one 6 x 6 block per node there): the LDL^T factorisation with its pivot
+// rule, the two triangular solves, and M(x): dR = Rz(gamma) Ry(beta) Rx(alpha) with T <- [dR, td] T.  The arrays are indexed at
+// run time: LDS in the one-thread callers below, per-thread arrays (unrolled by the compiler) in posegraph.hip.
+// A = L D L^T, L unit lower triangular; every pivot is held against its own diagonal entry (scale-free per unknown).  false: a
+// pivot that is not finite or is <= GSR_ICP_PIVOT_MIN x its diagonal entry
+__device__ __forceinline__ bool gsr_ldlt6_factor(const double (&A)[6][6], double (&L)[6][6], double (&D)[6]) {
   for (int j = 0; j < 6; j++) {
     double d = A[j][j];
     for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * D[k];
-    if (!(fabs(d) < (double)KNN_INF) || !(d > GSR_ICP_PIVOT_MIN * A[j][j])) {
-      stats[3] = 2.0;      // the correspondences do not fix this unknown (one plane, or sums that overflowed): T stays
-      return;
-    }
+    if (!(fabs(d) < (double)KNN_INF) || !(d > GSR_ICP_PIVOT_MIN * A[j][j])) return false;
     D[j] = d;
     L[j][j] = 1.0;
     for (int i = j + 1; i < 6; i++) {
@@ -66,6 +62,11 @@ __device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L
       L[i][j] = v / d;
     }
   }
+  return true;
+}
+// L D L^T x = g
+__device__ __forceinline__ void gsr_ldlt6_solve(const double (&L)[6][6], const double (&D)[6], const double (&g)[6],
+                                                double (&x)[6]) {
   for (int i = 0; i < 6; i++) {      // L y = g
     double v = g[i];
     for (int k = 0; k < i; k++) v -= L[i][k] * x[k];
@@ -77,27 +78,19 @@ __device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L
     for (int k = i + 1; k < 6; k++) v -= L[k][i] * x[k];
     x[i] = v;
   }
-  double ok = 0.0;
-  for (int i = 0; i < 6; i++) ok += x[i];
-  if (!(fabs(ok) < (double)KNN_INF)) {
-    stats[3] = 2.0;
-    return;
-  }
-  // dR = Rz(gamma) Ry(beta) Rx(alpha)
+}
+// dR = Rz(gamma) Ry(beta) Rx(alpha) from x[0..2] = (alpha, beta, gamma)
+__device__ __forceinline__ void gsr_rotation6(const double (&x)[6], double (&R)[3][3]) {
   double sa, ca, sb, cb, sg, cg;
   sincos(x[0], &sa, &ca);
   sincos(x[1], &sb, &cb);
   sincos(x[2], &sg, &cg);
-  double R[3][3];
   R[0][0] = cb * cg; R[0][1] = sa * sb * cg - ca * sg; R[0][2] = ca * sb * cg + sa * sg;
   R[1][0] = cb * sg; R[1][1] = sa * sb * sg + ca * cg; R[1][2] = ca * sb * sg - sa * cg;
   R[2][0] = -sb;     R[2][1] = sa * cb;                R[2][2] = ca * cb;
-  // dT y = dR (y - c) + t + c
-  double td[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    td[a] = (x[3 + a] + shift[a]) - ((R[a][0] * shift[0] + R[a][1] * shift[1]) + R[a][2] * shift[2]);
-  // T <- dT T
+}
+// T <- [R, td] T, row 3 written as 0 0 0 1
+__device__ __forceinline__ void gsr_rigid_left6(const double (&R)[3][3], const double (&td)[3], double* __restrict__ T_dev) {
   double Tn[12];
 #pragma unroll
   for (int a = 0; a < 3; a++) {
@@ -109,6 +102,33 @@ __device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L
   for (int i = 0; i < 12; i++) T_dev[i] = Tn[i];
   T_dev[12] = T_dev[13] = T_dev[14] = 0.0;
   T_dev[15] = 1.0;
+}
+
+// thread 0 of the final kernel: J^T J x = -J^T r on the matrix in A and the right-hand side in g, both filled by the caller; then
+// dR, dT and T <- dT T.  stats[3] = 0, or 2 with T as it was.  The arrays are LDS: indexed at run time, which registers cannot
+// be.  `shift`: the point dT is formed about (three zeros: about the origin).
+__device__ __forceinline__ void icp_solve6_compose(double (&A)[6][6], double (&L)[6][6], double (&D)[6], double (&g)[6],
+                                                   double (&x)[6], const double* __restrict__ shift, double* __restrict__ T_dev,
+                                                   double* __restrict__ stats) {
+  if (!gsr_ldlt6_factor(A, L, D)) {
+    stats[3] = 2.0;      // the correspondences do not fix this unknown (one plane, or sums that overflowed): T stays
+    return;
+  }
+  gsr_ldlt6_solve(L, D, g, x);
+  double ok = 0.0;
+  for (int i = 0; i < 6; i++) ok += x[i];
+  if (!(fabs(ok) < (double)KNN_INF)) {
+    stats[3] = 2.0;
+    return;
+  }
+  double R[3][3];
+  gsr_rotation6(x, R);
+  // dT y = dR (y - c) + t + c
+  double td[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    td[a] = (x[3 + a] + shift[a]) - ((R[a][0] * shift[0] + R[a][1] * shift[1]) + R[a][2] * shift[2]);
+  gsr_rigid_left6(R, td, T_dev);
   stats[3] = 0.0;
 }
 

@@ -277,6 +277,25 @@ EXPORTS = {
     "gsr_odometry_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_odometry_update": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double)] + [C.c_void_p] * 5 +
                             [C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # Pt, target, Ps, idx, info_out, stats_dev, workspace + bytes, stream
+    "gsr_information_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_registration_information": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]),
+    # N, E, edges (host int32 [E,2]), fixed (host uint8 [N]), host scratch (topology bytes), topology + bytes, stream
+    "gsr_posegraph_topology_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gsr_posegraph_topology": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    "gsr_posegraph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    # N, E, topology, poses, edge_T, edge_info, edge_uncertain, mu, edge_out, node_out, scalars_out, stream
+    "gsr_posegraph_linearize": (C.c_int, [C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 4),
+    # N, E, topology, edge_rec, node_rec, lambda, cg_rtol, cg_max_iteration, delta_out, stats_dev, workspace + bytes, stream
+    "gsr_posegraph_solve": (C.c_int, [C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_int32, C.c_void_p,
+                                                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # N, E, topology, poses, edge_T, edge_info, edge_uncertain, mu, max_iteration, min_relative_increment,
+    # min_relative_residual_increment, cg_rtol, cg_max_iteration, edge_w_out, edge_r_out, stats_dev, workspace + bytes, stream
+    "gsr_posegraph_optimize": (C.c_int, [C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.c_int32, C.c_double, C.c_double,
+                                                                                    C.c_double, C.c_int32] + [C.c_void_p] * 4 +
+                               [C.c_size_t, C.c_void_p]),
     # P, points, normals, radius, max_nn, fpfh, spfh_counts, count, workspace + bytes, stream
     "gsr_fpfh_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gsr_compute_fpfh": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

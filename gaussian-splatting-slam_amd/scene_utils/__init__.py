@@ -26,3 +26,4 @@ from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, 
     frame_from_messages, frame_from_visual_merged
 from .odometry import OdometryLevel, OdometryResult, prepare_odometry_level, odometry_update, rgbd_odometry, \
     camera_after_odometry
+from .posegraph import PoseGraph, PoseGraphResult, information_from_point_clouds

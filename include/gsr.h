@@ -63,6 +63,9 @@ extern "C" {
  *    ICP - the colour gradient of a cloud and the joint geometric / photometric update (additions only);
  *    gsr_odometry_prepare, gsr_odometry_workspace_bytes, gsr_odometry_update: dense frame-to-frame RGB-D odometry on the pixel
  *    grid - intensity / depth / Sobel planes and the hybrid photometric + depth Gauss-Newton update (additions only);
+ *    gsr_information_workspace_bytes, gsr_registration_information, gsr_posegraph_topology_bytes, gsr_posegraph_topology,
+ *    gsr_posegraph_workspace_bytes, gsr_posegraph_linearize, gsr_posegraph_solve, gsr_posegraph_optimize: an information matrix
+ *    per edge and robust pose-graph optimisation in one launch (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -862,6 +865,114 @@ int gsr_odometry_update(int32_t w, int32_t h, const double* K /*HOST [4]*/, cons
                         const float* tgt_grad /*[4,h,w]*/, double lambda_geometric, double depth_diff_max, int32_t apply,
                         double* T_dev /*[16] in/out*/, double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* ---- pose graph (csrc/posegraph.hip): the edges that gsr_icp_update*, gsr_ransac_feature_matching
+ * and gsr_odometry_update produce become the per-keyframe corrections that gsr_transform_gaussians consumes.  Float64 throughout,
+ * no float atomics, no allocation on the device, deterministic: two runs give identical bits. ---- */
+
+/* Information matrix of a registration (Open3D's GetInformationMatrixFromPointClouds).  Row i takes part iff 0 <= idx[i] < Pt and
+ * p = target[idx[i]] is finite.  Per row, G^T G is added for the three rows G_1 = [0, z, -y, 1, 0, 0], G_2 = [-z, 0, x, 0, 1, 0],
+ * G_3 = [y, -x, 0, 0, 0, 1] of p = (x, y, z): 21 float64 sums plus n, with the summation structure of gsr_icp_update (at most 256
+ * workgroups over fixed slices, a fixed in-wave butterfly, wave and workgroup sums added in order).  info_out[36]: the symmetric
+ * 6 x 6 row-major, unknowns (alpha, beta, gamma, tx, ty, tz); entry [3][3] = n.  stats_dev[4] = n, 0, 0, 0.  n = 0 gives a zero
+ * matrix.  Errors before any launch: sizes outside [1, 2^30 - 1], a NULL pointer: GSR_ERR_INVALID_ARGUMENT; workspace below
+ * gsr_information_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_information_workspace_bytes(int64_t Ps);
+int gsr_registration_information(int64_t Pt, const float* target /*[Pt,3]*/, int64_t Ps, const int32_t* idx /*[Ps]*/,
+                                 double* info_out /*[36]*/, double* stats_dev /*[4]*/, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* The pose graph.  Nodes i = 0 .. N-1 with poses X_i (float64 row-major 4 x 4, node frame to world) and fixed[i] (the node does not
+ * move).  Edges k = 0 .. E-1 with s_k != t_k, T_k (takes coordinates of node s_k to coordinates of node t_k: what gsr_icp_update
+ * leaves in T_dev for source s_k and target t_k), Lambda_k (symmetric float64 6 x 6) and uncertain_k (a loop closure).  Unknowns in
+ * the order (alpha, beta, gamma, tx, ty, tz); M(delta) = [Rz(gamma) Ry(beta) Rx(alpha), t], the composition of gsr_icp_update_plane
+ * (one body, csrc/solve6_common.h).
+ *   residual   D_k = T_k^-1 X_t^-1 X_s, e_k = vec6(D_k), the inverse of M: with sy = sqrt(R00^2 + R10^2), sy > 1e-6: alpha =
+ *              atan2(R21, R22), beta = atan2(-R20, sy), gamma = atan2(R10, R00); otherwise alpha = atan2(-R12, R11), beta =
+ *              atan2(-R20, sy), gamma = 0; t = the last column.  Rigid inverses are [R^T, -R^T t]; X_t^-1 X_s is formed as
+ *              [Rt^T Rs, Rt^T (ts - tt)], the difference first, so a graph far from the origin loses nothing.
+ *   Jacobian   (Open3D's linearisation) column j of J_k = lin6(T_k^-1 X_t^-1 G_j X_s), G_0..2 the generators of rotation about x, y,
+ *              z, G_3..5 the translations, lin6(M) = ((M21 - M12) / 2, (M02 - M20) / 2, (M10 - M01) / 2, M03, M13, M23); delta_s
+ *              enters with +J_k, delta_t with -J_k.
+ *   objective  r_k = e_k^T Lambda_k e_k; F = sum over certain edges of r_k + sum over uncertain edges of mu r_k / (mu + r_k) (the line
+ *              process at its optimum: Geman-McClure); w_k = 1 for a certain edge, (mu / (mu + r_k))^2 for an uncertain one;
+ *              W_k = w_k J_k^T Lambda_k J_k (upper triangle, 21 values, rows from the diagonal on), g_k = w_k J_k^T Lambda_k e_k.
+ *              Over free nodes: H_ii = the sum of W_k over the edges incident to i, the off-diagonal block of an edge is -W_k,
+ *              b_s += g_k, b_t -= g_k; an edge to a fixed node contributes only to the free node's H_ii and b.  A node sums its
+ *              edges in ascending k.  The records of a fixed node are zero.
+ *   solve      (H + lambda I) delta = -b by preconditioned conjugate gradients from delta = 0.  Every free node's H_ii is first
+ *              held to the LDL^T pivot rule of gsr_icp_update_plane, once per linearisation (lambda I would hide a node that its
+ *              edges do not fix, Lambda = 0 say), then H_ii + lambda I is factored by the same body: the block-Jacobi preconditioner.  Stops at |r|_2 <=
+ *              cg_rtol |b|_2 (status 0) or after cg_max_iteration products (status 1).  Status 2: a rejected pivot, or a direction
+ *              with p.Ap not > 0 (sums that are not finite); delta is then all zeros.  Rows of fixed nodes are exactly 0.
+ *   step       X_i <- M(delta_i) X_i (left product, row 3 written as 0 0 0 1).  rho = (F - F_new) / (delta^T (lambda delta - b)).
+ *              Accepted iff F_new < F: lambda <- lambda max(1/3, 1 - (2 rho - 1)^3), nu <- 2; otherwise lambda <- lambda nu, nu <-
+ *              2 nu.  Start: lambda = 1e-5 max diag(H), nu = 2.
+ *   stop       GSR_PG_MAX_ITERATION: max_iteration solves; GSR_PG_CONVERGED_STEP: |delta|_inf <= min_relative_increment (|x|_inf +
+ *              min_relative_increment), x the stacked vec6(X_i) of all nodes (the step is not applied; note that the rule is
+ *              relative to the LARGEST coordinate: 10 km from the origin 1e-6 stops at a centimetre - keep a graph near its own
+ *              origin, or tighten the figure); GSR_PG_CONVERGED_RESIDUAL: an accepted step with F - F_new <=
+ *              min_relative_residual_increment F; GSR_PG_ZERO_RESIDUAL: F == 0 (E = 0 too: nothing moves);
+ *              GSR_PG_LAMBDA: lambda not finite or above 1e32; GSR_PG_SOLVER_FAILED: solve status 2 - the poses are those of
+ *              the last accepted step, bit for bit the input when the first solve fails.
+ * Every launch is ONE workgroup of 256 lanes: work strided over nodes and edges, iterates in the workspace, LDS for the reductions
+ * only (N and E are bounded by 2^30 - 1, not by LDS), no grid-wide synchronisation, no cooperative launch, and every loop bounded by
+ * max_iteration, cg_max_iteration or a count.  Dot products: each thread's nodes in order, the fixed butterfly, the four wave sums
+ * in order. */
+enum {
+  GSR_PG_CONVERGED_STEP = 0,
+  GSR_PG_MAX_ITERATION = 1,
+  GSR_PG_SOLVER_FAILED = 2,
+  GSR_PG_CONVERGED_RESIDUAL = 3,
+  GSR_PG_ZERO_RESIDUAL = 4,
+  GSR_PG_LAMBDA = 5
+};
+#define GSR_PG_EDGE_STRIDE 35 /* e[6], r, w, W[21], g[6] */
+#define GSR_PG_NODE_STRIDE 27 /* H_ii[21], b[6] */
+
+/* The graph's topology on the device, built once on the host: the edge ends, fixed[], and the CSR node_ptr[N + 1] / node_edge[2E]
+ * (2 k + 1 where the node is edge k's target, 2 k where it is its source; ascending k per node).  edges_host: HOST int32 [E,2] =
+ * (s_k, t_k); fixed_host: HOST uint8 [N]; host_scratch: gsr_posegraph_topology_bytes(N, E) bytes of HOST memory, 4-byte
+ * aligned, that the blob is laid out in - the caller's, so nothing is allocated here.  The blob is then copied with ONE
+ * hipMemcpyAsync on `stream` and the call does not wait for it: host_scratch must stay valid and unchanged until the stream has
+ * passed the copy (scene_utils.PoseGraph keeps it beside the device blob).
+ * Errors before any device work: N outside [1, 2^30 - 1], E outside [0, 2^30 - 1], a NULL pointer (edges_host may be NULL with E =
+ * 0), an end outside [0, N), s_k == t_k: GSR_ERR_INVALID_ARGUMENT; topology_bytes below gsr_posegraph_topology_bytes(N, E):
+ * GSR_ERR_STATE_TOO_SMALL.  The three entries below trust the blob: it must be the one filled here for this N and E. */
+size_t gsr_posegraph_topology_bytes(int64_t N, int64_t E);
+int gsr_posegraph_topology(int64_t N, int64_t E, const int32_t* edges_host /*HOST [E,2]*/, const uint8_t* fixed_host /*HOST [N]*/,
+                           void* host_scratch /*HOST, topology_bytes*/, void* topology, size_t topology_bytes, void* stream);
+
+/* One workspace size for gsr_posegraph_solve and gsr_posegraph_optimize (0 for sizes out of range). */
+size_t gsr_posegraph_workspace_bytes(int64_t N, int64_t E);
+
+/* Linearisation at `poses`: edge_out[E,35] = e[6], r, w, W[21], g[6] per edge; node_out[N,27] = H_ii[21], b[6] per node;
+ * scalars_out[2] = F, max diag(H).  edge_uncertain: uint8 [E] on the device.  E = 0 is legal (the edge pointers may be NULL).
+ * Errors before the launch: sizes out of range, a NULL pointer, mu not > 0: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_posegraph_linearize(int64_t N, int64_t E, const void* topology, const double* poses /*[N,16]*/,
+                            const double* edge_T /*[E,16]*/, const double* edge_info /*[E,36]*/, const uint8_t* edge_uncertain /*[E]*/,
+                            double mu, double* edge_out /*[E,35]*/, double* node_out /*[N,27]*/, double* scalars_out /*[2]*/,
+                            void* stream);
+
+/* The solve above on records in the layout of gsr_posegraph_linearize (W and g of edge_rec, H_ii and b of node_rec are read):
+ * delta_out[N,6]; stats_dev[4] = products taken, the achieved |r| / |b|, status 0 / 1 / 2, 0.
+ * Errors before the launch: sizes out of range, a NULL pointer, lambda not finite or < 0, cg_rtol < 0 or NaN, cg_max_iteration <
+ * 1: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_posegraph_workspace_bytes(N, E): GSR_ERR_STATE_TOO_SMALL. */
+int gsr_posegraph_solve(int64_t N, int64_t E, const void* topology, const double* edge_rec /*[E,35]*/,
+                        const double* node_rec /*[N,27]*/, double lambda, double cg_rtol, int32_t cg_max_iteration,
+                        double* delta_out /*[N,6]*/, double* stats_dev /*[4]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The whole Levenberg-Marquardt loop above in ONE launch: poses[N,16] in place; edge_w_out[E] and edge_r_out[E] = w_k and r_k at the
+ * returned poses; stats_dev[16] = status (GSR_PG_*), solves, accepted steps, F at the start, F at the end, lambda at the end, the
+ * total of PCG products, the worst achieved |r| / |b| of a solve, then zeros.  Poses of fixed nodes are never written.
+ * Errors before the launch: sizes out of range, a NULL pointer (the edge pointers may be NULL with E = 0), mu not > 0,
+ * max_iteration < 0, an increment or cg_rtol < 0 or NaN, cg_max_iteration < 1: GSR_ERR_INVALID_ARGUMENT; workspace below
+ * gsr_posegraph_workspace_bytes(N, E): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+int gsr_posegraph_optimize(int64_t N, int64_t E, const void* topology, double* poses /*[N,16] in/out*/,
+                           const double* edge_T /*[E,16]*/, const double* edge_info /*[E,36]*/, const uint8_t* edge_uncertain /*[E]*/,
+                           double mu, int32_t max_iteration, double min_relative_increment, double min_relative_residual_increment,
+                           double cg_rtol, int32_t cg_max_iteration, double* edge_w_out /*[E]*/, double* edge_r_out /*[E]*/,
+                           double* stats_dev /*[16]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- global registration (csrc/features.hip) - what the reference's commented pipeline would take
  * from Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching.  Every result is a function of the input
