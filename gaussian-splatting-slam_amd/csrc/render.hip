@@ -271,7 +271,6 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
                                                     const uint32_t* __restrict__ status_src,
                                                     uint32_t* __restrict__ status_dst,
                                                     uint32_t* __restrict__ tile_cutoff /* in/out, or nullptr */,
-                                                    const uint32_t* __restrict__ depth_key,
                                                     const uint32_t* __restrict__ culled_any /* nullptr: lists not truncated */,
                                                     uint32_t frame_tag, uint32_t* __restrict__ meta, uint32_t margin_q8,
                                                     uint32_t margin_add, uint32_t* __restrict__ walk_cnt,
@@ -457,8 +456,11 @@ __global__ __launch_bounds__(256) void k_render_fwd(int W, int H, int grid_x, co
         // margin: need x margin_q8 / 256 + margin_add entries (GSR_CULL_MARGIN="q8,add" overrides the launcher's default)
         const uint32_t k = (uint32_t)(((unsigned long long)nd * margin_q8) >> 8) + margin_add;   // (positions are 1-based: index k is entry k + 1)
         if (k < len) {
+          // the key the emission compares with is the fp32 depth's bit pattern, and the record's depth word holds the same bits
+          // (k_preprocess_fwd writes both from t.z).  NOT depth_key[id]: in the global binning form that array has been
+          // radix-sorted in place by now, and entry id is the id-th smallest key (tests/test_tile_cull_cutoffs_gpu.py (c))
           const uint32_t id = point_list[range.x + k];
-          tile_cutoff[tile] = id != 0xFFFFFFFFu ? depth_key[id] : 0xFFFFFFFFu;
+          tile_cutoff[tile] = id != 0xFFFFFFFFu ? __float_as_uint(rec[3 * (size_t)id + 2].w) : 0xFFFFFFFFu;
         } else if (!truncated) {
           tile_cutoff[tile] = 0xFFFFFFFFu;                  // the margin reaches past the whole list: nothing to cut
         }                                                   // (else: keep the wider cut-off this frame was rendered with)
@@ -1492,7 +1494,6 @@ void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_
   // status words of the non-blocking forward: stored by the kernel itself where the caller's slot is mapped into the device
   const uint32_t* status_src = status_dst ? (const uint32_t*)F.meta() : nullptr;
   if (!(F.P > 0 && F.R > 0)) tile_cutoff = nullptr;                         // (no list was emitted: nothing to learn a cut-off from)
-  const uint32_t* depth_key = F.depth_key();
   const uint32_t* culled_any = cull_applied ? (const uint32_t*)(F.bin + F.BL.culled_any) : nullptr;
   uint32_t* meta = F.meta();
   uint32_t* walk_cnt = walk_classes ? F.walk_cnt() : nullptr;
@@ -1509,7 +1510,7 @@ void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_
 #define GSR_FWD_LAUNCH(M, A, C)                                                                                               \
   GSR_LAUNCH("render_fwd", (k_render_fwd<false, M, A, C>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
              ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,        \
-             status_dst, tile_cutoff, depth_key, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile,       \
+             status_dst, tile_cutoff, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile,                  \
              out_alpha, n_touched, touch_T_min, touch_cap)
 #define GSR_FWD_LAUNCH_A(M, C)                                                         \
   do { if (out_alpha) GSR_FWD_LAUNCH(M, true, C); else GSR_FWD_LAUNCH(M, false, C); } while (0)
@@ -1532,7 +1533,7 @@ void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* 
   // i.e. the unmasked walk; the masked production kernel evaluates fewer)
   hipLaunchKernelGGL((k_render_fwd<true, false>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, ranges,
                      point_list, rec, s->bg, (float*)nullptr, (float*)nullptr, (float*)nullptr, (uint32_t*)nullptr, pairs,
-                     (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
+                     (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                      (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                      (float*)nullptr, (uint32_t*)nullptr, 0.f, 0u);
 }

@@ -229,7 +229,9 @@ int gsr_forward_async(const gsr_settings* s, const gsr_gaussians* g, void* geome
 /* gsr_forward_async with TILE LISTS TRUNCATED BY DEPTH (round 4).  tile_depth_cutoff: `tiles` uint32 words owned by the caller, one
  * array per VIEW it renders repeatedly (a training set's cameras), initialised to 0xFFFFFFFF.  Every call UPDATES it: the
  * compositing kernel leaves, per tile, the depth bits of the list entry at 1.75 x (+ 48) the position of the deepest one any pixel
- * of the tile needed before it saturated (T < 1e-4) - 0xFFFFFFFF if a pixel never saturated.  With apply != 0 (honoured only for an
+ * of the tile needed before it saturated (T < 1e-4) - 0xFFFFFFFF if a pixel never saturated or the list is shorter than that.  Both
+ * binning forms (tile_local_sort 0 and 1) learn the same words; a call with P == 0 or capacity == 0 leaves the array as it was
+ * (tests/test_tile_cull_cutoffs_gpu.py holds every word to a float64 reconstruction).  With apply != 0 (honoured only for an
  * unverified frame, num_rendered_out == NULL, in the tile-local binning form, debug off) the array is also USED: a (tile, Gaussian)
  * instance whose depth lies behind its tile's cut-off is neither counted nor emitted - the tile's depth-ordered list loses its
  * tail.  If every pixel of a truncated tile still saturates inside its list, image, depth, final_T, n_contrib and all gradients
