@@ -1081,6 +1081,15 @@ int gsr_debug_binning_views(const void* binning_state, int32_t W, int32_t H, int
   return 0;
 }
 
+// (the buffer gsr_launch_render_bwd reads: the value array the tile sort's last pass wrote)
+int gsr_debug_slot_views(const void* binning_state, int32_t W, int32_t H, int64_t R, const uint32_t** slot_of_pos) {
+  const size_t tiles = gsr_tile_grid(W, H).tiles;
+  const GsrBinLayout BL = gsr_bin_layout((size_t)R, tiles);
+  const char* bin = (const char*)binning_state;
+  if (slot_of_pos) *slot_of_pos = (const uint32_t*)(bin + (gsr_tile_sort_result_buffer((int)tiles) ? BL.val_b : BL.val_a));
+  return 0;
+}
+
 int gsr_debug_count_pairs(const gsr_settings* s, int32_t P, const void* geometry_state, const void* binning_state,
                           int64_t num_rendered, uint32_t* pairs, void* stream) {
   if (!s || !geometry_state || !binning_state || !pairs || P <= 0) {

@@ -1173,18 +1173,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_TILE_WAV
 //             D1[i][5 + c] += C_c(i, k)              one MFMA per colour channel: the lane's sum of w * dL/dC_c over its pixels
 //   stage 2   D2[i'][j] = sum_i G[i'][i] * D1[i][j]  four MFMAs (D1's registers ARE the B operands: row = 4 (lane >> 4) + reg),
 //                                                    G = the X-side basis
-// D2 holds every product moment: the 27-instruction v_permlane / DPP tree, its nine zeroing moves and six of the eight
-// accumulation instructions per blended sub-block become 4 + 3 + (blended sub-blocks) MFMAs, each of which holds the vector issue
-// port for 8 cycles (two plain instructions) and otherwise runs beside the other waves' VALU work.  Coordinates are taken about
-// the tile centre (|X'|, |Y'| <= 7.5, all basis values exact in f32) to keep the cancellation of the final map small:
-//   X' = Xi' + Xs',  Xi' = (i & 7) - 3.5, Xs' = 8 (s & 1) - 4;     Y' = Yi' + Yks',  Yi' = (i >> 3) - 0.5, Yks' = 2 k + 8 (s >> 1) - 7
-//   columns j: 0: 1, 1: Yks', 2: Xs', 3: Yks'^2, 4: Xs' Yks', 5..8: colour / inverse-depth sums;  rows i': 0: 1, 1: Xi', 2: Yi',
-//   3: Xi'^2, 4: Xi' Yi'   (Xs'^2 = 16 and Yi'^2 = 1/4 are constants).
-// Lanes 0..2 store rows 0..3 of columns 0..2 (one ds_write_b128), lanes 3..8 and 16 one float each: 19 floats per entry in LDS; once
-// per batch lane j turns entry j's 19 numbers into its gradient record (gsr_mx_record) and stores it at the emission slot.
-// Every sum is still taken in a fixed order (bitwise reproducible); it is a DIFFERENT order than the swap tree's, so this form agrees
-// with the other two to rounding, not bit for bit (tests: parity against the float64 oracle at the same bar, and the basis / lane maps
-// against exact integer data, tests/test_parity_gpu.py::test_matrix_pipe_reduction_primitive).
+// D2 holds every product moment.  THAT FORM WAS WITHDRAWN: moments about the tile centre lose the second moments of a narrow splat
+// (sum h dx^2 = mu^2 sum h - 2 mu sum h X + sum h X^2, three terms up to a few hundred times the result, each rounded to float32
+// before the map: up to 1e-3 of the sum of the magnitudes, measured by tests/test_compositing_replay_gpu.py against a bound of 6e-5).
+// What runs now keeps the matrix pipe for the SUMMATION only: a lane forms its own terms h dx, h dy, h dx^2, h dx dy, h dy^2 about
+// the entry's mean, exactly as k_render_bwd_tile does (plain fma over its four sub-blocks), and
+//   stage 1   D1[i][c] += sum_k v_c(i, k)              one MFMA per record value c = 0..9: A = the lane's value, B = 1 in column c
+//   stage 2   D2[0][c]  = sum_i D1[i][c]               four MFMAs against a row of ones (D1's registers ARE the B operands)
+// so lane c < 12 holds record value c in D2[0] (columns 10 and 11 stay zero: the record's padding) and stores it into the entry's
+// 48-byte LDS slot, which IS the gradient record.  Every sum is still taken in a fixed order (bitwise reproducible); it is a
+// DIFFERENT order than the swap tree's, so this form agrees with the other two to rounding, not bit for bit (tests: every record
+// against the float64 replay of its frame, tests/test_compositing_replay_gpu.py, and the lane maps against exact integer data,
+// tests/test_parity_gpu.py::test_matrix_pipe_reduction_primitive).
 //
 // MEASURED OUT (opt-in, GSR_BWD_REDUCE=mfma): 27 % fewer vector instructions per launch (1.88e8 -> 1.38e8 + 1.38e7 MFMAs) and
 // 0.52 ms against the tree's 0.42 at C3.  The premise was wrong for THIS data type: on gfx950 an FP32-input MFMA executes on the
@@ -1195,76 +1195,55 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_TILE_WAV
 // ---------------------------------------------------------------------------------------------------------------
 typedef float gsr_f4v __attribute__((ext_vector_type(4)));
 #define GSR_MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#define GSR_MX_SLOT_F4 5            // 19 floats per entry, padded to 80 B
+#define GSR_MX_SLOT_F4 GSR_IGRAD_F4   // an entry's LDS slot is its gradient record
 
 struct gsr_mx_basis {
-  float Bs[4];   // stage 1, B operand of sub-block s:  B_s[k = lane >> 4][j = lane & 15]
-  float Bc[4];   // stage 1, B operand of colour channel c: 1 in column 5 + c
-  float G[4];    // stage 2, A operand of step r:  G[i' = lane & 15][i = 4 (lane >> 4) + r]
-  int qofs;      // byte offset of this lane's piece inside an entry's LDS slot (lanes 0..2: 16 lane; 3..8: 48 + 4 (lane - 3); 16: 72)
-  bool lane_a, lane_b;
+  float Bc[10];  // stage 1, B operand of record value c: 1 in column c (every k)
+  float G0;      // stage 2, A operand of every step: 1 in row i' = 0
+  bool lane_q;   // lanes 0..11: hold record float `lane` in D2[0]
 };
 
 __device__ __forceinline__ void gsr_mx_basis_init(const int lane, gsr_mx_basis& K) {
-  const int j = lane & 15, k = lane >> 4;
+  const int j = lane & 15;
 #pragma unroll
-  for (int s = 0; s < 4; s++) {
-    const float yks = (float)(2 * k + 8 * (s >> 1) - 7), xs = (float)(8 * (s & 1) - 4);
-    K.Bs[s] = j == 0 ? 1.0f : j == 1 ? yks : j == 2 ? xs : j == 3 ? yks * yks : j == 4 ? xs * yks : 0.0f;
-  }
-#pragma unroll
-  for (int c = 0; c < 4; c++) K.Bc[c] = j == 5 + c ? 1.0f : 0.0f;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int i = 4 * k + r;
-    const float xi = (float)(i & 7) - 3.5f, yi = (float)(i >> 3) - 0.5f;
-    K.G[r] = j == 0 ? 1.0f : j == 1 ? xi : j == 2 ? yi : j == 3 ? xi * xi : j == 4 ? xi * yi : 0.0f;
-  }
-  K.qofs = lane < 3 ? 16 * lane : lane < 9 ? 48 + 4 * (lane - 3) : 72;
-  K.lane_a = lane < 3;
-  K.lane_b = ((0x101F8ull >> lane) & 1ull) != 0ull;   // lanes 3..8 and 16
+  for (int c = 0; c < 10; c++) K.Bc[c] = j == c ? 1.0f : 0.0f;
+  K.G0 = j == 0 ? 1.0f : 0.0f;
+  K.lane_q = lane < 12;
 }
 
-// stage 2 + the entry's 19 numbers into its LDS slot (slot = base of the entry's 80 bytes)
-__device__ __forceinline__ void gsr_mx_finish(const gsr_f4v D1, const gsr_mx_basis& K, char* slot) {
+// a lane's terms of one (entry, pixel): v5 = the pixel's dL/dopacity_eff, d = mean - pixel; the operations of k_render_bwd_tile
+__device__ __forceinline__ void gsr_mx_accumulate(float (&acc)[6], const float v5, const float dx, const float dy) {
+  const float t0 = v5 * dx, t1 = v5 * dy;
+  acc[0] += t0;
+  acc[1] += t1;
+  acc[2] = __builtin_fmaf(t0, dx, acc[2]);
+  acc[3] = __builtin_fmaf(t0, dy, acc[3]);
+  acc[4] = __builtin_fmaf(t1, dy, acc[4]);
+  acc[5] += v5;
+}
+
+// the wave's sums of the lanes' ten values (NV = 9: no tenth) -> the entry's record in its LDS slot (slot = base of its 48 bytes)
+template <int NV>
+__device__ __forceinline__ void gsr_mx_reduce(const float (&acc)[6], const float c0, const float c1, const float c2, const float c3,
+                                              const gsr_mx_basis& K, const int lane, char* slot) {
   const gsr_f4v zero = {0.f, 0.f, 0.f, 0.f};
-  gsr_f4v D2 = GSR_MFMA4(K.G[0], D1[0], zero);
-  D2 = GSR_MFMA4(K.G[1], D1[1], D2);
-  D2 = GSR_MFMA4(K.G[2], D1[2], D2);
-  D2 = GSR_MFMA4(K.G[3], D1[3], D2);
-  char* dst = slot + K.qofs;
-  if (K.lane_a) *reinterpret_cast<float4*>(dst) = make_float4(D2[0], D2[1], D2[2], D2[3]);
-  if (K.lane_b) *reinterpret_cast<float*>(dst) = D2[0];
-}
-
-// an entry's 19 numbers -> its gradient record; (mux, muy) = the Gaussian's 2-D mean relative to the tile CENTRE (tile origin + 7.5)
-__device__ __forceinline__ void gsr_mx_record(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const float4 q4,
-                                              const float mux, const float muy, float4& o0, float4& o1, float4& o2) {
-  // q0 = column 0 (1): rows (1, Xi', Yi', Xi'^2); q1 = column 1 (Yks'); q2 = column 2 (Xs'); q3 = (Q[1][Yks'^2], Q[1][Xs'Yks'], c0, c1);
-  // q4 = (c2, c3, Q[Xi'Yi'][1], -)
-  const float M00 = q0.x;
-  const float M10 = q0.y + q2.x;                                   // sum h X'
-  const float M01 = q0.z + q1.x;                                   // sum h Y'
-  const float M20 = __builtin_fmaf(16.0f, M00, __builtin_fmaf(2.0f, q2.y, q0.w));
-  const float M02 = __builtin_fmaf(0.25f, M00, __builtin_fmaf(2.0f, q1.z, q3.x));
-  const float M11 = (q1.y + q4.z) + (q3.y + q2.z);
-  // d = mean - pixel = mu - X'
-  o0.x = __builtin_fmaf(mux, M00, -M10);
-  o0.y = __builtin_fmaf(muy, M00, -M01);
-  o0.z = __builtin_fmaf(mux, __builtin_fmaf(mux, M00, -2.0f * M10), M20);
-  o0.w = __builtin_fmaf(mux, __builtin_fmaf(muy, M00, -M01), __builtin_fmaf(-muy, M10, M11));
-  o1.x = __builtin_fmaf(muy, __builtin_fmaf(muy, M00, -2.0f * M01), M02);
-  o1.y = M00;
-  o1.z = q3.z;
-  o1.w = q3.w;
-  o2.x = q4.x;
-  o2.y = q4.y;
-  o2.z = 0.f;
-  o2.w = 0.f;
+  gsr_f4v D1 = zero;
+#pragma unroll
+  for (int c = 0; c < 6; c++) D1 = GSR_MFMA4(acc[c], K.Bc[c], D1);
+  D1 = GSR_MFMA4(c0, K.Bc[6], D1);
+  D1 = GSR_MFMA4(c1, K.Bc[7], D1);
+  D1 = GSR_MFMA4(c2, K.Bc[8], D1);
+  if (NV > 9) D1 = GSR_MFMA4(c3, K.Bc[9], D1);
+  gsr_f4v D2 = GSR_MFMA4(K.G0, D1[0], zero);
+  D2 = GSR_MFMA4(K.G0, D1[1], D2);
+  D2 = GSR_MFMA4(K.G0, D1[2], D2);
+  D2 = GSR_MFMA4(K.G0, D1[3], D2);
+  if (K.lane_q) reinterpret_cast<float*>(slot)[lane] = D2[0];
 }
 
 // test hook (tests/test_parity_gpu.py::test_matrix_pipe_reduction_primitive): in = h[4][64] (sub-block s, lane), c[4][64] (the lane's
-// four channel sums), mu[2]; out = the 10 record values, through the very stage-1 / stage-2 / store / record code of the kernel
+// four channel sums), mu[2] (the mean relative to the tile centre); out = the 10 record values, through the very accumulate / stage-1 /
+// stage-2 / store code of the kernel
 __global__ void k_debug_mx_reduce(const float* __restrict__ in, float* __restrict__ out) {
   __shared__ float4 q[GSR_MX_SLOT_F4];
   const int lane = threadIdx.x & 63;
@@ -1272,19 +1251,16 @@ __global__ void k_debug_mx_reduce(const float* __restrict__ in, float* __restric
   gsr_mx_basis_init(lane, K);
   if (lane < GSR_MX_SLOT_F4) q[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();
-  gsr_f4v D1 = {0.f, 0.f, 0.f, 0.f};
+  float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int s = 0; s < 4; s++) D1 = GSR_MFMA4(in[s * 64 + lane], K.Bs[s], D1);
-#pragma unroll
-  for (int c = 0; c < 4; c++) D1 = GSR_MFMA4(in[(4 + c) * 64 + lane], K.Bc[c], D1);
-  gsr_mx_finish(D1, K, reinterpret_cast<char*>(q));
-  __syncthreads();
-  if (lane == 0) {
-    float4 o0, o1, o2;
-    gsr_mx_record(q[0], q[1], q[2], q[3], q[4], in[512], in[513], o0, o1, o2);
-    out[0] = o0.x; out[1] = o0.y; out[2] = o0.z; out[3] = o0.w; out[4] = o1.x; out[5] = o1.y; out[6] = o1.z; out[7] = o1.w;
-    out[8] = o2.x; out[9] = o2.y;
+  for (int s = 0; s < 4; s++) {
+    const float X = (float)((lane & 7) + 8 * (s & 1)) - 7.5f, Y = (float)((lane >> 3) + 8 * (s >> 1)) - 7.5f;
+    gsr_mx_accumulate(acc, in[s * 64 + lane], in[512] - X, in[513] - Y);
   }
+  gsr_mx_reduce<10>(acc, in[4 * 64 + lane], in[5 * 64 + lane], in[6 * 64 + lane], in[7 * 64 + lane], K, lane,
+                    reinterpret_cast<char*>(q));
+  __syncthreads();
+  if (lane < 10) out[lane] = reinterpret_cast<const float*>(q)[lane];
 }
 
 extern "C" int gsr_debug_mx_reduce(const float* in514, float* out10, void* stream) {
@@ -1373,9 +1349,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
   const float4 *s0v = s0 + vzero, *s1v = s1 + vzero, *s2v = s2 + vzero;
   gsr_mx_basis K;
   gsr_mx_basis_init(lane, K);
-  const float cx = (float)(tile_x * GSR_TILE) + 7.5f, cy = (float)(tile_y * GSR_TILE) + 7.5f;
-  const gsr_f4v zero4 = {0.f, 0.f, 0.f, 0.f};
-  gsr_f4v D1 = zero4;
+  float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   gsr_f2 C01 = {0.f, 0.f}, C23 = {0.f, 0.f};
 
   const int rounds = (toDo + BWD1_BATCH - 1) / BWD1_BATCH;
@@ -1439,7 +1413,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
           S[s] = __builtin_fmaf(a_e, diff, S[s]);
           const float dL_dalpha = diff * T[s] + nTb[s] * rcp;
           const float v5 = G_e * dL_dalpha;               // this pixel's dL/dopacity_eff (see k_render_bwd_tile)
-          D1 = GSR_MFMA4(v5, K.Bs[s], D1);
+          gsr_mx_accumulate(acc, v5, dx, dy);
           C01 = __builtin_elementwise_fma(gsr_f2{dch, dch}, gp01[s], C01);
           C23.x = __builtin_fmaf(dch, gp2[s], C23.x);
           if (DEPTH) C23.y = __builtin_fmaf(dch, gd[s], C23.y);
@@ -1449,13 +1423,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
         bb = s1v[jn];
         __builtin_amdgcn_sched_barrier(0);
         if (any) {
-          D1 = GSR_MFMA4(C01.x, K.Bc[0], D1);
-          D1 = GSR_MFMA4(C01.y, K.Bc[1], D1);
-          D1 = GSR_MFMA4(C23.x, K.Bc[2], D1);
-          if (DEPTH) D1 = GSR_MFMA4(C23.y, K.Bc[3], D1);
-          gsr_mx_finish(D1, K, reinterpret_cast<char*>(qbuf) + j * (GSR_MX_SLOT_F4 * 16));
+          gsr_mx_reduce<DEPTH ? 10 : 9>(acc, C01.x, C01.y, C23.x, C23.y, K, lane,
+                                        reinterpret_cast<char*>(qbuf) + j * (GSR_MX_SLOT_F4 * 16));
           done |= 1ull << j;
-          D1 = zero4;
+#pragma unroll
+          for (int c = 0; c < 6; c++) acc[c] = 0.f;
           C01 = C23 = gsr_f2{0.f, 0.f};
         }
         if (todo == 0ull) break;
@@ -1463,17 +1435,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
       }
     }
     __syncthreads();
-    D1 = zero4;
+#pragma unroll
+    for (int c = 0; c < 6; c++) acc[c] = 0.f;
     C01 = C23 = gsr_f2{0.f, 0.f};
-    // flush the batch: lane j turns entry j's numbers into its record, at the entry's emission slot
+    // flush the batch: lane j copies entry j's record to the entry's emission slot
     if (lane < n) {
       const int e = toDo - 1 - (b * BWD1_BATCH + lane);
       const uint32_t slot = slot_of_pos[range.x + e];
       float4 o0 = z4, o1 = z4, o2 = z4;
       if ((done >> lane) & 1ull) {
         const float4* q = qbuf + GSR_MX_SLOT_F4 * lane;
-        const float4 m = s0[lane];
-        gsr_mx_record(q[0], q[1], q[2], q[3], q[4], m.x - cx, m.y - cy, o0, o1, o2);
+        o0 = q[0]; o1 = q[1]; o2 = q[2];
       }
       float4* dst = igrad + (size_t)GSR_IGRAD_F4 * slot;
       dst[0] = o0; dst[1] = o1; dst[2] = o2;

@@ -182,6 +182,7 @@ EXPORTS = {
     "gsr_debug_mx_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_debug_binning_views": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p)]),
+    "gsr_debug_slot_views": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "gsr_debug_count_pairs": (C.c_int, [C.POINTER(gsr_settings), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p]),
     "gsr_debug_radix_tmp_bytes": (C.c_size_t, [C.c_int64]),

@@ -66,6 +66,7 @@ extern "C" {
  *    gsr_information_workspace_bytes, gsr_registration_information, gsr_posegraph_topology_bytes, gsr_posegraph_topology,
  *    gsr_posegraph_workspace_bytes, gsr_posegraph_linearize, gsr_posegraph_solve, gsr_posegraph_optimize: an information matrix
  *    per edge and robust pose-graph optimisation in one launch (additions only);
+ *    gsr_debug_slot_views: the emission slot of every list position, for tests that read the backward's gradient records;
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -433,13 +434,20 @@ int gsr_debug_geometry_views(const void* geometry_state, int32_t P, const float*
 int gsr_debug_wave_reduce(const float* in640, float* out20, void* stream);
 /* the same sums through the packed-pair trees (v_pk_add_f32 behind the swap stages) of k_render_bwd_tile; same layout */
 int gsr_debug_wave_reduce_pk(const float* in640, float* out20, void* stream);
-/* test hook: the matrix-pipe form of the same reduction (k_render_bwd_tile_mx: v_mfma_f32_16x16x4_f32 against the tile's pixel basis).
+/* test hook: the matrix-pipe form of the same reduction (k_render_bwd_tile_mx: each lane's terms about the mean, summed over the wave by
+ * v_mfma_f32_16x16x4_f32).
  * in[514] = h[4][64] (sub-block s = 0..3, lane: the pixel's dL/dopacity_eff), c[4][64] (the lane's channel sums), mu[2] (the 2-D mean
  * relative to the tile centre); out[10] = the gradient record's ten values (sum h dx, sum h dy, sum h dx^2, sum h dx dy, sum h dy^2,
  * sum h, c0..c3) with d = mu - pixel, pixel (x, y) of (s, lane) = ((lane & 7) + 8 (s & 1) - 7.5, (lane >> 3) + 8 (s >> 1) - 7.5) */
 int gsr_debug_mx_reduce(const float* in514, float* out10, void* stream);
 int gsr_debug_binning_views(const void* binning_state, int32_t image_width, int32_t image_height,
                             int64_t num_rendered, const uint32_t** point_list, const uint32_t** ranges);
+/* slot_of_pos[num_rendered]: the emission slot of every position of point_list, as a forward with a backward to follow leaves it
+ * (for_backward != 0; either binning form).  gsr_backward writes the per-instance gradient record of list position p, three
+ * float4 = (sum h dx, sum h dy, sum h dx^2, sum h dx dy) (sum h dy^2, sum h, d_r, d_g) (d_b, d_depth, -, -), at record index
+ * slot_of_pos[p] of the caller's scratch buffer. */
+int gsr_debug_slot_views(const void* binning_state, int32_t image_width, int32_t image_height, int64_t num_rendered,
+                         const uint32_t** slot_of_pos);
 /* Pair evaluations of the compositing forward (SURVEY.md 8(d) "FLOP model"): pairs[2*H*W] (uint32) = per pixel, the number of
  * list entries evaluated while the pixel was still compositing [0, H*W) and the number of entries it blended [H*W, 2*H*W),
  * counted by an instrumented build of the forward kernel on the state buffers of a finished forward.  (The backward's count is

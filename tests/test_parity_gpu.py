@@ -230,12 +230,17 @@ def test_backward_subblock_masks_change_no_bit(depth, aa, aniso):
             assert float((gb - gm).norm()) <= 2e-6 * float(gb.norm()) + 1e-30, (k, float((gb - gm).norm() / gb.norm()))
             assert float((gb - gm).abs().max()) <= 1e-5 * float(gb.abs().max()) + 1e-30, (k, float((gb - gm).abs().max()))
         else:
-            # needles: float32 itself is 1e-3 .. 1e-2 away from float64 on this scene (ill-conditioned conics; measured for both
-            # forms, tests/sweeps/mx_vs_swap_error.py), so the two orders of summation differ by that much from each other; what
-            # is asked of the matrix-pipe form is that it is no farther from float64 than the tree
+            # needles: end to end the kernels' gradients are 1e-3 .. 1e-2 away from float64 on this scene (measured for both forms,
+            # tests/sweeps/mx_vs_swap_error.py).  Established since: not by the compositing stage - from the frame's own records
+            # the default forms are within 6e-6 of a float64 replay, the slot-order sum and the moment -> mean map within 3e-7
+            # (tests/test_compositing_replay_gpu.py); not established: which step of conic -> cov2D -> Sigma -> (s, q) in
+            # k_preprocess_bwd loses the digits.  What is asked of the matrix-pipe form here is that it is no farther from
+            # float64 than the tree
             eb, em = float((gb - gr).norm() / gr.norm()), float((gm - gr).norm() / gr.norm())
             assert em <= 1.5 * eb + 2e-6, (k, em, eb)
-    if not aniso:      # (the needle scene is there for the masks; its conics are too ill-conditioned for the 2e-5 image bar)
+    # (the needle scene is there for the masks.  Its end-to-end comparison stays out: the compositing stage holds its per-pixel and
+    # per-record bounds on such scenes, tests/test_compositing_replay_gpu.py; the projection and its backward are not pinned there)
+    if not aniso:
         check_forward(b, ref)
         check_grads(b, ref)
         check_grads(m, ref)
@@ -571,7 +576,7 @@ def test_validity_flags_of_the_gradient_records_change_nothing(depth, aa, P, sca
 
 def test_matrix_pipe_reduction_primitive():
     """Round 4 (opt-in form, GSR_BWD_REDUCE=mfma; measured slower, kept as evidence): k_render_bwd_tile_mx takes an entry's ten sums over the tile's 256 pixels on the matrix pipe (v_mfma_f32_16x16x4_f32
-    against the tile's separable pixel basis, csrc/render.hip).  The hook runs that very stage-1 / stage-2 / LDS slot / record code
+    over each lane's own terms about the mean, csrc/render.hip).  The hook runs that very accumulate / stage-1 / stage-2 / LDS slot code
     on h[4][64], c[4][64] and a mean; with small integer h and half-integer means every product and partial sum is exact in float32,
     so a wrong lane map, basis entry or slot offset shows as a wrong number (asymmetric random data: no row <-> column swap can hide)."""
     import numpy as np
