@@ -11,24 +11,10 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from .cameras import camera_from_intrinsics, camera_intrinsics, scaled_camera
 
 MAX_LEVELS = 3
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
-
-
-def _k4(K, what):
-    """(fx, fy, cx, cy) from a 3x3 K matrix or four numbers."""
-    K = np.asarray(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
-    if K.shape == (3, 3):
-        return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
-    if K.shape == (4,):
-        return tuple(float(v) for v in K)
-    raise ValueError(f"{what}: expected a 3x3 matrix or (fx, fy, cx, cy), got shape {K.shape}")
 
 
 def _device_plane(t, name, H, W, n=1):
@@ -43,7 +29,7 @@ def undistort(image, depth, K, dist=None, size=None, new_K=None):
     and distortion `dist` (None: none) -> (image [3,H,W], depth [H,W] or None, mask [H,W]) of an ideal pinhole camera with
     intrinsics `new_K` (default K) and `size` = (W, H) (default the source's).  Colour is bilinear, depth the nearest reading
     (never blended), mask 1 where the bilinear taps lie inside the source - elsewhere all three are 0."""
-    _C = _gsr()
+    _C = A.gsr()
     if not (isinstance(image, torch.Tensor) and image.is_cuda) or (depth is not None and not (isinstance(depth, torch.Tensor)
                                                                                              and depth.is_cuda)):
         raise _C.GsrError("undistort needs image and depth on the HIP device (no CPU path)")
@@ -54,8 +40,8 @@ def undistort(image, depth, K, dist=None, size=None, new_K=None):
     dev = image.device
     src = _device_plane(image, "image", Hs, Ws, 3)
     d = None if depth is None else _device_plane(depth.to(dev), "depth", Hs, Ws)
-    k_src = (C.c_float * 4)(*_k4(K, "K"))
-    k_dst = None if new_K is None else (C.c_float * 4)(*_k4(new_K, "new_K"))
+    k_src = (C.c_float * 4)(*A.k4(K, "K"))
+    k_dst = None if new_K is None else (C.c_float * 4)(*A.k4(new_K, "new_K"))
     coef = [0.0] * 5 if dist is None else [float(v) for v in np.asarray(
         dist.detach().cpu().numpy() if isinstance(dist, torch.Tensor) else dist, dtype=np.float64).reshape(-1)]
     if len(coef) == 4:
@@ -76,7 +62,7 @@ def build_pyramid(image, depth, mask, levels, depth_band=0.05):
     -> three lists (None where the input is): each level halves the one below (a trailing odd row or column is dropped); colour
     is the mean of the 2 x 2 quad, depth the mean of the quad's valid readings within `depth_band` (relative) of the nearest one,
     mask the AND of the quad."""
-    _C = _gsr()
+    _C = A.gsr()
     for t in (image, depth, mask):
         if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
             raise _C.GsrError("build_pyramid needs its tensors on the HIP device (no CPU path)")
@@ -116,11 +102,11 @@ class Frame:
         """A frame as the sensor hands it over: `image` [3,Hs,Ws] and `depth` ([Hs,Ws] or None) on the HIP device, `K` (3x3 or
         (fx, fy, cx, cy)), `dist` (k1, k2, p1, p2, k3) or None, `pose` the 4x4 world-to-camera matrix (None: the identity).  One
         undistort launch; the camera is camera_from_intrinsics(new_K or K, size or the source's size)."""
-        _C = _gsr()
+        _C = A.gsr()
         if not (isinstance(image, torch.Tensor) and image.is_cuda):
             raise _C.GsrError("Frame.from_sensor needs the image (and depth) on the HIP device (no CPU path)")
         W, H = (int(image.shape[-1]), int(image.shape[-2])) if size is None else (int(size[0]), int(size[1]))
-        fx, fy, cx, cy = _k4(K if new_K is None else new_K, "K")
+        fx, fy, cx, cy = A.k4(K if new_K is None else new_K, "K")
         cam = camera_from_intrinsics(fx, fy, cx, cy, W, H, w2c=pose, znear=znear, zfar=zfar, device=image.device, name=name)
         color, d, mask = undistort(image, depth, K, dist, size=(W, H), new_K=new_K)
         return cls(color, d, mask, cam)
@@ -131,7 +117,7 @@ class FramePyramid:
     scaled_camera(frame.camera, i).  One gsr_frame_pyramid launch for all levels."""
 
     def __init__(self, frame, levels, depth_band=0.05):
-        _C = _gsr()
+        _C = A.gsr()
         if not (isinstance(frame.image, torch.Tensor) and frame.image.is_cuda):
             raise _C.GsrError("FramePyramid needs the frame on the HIP device (no CPU path)")
         levels = int(levels)

@@ -11,13 +11,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _args as A
 from .model import GaussianModel, _PARAM_ATTRS, _inverse_sigmoid, _replace_params
 from .sh import RGB2SH
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
 
 
 def _as_tensor(a):
@@ -44,7 +40,7 @@ def create_from_pcd(self, points, colors=None, spatial_lr_scale=1.0, anchor=None
         points = _as_tensor(points).cuda()           # arrays go to the device, as in the reference (:132)
     xyz, rgb = _as_tensor(points), _as_tensor(colors)
     if not xyz.is_cuda:
-        raise _gsr().GsrError("create_from_pcd: points must be on the HIP device (the neighbour search has no CPU path)")
+        raise A.gsr().GsrError("create_from_pcd: points must be on the HIP device (the neighbour search has no CPU path)")
     if voxel_size is not None or nb_neighbors is not None:
         from .pointcloud import condition_point_cloud
         xyz, rgb = condition_point_cloud(xyz, rgb.detach().to(xyz.device).float(), voxel_size, nb_neighbors, std_ratio)
@@ -82,7 +78,7 @@ def unproject_rgbd(cam, image, depth, alpha=None, rendered_z=None, stride=1, min
     opacity of the map's render of this view) only where alpha < alpha_below or, given `rendered_z` (the "depth" of a
     render(..., depth="z")) too, where the reading lies in front of the rendered surface: d < rendered_z / alpha - front_margin d.
     One read-back (the count, to slice the outputs)."""
-    _C = _gsr()
+    _C = A.gsr()
     if not (isinstance(depth, torch.Tensor) and depth.is_cuda and isinstance(image, torch.Tensor) and image.is_cuda):
         raise _C.GsrError("unproject_rgbd needs image and depth on the HIP device (no CPU path)")
     H, W = int(cam.image_height), int(cam.image_width)
@@ -133,7 +129,7 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
     `nb_neighbors` (+ `std_ratio`): the NEW points are conditioned (scene_utils.pointcloud.condition_point_cloud) before the
     neighbour search that sizes them - one Gaussian per occupied voxel instead of one per pixel, depth-edge flying pixels
     dropped; the map's rows are not touched.  None, the default: every selected pixel becomes a Gaussian."""
-    _C = _gsr()
+    _C = A.gsr()
     if self._xyz is not None and not self._xyz.is_cuda:
         raise _C.GsrError("add_from_rgbd runs in HIP kernels (no CPU path): the model must live on the HIP device")
     if scale not in ("knn", "pixel"):
@@ -141,8 +137,8 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
     if not 0.0 < float(init_opacity) < 1.0:
         raise ValueError(f"init_opacity={init_opacity}: expected a value in (0, 1)")
     if voxel_size is not None or nb_neighbors is not None:
-        from .pointcloud import _check_conditioning
-        _check_conditioning(voxel_size, voxel_origin, nb_neighbors, std_ratio)
+        from .pointcloud import check_conditioning
+        check_conditioning(voxel_size, voxel_origin, nb_neighbors, std_ratio)
     alpha = rendered_z = None
     if render_pkg is not None:
         if "alpha" not in render_pkg:
@@ -192,8 +188,8 @@ def add_from_rgbd(self, cam, image, depth, render_pkg=None, init_opacity=0.5, sc
             else:
                 moments.append(None)
         _replace_params(self, tensors, moments)
-        from .transform import _extend_anchors
-        _extend_anchors(self, P, n, anchor, dev)
+        from .transform import extend_anchors
+        extend_anchors(self, P, n, anchor, dev)
         if getattr(self, "xyz_gradient_accum", None) is not None:
             self.xyz_gradient_accum = torch.cat([self.xyz_gradient_accum, torch.zeros((n, 1), device=dev)], dim=0)
             self.denom = torch.cat([self.denom, torch.zeros((n, 1), device=dev)], dim=0)

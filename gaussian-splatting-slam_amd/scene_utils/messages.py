@@ -16,18 +16,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 import warnings
 
 import torch
 
-from .pointcloud import _check_cloud, _check_normals, _check_voxel_size, estimate_normals, voxel_down_sample
-from .registration import _check_transform, _device_T, register_and_merge
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
+from . import _args as A
+from .pointcloud import NB_NEIGHBORS_MAX, estimate_normals, voxel_down_sample
+from .registration import register_and_merge
 
 
 class PointField:
@@ -59,11 +54,7 @@ class PointCloud2:
 
 
 def _check_size(name, value):
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
-        raise TypeError(f"{name}={value!r}: expected an int")
-    if not 0 <= value <= 0xFFFFFFFF:      # (uint32 in the message and in gsr_pc2_layout)
-        raise ValueError(f"{name}={value}: expected a value in [0, 2^32 - 1]")
-    return int(value)
+    return A.integer(name, value, 0, 0xFFFFFFFF, "a value in [0, 2^32 - 1]")      # (uint32 in the message and in gsr_pc2_layout)
 
 
 def _field_record(f):
@@ -79,7 +70,7 @@ def _field_record(f):
 
 def _check_field(name, offset, datatype, count, point_step, datatypes=None):
     for what, v in (("offset", offset), ("datatype", datatype), ("count", count)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        if not A.is_integer(v):
             raise TypeError(f"field {name!r}: {what}={v!r}: expected an int")
     if count != 1:
         raise ValueError(f"field {name!r}: count={count}: expected 1")
@@ -132,7 +123,7 @@ def _check_layout(msg, color_field):
 
 def _check_crop(min_y, max_range):
     for name, v in (("min_y", min_y), ("max_range", max_range)):
-        if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real)):
+        if v is not None and not A.is_number(v):
             raise TypeError(f"{name}={v!r}: expected a number or None")
     if min_y is not None and math.isnan(min_y):
         raise ValueError("min_y is NaN")
@@ -162,7 +153,7 @@ def _check_data(data, need):
         raise ValueError(f"msg.data: {n} bytes, the layout needs {need}")
     if isinstance(data, torch.Tensor):
         if not data.is_cuda:
-            raise _gsr().GsrError("decode_pointcloud2: a tensor msg.data must live on the HIP device (host data: bytes or numpy)")
+            raise A.gsr().GsrError("decode_pointcloud2: a tensor msg.data must live on the HIP device (host data: bytes or numpy)")
         return "device", data.detach().reshape(-1).contiguous()
     if isinstance(data, np.ndarray):
         return "host", np.ascontiguousarray(data).reshape(-1)
@@ -183,10 +174,10 @@ def decode_pointcloud2(msg, transform=None, min_y=None, max_range=None, skip_nan
     `rgba`, if the message has one; a string names the field.  Host data is uploaded once, a device uint8 tensor is used in place.
     One read-back (count and status).  An empty message returns empty tensors without a launch."""
     lay, need = _check_layout(msg, color_field)
-    T = _check_transform(transform, "transform")
+    T = A.transform(transform, "transform")
     lo, r2 = _check_crop(min_y, max_range)
     where, data = _check_data(msg.data, need)
-    _C = _gsr()
+    _C = A.gsr()
     if where == "host":
         data = _upload(data) if lay["width"] * lay["height"] else None
     dev = data.device if data is not None else torch.device("cuda", torch.cuda.current_device())
@@ -201,7 +192,7 @@ def decode_pointcloud2(msg, transform=None, min_y=None, max_range=None, skip_nan
         L = _C.gsr_pc2_layout(lay["width"], lay["height"], lay["point_step"], lay["row_step"], lay["is_bigendian"],
                               (C.c_int32 * 3)(*lay["offset"]), (C.c_int32 * 3)(*lay["datatype"]), lay["color_offset"],
                               lay["color_datatype"])
-        Td = None if T is None else _device_T(T, dev)
+        Td = None if T is None else A.device_T(T, dev)
         count = torch.empty(2, dtype=torch.int64, device=dev)
         with _C.on_device(dev):
             ws = torch.empty(lib.gsr_pc2_decode_workspace_bytes(N), dtype=torch.uint8, device=dev)
@@ -227,7 +218,7 @@ def _xyz(v, name, with_w):
     except TypeError:
         raise TypeError(f"{name}={v!r}: expected {len(names)} numbers or an object with {' '.join('.' + a for a in names)}") from None
     for c in vals:
-        if isinstance(c, bool) or not isinstance(c, numbers.Real):
+        if not A.is_number(c):
             raise TypeError(f"{name}={v!r}: expected {len(names)} numbers")
     if len(vals) != len(names):
         raise ValueError(f"{name}: expected {len(names)} values, got {len(vals)}")
@@ -254,9 +245,9 @@ def pose_matrix(quaternion_xyzw, translation):
 
 def _check_process(voxel_size, normal_radius, normal_max_nn):
     if voxel_size is not None:
-        _check_voxel_size(voxel_size)
+        A.voxel_size(voxel_size)
     if normal_radius is not None:
-        _check_normals(normal_radius, normal_max_nn)
+        A.neighbourhood(normal_radius, normal_max_nn, 3, NB_NEIGHBORS_MAX)
 
 
 def process_pointcloud(msg, xyz_offset, quaternion, distance_threshold=10.0, min_y=-0.1, voxel_size=0.05, normal_radius=0.1,
@@ -302,11 +293,11 @@ def encode_pointcloud2(points, colors=None):
     point_step 16, height 1) whose data is a uint8 tensor on the HIP device: what pointcloud_aligner.py:13-44 builds to publish a
     moved cloud.  Coordinates keep their bits; a colour channel becomes the byte (int)(min(max(c, 0), 1) * 255 + 0.5), NaN -> 0;
     without colours the rgb word is 0."""
-    pts, col = _check_cloud(points, colors, "encode_pointcloud2")
+    pts, col = A.cloud(points, colors, "encode_pointcloud2")
     P, dev = int(pts.shape[0]), pts.device
     data = torch.empty(16 * P, dtype=torch.uint8, device=dev)
     if P > 0:
-        _C = _gsr()
+        _C = A.gsr()
         with _C.on_device(dev):
             _C.check(_C.lib().gsr_pc2_encode(P, _C.ptr(pts), _C.ptr(col), _C.ptr(data), _C._stream()))
     fields = [PointField("x", 0, PointField.FLOAT32, 1), PointField("y", 4, PointField.FLOAT32, 1),
@@ -371,7 +362,7 @@ def _check_depth_options(encoding, depth_scale, depth_range, as_depth):
     """-> (is depth, scale, lo, hi); type before value"""
     if as_depth is not None and not isinstance(as_depth, bool):
         raise TypeError(f"as_depth={as_depth!r}: expected True, False or None")
-    if depth_scale is not None and (isinstance(depth_scale, bool) or not isinstance(depth_scale, numbers.Real)):
+    if depth_scale is not None and not A.is_number(depth_scale):
         raise TypeError(f"depth_scale={depth_scale!r}: expected a number or None")
     lo = hi = None
     if depth_range is not None:
@@ -380,7 +371,7 @@ def _check_depth_options(encoding, depth_scale, depth_range, as_depth):
         except (TypeError, ValueError):
             raise TypeError(f"depth_range={depth_range!r}: expected (lo, hi), either may be None") from None
         for v in (lo, hi):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real)):
+            if v is not None and not A.is_number(v):
                 raise TypeError(f"depth_range={depth_range!r}: expected numbers or None")
     can_depth = encoding in DEPTH_ENCODINGS or encoding == "mono16"
     if as_depth is True and not can_depth:
@@ -411,7 +402,7 @@ def decode_image(msg, depth_scale=None, depth_range=None, as_depth=None):
     lay, need = _check_image(msg)
     is_depth, scale, lo, hi = _check_depth_options(lay["encoding"], depth_scale, depth_range, as_depth)
     where, data = _check_data(msg.data, need)
-    _C = _gsr()
+    _C = A.gsr()
     W, H = lay["width"], lay["height"]
     if where == "host":
         data = _upload(data) if W * H else None
@@ -438,7 +429,7 @@ def encode_image(image):
     H, W = int(image.shape[1]), int(image.shape[2])
     if W * H > MAX_POINTS:
         raise ValueError(f"image: {W} x {H}: at most 2^30 - 1 pixels")
-    _C = _gsr()
+    _C = A.gsr()
     if not image.is_cuda:
         raise _C.GsrError("encode_image needs the image on the HIP device (no CPU path)")
     src = image.detach().contiguous()
@@ -559,7 +550,6 @@ def register_depth(depth, K_depth, K_color, depth_to_color=None, size=None):
     colour-camera frame (None: the identity).  Every reading covers the rectangle between its two projected pixel corners; the
     nearest reading wins; a pixel none reaches is 0.  Both cameras are ideal pinholes.  fx_c > 4 fx_d or fy_c > 4 fy_d: ValueError
     (a footprint would exceed the kernel's 8 x 8).  One read-back (the status word)."""
-    from .frames import _k4
     if not isinstance(depth, torch.Tensor):
         raise TypeError(f"depth: expected a tensor, got {type(depth).__name__}")
     if depth.dtype != torch.float32:
@@ -571,14 +561,14 @@ def register_depth(depth, K_depth, K_color, depth_to_color=None, size=None):
         raise ValueError(f"depth: expected [H,W] with 1 .. 2^30 - 1 pixels, got {tuple(depth.shape)}")
     Hd, Wd = int(depth.shape[0]), int(depth.shape[1])
     Wc, Hc = (Wd, Hd) if size is None else _check_wh(size, "size")
-    kd, kc = _k4(K_depth, "K_depth"), _k4(K_color, "K_color")
+    kd, kc = A.k4(K_depth, "K_depth"), A.k4(K_color, "K_color")
     for name, k in (("K_depth", kd), ("K_color", kc)):
         if not all(math.isfinite(v) for v in k) or not (k[0] > 0.0 and k[1] > 0.0):
             raise ValueError(f"{name}: (fx, fy, cx, cy) = {k}: expected finite values, fx and fy positive")
     if kc[0] > MAX_FOCAL_RATIO * kd[0] or kc[1] > MAX_FOCAL_RATIO * kd[1]:
         raise ValueError(f"K_color: focal lengths ({kc[0]}, {kc[1]}) above {MAX_FOCAL_RATIO:g} x K_depth's ({kd[0]}, {kd[1]}): a "
                          "reading's footprint would exceed 8 x 8 colour pixels")
-    _C = _gsr()
+    _C = A.gsr()
     if not depth.is_cuda:
         raise _C.GsrError("register_depth needs the depth image on the HIP device (no CPU path)")
     src = depth.detach().contiguous()

@@ -12,23 +12,18 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import _args as A
 from .cameras import camera_from_intrinsics, camera_intrinsics
-from .frames import Frame, FramePyramid, MAX_LEVELS, _k4
-from .registration import LAMBDA_GEOMETRIC, _check_lambda, _check_transform, _device_T
+from .frames import Frame, FramePyramid, MAX_LEVELS
+from .registration import LAMBDA_GEOMETRIC, check_lambda
 
 DEPTH_MIN, DEPTH_MAX, DEPTH_DIFF_MAX = 0.0, 4.0, 0.03      # Open3D's OdometryOption defaults
 MAX_ITERATIONS = (20, 10, 5)                               # per level, coarse to fine (Open3D's iteration_number_per_pyramid_level)
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
 
 
 class OdometryLevel(NamedTuple):
@@ -48,37 +43,25 @@ class OdometryResult(NamedTuple):
     status: int                       # of the closing evaluation: 0 = a step could be taken, 1 = n < 6, 2 = a rejected pivot
 
 
-def _check_number(name, value):
-    if isinstance(value, bool) or not isinstance(value, numbers.Real):
-        raise TypeError(f"{name}={value!r}: expected a number")
-    return float(value)
-
-
 def _check_depth_range(depth_min, depth_max):
-    lo, hi = _check_number("depth_min", depth_min), _check_number("depth_max", depth_max)
+    lo, hi = A.number("depth_min", depth_min), A.number("depth_max", depth_max)
     if math.isnan(lo) or math.isnan(hi) or not hi > lo:
         raise ValueError(f"depth_min={lo}, depth_max={hi}: expected depth_min < depth_max")
     return lo, hi
 
 
 def _check_depth_diff(depth_diff_max):
-    v = _check_number("depth_diff_max", depth_diff_max)
+    v = A.number("depth_diff_max", depth_diff_max)
     if not v > 0:      # (false for NaN)
         raise ValueError(f"depth_diff_max={v}: expected a value > 0")
     return v
 
 
 def _check_K(K):
-    k = _k4(K, "K")
+    k = A.k4(K, "K")
     if not all(math.isfinite(v) for v in k) or not (k[0] > 0 and k[1] > 0):
         raise ValueError(f"K={k}: expected finite (fx, fy, cx, cy) with fx, fy > 0")
     return k
-
-
-def _plane_shape(t, name, H, W):
-    if not isinstance(t, torch.Tensor) or not t.is_floating_point() or t.dim() not in (2, 3) or \
-            tuple(t.shape[-2:]) != (H, W) or t.numel() != H * W:
-        raise ValueError(f"{name}: expected a floating-point tensor of shape ({H}, {W})")
 
 
 def prepare_odometry_level(image, depth, mask, K, depth_min=DEPTH_MIN, depth_max=DEPTH_MAX, gradients=True):
@@ -91,12 +74,12 @@ def prepare_odometry_level(image, depth, mask, K, depth_min=DEPTH_MIN, depth_max
     H, W = int(image.shape[1]), int(image.shape[2])
     if H * W > 0x3FFFFFFF:
         raise ValueError(f"image: {W} x {H} is more than 2^30 - 1 pixels")
-    _plane_shape(depth, "depth", H, W)
+    A.tensor(depth, "depth", (H, W), also=(1, H, W), convert=False)
     if mask is not None:
-        _plane_shape(mask, "mask", H, W)
+        A.tensor(mask, "mask", (H, W), also=(1, H, W), convert=False)
     k = _check_K(K)
     lo, hi = _check_depth_range(depth_min, depth_max)
-    _C = _gsr()
+    _C = A.gsr()
     if not image.is_cuda or not depth.is_cuda or (mask is not None and not mask.is_cuda):
         raise _C.GsrError("prepare_odometry_level needs image, depth and mask on the HIP device (no CPU path)")
     dev = image.device
@@ -120,7 +103,7 @@ def _check_levels(source_level, target_level):
         if not isinstance(lv, OdometryLevel):
             raise TypeError(f"{name}={lv!r}: expected an OdometryLevel (prepare_odometry_level)")
         for n, v in (("width", lv.width), ("height", lv.height)):
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+            if not A.is_integer(v) or v < 1:
                 raise ValueError(f"{name}.{n}={v!r}: expected an int >= 1")
         if lv.width * lv.height > 0x3FFFFFFF:
             raise ValueError(f"{name}: {lv.width} x {lv.height} is more than 2^30 - 1 pixels")
@@ -137,12 +120,10 @@ def _check_levels(source_level, target_level):
               (t.intensity, "target_level.intensity", (H, W)), (t.depth, "target_level.depth", (H, W)),
               (t.grad, "target_level.grad", (4, H, W))]
     for p, name, shape in planes:
-        if not isinstance(p, torch.Tensor) or not p.is_floating_point() or tuple(p.shape) != shape:
-            raise ValueError(f"{name}: expected a floating-point tensor of shape {shape}, got "
-                             f"{tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__}")
+        A.tensor(p, name, shape, f", got {tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__}", convert=False)
     for p, name, _ in planes:
         if not p.is_cuda:
-            raise _gsr().GsrError(f"{name} must live on the HIP device (no CPU path)")
+            raise A.gsr().GsrError(f"{name} must live on the HIP device (no CPU path)")
     dev = s.intensity.device
     for p, name, _ in planes:
         if p.device != dev:
@@ -155,7 +136,7 @@ class _Updater:
     """gsr_odometry_update on two fixed levels that _check_levels has passed: the workspace is allocated once"""
 
     def __init__(self, src, tgt, lam, ddm):
-        _C = _gsr()
+        _C = A.gsr()
         self.src, self.tgt, self.lam, self.ddm = src, tgt, lam, ddm
         self.K = (C.c_double * 4)(*src.K)
         self.dev = src.intensity.device
@@ -163,7 +144,7 @@ class _Updater:
             self.ws = torch.empty(_C.lib().gsr_odometry_workspace_bytes(src.width, src.height), dtype=torch.uint8, device=self.dev)
 
     def __call__(self, Td, stats, apply=True):
-        _C = _gsr()
+        _C = A.gsr()
         s, t = self.src, self.tgt
         with _C.on_device(self.dev):
             _C.check(_C.lib().gsr_odometry_update(s.width, s.height, self.K, _C.ptr(s.intensity), _C.ptr(s.depth), _C.ptr(t.intensity),
@@ -177,12 +158,12 @@ def odometry_update(source_level, target_level, transformation, lambda_geometric
     device, stats float64 [8] on the device: n, fitness, inlier_rmse, status, sum r_D^2, sum r_I^2, 0, 0 - all of the
     transformation that was passed in).  status 1 (n < 6) or 2 (a rejected pivot), or apply=False, return the transformation as
     it was, bit for bit.  No read-back."""
-    T = _check_transform(transformation)
-    lam = _check_lambda(lambda_geometric)
+    T = A.transform(transformation)
+    lam = check_lambda(lambda_geometric)
     ddm = _check_depth_diff(depth_diff_max)
     source_level, target_level = _check_levels(source_level, target_level)
     dev = source_level.intensity.device
-    Td = _device_T(T, dev)
+    Td = A.device_T(T, dev)
     stats = torch.zeros(8, dtype=torch.float64, device=dev)
     _Updater(source_level, target_level, lam, ddm)(Td, stats, bool(apply))
     return Td, stats
@@ -194,7 +175,7 @@ def _check_iterations(max_iterations):
     except TypeError:
         raise TypeError(f"max_iterations={max_iterations!r}: expected a sequence of ints, one per level, coarse to fine") from None
     for n in its:
-        if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+        if not A.is_integer(n):
             raise TypeError(f"max_iterations={max_iterations!r}: expected ints")
     if not 1 <= len(its) <= MAX_LEVELS + 1 or min(its) < 0:
         raise ValueError(f"max_iterations={its}: expected 1 .. {MAX_LEVELS + 1} counts >= 0, one per level, coarse to fine")
@@ -234,17 +215,13 @@ def rgbd_odometry(source, target, init=None, max_iterations=MAX_ITERATIONS, lamb
     fitness, inlier_rmse and status of the result come from one closing apply=False evaluation at level 0."""
     its = _check_iterations(max_iterations)
     levels = len(its) - 1
-    T = _check_transform(init, "init")
-    lam = _check_lambda(lambda_geometric)
+    T = A.transform(init, "init")
+    lam = check_lambda(lambda_geometric)
     lo, hi = _check_depth_range(depth_min, depth_max)
     ddm = _check_depth_diff(depth_diff_max)
     for n, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
-        if not (math.isfinite(_check_number(n, v)) and v >= 0):
-            raise ValueError(f"{n}={v}: expected a finite value >= 0")
-    if isinstance(check_every, bool) or not isinstance(check_every, numbers.Integral):
-        raise TypeError(f"check_every={check_every!r}: expected an int")
-    if check_every < 0:
-        raise ValueError(f"check_every={check_every}: expected >= 0")
+        A.number(n, v, lambda v: math.isfinite(v) and v >= 0, "a finite value >= 0")
+    A.integer("check_every", check_every, 0)
     pyr = [_as_pyramid(source, levels, "source"), _as_pyramid(target, levels, "target")]
     base = [p[0] if p is not None else f for p, f in zip(pyr, (source, target))]
     for f, name in zip(base, ("source", "target")):
@@ -254,13 +231,13 @@ def rgbd_odometry(source, target, init=None, max_iterations=MAX_ITERATIONS, lamb
     Ks = [camera_intrinsics(f.camera) for f in base]
     if size[0] != size[1] or Ks[0] != Ks[1]:
         raise ValueError(f"rgbd_odometry: source {size[0]} K {Ks[0]}, target {size[1]} K {Ks[1]}: expected one size and one camera")
-    _C = _gsr()
+    _C = A.gsr()
     for f in base:
         if not (isinstance(f.image, torch.Tensor) and f.image.is_cuda):
             raise _C.GsrError("rgbd_odometry needs both frames on the HIP device (no CPU path)")
     pyr = [p if p is not None else FramePyramid(f, levels) for p, f in zip(pyr, (source, target))]
     dev = base[0].image.device
-    Td = _device_T(T, dev)
+    Td = A.device_T(T, dev)
     iterations = 0
     closing = None
     for level, n in zip(range(levels, -1, -1), its):
@@ -293,7 +270,7 @@ def camera_after_odometry(target_camera, transformation):
     """The camera of the SOURCE frame, given the target's and the odometry result T (source-camera to target-camera coordinates):
     world-to-camera = T^-1 . W2C_target, the target's intrinsics, size, clip planes and device.  With the source the new frame and
     the target the last tracked one this is the start pose of track_pose."""
-    T = _check_transform(transformation)
+    T = A.transform(transformation)
     if T is None:
         raise ValueError("transformation: expected a floating-point [4,4] matrix, got None")
     T = T.detach().cpu().double().numpy()

@@ -14,24 +14,19 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import _args as A
 from .odometry import OdometryResult
-from .registration import NeighborIndex, RegistrationResult, _check_distance, _device_T, _prepare, _check_transform
+from .registration import RegistrationResult, prepare
 from .transform import validate_transforms
 
 STATUS_NAMES = ("converged: step", "max_iteration", "solver failed", "converged: residual", "converged: zero residual", "lambda")
 CONVERGED = (0, 3, 4)      # GSR_PG_CONVERGED_STEP, GSR_PG_CONVERGED_RESIDUAL, GSR_PG_ZERO_RESIDUAL
 SYMMETRY_TOL = 1e-9        # |L - L^T| <= SYMMETRY_TOL max |L|
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
 
 
 class PoseGraphResult(NamedTuple):
@@ -54,13 +49,13 @@ def information_from_point_clouds(source, target, max_correspondence_distance, t
     correspondences (nearest target point within max_correspondence_distance of every source point moved by `transformation`),
     unknowns (alpha, beta, gamma, tx, ty, tz); entry [3,3] is the number of correspondences.  One NeighborIndex query (`index`:
     an index built over `target` earlier), then gsr_registration_information.  No read-back."""
-    src, index, md2, T = _prepare(source, target, max_correspondence_distance, transformation, index, "information_from_point_clouds")
-    _C = _gsr()
+    src, index, md2, T = prepare(source, target, max_correspondence_distance, transformation, index, "information_from_point_clouds")
+    _C = A.gsr()
     lib = _C.lib()
     dev = src.device
     Ps = int(src.shape[0])
     idx = torch.empty(Ps, dtype=torch.int32, device=dev)
-    index._search(src, _device_T(T, dev), md2, None, idx, None)
+    index._search(src, A.device_T(T, dev), md2, None, idx, None)
     info = torch.empty(6, 6, dtype=torch.float64, device=dev)
     stats = torch.empty(4, dtype=torch.float64, device=dev)
     with _C.on_device(dev):
@@ -89,7 +84,7 @@ def _check_information(info):
 def _check_rigid(T, name):
     """a [4,4] matrix as _check_transform takes it; given on the host it is held to validate_transforms"""
     on_host = not (isinstance(T, torch.Tensor) and T.is_cuda)
-    T = _check_transform(T, name)
+    T = A.transform(T, name)
     if T is None:
         raise ValueError(f"{name}: expected a [4,4] matrix, got None")
     if on_host:
@@ -100,12 +95,12 @@ def _check_rigid(T, name):
     return T.detach().to(torch.float64)
 
 
-def _check_positive(name, value, allow_zero=False):
-    if isinstance(value, bool) or not isinstance(value, numbers.Real):
-        raise TypeError(f"{name}={value!r}: expected a number")
-    if not (math.isfinite(value) and (value >= 0 if allow_zero else value > 0)):
-        raise ValueError(f"{name}={value}: expected a finite value {'>= 0' if allow_zero else '> 0'}")
-    return float(value)
+def _check_positive(name, value):
+    return A.number(name, value, lambda v: math.isfinite(v) and v > 0, "a finite value > 0")
+
+
+def _check_nonnegative(name, value):
+    return A.number(name, value, lambda v: math.isfinite(v) and v >= 0, "a finite value >= 0")
 
 
 class PoseGraph:
@@ -229,7 +224,8 @@ class PoseGraph:
             return 1.0      # (no uncertain edge reads it)
         if max_correspondence_distance is None:
             raise ValueError("optimize: the graph has uncertain edges: give max_correspondence_distance or line_process_weight")
-        md = _check_distance("max_correspondence_distance", max_correspondence_distance, False)
+        md = A.number("max_correspondence_distance", max_correspondence_distance, lambda v: v >= 0 and not math.isinf(v),
+                      "a value >= 0, finite")      # (false for NaN; worded as registration's distances are)
         pref = _check_positive("preference_loop_closure", preference_loop_closure)
         mu = pref * md * md * float(np.mean([e[3][3, 3] for e in self._edges]))
         if not mu > 0:
@@ -238,7 +234,7 @@ class PoseGraph:
         return mu
 
     def _build_topology(self):
-        _C = _gsr()
+        _C = A.gsr()
         lib = _C.lib()
         N, E = len(self._ids), len(self._edges)
         ends = np.ascontiguousarray(np.array([(s, t) for s, t, _, _, _ in self._edges], dtype=np.int32).reshape(E, 2))
@@ -269,20 +265,20 @@ class PoseGraph:
         few chords reaches the cap before `cg_rtol` - the approximate step is then judged by the gain test, and a run can stop
         early (`result.cg_worst_residual` far above `cg_rtol` says so): give such graphs a larger cap or a looser `cg_rtol`.  ValueError before any device work: a component without a fixed
         node, bad options.  A graph on the CPU raises GsrError: there is no CPU path."""
-        _C = _gsr()
+        _C = A.gsr()
         self._validate()
         mu = self._default_mu(max_correspondence_distance, preference_loop_closure, line_process_weight)
-        if isinstance(max_iteration, bool) or not isinstance(max_iteration, numbers.Integral) or max_iteration < 0:
+        if not A.is_integer(max_iteration) or max_iteration < 0:
             raise ValueError(f"max_iteration={max_iteration!r}: expected an int >= 0")
         N = len(self._ids)
         if cg_max_iteration is None:
             cg_max_iteration = min(6 * N, 1000)
-        if isinstance(cg_max_iteration, bool) or not isinstance(cg_max_iteration, numbers.Integral) or cg_max_iteration < 1:
+        if not A.is_integer(cg_max_iteration) or cg_max_iteration < 1:
             raise ValueError(f"cg_max_iteration={cg_max_iteration!r}: expected an int >= 1")
-        mri = _check_positive("min_relative_increment", min_relative_increment, True)
-        mrri = _check_positive("min_relative_residual_increment", min_relative_residual_increment, True)
-        rtol = _check_positive("cg_rtol", cg_rtol, True)
-        thr = _check_positive("prune_threshold", prune_threshold, True)
+        mri = _check_nonnegative("min_relative_increment", min_relative_increment)
+        mrri = _check_nonnegative("min_relative_residual_increment", min_relative_residual_increment)
+        rtol = _check_nonnegative("cg_rtol", cg_rtol)
+        thr = _check_nonnegative("prune_threshold", prune_threshold)
         if self.device.type != "cuda":
             raise _C.GsrError("PoseGraph.optimize runs in HIP kernels (no CPU path): the graph must live on the HIP device")
         first = self._run(mu, int(max_iteration), mri, mrri, rtol, int(cg_max_iteration))
@@ -297,7 +293,7 @@ class PoseGraph:
                                cg_worst_residual=max(first.cg_worst_residual, second.cg_worst_residual), pruned=pruned)
 
     def _run(self, mu, max_iteration, mri, mrri, rtol, cg_max):
-        _C = _gsr()
+        _C = A.gsr()
         lib = _C.lib()
         if self._topo is None:
             self._build_topology()
@@ -322,7 +318,7 @@ class PoseGraph:
     def prune_edges(self, threshold=0.25):
         """Drops the uncertain edges whose weight of the last `optimize` is below `threshold` -> [(source id, target id)] of the
         dropped edges.  One read-back (the weights)."""
-        thr = _check_positive("threshold", threshold, True)
+        thr = _check_nonnegative("threshold", threshold)
         if self._weights is None:
             raise ValueError("prune_edges: no weights: call optimize first (and do not change the graph in between)")
         w = self._weights.cpu().tolist()

@@ -13,20 +13,14 @@ lines the reference has commented out at :198-213 - whose result starts ICP (`re
 from __future__ import annotations
 
 import math
-import numbers
 from typing import NamedTuple
 
 import torch
 
-from .pointcloud import _check_cloud, _check_gradient, _check_normals, _check_rows3, _check_rows3_shape, _check_voxel_size, \
-    estimate_color_gradients, estimate_normals, voxel_down_sample
+from . import _args as A
+from .pointcloud import NB_NEIGHBORS_MAX, ROW_PER_POINT, estimate_color_gradients, estimate_normals, voxel_down_sample
 
 USE_QUERY_ORDER = True      # registration_icp Morton-sorts the queries once (profiles/README.md, registration_bench: measured)
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
 
 
 class RegistrationResult(NamedTuple):
@@ -39,24 +33,15 @@ class RegistrationResult(NamedTuple):
 
 
 def _check_distance(name, value, allow_inf):
-    if isinstance(value, bool) or not isinstance(value, numbers.Real):
-        raise TypeError(f"{name}={value!r}: expected a number")
-    if math.isnan(value) or value < 0 or (math.isinf(value) and not allow_inf):
-        raise ValueError(f"{name}={value}: expected a value >= 0" + ("" if allow_inf else ", finite"))
-    return float(value)
+    return A.number(name, value, lambda v: v >= 0 and (allow_inf or not math.isinf(v)),      # (false for NaN)
+                    "a value >= 0" + ("" if allow_inf else ", finite"))
 
 
 def _check_icp(relative_fitness, relative_rmse, max_iteration, check_every):
     for n, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real):
-            raise TypeError(f"{n}={v!r}: expected a number")
-        if not (math.isfinite(v) and v >= 0):
-            raise ValueError(f"{n}={v}: expected a finite value >= 0")
-    for n, v, lo in (("max_iteration", max_iteration, 1), ("check_every", check_every, 0)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise TypeError(f"{n}={v!r}: expected an int")
-        if v < lo:
-            raise ValueError(f"{n}={v}: expected >= {lo}")
+        A.number(n, v, lambda v: math.isfinite(v) and v >= 0, "a finite value >= 0")
+    A.integer("max_iteration", max_iteration, 1)
+    A.integer("check_every", check_every, 0)
 
 
 ESTIMATIONS = ("point_to_point", "point_to_plane", "colored")
@@ -71,58 +56,19 @@ def _check_estimation(estimation):
     return estimation
 
 
-def _check_lambda(lambda_geometric):
-    if isinstance(lambda_geometric, bool) or not isinstance(lambda_geometric, numbers.Real):
-        raise TypeError(f"lambda_geometric={lambda_geometric!r}: expected a number")
-    if not 0.0 <= lambda_geometric <= 1.0:      # (false for NaN)
-        raise ValueError(f"lambda_geometric={lambda_geometric}: expected 0 .. 1")
-    return float(lambda_geometric)
+def check_lambda(lambda_geometric):
+    return A.number("lambda_geometric", lambda_geometric, lambda v: 0.0 <= v <= 1.0, "0 .. 1")      # (false for NaN)
 
 
-def _rows(cloud):
-    return int(cloud.shape[0]) if isinstance(cloud, torch.Tensor) and cloud.dim() == 2 else None
+def _check_rows3(t, name, rows, convert=True):
+    """colours or gradients, one row per point: A.tensor of [rows,3] (rows=None: any number)"""
+    return A.tensor(t, name, ("P" if rows is None else rows, 3), ROW_PER_POINT, convert=convert)
 
 
-def _check_target_normals(normals, rows=None):
-    """None, or a floating-point [rows,3] tensor on the HIP device -> contiguous float32; type and shape first"""
-    if normals is None:
-        return None
-    if not isinstance(normals, torch.Tensor) or not normals.is_floating_point() or normals.dim() != 2 or \
-            normals.shape[1] != 3 or (rows is not None and int(normals.shape[0]) != rows):
-        raise ValueError("target_normals: expected a floating-point tensor of shape "
-                         f"({'Pt' if rows is None else rows}, 3), one row per target row")
-    if not normals.is_cuda:
-        raise _gsr().GsrError("target_normals must live on the HIP device (no CPU path)")
-    return normals.detach().float().contiguous()
-
-
-def _check_transform(T, name="transformation"):
-    """None, or anything that gives a [4,4] matrix -> None / (tensor or array as given); shape and type only"""
-    if T is None:
-        return None
-    if not isinstance(T, torch.Tensor):
-        T = torch.as_tensor(T, dtype=torch.float64)
-    if tuple(T.shape) != (4, 4) or not T.is_floating_point():
-        raise ValueError(f"{name}: expected a floating-point [4,4] matrix, got {T.dtype} {tuple(T.shape)}")
-    return T
-
-
-def _sq(distance):
-    """float32 square of a distance, as the kernel compares it (+inf stays +inf)"""
-    d = torch.tensor(distance, dtype=torch.float32)
-    return float(d * d)
-
-
-def _device_T(T, dev):
-    """a fresh contiguous float64 [4,4] on `dev` (the identity for None): ICP updates it in place"""
-    if T is None:
-        return torch.eye(4, dtype=torch.float64, device=dev)
-    return T.detach().to(device=dev, dtype=torch.float64).contiguous().clone()
-
-
-def _nonempty(pts, who, what):
-    if int(pts.shape[0]) == 0:
-        raise ValueError(f"{who}: the {what} cloud is empty")
+def _check_target_normals(normals, rows):
+    """None, or A.tensor of [rows,3] (rows=None: any number)"""
+    return None if normals is None else A.tensor(normals, "target_normals", ("Pt" if rows is None else rows, 3),
+                                                 ", one row per target row")
 
 
 class NeighborIndex:
@@ -130,9 +76,9 @@ class NeighborIndex:
     any number of times; the target's rows keep their numbers."""
 
     def __init__(self, target):
-        pts, _ = _check_cloud(target, None, "NeighborIndex")
-        _nonempty(pts, "NeighborIndex", "target")
-        _C = _gsr()
+        pts, _ = A.cloud(target, None, "NeighborIndex")
+        A.nonempty(pts, "NeighborIndex", "target")
+        _C = A.gsr()
         lib = _C.lib()
         self.points = pts
         self.size = int(pts.shape[0])
@@ -142,7 +88,7 @@ class NeighborIndex:
             _C.check(lib.gsr_nn_index_build(self.size, _C.ptr(pts), _C.ptr(self.blob), self.blob.numel(), _C._stream()))
 
     def _source(self, points, who):
-        pts, _ = _check_cloud(points, None, who)
+        pts, _ = A.cloud(points, None, who)
         if pts.device != self.device:
             raise ValueError(f"{who}: points on {pts.device}, the index on {self.device}")
         return pts
@@ -150,14 +96,14 @@ class NeighborIndex:
     def query_order(self, points, transform=None):
         """int32 [P]: the rows of `points` sorted by the Morton code of T p in the target's bounding box - handed to `query` as
         `order`, it gives the lanes of a wave neighbouring queries.  It never changes an answer."""
-        T = _check_transform(transform, "transform")
+        T = A.transform(transform, "transform")
         pts = self._source(points, "NeighborIndex.query_order")
         P = int(pts.shape[0])
         order = torch.empty(P, dtype=torch.int32, device=self.device)
         if P:
-            _C = _gsr()
+            _C = A.gsr()
             lib = _C.lib()
-            Td = None if T is None else _device_T(T, self.device)
+            Td = None if T is None else A.device_T(T, self.device)
             with _C.on_device(self.device):
                 ws = torch.empty(lib.gsr_nn_order_workspace_bytes(P), dtype=torch.uint8, device=self.device)
                 _C.check(lib.gsr_nn_query_order(self.size, _C.ptr(self.blob), P, _C.ptr(pts), _C.ptr(Td), _C.ptr(order), _C.ptr(ws),
@@ -165,7 +111,7 @@ class NeighborIndex:
         return order
 
     def _search(self, pts, Td, max_dist2, order, idx, dist2):
-        _C = _gsr()
+        _C = A.gsr()
         with _C.on_device(self.device):
             _C.check(_C.lib().gsr_nn_search(self.size, _C.ptr(self.blob), int(pts.shape[0]), _C.ptr(pts), _C.ptr(Td), max_dist2,
                                             _C.ptr(order), _C.ptr(idx), _C.ptr(dist2), _C._stream()))
@@ -175,7 +121,7 @@ class NeighborIndex:
         row of its nearest target point and the squared distance; among equal float32 distances the smallest row.  idx = -1 and
         dist2 = +inf where the distance exceeds `max_distance` or the row is not finite."""
         md = _check_distance("max_distance", max_distance, True)
-        T = _check_transform(transform, "transform")
+        T = A.transform(transform, "transform")
         pts = self._source(points, "NeighborIndex.query")
         P = int(pts.shape[0])
         if order is not None:
@@ -185,26 +131,26 @@ class NeighborIndex:
         idx = torch.empty(P, dtype=torch.int32, device=self.device)
         dist2 = torch.empty(P, dtype=torch.float32, device=self.device)
         if P:
-            self._search(pts, None if T is None else _device_T(T, self.device), _sq(md), order, idx, dist2)
+            self._search(pts, None if T is None else A.device_T(T, self.device), A.sq(md), order, idx, dist2)
         return idx, dist2
 
 
 def nn_search(query, target, transform=None, max_distance=math.inf):
     """NeighborIndex(target).query(query, ...) in one call (also `simple_knn.nn_search`)."""
     md = _check_distance("max_distance", max_distance, True)
-    T = _check_transform(transform, "transform")
+    T = A.transform(transform, "transform")
     return NeighborIndex(target).query(query, T, md)
 
 
 def transform_points(points, transformation):
     """float32 [P,3]: every row moved by the [4,4] `transformation`, q = (float32)(R p + t) as the search evaluates it."""
-    T = _check_transform(transformation)
-    pts, _ = _check_cloud(points, None, "transform_points")
+    T = A.transform(transformation)
+    pts, _ = A.cloud(points, None, "transform_points")
     out = torch.empty_like(pts)
     P = int(pts.shape[0])
     if P:
-        _C = _gsr()
-        Td = None if T is None else _device_T(T, pts.device)
+        _C = A.gsr()
+        Td = None if T is None else A.device_T(T, pts.device)
         with _C.on_device(pts.device):
             _C.check(_C.lib().gsr_transform_points(P, _C.ptr(pts), _C.ptr(Td), _C.ptr(out), _C._stream()))
     return out
@@ -215,14 +161,14 @@ class _Updater:
     gradients, lambda_geometric) besides them gsr_icp_update_colored - on fixed clouds: the workspace is allocated once"""
 
     def __init__(self, src, tgt, normals=None, colored=None):
-        _C = _gsr()
+        _C = A.gsr()
         self.src, self.tgt, self.normals, self.colored = src, tgt, normals, colored
         size = _C.lib().gsr_icp_workspace_bytes if colored is None else _C.lib().gsr_icp_colored_workspace_bytes
         with _C.on_device(src.device):
             self.ws = torch.empty(size(int(src.shape[0])), dtype=torch.uint8, device=src.device)
 
     def __call__(self, idx, Td, stats):
-        _C = _gsr()
+        _C = A.gsr()
         with _C.on_device(self.src.device):
             if self.colored is not None:
                 scol, tcol, grad, lam = self.colored
@@ -251,30 +197,30 @@ def icp_update(source, target, correspondences, transformation, target_normals=N
     source_colors ([Ps,3]), target_colors and target_gradients ([Pt,3]; estimate_color_gradients of the target) besides the
     normals: the coloured update (gsr_icp_update_colored; stats[5] and stats[6] = the sums of the squared geometric and
     photometric residuals, unweighted).  Some of the four without the others is a ValueError."""
-    T = _check_transform(transformation)
-    lam = _check_lambda(lambda_geometric)
+    T = A.transform(transformation)
+    lam = check_lambda(lambda_geometric)
     given = [a is not None for a in (source_colors, target_colors, target_gradients)]
     if any(given) and not (all(given) and target_normals is not None):
         raise ValueError("icp_update: the coloured update needs target_normals, source_colors, target_colors and target_gradients "
                          "together")
     if all(given):      # (every shape before any device check)
-        for t, name, rows in ((source_colors, "source_colors", _rows(source)), (target_colors, "target_colors", _rows(target)),
-                              (target_gradients, "target_gradients", _rows(target))):
-            _check_rows3_shape(t, name, rows)
-    nrm = _check_target_normals(target_normals, _rows(target))
+        for t, name, rows in ((source_colors, "source_colors", A.rows(source)), (target_colors, "target_colors", A.rows(target)),
+                              (target_gradients, "target_gradients", A.rows(target))):
+            _check_rows3(t, name, rows, convert=False)
+    nrm = _check_target_normals(target_normals, A.rows(target))
     colored = None
     if all(given):
-        colored = (_check_rows3(source_colors, "source_colors", _rows(source)),
-                   _check_rows3(target_colors, "target_colors", _rows(target)),
-                   _check_rows3(target_gradients, "target_gradients", _rows(target)), lam)
-    src, _ = _check_cloud(source, None, "icp_update")
-    tgt, _ = _check_cloud(target, None, "icp_update")
-    _nonempty(src, "icp_update", "source")
-    _nonempty(tgt, "icp_update", "target")
+        colored = (_check_rows3(source_colors, "source_colors", A.rows(source)),
+                   _check_rows3(target_colors, "target_colors", A.rows(target)),
+                   _check_rows3(target_gradients, "target_gradients", A.rows(target)), lam)
+    src, _ = A.cloud(source, None, "icp_update")
+    tgt, _ = A.cloud(target, None, "icp_update")
+    A.nonempty(src, "icp_update", "source")
+    A.nonempty(tgt, "icp_update", "target")
     idx = correspondences
     if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or tuple(idx.shape) != (int(src.shape[0]),):
         raise ValueError(f"correspondences: expected an int32 tensor of shape ({int(src.shape[0])},)")
-    Td = _device_T(T, src.device)
+    Td = A.device_T(T, src.device)
     stats = torch.zeros(8, dtype=torch.float64, device=src.device)
     if colored is not None:
         colored = tuple(c.to(src.device) for c in colored[:3]) + (lam,)
@@ -283,22 +229,22 @@ def icp_update(source, target, correspondences, transformation, target_normals=N
     return Td, stats
 
 
-def _prepare(source, target, max_correspondence_distance, T, index, who):
+def prepare(source, target, max_correspondence_distance, T, index, who):
     md = _check_distance("max_correspondence_distance", max_correspondence_distance, True)
-    T = _check_transform(T, "init" if who == "registration_icp" else "transformation")
+    T = A.transform(T, "init" if who == "registration_icp" else "transformation")
     if index is not None and not isinstance(index, NeighborIndex):
         raise TypeError(f"index={index!r}: expected a NeighborIndex")
-    src, _ = _check_cloud(source, None, who)
-    _nonempty(src, who, "source")
+    src, _ = A.cloud(source, None, who)
+    A.nonempty(src, who, "source")
     if index is None:
         index = NeighborIndex(target)
     elif target is not None:
-        tgt, _ = _check_cloud(target, None, who)
+        tgt, _ = A.cloud(target, None, who)
         if int(tgt.shape[0]) != index.size:
             raise ValueError(f"{who}: target has {int(tgt.shape[0])} rows, the index {index.size}")
     if src.device != index.device:
         raise ValueError(f"{who}: source on {src.device}, target on {index.device}")
-    return src, index, _sq(md), T
+    return src, index, A.sq(md), T
 
 
 def _evaluate(src, index, md2, Td, order, updater):
@@ -315,8 +261,8 @@ def _evaluate(src, index, md2, Td, order, updater):
 def evaluate_registration(source, target, max_correspondence_distance, transformation=None, index=None):
     """Fitness and inlier RMSE of `transformation` (None = identity) as Open3D's evaluate_registration defines them:
     correspondences = nearest target point within max_correspondence_distance.  iterations = 0."""
-    src, index, md2, T = _prepare(source, target, max_correspondence_distance, transformation, index, "evaluate_registration")
-    Td = _device_T(T, src.device)
+    src, index, md2, T = prepare(source, target, max_correspondence_distance, transformation, index, "evaluate_registration")
+    Td = A.device_T(T, src.device)
     fitness, rmse, idx = _evaluate(src, index, md2, Td, None, _Updater(src, index.points))
     return RegistrationResult(Td, fitness, rmse, 0, False, idx)
 
@@ -356,18 +302,18 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
         raise ValueError(f'registration_icp: colours / gradients given, but estimation="{est}" uses none')
     if target_normals is not None and normal_radius is not None:
         raise ValueError("registration_icp: target_normals and normal_radius both given - pass the normals or have them estimated")
-    target_rows = index.size if isinstance(index, NeighborIndex) else _rows(target)
+    target_rows = index.size if isinstance(index, NeighborIndex) else A.rows(target)
     if colored:      # (every shape before any device check)
-        for t, name, rows in ((source_colors, "source_colors", _rows(source)), (target_colors, "target_colors", target_rows),
+        for t, name, rows in ((source_colors, "source_colors", A.rows(source)), (target_colors, "target_colors", target_rows),
                               (target_gradients, "target_gradients", target_rows)):
             if t is not None:
-                _check_rows3_shape(t, name, rows)
+                _check_rows3(t, name, rows, convert=False)
     nrm = _check_target_normals(target_normals, target_rows)
     if plane and nrm is None:
         if normal_radius is None:
             raise ValueError(f'registration_icp: estimation="{est}" needs target_normals, or normal_radius to estimate them')
-        _check_normals(normal_radius, normal_max_nn)
-    lam = _check_lambda(lambda_geometric)
+        A.neighbourhood(normal_radius, normal_max_nn, 3, NB_NEIGHBORS_MAX)
+    lam = check_lambda(lambda_geometric)
     scol = tcol = grd = None
     if colored:
         if source_colors is None or target_colors is None:
@@ -379,13 +325,13 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
             if gradient_radius is None:
                 raise ValueError('registration_icp: estimation="colored" needs target_gradients, or gradient_radius to estimate '
                                  'them')
-            _check_gradient(gradient_radius, gradient_max_nn, ("gradient_radius", "gradient_max_nn"))
-        scol = _check_rows3(source_colors, "source_colors", _rows(source))
+            A.neighbourhood(gradient_radius, gradient_max_nn, 4, NB_NEIGHBORS_MAX, ("gradient_radius", "gradient_max_nn"))
+        scol = _check_rows3(source_colors, "source_colors", A.rows(source))
         tcol = _check_rows3(target_colors, "target_colors", target_rows)
         grd = None if target_gradients is None else _check_rows3(target_gradients, "target_gradients", target_rows)
-    src, index, md2, T = _prepare(source, target, max_correspondence_distance, init, index, "registration_icp")
+    src, index, md2, T = prepare(source, target, max_correspondence_distance, init, index, "registration_icp")
     dev, P = src.device, int(src.shape[0])
-    Td = _device_T(T, dev)
+    Td = A.device_T(T, dev)
     order = index.query_order(src, Td) if (USE_QUERY_ORDER if use_order is None else use_order) else None
     if plane and nrm is None:
         nrm = estimate_normals(index.points, normal_radius, normal_max_nn)
@@ -415,56 +361,22 @@ def registration_icp(source, target, max_correspondence_distance, init=None, rel
 FPFH_WIDTH = 33
 
 
-def _check_int(name, value, lo, hi=None):
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
-        raise TypeError(f"{name}={value!r}: expected an int")
-    if value < lo or (hi is not None and value > hi):
-        raise ValueError(f"{name}={value}: expected {lo} .. {hi}" if hi is not None else f"{name}={value}: expected >= {lo}")
-    return int(value)
-
-
 def _check_seed(seed):
-    return _check_int("seed", seed, 0, 2 ** 64 - 1)
+    return A.integer("seed", seed, 0, 2 ** 64 - 1)
 
 
-def _check_fpfh(radius, max_nn):
-    if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
-        raise TypeError(f"radius={radius!r}: expected a number")
-    if math.isnan(radius) or not radius > 0:
-        raise ValueError(f"radius={radius}: expected a value > 0")
-    if isinstance(max_nn, bool) or not isinstance(max_nn, numbers.Integral):
-        raise TypeError(f"max_nn={max_nn!r}: expected an int")
-    if max_nn != 0 and not 3 <= max_nn <= 33:
-        raise ValueError(f"max_nn={max_nn}: expected 3 .. 33, or 0 for the radius alone")
-    if max_nn == 0 and math.isinf(radius):
-        raise ValueError("max_nn=0 (the radius alone) needs a finite radius")
-    return float(radius), int(max_nn)
-
-
-def _feature_shape(feature, name, rows=None):
-    if not isinstance(feature, torch.Tensor) or not feature.is_floating_point() or feature.dim() != 2 or \
-            feature.shape[1] != FPFH_WIDTH or (rows is not None and int(feature.shape[0]) != rows):
-        raise ValueError(f"{name}: expected a floating-point tensor of shape ({'N' if rows is None else rows}, {FPFH_WIDTH})")
-
-
-def _check_feature(feature, name, rows=None):
-    """a floating-point [rows,33] tensor on the HIP device -> contiguous float32; type and shape first"""
-    _feature_shape(feature, name, rows)
-    if not feature.is_cuda:
-        raise _gsr().GsrError(f"{name} must live on the HIP device (no CPU path)")
-    return feature.detach().float().contiguous()
+def _check_feature(feature, name, rows=None, convert=True):
+    """A.tensor of [rows,33] (rows=None: any number)"""
+    return A.tensor(feature, name, ("N" if rows is None else rows, FPFH_WIDTH), convert=convert)
 
 
 def _check_ransac(max_correspondence_distance, ransac_n, edge_length_threshold, max_iteration, confidence, seed, batch):
     md = _check_distance("max_correspondence_distance", max_correspondence_distance, False)
-    n = _check_int("ransac_n", ransac_n, 3, 8)
-    for name, v, hi in (("edge_length_threshold", edge_length_threshold, 1.0), ("confidence", confidence, 1.0)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real):
-            raise TypeError(f"{name}={v!r}: expected a number")
-        if not 0.0 <= v <= hi:      # (false for NaN)
-            raise ValueError(f"{name}={v}: expected 0 .. {hi}")
-    _check_int("max_iteration", max_iteration, 1)
-    _check_int("batch", batch, 1, 1 << 20)
+    n = A.integer("ransac_n", ransac_n, 3, 8)
+    for name, v in (("edge_length_threshold", edge_length_threshold), ("confidence", confidence)):
+        A.number(name, v, lambda v: 0.0 <= v <= 1.0, "0 .. 1.0")      # (false for NaN)
+    A.integer("max_iteration", max_iteration, 1)
+    A.integer("batch", batch, 1, 1 << 20)
     return md, n, float(edge_length_threshold), float(confidence), _check_seed(seed)
 
 
@@ -472,7 +384,7 @@ def _check_pairs(pairs):
     if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError("pairs: expected an int32 tensor of shape (M, 2): source row, target row")
     if not pairs.is_cuda:
-        raise _gsr().GsrError("pairs must live on the HIP device (no CPU path)")
+        raise A.gsr().GsrError("pairs must live on the HIP device (no CPU path)")
     return pairs.contiguous()
 
 
@@ -483,12 +395,12 @@ def compute_fpfh_feature(points, normals, radius, max_nn=0, return_stats=False):
     served: a ball of five voxel sizes on a voxel-sampled surface holds fewer than 100 rows.  Rows are features (Open3D stores the
     transpose).  A row with a non-finite point or normal: NaN, and nobody's neighbour.  `return_stats`: also (spfh_counts int32
     [P,33], count int32 [P] - the neighbourhood's size, the row included).  No read-back."""
-    r, nn = _check_fpfh(radius, max_nn)
-    nrm = _check_target_normals(normals, _rows(points))
-    pts, _ = _check_cloud(points, None, "compute_fpfh_feature")
+    r, nn = A.neighbourhood(radius, max_nn, 3, NB_NEIGHBORS_MAX, radius_alone=True)
+    nrm = _check_target_normals(normals, A.rows(points))
+    pts, _ = A.cloud(points, None, "compute_fpfh_feature")
     if nrm is None:
         raise ValueError("normals: expected a floating-point tensor of shape (P, 3), one row per point")
-    _C = _gsr()
+    _C = A.gsr()
     P, dev = int(pts.shape[0]), pts.device
     out = torch.empty((P, FPFH_WIDTH), dtype=torch.float32, device=dev)
     counts = torch.empty((P, FPFH_WIDTH), dtype=torch.int32, device=dev) if return_stats else None
@@ -507,8 +419,8 @@ def feature_nn(query_feature, target_feature):
     """-> (idx int32 [Nq], dist2 float32 [Nq]): the target row nearest to every query row in the 33-dimensional feature space
     (float32 squared distance; among equal distances the smallest row).  A query with a NaN: -1 / NaN; target rows with a NaN
     never win."""
-    _feature_shape(query_feature, "query_feature")
-    _feature_shape(target_feature, "target_feature")
+    _check_feature(query_feature, "query_feature", convert=False)
+    _check_feature(target_feature, "target_feature", convert=False)
     q = _check_feature(query_feature, "query_feature")
     t = _check_feature(target_feature, "target_feature")
     if q.device != t.device:
@@ -517,7 +429,7 @@ def feature_nn(query_feature, target_feature):
     idx = torch.full((Nq,), -1, dtype=torch.int32, device=q.device)
     dist2 = torch.full((Nq,), math.inf, dtype=torch.float32, device=q.device)
     if Nq and Nt:
-        _C = _gsr()
+        _C = A.gsr()
         lib = _C.lib()
         with _C.on_device(q.device):
             ws = torch.empty(lib.gsr_feature_nn_workspace_bytes(Nq), dtype=torch.uint8, device=q.device)
@@ -531,8 +443,8 @@ def match_features(source_feature, target_feature, mutual_filter=False):
     mutual_filter: only the pairs whose target row j has i as ITS nearest source feature (a second search, roles swapped)."""
     if not isinstance(mutual_filter, bool):
         raise TypeError(f"mutual_filter={mutual_filter!r}: expected a bool")
-    _feature_shape(source_feature, "source_feature")
-    _feature_shape(target_feature, "target_feature")
+    _check_feature(source_feature, "source_feature", convert=False)
+    _check_feature(target_feature, "target_feature", convert=False)
     s = _check_feature(source_feature, "source_feature")
     t = _check_feature(target_feature, "target_feature")
     fwd, _ = feature_nn(s, t)
@@ -569,19 +481,19 @@ def ransac_trials(source, target, pairs, max_correspondence_distance, ransac_n, 
     place and returned).  debug: also (samples int32 [trials,8], status int32 [trials], T float64 [trials,4,4]) of the
     hypothesis stage.  No read-back."""
     md, n, theta, _, sd = _check_ransac(max_correspondence_distance, ransac_n, edge_length_threshold, 1, 1.0, seed, 1)
-    t0 = _check_int("first_trial", first_trial, 0)
-    cnt = _check_int("trials", trials, 1, 1 << 20)
+    t0 = A.integer("first_trial", first_trial, 0)
+    cnt = A.integer("trials", trials, 1, 1 << 20)
     prs = _check_pairs(pairs)
-    src, _ = _check_cloud(source, None, "ransac_trials")
-    tgt, _ = _check_cloud(target, None, "ransac_trials")
-    _nonempty(src, "ransac_trials", "source")
-    _nonempty(tgt, "ransac_trials", "target")
+    src, _ = A.cloud(source, None, "ransac_trials")
+    tgt, _ = A.cloud(target, None, "ransac_trials")
+    A.nonempty(src, "ransac_trials", "source")
+    A.nonempty(tgt, "ransac_trials", "target")
     M, dev = int(prs.shape[0]), src.device
     if M == 0:
         raise ValueError("ransac_trials: no pairs")
     if record is None:
         record = new_ransac_record(dev)
-    _C = _gsr()
+    _C = A.gsr()
     lib = _C.lib()
     dbg = None
     out = None
@@ -625,14 +537,14 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     if not isinstance(mutual_filter, bool):
         raise TypeError(f"mutual_filter={mutual_filter!r}: expected a bool")
     if pairs is None:
-        _feature_shape(source_feature, "source_feature", _rows(source))
-        _feature_shape(target_feature, "target_feature", _rows(target))
+        _check_feature(source_feature, "source_feature", A.rows(source), convert=False)
+        _check_feature(target_feature, "target_feature", A.rows(target), convert=False)
     elif not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError("pairs: expected an int32 tensor of shape (M, 2): source row, target row")
-    src, _ = _check_cloud(source, None, "registration_ransac_based_on_feature_matching")
-    tgt, _ = _check_cloud(target, None, "registration_ransac_based_on_feature_matching")
-    _nonempty(src, "registration_ransac_based_on_feature_matching", "source")
-    _nonempty(tgt, "registration_ransac_based_on_feature_matching", "target")
+    src, _ = A.cloud(source, None, "registration_ransac_based_on_feature_matching")
+    tgt, _ = A.cloud(target, None, "registration_ransac_based_on_feature_matching")
+    A.nonempty(src, "registration_ransac_based_on_feature_matching", "source")
+    A.nonempty(tgt, "registration_ransac_based_on_feature_matching", "target")
     dev = src.device
     if pairs is not None:
         pairs = _check_pairs(pairs)
@@ -659,10 +571,10 @@ def global_registration(source, target, voxel_size, seed=0, **ransac):
     """The reference's commented pipeline on clouds that are already down-sampled at `voxel_size`: normals (radius 2 v, max_nn 30,
     towards the cloud's mean - a rule that turns with the cloud, which the default sign rule does not), FPFH (radius 5 v,
     radius-only), mutual matching, RANSAC (1.5 v, ransac_n 4, edge length 0.9) -> RegistrationResult."""
-    v = _check_voxel_size(voxel_size)
+    v = A.voxel_size(voxel_size)
     _check_seed(seed)
-    src, _ = _check_cloud(source, None, "global_registration")
-    tgt, _ = _check_cloud(target, None, "global_registration")
+    src, _ = A.cloud(source, None, "global_registration")
+    tgt, _ = A.cloud(target, None, "global_registration")
     feats = []
     for pts in (src, tgt):
         ok = torch.isfinite(pts).all(dim=1)
@@ -701,8 +613,8 @@ def registration_multiscale(source, source_colors, target, target_colors, voxel_
     -> (the last level's RegistrationResult - its correspondences number the rows of that level's down-sampled clouds -, the list of
     every level's result)."""
     est = _check_estimation(estimation)
-    lam = _check_lambda(lambda_geometric)
-    T = _check_transform(init, "init")
+    lam = check_lambda(lambda_geometric)
+    T = A.transform(init, "init")
     try:
         voxels, iterations = list(voxel_sizes), list(max_iterations)
     except TypeError:
@@ -710,8 +622,8 @@ def registration_multiscale(source, source_colors, target, target_colors, voxel_
     if not voxels or len(voxels) != len(iterations):
         raise ValueError(f"registration_multiscale: {len(voxels)} voxel sizes and {len(iterations)} iteration counts: expected "
                          "as many of one as of the other, at least one")
-    voxels = [_check_voxel_size(v) for v in voxels]
-    iterations = [_check_int("max_iterations", n, 1) for n in iterations]
+    voxels = [A.voxel_size(v) for v in voxels]
+    iterations = [A.integer("max_iterations", n, 1) for n in iterations]
     for k in ("index", "max_iteration", "estimation") + _COLORED_OWN:
         if k in icp:
             raise TypeError(f"registration_multiscale: {k} is decided per level, not accepted")
@@ -719,8 +631,8 @@ def registration_multiscale(source, source_colors, target, target_colors, voxel_
         raise ValueError("registration_multiscale: colours for both clouds or for neither")
     if est == "colored" and source_colors is None:
         raise ValueError('registration_multiscale: estimation="colored" needs the colours of both clouds')
-    src, scol = _check_cloud(source, source_colors, "registration_multiscale")
-    tgt, tcol = _check_cloud(target, target_colors, "registration_multiscale")
+    src, scol = A.cloud(source, source_colors, "registration_multiscale")
+    tgt, tcol = A.cloud(target, target_colors, "registration_multiscale")
     results = []
     for v, n in zip(voxels, iterations):
         sd, sc = voxel_down_sample(src, scol, v)
@@ -754,10 +666,10 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
     if not isinstance(global_init, bool):
         raise TypeError(f"global_init={global_init!r}: expected a bool")
     _check_seed(global_seed)
-    v = _check_voxel_size(voxel_size)
+    v = A.voxel_size(voxel_size)
     est = _check_estimation(estimation)
     plane, colored = est == "point_to_plane", est == "colored"
-    mv = None if merge_voxel_size is None else _check_voxel_size(merge_voxel_size)
+    mv = None if merge_voxel_size is None else A.voxel_size(merge_voxel_size)
     md = 5.0 * v if max_correspondence_distance is None else _check_distance("max_correspondence_distance",
                                                                              max_correspondence_distance, True)
     if (source_colors is None) != (target_colors is None):
@@ -772,8 +684,8 @@ def register_and_merge(source, source_colors, target, target_colors, voxel_size=
                             "normals and gradients itself (radius 2 * voxel_size, max_nn 30)")
         if source_colors is None:
             raise ValueError('register_and_merge: estimation="colored" needs the colours of both clouds')
-    src, scol = _check_cloud(source, source_colors, "register_and_merge")
-    tgt, tcol = _check_cloud(target, target_colors, "register_and_merge")
+    src, scol = A.cloud(source, source_colors, "register_and_merge")
+    tgt, tcol = A.cloud(target, target_colors, "register_and_merge")
     src_down, scol_down = voxel_down_sample(src, scol if colored else None, v)
     tgt_down, tcol_down = voxel_down_sample(tgt, tcol if colored else None, v)
     if colored:
@@ -796,10 +708,10 @@ def align_map(model, target_points, max_correspondence_distance, ids=None, voxel
     model by the result through `model.transform_(T, ids=ids)`: rotations, SH bands and moments follow as that call defines.
     voxel_size: down-sample the means first (the target is taken as given).  -> RegistrationResult."""
     md = _check_distance("max_correspondence_distance", max_correspondence_distance, True)
-    v = None if voxel_size is None else _check_voxel_size(voxel_size)
+    v = None if voxel_size is None else A.voxel_size(voxel_size)
     xyz = model.get_xyz
     if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
-        raise _gsr().GsrError("align_map runs in HIP kernels (no CPU path): the model must live on the HIP device")
+        raise A.gsr().GsrError("align_map runs in HIP kernels (no CPU path): the model must live on the HIP device")
     src = xyz.detach()
     if ids is not None:
         ids = [int(i) for i in ids]

@@ -14,16 +14,12 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _args as A
 from .cameras import MiniCam, camera_projection
 from .model import GaussianModel
 
 _MOVED_GROUPS = ("_xyz", "_rotation", "_scaling", "_features_rest")      # the order of gsr_transform_gaussians' moments8
 ORTHO_TOL = 1e-6       # max |R R^T - I|, |s - 1| and the bottom row's deviation a validated matrix may show
-
-
-def _gsr():
-    from diff_gaussian_rasterization import _C
-    return _C
 
 
 def _as_stack(T):
@@ -102,7 +98,7 @@ def set_anchors(self, anchors):
     return self
 
 
-def _extend_anchors(model, old_rows, new_rows, anchor, device):
+def extend_anchors(model, old_rows, new_rows, anchor, device):
     """Bookkeeping of a row insertion: `new_rows` rows appended behind `old_rows`.  With `anchor` they get it (and a model
     without anchors so far labels its old rows -1); without, they get -1 if the model has anchors and nothing happens otherwise."""
     cur = getattr(model, "_anchor", None)
@@ -140,7 +136,7 @@ def transform_(self, T, ids=None, moments="reset", check=None, allow_scale=False
     old frame; f_dc and opacity are invariant and keep theirs), as reset_opacity does for its group; "keep" leaves them.
     The model's resize hooks are called around the move, so a Trainer in flight settles first and relearns its tile cut-offs
     (under exchange="sharded" its hook raises, as for prune_points).  Runs in HIP kernels: a CPU model raises GsrError."""
-    _C = _gsr()
+    _C = A.gsr()
     if moments not in ("reset", "keep"):
         raise ValueError(f"moments={moments!r}: expected 'reset' or 'keep'")
     T, on_host = _as_stack(T)

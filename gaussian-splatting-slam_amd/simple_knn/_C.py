@@ -45,10 +45,8 @@ def knn_k(points, k, return_dist2=True, return_mean=False):
     that returns the query; root and sum in float64 on the device, rounded once.  P == 1 gives 0.
     Exact neighbours, the float32 distances of `knn_dist2` (k = 3: the three values whose mean it returns).  A row with a
     non-finite coordinate gets +inf / NaN and is nobody's neighbour.  Returns dist2, mean, or (dist2, mean) as asked."""
-    if isinstance(k, bool) or not isinstance(k, int):
-        raise TypeError(f"k={k!r}: expected an int")
-    if not 1 <= k <= KNN_K_MAX:
-        raise ValueError(f"k={k}: expected 1 .. {KNN_K_MAX}")
+    from scene_utils._args import integer
+    k = integer("k", k, 1, KNN_K_MAX)
     if not (return_dist2 or return_mean):
         raise ValueError("knn_k: nothing asked for (return_dist2 and return_mean both False)")
     if not isinstance(points, torch.Tensor) or not points.is_cuda:
