@@ -128,6 +128,23 @@ IMG_TILE_W = 256             # GSR_IMG_TILE_W: pixels of one row per workgroup o
 IMG_TILE_H = 1               # rows per workgroup: rows are not tiled (Bayer stages the rows above and below as halo)
 DEPTH_REGISTER_CAP = 8       # columns / rows of a footprint of gsr_depth_register before it is cut
 
+class gsr_tsdf_volume(C.Structure):
+    # HOST struct: the lattice of a TSDF volume (csrc/tsdf.hip)
+    _fields_ = [("origin", C.c_double * 3), ("voxel_size", C.c_double), ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float),
+                ("max_weight", C.c_float), ("reserved", C.c_float)]
+
+
+class gsr_tsdf_frame(C.Structure):
+    # HOST struct: one depth frame; w2c = the first three rows of the world-to-camera matrix, row-major float64
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("K", C.c_float * 4), ("w2c", C.c_double * 12),
+                ("depth", C.c_void_p), ("mask", C.c_void_p), ("color", C.c_void_p)]
+
+
+TSDF_BLOCK = 8               # GSR_TSDF_BLOCK: voxels per block edge
+TSDF_TOUCH_SLOTS = 27        # GSR_TSDF_TOUCH_SLOTS
+TSDF_MAX_BLOCKS = 1 << 19    # GSR_TSDF_MAX_BLOCKS
+TSDF_NO_KEY = (1 << 63) - 1  # GSR_TSDF_NO_KEY
+
 ODOMETRY_TILE_W = 32         # GSR_ODO_TILE_W x GSR_ODO_TILE_H: pixels per workgroup of gsr_odometry_prepare (csrc/odometry.hip)
 ODOMETRY_TILE_H = 8
 
@@ -352,6 +369,20 @@ EXPORTS = {
     # P, anchor, K, transforms, workspace + bytes, xyz, rotation, scaling, features_rest, sh_coeffs_rest, moments8 (host), stream
     "gsr_transform_gaussians": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 +
                                 [C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
+    # volume (host), frame (host), keys_out, stream
+    "gsr_tsdf_touch": (C.c_int, [C.POINTER(gsr_tsdf_volume), C.POINTER(gsr_tsdf_frame), C.c_void_p, C.c_void_p]),
+    # volume, frame, n_blocks, keys, rows, n_rows, tsdf, weight, color, stream
+    "gsr_tsdf_integrate": (C.c_int, [C.POINTER(gsr_tsdf_volume), C.POINTER(gsr_tsdf_frame), C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_tsdf_extract_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    # volume, B, keys_sorted, row_of_sorted, tsdf, weight, color, min_weight, capacity, points, normals, colors, count_dev,
+    # workspace + bytes, stream
+    "gsr_tsdf_extract_points": (C.c_int, [C.POINTER(gsr_tsdf_volume), C.c_int64] + [C.c_void_p] * 5 + [C.c_float, C.c_int64] +
+                                [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    # volume, B, keys_sorted, row_of_sorted, tsdf, weight, color, min_weight, capacity, positions, colors, count_dev,
+    # workspace + bytes, stream
+    "gsr_tsdf_extract_triangles": (C.c_int, [C.POINTER(gsr_tsdf_volume), C.c_int64] + [C.c_void_p] * 5 + [C.c_float, C.c_int64] +
+                                   [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "gsr_profile_enable": (None, [C.c_int32]),
     "gsr_profile_reset": (None, []),
     "gsr_profile_read": (C.c_int32, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

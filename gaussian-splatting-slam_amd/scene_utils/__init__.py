@@ -8,7 +8,7 @@ from .losses import l1_loss, psnr, training_loss_fused
 from .parallel import init_from_env, shard_views, GradBucket, ShardedStep, reduce_densification_stats, \
     rank1_sh_exchange, exchange_bytes_per_gaussian
 from .trainer import Trainer
-from .io import save_ply, load_ply, read_ply_vertices, capture, restore
+from .io import save_ply, load_ply, read_ply_vertices, capture, restore, save_mesh_ply, read_mesh_ply
 from .pose import se3_exp, PoseCamera, refine_pose, pose_error, DevicePoseCamera, track_pose
 from .mapping import unproject_rgbd, create_from_pcd, add_from_rgbd
 from .keyframes import covisibility, KeyframeWindow, prune_unobserved
@@ -27,3 +27,4 @@ from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, 
 from .odometry import OdometryLevel, OdometryResult, prepare_odometry_level, odometry_update, rgbd_odometry, \
     camera_after_odometry
 from .posegraph import PoseGraph, PoseGraphResult, information_from_point_clouds
+from .tsdf import TSDFVolume, fuse_views, weld_triangles

@@ -101,6 +101,95 @@ def read_ply_vertices(path: str):
         raise ValueError(f"{path}: unsupported PLY format {fmt}")
 
 
+def _host(a, dtype, width, name, rows=None):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
+    if a.ndim != 2 or a.shape[1] != width or (rows is not None and a.shape[0] != rows):
+        raise ValueError(f"{name}: expected [{'N' if rows is None else rows}, {width}], got {a.shape}")
+    return a.astype(dtype)
+
+
+def save_mesh_ply(path: str, vertices, triangles, colors=None, normals=None):
+    """A triangle mesh (or, with no faces, a point cloud with normals) as binary little-endian PLY: vertex x y z [nx ny nz]
+    [red green blue as uchar, colours in 0 .. 1 rounded to 0 .. 255], face `vertex_indices` as a uchar-counted int list.
+    `triangles`: [T,3] integers or None."""
+    v = _host(vertices, "<f4", 3, "vertices")
+    n = _host(normals, "<f4", 3, "normals", v.shape[0])
+    c = _host(colors, np.float64, 3, "colors", v.shape[0])
+    t = _host(triangles, "<i4", 3, "triangles") if triangles is not None else np.zeros((0, 3), "<i4")
+    if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
+        raise ValueError(f"triangles: indices outside 0 .. {v.shape[0] - 1}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if n is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if c is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.zeros(v.shape[0], dtype=fields)
+    for i, a in enumerate("xyz"):
+        rec[a] = v[:, i]
+        if n is not None:
+            rec["n" + a] = n[:, i]
+    if c is not None:
+        c8 = np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype("u1")
+        rec["red"], rec["green"], rec["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    names = {"<f4": "float", "u1": "uchar"}
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+    header += "".join(f"property {names[d]} {f}\n" for f, d in fields)
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % t.shape[0]
+    faces = np.zeros(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    faces["n"], faces["i"] = 3, t
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
+
+
+def read_mesh_ply(path: str):
+    """-> dict: "vertices" float32 [N,3], "triangles" int64 [T,3], "colors" float32 [N,3] in 0 .. 1 or None, "normals" float32
+    [N,3] or None.  Reads what save_mesh_ply writes: binary little-endian, scalar vertex properties, then triangular faces."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, counts, props = None, {}, []
+        element = None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated header")
+            tok = line.decode("ascii").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                counts[element] = int(tok[2])
+            elif tok[0] == "property" and element == "vertex":
+                if tok[1] == "list" or tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: vertex property {' '.join(tok[1:])} is not supported")
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "property" and element == "face":
+                if tok[1:4] != ["list", "uchar", "int"] and tok[1:4] != ["list", "uchar", "uint"]:
+                    raise ValueError(f"{path}: face property {' '.join(tok[1:])} is not supported")
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or list(counts)[:1] != ["vertex"]:
+            raise ValueError(f"{path}: expected a binary little-endian PLY whose first element is vertex")
+        N, T = counts["vertex"], counts.get("face", 0)
+        vert = np.frombuffer(f.read(N * np.dtype(props).itemsize), dtype=np.dtype(props), count=N)
+        faces = np.frombuffer(f.read(T * 13), dtype=[("n", "u1"), ("i", "<i4", (3,))], count=T)
+    if T and np.any(faces["n"] != 3):
+        raise ValueError(f"{path}: a face that is no triangle")
+    have = {n for n, _ in props}
+
+    def cols(names, scale=1.0):
+        return np.stack([vert[n].astype(np.float32) for n in names], axis=1) * np.float32(scale) if have.issuperset(names) else None
+    return {"vertices": cols(("x", "y", "z")), "triangles": faces["i"].astype(np.int64).reshape(T, 3),
+            "colors": cols(("red", "green", "blue"), 1.0 / 255.0), "normals": cols(("nx", "ny", "nz"))}
+
+
 def load_ply(model, path: str, device="cuda"):
     """Fills `model` (a scene_utils.GaussianModel) exactly as reference load_ply (:231-272) does."""
     v = read_ply_vertices(path)

@@ -67,6 +67,8 @@ extern "C" {
  *    gsr_posegraph_workspace_bytes, gsr_posegraph_linearize, gsr_posegraph_solve, gsr_posegraph_optimize: an information matrix
  *    per edge and robust pose-graph optimisation in one launch (additions only);
  *    gsr_debug_slot_views: the emission slot of every list position, for tests that read the backward's gradient records;
+ *    gsr_tsdf_volume, gsr_tsdf_frame, gsr_tsdf_touch, gsr_tsdf_integrate, gsr_tsdf_extract_workspace_bytes, gsr_tsdf_extract_points,
+ *    gsr_tsdf_extract_triangles: depth frames fused into a block-sparse TSDF volume, out as a cloud and a mesh (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -1385,6 +1387,97 @@ size_t gsr_transform_workspace_bytes(int32_t K);
 int gsr_transform_gaussians(int64_t P, const int32_t* anchor, int32_t K, const double* transforms, void* workspace,
                             size_t workspace_bytes, float* xyz, float* rotation, float* scaling_raw, float* features_rest,
                             int32_t sh_coeffs_rest, float* const* moments8, void* stream);
+
+/* ---- TSDF fusion: depth frames into a block-sparse signed distance volume, out as a cloud and a mesh (csrc/tsdf.hip; DESIGN.md
+ * section 4 item 38) ----
+ *
+ * THE VOLUME.  Voxels have edge voxel_size; a block is 8 x 8 x 8 voxels and is named by its signed integer coordinate (bx, by, bz),
+ * each in -2^20 .. 2^20 - 1.  key = ((bx + 2^20) << 42) | ((by + 2^20) << 21) | (bz + 2^20), an int64 >= 0: key order is block order,
+ * x highest.  Voxel (lx, ly, lz) of a block has the linear index lx + 8 ly + 64 lz and the global integer coordinate g = 8 b + l; its
+ * centre is origin + (g + 0.5) voxel_size.  The float32 world position of a centre is a function of g alone: per axis
+ * float32(origin_a + (g_a + 0.5) * voxel_size) with the product and the sum each rounded to float64 (no fused multiply-add) and ONE
+ * rounding to float32 - two blocks that name the same centre produce the same bits.
+ * Storage, owned by the caller: rows in allocation order, append-only - tsdf [B,512], weight [B,512], color [B,512,3] float32, zero
+ * when allocated; beside them keys_sorted int64 [B] (strictly ascending) and row_of_sorted int32 [B] (the row of each sorted key).  A
+ * block is found by binary search in keys_sorted.  B <= GSR_TSDF_MAX_BLOCKS.
+ * A FRAME is depth [H,W] (view-space z, 0 = no reading), mask [H,W] (NULL: every pixel; else pixels with mask != 0), color [3,H,W]
+ * (NULL: colours are not touched), K = (fx, fy, cx, cy) in float32 pixels (centre of pixel (0, 0) at (0, 0)) and `w2c`, HOST
+ * float64[12]: the first three rows of the rigid world-to-camera matrix, row-major (x_cam = R x_world + t; rigidity is trusted).
+ *
+ * TOUCH.  Every pixel with mask != 0 and 0 < depth <= depth_trunc is unprojected, p = R^T (((u - cx) / fx d, (v - cy) / fy d, d) - t),
+ * in float64; every block that intersects the axis-aligned box p +- sdf_trunc is touched: per axis the blocks
+ * floor((p_a - sdf_trunc - origin_a) / (8 voxel_size)) .. floor((p_a + sdf_trunc - origin_a) / (8 voxel_size)).  voxel_size <=
+ * sdf_trunc <= 8 voxel_size, so these are at most 3 per axis.  gsr_tsdf_touch writes 27 candidate keys per pixel, slot-major
+ * (keys_out int64 [27, H W]); unused slots, and blocks outside the coordinate range, hold GSR_TSDF_NO_KEY.  The caller uniques them,
+ * merges them into keys_sorted and appends zeroed rows.
+ *
+ * INTEGRATE.  One workgroup per touched block (`keys`, `rows` [n]: its key and its row), 256 lanes, voxels lane and lane + 256.  The
+ * camera-space position of the centre of voxel (0, 0, 0) of the block, c = R (origin + (8 b + 0.5) voxel_size) + t, is formed in
+ * float64 and rounded to float32; the steps a_k = float32(R[:,k] voxel_size) likewise; the voxel's camera-space position is
+ * (x, y, z) = c + lx a_0 + ly a_1 + lz a_2 in float32 - its error does not grow with the distance from the world origin.  With z > 0:
+ * u = fx x / z + cx, v = fy y / z + cy; the pixel is (floor(u + 0.5), floor(v + 0.5)), inside the image, with mask != 0; d = its
+ * depth, 0 < d <= depth_trunc; sdf = (d - z) sqrt(1 + (x/z)^2 + (y/z)^2), the distance along the ray; sdf <= -sdf_trunc: skipped;
+ * f = min(1, sdf / sdf_trunc); tsdf <- (tsdf w + f) / (w + 1), each colour channel likewise from the pixel's colour;
+ * w <- min(w + 1, max_weight) (max_weight >= 1).  A voxel is read and written by exactly one lane; no LDS, no atomics.
+ *
+ * SURFACE POINTS.  Voxel i is observed when weight > min_weight.  An edge runs from an observed voxel i to its +x, +y or +z
+ * neighbour j (possibly in the next block), also observed, where exactly one of the two has tsdf < 0.  With lo = i, hi = j (lo is
+ * the endpoint with the smaller global coordinate) and t = f_lo / (f_lo - f_hi), float32: point = p_lo + t (p_hi - p_lo) on the
+ * float32 centres; colour interpolated the same way; normal = normalise(g_lo + t (g_hi - g_lo)), g the gradient of tsdf in voxel
+ * units: per axis (f+ - f-) / 2 when both neighbours are observed, f+ - f0 or f0 - f- when one is, 0 when none is.  The normal
+ * points toward positive tsdf (where the cameras were); a zero vector stays (0, 0, 0).  Output order: blocks in key order, voxels in
+ * linear order, axes x, y, z.
+ *
+ * TRIANGLES.  Marching tetrahedra.  The cube of voxel g has the corners g + (c & 1, (c >> 1) & 1, c >> 2), c = 0 .. 7, and is used
+ * when all eight are observed.  It is split into the six Kuhn tetrahedra around the diagonal corner 0 -> corner 7: for each order
+ * (a, b, c) of the axes - xyz, xzy, yxz, yzx, zxy, zyx, in this order - the tetrahedron (v0, v0 + e_a, v0 + e_a + e_b, v7).  Every
+ * cube face is cut along the diagonal from its lowest to its highest corner.  "Inside" is tsdf < 0: 1 or 3 inside corners give one
+ * triangle, 2 give two (the quad AC, AD, BD, BC of inside A < B and outside C < D in path order, cut along AC - BD: both triangles start with AC; the triangle of a single corner k starts with the edge to the lowest
+ * other corner).  The vertex on
+ * the edge of two corners is p_lo + t (p_hi - p_lo) as above, lo the corner earlier on the path (smaller in every coordinate), so
+ * every cube and tetrahedron that shares an edge produces the same bits.  Triangles are wound so that the right-hand normal points
+ * toward positive tsdf.  Output: triangle soup, positions [T,3,3] and colours [T,3,3]; order: block key, voxel, tetrahedron, triangle.
+ *
+ * The extract calls take an output capacity and report the count they needed in count_dev[0] (device int64); rows beyond the
+ * capacity are never written; capacity == 0 with NULL outputs counts only.  Two launches and one scan each; deterministic.
+ * Every call checks its arguments before any device work (GSR_ERR_INVALID_ARGUMENT; a short workspace GSR_ERR_STATE_TOO_SMALL):
+ * NULL or non-finite volume fields, voxel_size <= 0, sdf_trunc outside [voxel_size, 8 voxel_size], depth_trunc <= 0, max_weight < 1,
+ * an image side < 1 or W H > 2^26, fx or fy <= 0, non-finite K / w2c, NULL depth, a block count < 0 or > GSR_TSDF_MAX_BLOCKS, NULL
+ * arrays where the count is > 0, a negative capacity, outputs NULL with capacity > 0, min_weight negative or NaN.  A block count
+ * of 0 launches nothing (the extract calls then write count 0). */
+#define GSR_TSDF_BLOCK 8
+#define GSR_TSDF_BLOCK_VOXELS 512
+#define GSR_TSDF_TOUCH_SLOTS 27
+#define GSR_TSDF_MAX_BLOCKS (1 << 19)
+#define GSR_TSDF_NO_KEY INT64_MAX
+
+typedef struct gsr_tsdf_volume {   /* HOST struct */
+  double origin[3];
+  double voxel_size;
+  float sdf_trunc, depth_trunc, max_weight, reserved;
+} gsr_tsdf_volume;
+
+typedef struct gsr_tsdf_frame {    /* HOST struct; depth / mask / color are device pointers */
+  int32_t width, height;
+  float K[4];
+  double w2c[12];
+  const float* depth;
+  const float* mask;
+  const float* color;
+} gsr_tsdf_frame;
+
+int gsr_tsdf_touch(const gsr_tsdf_volume* vol, const gsr_tsdf_frame* frame, int64_t* keys_out /*[H W 27]*/, void* stream);
+int gsr_tsdf_integrate(const gsr_tsdf_volume* vol, const gsr_tsdf_frame* frame, int64_t n_blocks, const int64_t* keys /*[n]*/,
+                       const int32_t* rows /*[n]*/, int64_t n_rows, float* tsdf, float* weight, float* color, void* stream);
+size_t gsr_tsdf_extract_workspace_bytes(int64_t B);
+int gsr_tsdf_extract_points(const gsr_tsdf_volume* vol, int64_t B, const int64_t* keys_sorted, const int32_t* row_of_sorted,
+                            const float* tsdf, const float* weight, const float* color, float min_weight, int64_t capacity,
+                            float* points /*[cap,3]*/, float* normals /*[cap,3]*/, float* colors /*[cap,3]*/,
+                            int64_t* count_dev /*[1]*/, void* workspace, size_t workspace_bytes, void* stream);
+int gsr_tsdf_extract_triangles(const gsr_tsdf_volume* vol, int64_t B, const int64_t* keys_sorted, const int32_t* row_of_sorted,
+                               const float* tsdf, const float* weight, const float* color, float min_weight, int64_t capacity,
+                               float* positions /*[cap,3,3]*/, float* colors /*[cap,3,3]*/, int64_t* count_dev /*[1]*/,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py's roofline block).  A measurement aid, process-
  * global and meant for ONE host thread driving the library at a time: enabling it while several host threads launch
