@@ -53,7 +53,7 @@ int gsr_launch_status(const char* what) {
 // status0: the frame's first status word on the device (meta[0]); with debug = 1 a stage that left GSR_STATUS_SORT_TIMEOUT there
 // fails the call (reference README.md:168-171: with --debug a failing rasterizer call raises and dumps its inputs).
 static int debug_sync_status(const gsr_settings* s, hipStream_t st, const char* stage, const uint32_t* status0) {
-  static const bool trace = getenv("GSR_TRACE") != nullptr;   // GSR_TRACE=1: name every stage on stderr as it completes
+  static const bool trace = gsr_read_switches(GSR_SW_TRACE).trace;   // GSR_TRACE=1: name every stage on stderr as it completes
   if (trace) {
     fprintf(stderr, "[gsr] launched: %s\n", stage);
     fflush(stderr);
@@ -84,13 +84,11 @@ static int debug_sync(const gsr_settings* s, hipStream_t st, const char* stage) 
 // per-kernel profiling (HIP events on the launch stream)
 // ---------------------------------------------------------------------------------------------------
 int g_gsr_profile_on = 0;
-// frames with at least this many instances flag their gradient records (gsr_common.h); GSR_FLAGS_MIN_R in the environment of the
-// process sets the starting value (0 = always: how the seeded sweeps run their small scenes through the flagged form)
-static unsigned flags_min_r_from_env() {
-  const char* e = getenv("GSR_FLAGS_MIN_R");
-  return e && *e ? (unsigned)strtoul(e, nullptr, 10) : GSR_FLAGS_MIN_R;
-}
-unsigned g_gsr_flags_min_r = flags_min_r_from_env();
+// the one reader of the process' environment
+GsrSwitches gsr_read_switches(unsigned scopes) { return gsr_switches_read(getenv, scopes); }
+// frames with at least this many instances flag their gradient records (gsr_common.h); the switch sets the starting value, a
+// backward reads the live one once and hands it to both of its kernels
+unsigned g_gsr_flags_min_r = gsr_read_switches(GSR_SW_FLAGS_MIN_R).flags_min_r;
 namespace {
 struct Pending { const char* name; hipEvent_t a, b; };
 std::mutex g_prof_mu;
@@ -325,6 +323,7 @@ struct ForwardCall {
   bool cull_applied = false;           // ... and the lists are counted and emitted with the cut-off
   uint32_t frame_tag = 0;
   const gsr_render_extras* extras = nullptr;   // depth kind, out_alpha, n_touched
+  const GsrSwitches* sw = nullptr;     // the call's switches, where an outer entry point has read them already
 };
 
 // gsr_radix_sort_pairs without its optional pieces: no second payload riding along; the number of keys is `n` itself, not a word on
@@ -413,7 +412,7 @@ static int forward_geometry(const gsr_settings* s, const gsr_gaussians* g, void*
 // the 16-byte copy - first spinning (the count is ~50 us of device time away once the frame has started), then with short sleeps,
 // and gives up loudly after GSR_COUNT_TIMEOUT_S seconds (default 120; a device fault aborts the process long before).
 static int64_t wait_for_count(uint32_t* host, hipEvent_t ev, bool early_word) {
-  static const double limit_s = getenv("GSR_COUNT_TIMEOUT_S") ? atof(getenv("GSR_COUNT_TIMEOUT_S")) : 120.0;
+  static const double limit_s = gsr_read_switches(GSR_SW_COUNT_TIMEOUT).count_timeout_s;
   volatile unsigned long long* w = (volatile unsigned long long*)(host + 8);
   unsigned long long v = 0;
   struct timespec t0;
@@ -524,6 +523,7 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
   if ((rc = check_extras(ex))) return rc;
   GsrFrame F;
   if ((rc = frame_view(F, s, g->P, num_rendered, geometry_state, binning_state, binning_bytes, image_state, image_bytes))) return rc;
+  const GsrSwitches sw = c.sw ? *c.sw : gsr_read_switches(GSR_SW_RENDER);
   uint32_t* n_touched = (ex && g->P > 0) ? ex->n_touched : nullptr;
   const bool for_backward = c.for_backward, tile_local = c.tile_local, shade_late = c.shade_late;
   const hipEvent_t sh_ready = c.sh_ready;
@@ -544,11 +544,10 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
   } else {
     // (round 4) tile-local form: the emission counts the tile sort's digit histograms and clears its look-back table, the sort's
     // last pass leaves the tile ranges, the first per-tile kernel decodes them: no k_radix_hist_all, no k_finalize_bins
-    // (GSR_TILE_HIST=0: the round-3 chain, for the A/B).  The sort's head must be clear BEFORE the emission's workgroups add
+    // (gsr_plan_fused_bins; otherwise the round-3 chain).  The sort's head must be clear BEFORE the emission's workgroups add
     // to it: the projection kernel of this call did that, or (re-render on another binning state) a memset here.
-    const char* th = getenv("GSR_TILE_HIST");
-    // (the emission kernel's LDS histograms cover two passes = 16 tile bits: a frame of more than 65536 tiles takes the chain)
-    const bool fused_bins = tile_local && !(th && th[0] == '0') && gsr_tile_bits(tiles) <= 2 * GSR_RADIX_BITS;
+    static_assert(GSR_PLAN_FUSED_BINS_MAX_BITS == 2 * GSR_RADIX_BITS, "the emission kernel's LDS histograms hold two passes");
+    const bool fused_bins = gsr_plan_fused_bins(sw, tile_local, gsr_tile_bits(tiles));
     if (fused_bins && !c.sort_head &&
         (rc = gsr_check(hipMemsetAsync(bin + BL.radix_tmp, 0, GSR_RADIX_HEAD_WORDS * 4, st), "memset sort head")))
       return rc;
@@ -619,8 +618,10 @@ static int forward_render_impl(const gsr_settings* s, const gsr_gaussians* g, vo
   // all forward paths share, so a frame whose phase 2 is repeated (capacity did not hold, culled frame flagged, re-render) starts
   // from zero again and nothing is counted twice
   if (n_touched && (rc = gsr_check(hipMemsetAsync(n_touched, 0, (size_t)g->P * 4, st), "memset n_touched"))) return rc;
-  gsr_launch_render_fwd(s, F, out_color, out_invdepth, ex ? ex->out_alpha : nullptr, n_touched, n_touched ? ex->touched_T_min : 0.f,
-                        /*walk_classes=*/for_backward, status_dev, c.tile_cutoff, c.cull_applied, c.frame_tag, st);
+  float* out_alpha = ex ? ex->out_alpha : nullptr;
+  gsr_launch_render_fwd(gsr_plan_render_fwd(sw, out_alpha != nullptr, n_touched != nullptr), s, F, out_color, out_invdepth, out_alpha,
+                        n_touched, n_touched ? ex->touched_T_min : 0.f, /*walk_classes=*/for_backward, status_dev, c.tile_cutoff,
+                        c.cull_applied, c.frame_tag, st);
   if ((rc = debug_sync(s, st, "render forward"))) return rc;
   return gsr_launch_status("forward");
 }
@@ -682,10 +683,10 @@ static int forward_async_impl(const gsr_settings* s, const gsr_gaussians* g, voi
                                out_invdepth, empty, stream);
   }
   const bool late = c.defer_color && !g->colors_precomp;
-  const char* aside_str = getenv("GSR_SHADE_STREAM");      // (read per call: tests switch it inside one process)
-  const int aside_env = aside_str ? atoi(aside_str) : -1;
-  const bool want_aside = aside_env < 0 ? g->P >= 200000 : aside_env != 0;
-  c.shade_aside = (want_aside && !late && !g->colors_precomp && (g->shs || g->dc) && !s->debug) ? side_shade() : nullptr;
+  const GsrSwitches sw = gsr_read_switches(GSR_SW_ASYNC | GSR_SW_RENDER);   // (per call: tests switch them inside one process)
+  c.sw = &sw;
+  c.shade_aside =
+      gsr_plan_shade_aside(sw, g->P, late, g->colors_precomp != nullptr, g->shs || g->dc, s->debug != 0) ? side_shade() : nullptr;
   c.defer_color = late || c.shade_aside != nullptr;
   c.shade_late = c.shade_aside ? false : late;
   if (c.shade_aside) c.sh_ready = c.shade_aside->join;
@@ -917,8 +918,12 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   GsrFrame F;
   if ((rc = frame_view(F, s, g->P, num_rendered, geometry_state, binning_state, GSR_UNSIZED, image_state, GSR_UNSIZED))) return rc;
   float4* igrad = (float4*)scratch;
+  const unsigned flags_min_r = g_gsr_flags_min_r;      // (one read: the two kernels below must agree on it)
   if (F.R > 0) {
-    gsr_launch_render_bwd(s, F, dL_dcolor, dL_dinvdepth, ex ? ex->dL_dalpha : nullptr, igrad, st);
+    const float* dL_dalpha = ex ? ex->dL_dalpha : nullptr;
+    const GsrSwitches sw = gsr_read_switches(GSR_SW_BACKWARD);   // (per call: the tests switch forms inside one process)
+    gsr_launch_render_bwd(gsr_plan_render_bwd(sw, F.tiles, dL_dinvdepth != nullptr, dL_dalpha != nullptr, flags_min_r), s, F,
+                          dL_dcolor, dL_dinvdepth, dL_dalpha, igrad, st);
     if ((rc = debug_sync(s, st, "render backward"))) return rc;
   }
   GsrAdamArgs A;
@@ -926,7 +931,7 @@ static int backward_impl(const gsr_settings* s, const gsr_gaussians* g, const in
   // rows: 0 every row (dense) / 1 rows with radii > 0, no bias correction (sparse) / 2 dense, rows with instances only
   const int mode = !opt ? 0 : (opt->sparse == 1 ? 2 : (opt->sparse == 2 ? 3 : 1));
   const int groups = gsr_launch_preprocess_bwd(s, g, radii, F.geom, F.GL, igrad, (uint32_t)F.R, grads, opt ? &A : nullptr, mode,
-                                               cam_rows, ex_depth_z(ex), c.cam_only, st);
+                                               cam_rows, ex_depth_z(ex), c.cam_only, flags_min_r, st);
   if (groups < 0) {
     gsr_set_error("backward_adam needs the raw-parameter call form with dc / shs passed separately (raw_activations = 1, "
                   "dc != NULL, no colors_precomp / cov3D_precomp, every stored SH coefficient active)");

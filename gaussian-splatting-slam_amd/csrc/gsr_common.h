@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "../../include/gsr.h"
+#include "launch_plan.h"
 
 #define GSR_TILE 16                 // 16x16 pixel tiles
 #define GSR_BLOCK_CULLED 0x80000000u  // top bit of a projection workgroup's instance total (tile-local form): a prefiltered point of it was culled
@@ -294,6 +296,8 @@ extern int g_gsr_profile_on;
 // wait for the device); the entry point's final gsr_launch_status() then reports the first failing stage, not the last one.
 void gsr_note_launch_failure(const char* stage, hipError_t e);
 int gsr_launch_status(const char* what);
+// the switches of the given scopes (launch_plan.h) as the process' environment has them now
+GsrSwitches gsr_read_switches(unsigned scopes);
 #define GSR_LAUNCH(name, kern, grid, block, shmem, st, ...)                    \
   do {                                                                         \
     if (g_gsr_profile_on) gsr_prof_begin(name, st);                            \
@@ -305,6 +309,22 @@ int gsr_launch_status(const char* what);
     }                                                                          \
   } while (0)
 
+// Runtime template arguments: gsr_dispatch(f, a, b, ...) calls the generic lambda f with one std::bool_constant per bool and one
+// std::integral_constant<int, i> per GsrBelow<N>{i} (0 <= i < N), in order - `[&](auto D, auto M) { ...k<D(), M()>... }` - so that
+// a launcher writes its kernel's argument list once, whichever instantiation runs.
+template <int N> struct GsrBelow { int v; };
+template <class F> inline void gsr_dispatch(F&& f) { f(); }
+template <class F, class... R> inline void gsr_dispatch(F&& f, bool b, R... r) {
+  if (b) gsr_dispatch([&](auto... c) { f(std::true_type{}, c...); }, r...);
+  else gsr_dispatch([&](auto... c) { f(std::false_type{}, c...); }, r...);
+}
+template <class F, int N, class... R> inline void gsr_dispatch(F&& f, GsrBelow<N> i, R... r) {
+  if constexpr (N > 0) {
+    if (i.v == N - 1) gsr_dispatch([&](auto... c) { f(std::integral_constant<int, N - 1>{}, c...); }, r...);
+    else gsr_dispatch(f, GsrBelow<N - 1>{i.v}, r...);
+  }
+}
+
 // The launchers of the kernel files, declared ONCE and with parameter names: the kernel files and api.hip see the same prototype.
 // preprocess.hip
 void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, int32_t* radii, char* geom, const GsrGeomLayout& L,
@@ -315,7 +335,8 @@ void gsr_launch_shade(const gsr_settings* s, const gsr_gaussians* g, char* geom,
 void gsr_launch_sum_tiles(int P, const char* geom, const GsrGeomLayout& L, uint32_t* meta, hipStream_t st);
 int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii, const char* geom,
                               const GsrGeomLayout& L, const float4* igrad, uint32_t cap, const gsr_grads* gr,
-                              const GsrAdamArgs* adam, int adam_mode, float* cam_rows, bool depth_z, bool cam_only, hipStream_t st);
+                              const GsrAdamArgs* adam, int adam_mode, float* cam_rows, bool depth_z, bool cam_only,
+                              unsigned flags_min_r, hipStream_t st);
 void gsr_launch_adam_culled_rows(int P, int sh_stride, const char* geom, const GsrGeomLayout& L, const GsrAdamArgs& A, uint32_t cap,
                                  hipStream_t st);
 size_t gsr_cam_scratch_floats(int P);
@@ -333,12 +354,13 @@ void gsr_launch_tile_depth_sort(const GsrFrame& F, bool for_backward, bool range
 // render.hip
 // walk_classes: file every tile under its walk class (a backward follows); status_dst: the caller's pinned status slot as the device
 // sees it, or nullptr; tile_cutoff: updated per tile, and with cull_applied the frame was counted and emitted with it
-void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_color, float* out_invdepth, float* out_alpha,
-                           uint32_t* n_touched, float touch_T_min, bool walk_classes, uint32_t* status_dst, uint32_t* tile_cutoff,
-                           bool cull_applied, uint32_t frame_tag, hipStream_t st);
+// (out_alpha / n_touched, dL_dinvdepth / dL_dalpha: present exactly where the plan says so)
+void gsr_launch_render_fwd(const GsrRenderFwdPlan& plan, const gsr_settings* s, const GsrFrame& F, float* out_color,
+                           float* out_invdepth, float* out_alpha, uint32_t* n_touched, float touch_T_min, bool walk_classes,
+                           uint32_t* status_dst, uint32_t* tile_cutoff, bool cull_applied, uint32_t frame_tag, hipStream_t st);
 void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* pairs, hipStream_t st);
-void gsr_launch_render_bwd(const gsr_settings* s, const GsrFrame& F, const float* dL_dpix, const float* dL_dinvdepth,
-                           const float* dL_dalpha, float4* igrad, hipStream_t st);
+void gsr_launch_render_bwd(const GsrRenderBwdPlan& plan, const gsr_settings* s, const GsrFrame& F, const float* dL_dpix,
+                           const float* dL_dinvdepth, const float* dL_dalpha, float4* igrad, hipStream_t st);
 
 // sort_scan.hip
 // Exclusive (inclusive=0) or inclusive scan of n u32 values: out[i] = scan(src[idx ? idx[i] : i]).
@@ -441,11 +463,8 @@ __device__ __forceinline__ uint32_t gsr_eff_n(const uint32_t* __restrict__ n_dev
 // instance count, which all of them read anyway.  Small frames keep the round-3 form (zero records written and read): there the
 // projection backward is one partial round of workgroups whose length is a thread's chain of dependent memory round trips, and the
 // flags are one more link of it (100 k Gaussians / 1.3 M instances: +7 .. 13 us on a 61 us kernel, nothing gained elsewhere).
-#ifndef GSR_FLAGS_MIN_R
-#define GSR_FLAGS_MIN_R 2500000u
-#endif
-// (the threshold travels as a launch argument: tests set it to 0 / ~0 through gsr_debug_set_flags_min_r to force either form)
-extern unsigned g_gsr_flags_min_r;
+// (GSR_FLAGS_MIN_R, launch_plan.h; the threshold travels as a launch argument, the same one to both backward kernels of a step:
+// tests set it to 0 / ~0 through gsr_debug_set_flags_min_r to force either form)
 __device__ __forceinline__ bool gsr_flags_on(const uint32_t* __restrict__ n_dev, uint32_t cap, uint32_t min_r) {
   return gsr_eff_n(n_dev, cap) >= min_r;
 }

@@ -1423,7 +1423,7 @@ void gsr_launch_preprocess_fwd(const gsr_settings* s, const gsr_gaussians* g, in
 int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, const int32_t* radii,
                               const char* geom, const GsrGeomLayout& L, const float4* igrad, uint32_t cap,
                               const gsr_grads* gr, const GsrAdamArgs* adam, int adam_mode, float* cam_rows,
-                              bool depth_z, bool cam_only, hipStream_t st) {
+                              bool depth_z, bool cam_only, unsigned flags_min_r, hipStream_t st) {
   const int P = g->P;
   size_t lds = 0;
   GsrAdamArgs A;
@@ -1444,54 +1444,38 @@ int gsr_launch_preprocess_bwd(const gsr_settings* s, const gsr_gaussians* g, con
             (cam_only || (gr->dL_dshs ? (((uintptr_t)gr->dL_dshs & 15) == 0) : gr->dL_ddc != nullptr));
     if (stage) lds = (lds / 256) * GSR_BWD_PLAIN_BT;
   }
-#define GSR_PRE_BWD_ARGS                                                                                              \
-  P, s->sh_degree, g->sh_coeffs, g->means3D, g->dc, g->shs, g->colors_precomp, g->opacities, g->scales, g->rotations, \
-      g->cov3D_precomp, s->scale_modifier, s->viewmatrix, s->projmatrix, s->campos, s->image_width, s->image_height,  \
-      s->tanfovx, s->tanfovy, s->antialiasing, (int)g->raw_activations, radii, (const uint8_t*)(geom + L.clamped),     \
-      (const uint32_t*)(geom + L.tiles_touched), (const uint32_t*)(geom + L.slot_start), igrad,                       \
-      (const uint32_t*)(geom + L.meta) + 2, cap, gr->dL_dmeans3D,                                                      \
-      gr->dL_dmeans2D, gr->dL_ddc, gr->dL_dshs, gr->dL_dcolors, gr->dL_dopacities, gr->dL_dscales, gr->dL_drotations, \
-      gr->dL_dcov3D, gr->xyz_gradient_accum, gr->denom, gr->max_radii2D, A, g_gsr_flags_min_r, cam_rows
-#define GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, ZD_, CO_, NAME)                                                              \
-  do {                                                                                                                 \
-    if (lds > 48 * 1024)                                                                                               \
-      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_, CO_>,                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    GSR_LAUNCH(NAME, (k_preprocess_bwd<ST, AD, BT_, CAM_, ZD_, CO_>),                                                  \
-               dim3((P + BT_ - 1) / BT_), dim3(BT_), ST ? lds : 0, st, GSR_PRE_BWD_ARGS);                              \
-    groups = (P + BT_ - 1) / BT_;                                                                                      \
-  } while (0)
-  // (z-depth: the ZD instantiations; without it every launch below is the one it was)
-#define GSR_PRE_BWD_KC(ST, AD, BT_, CAM_, CO_, NAME)                                                                   \
-  do {                                                                                                                 \
-    if (depth_z) GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, true, CO_, NAME);                                                   \
-    else GSR_PRE_BWD_KZ(ST, AD, BT_, CAM_, false, CO_, NAME);                                                          \
-  } while (0)
-#define GSR_PRE_BWD_K(ST, AD, BT_, CAM_, NAME) GSR_PRE_BWD_KC(ST, AD, BT_, CAM_, false, NAME)
-  int groups = 0;
-#define GSR_PRE_BWD(ST, AD, BT_) GSR_PRE_BWD_K(ST, AD, BT_, false, AD ? "preprocess_bwd_adam" : "preprocess_bwd")
+  // which of the six forms (plain / camera / camera-only / the three folded optimizer steps), with the staged and the z-depth
+  // variant of each: ADAM, CAM, CAM_ONLY and the rows per workgroup follow from it
+  int form;
   if (cam_only) {
     if (adam || !cam_rows) return -1;
-    if (stage) GSR_PRE_BWD_KC(true, 0, GSR_BWD_PLAIN_BT, true, true, "preprocess_bwd_cam_only");
-    else GSR_PRE_BWD_KC(false, 0, 256, true, true, "preprocess_bwd_cam_only");
+    form = 2;
   } else if (cam_rows) {
     if (adam) return -1;
-    if (stage) GSR_PRE_BWD_K(true, 0, GSR_BWD_PLAIN_BT, true, "preprocess_bwd_cam");
-    else GSR_PRE_BWD_K(false, 0, 256, true, "preprocess_bwd_cam");
-  } else if (!adam) {
-    if (stage) GSR_PRE_BWD(true, 0, GSR_BWD_PLAIN_BT); else GSR_PRE_BWD(false, 0, 256);
-  } else if (adam_mode == 2) {
-    if (stage) GSR_PRE_BWD(true, 2, GSR_BWD_ADAM_BT); else GSR_PRE_BWD(false, 2, 256);
-  } else if (adam_mode == 3) {
-    if (stage) GSR_PRE_BWD(true, 3, GSR_BWD_ADAM_BT); else GSR_PRE_BWD(false, 3, 256);
+    form = 1;
   } else {
-    if (stage) GSR_PRE_BWD(true, 1, GSR_BWD_ADAM_BT); else GSR_PRE_BWD(false, 1, 256);
+    form = !adam ? 0 : (adam_mode == 2 ? 4 : (adam_mode == 3 ? 5 : 3));
   }
-#undef GSR_PRE_BWD
-#undef GSR_PRE_BWD_K
-#undef GSR_PRE_BWD_KC
-#undef GSR_PRE_BWD_KZ
-#undef GSR_PRE_BWD_ARGS
+  static const char* const names[6] = {"preprocess_bwd", "preprocess_bwd_cam", "preprocess_bwd_cam_only",
+                                       "preprocess_bwd_adam", "preprocess_bwd_adam", "preprocess_bwd_adam"};
+  int groups = 0;
+  gsr_dispatch([&](auto ST, auto FORM, auto ZD) {
+    constexpr int AD = FORM() < 3 ? 0 : FORM() - 2;
+    constexpr bool CAM = FORM() == 1 || FORM() == 2, CO = FORM() == 2;
+    constexpr int BT = !ST() ? 256 : (AD ? GSR_BWD_ADAM_BT : GSR_BWD_PLAIN_BT);
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)k_preprocess_bwd<ST(), AD, BT, CAM, ZD(), CO>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    GSR_LAUNCH(names[FORM()], (k_preprocess_bwd<ST(), AD, BT, CAM, ZD(), CO>), dim3((P + BT - 1) / BT), dim3(BT), ST() ? lds : 0, st,
+               P, s->sh_degree, g->sh_coeffs, g->means3D, g->dc, g->shs, g->colors_precomp, g->opacities, g->scales, g->rotations,
+               g->cov3D_precomp, s->scale_modifier, s->viewmatrix, s->projmatrix, s->campos, s->image_width, s->image_height,
+               s->tanfovx, s->tanfovy, s->antialiasing, (int)g->raw_activations, radii, (const uint8_t*)(geom + L.clamped),
+               (const uint32_t*)(geom + L.tiles_touched), (const uint32_t*)(geom + L.slot_start), igrad,
+               (const uint32_t*)(geom + L.meta) + 2, cap, gr->dL_dmeans3D, gr->dL_dmeans2D, gr->dL_ddc, gr->dL_dshs,
+               gr->dL_dcolors, gr->dL_dopacities, gr->dL_dscales, gr->dL_drotations, gr->dL_dcov3D, gr->xyz_gradient_accum,
+               gr->denom, gr->max_radii2D, A, flags_min_r, cam_rows);
+    groups = (P + BT - 1) / BT;
+  }, stage, GsrBelow<6>{form}, depth_z);
   return groups;
 }
 

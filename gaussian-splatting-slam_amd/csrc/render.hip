@@ -1454,9 +1454,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BWD_MX_WAVES
   }
 }
 
-void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_color, float* out_invdepth, float* out_alpha,
-                           uint32_t* n_touched, float touch_T_min, bool walk_classes, uint32_t* status_dst, uint32_t* tile_cutoff,
-                           bool cull_applied, uint32_t frame_tag, hipStream_t st) {
+void gsr_launch_render_fwd(const GsrRenderFwdPlan& plan, const gsr_settings* s, const GsrFrame& F, float* out_color,
+                           float* out_invdepth, float* out_alpha, uint32_t* n_touched, float touch_T_min, bool walk_classes,
+                           uint32_t* status_dst, uint32_t* tile_cutoff, bool cull_applied, uint32_t frame_tag, hipStream_t st) {
   const int tiles = F.tiles, grid_x = F.gx;
   const uint2* ranges = F.ranges();
   const uint32_t* point_list = F.point_list();
@@ -1472,28 +1472,12 @@ void gsr_launch_render_fwd(const gsr_settings* s, const GsrFrame& F, float* out_
   uint32_t* walk_list = walk_cnt ? (uint32_t*)(F.img + F.IL.walk_list) : nullptr;
   uint32_t* walk_of_tile = walk_cnt ? (uint32_t*)(F.img + F.IL.walk_of_tile) : nullptr;
   const uint32_t touch_cap = (uint32_t)F.R;
-  // cut-off margin of the depth-truncated lists: 1.75 x the entries a tile needed + 48 (measured, profiles/r04_tile_cull.txt: 1.25 x + 16
-  // flags 54 % of the frames of a run that trains from scratch, 1.5 x + 32 1 %, 1.75 x + 48 none; C3 and the 2 x splats scene)
-  unsigned mq8 = 448, madd = 48;
-  if (const char* mg = getenv("GSR_CULL_MARGIN")) sscanf(mg, "%u,%u", &mq8, &madd);
-  // GSR_FWD_MASK=1 selects the masked walk (measured: 0.208 against 0.179 ms at C3, profiles/r04_fwd_mask_ab.txt - not the default)
-  const char* mk = getenv("GSR_FWD_MASK");          // (read per call: the tests switch inside one process)
-  const bool masked = mk && !strcmp(mk, "1");
-#define GSR_FWD_LAUNCH(M, A, C)                                                                                               \
-  GSR_LAUNCH("render_fwd", (k_render_fwd<false, M, A, C>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
-             ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,        \
-             status_dst, tile_cutoff, culled_any, frame_tag, meta, mq8, madd, walk_cnt, walk_list, walk_of_tile,                  \
-             out_alpha, n_touched, touch_T_min, touch_cap)
-#define GSR_FWD_LAUNCH_A(M, C)                                                         \
-  do { if (out_alpha) GSR_FWD_LAUNCH(M, true, C); else GSR_FWD_LAUNCH(M, false, C); } while (0)
-  // n_touched (gsr_render_extras): the TOUCH instantiations; without it every launch below is the one it was
-  if (n_touched) {
-    if (masked) GSR_FWD_LAUNCH_A(true, true); else GSR_FWD_LAUNCH_A(false, true);
-  } else {
-    if (masked) GSR_FWD_LAUNCH_A(true, false); else GSR_FWD_LAUNCH_A(false, false);
-  }
-#undef GSR_FWD_LAUNCH_A
-#undef GSR_FWD_LAUNCH
+  gsr_dispatch([&](auto M, auto A, auto C) {
+    GSR_LAUNCH("render_fwd", (k_render_fwd<false, M(), A(), C()>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height,
+               grid_x, ranges, point_list, rec, s->bg, out_color, out_invdepth, final_T, n_contrib, (uint32_t*)nullptr, status_src,
+               status_dst, tile_cutoff, culled_any, frame_tag, meta, plan.mq8, plan.madd, walk_cnt, walk_list, walk_of_tile,
+               out_alpha, n_touched, touch_T_min, touch_cap);
+  }, plan.masked, plan.alpha, plan.touch);
 }
 
 void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* pairs, hipStream_t st) {
@@ -1510,8 +1494,8 @@ void gsr_launch_count_pairs(const gsr_settings* s, const GsrFrame& F, uint32_t* 
                      (float*)nullptr, (uint32_t*)nullptr, 0.f, 0u);
 }
 
-void gsr_launch_render_bwd(const gsr_settings* s, const GsrFrame& F, const float* dL_dpix, const float* dL_dinvdepth,
-                           const float* dL_dalpha, float4* igrad, hipStream_t st) {
+void gsr_launch_render_bwd(const GsrRenderBwdPlan& plan, const gsr_settings* s, const GsrFrame& F, const float* dL_dpix,
+                           const float* dL_dinvdepth, const float* dL_dalpha, float4* igrad, hipStream_t st) {
   const int tiles = F.tiles, grid_x = F.gx;
   const uint2* ranges = F.ranges();
   const uint32_t* point_list = F.point_list();
@@ -1522,65 +1506,27 @@ void gsr_launch_render_bwd(const gsr_settings* s, const GsrFrame& F, const float
   const uint32_t* slot_of_pos = (const uint32_t*)(F.bin + (gsr_tile_sort_result_buffer(tiles) ? F.BL.val_b : F.BL.val_a));
   const uint32_t* n_dev = F.n_dev();
   const uint32_t cap = (uint32_t)F.R;
-  const uint32_t* walk_cnt = F.walk_cnt();
+  const uint32_t* walk_cnt = plan.walk ? F.walk_cnt() : nullptr;          // nullptr: tiles in index order
   const uint32_t* walk_list = (const uint32_t*)(F.img + F.IL.walk_list);
   const uint32_t* walk_of_tile = (const uint32_t*)(F.img + F.IL.walk_of_tile);
-  // GSR_BWD_LPT=0: tiles in index order (the A/B of the walk classes, profiles/r04_bwd_lpt_ab.txt)
-  if (const char* lp = getenv("GSR_BWD_LPT")) {
-    if (lp[0] == '0') walk_cnt = nullptr;
+  const int p1 = plan.prio[0], p2 = plan.prio[1], p3 = plan.prio[2];
+  if (plan.form == GsrRenderBwdPlan::TILE_MX) {
+    gsr_dispatch([&](auto D, auto A) {
+      GSR_LAUNCH("render_bwd", (k_render_bwd_tile_mx<D(), A()>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height,
+                 grid_x, ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,
+                 p1, p2, p3, plan.flags_min_r, dL_dalpha);
+    }, plan.depth, plan.alpha);
+  } else if (plan.form == GsrRenderBwdPlan::TILE) {
+    gsr_dispatch([&](auto D, auto M, auto A) {
+      GSR_LAUNCH("render_bwd", (k_render_bwd_tile<D(), M(), A()>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height,
+                 grid_x, ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,
+                 p1, p2, p3, walk_cnt, walk_list, walk_of_tile, plan.flags_min_r, dL_dalpha);
+    }, plan.depth, plan.mask, plan.alpha);
+  } else {
+    gsr_dispatch([&](auto D, auto A) {
+      GSR_LAUNCH("render_bwd", (k_render_bwd<D(), A()>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x,
+                 ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,
+                 walk_cnt, walk_list, walk_of_tile, plan.flags_min_r, dL_dalpha);
+    }, plan.depth, plan.alpha);
   }
-  // One wave per tile needs enough tiles to keep 1024 SIMDs busy: below ~6 tiles per SIMD (720p: 3600 tiles) the four-waves-per-tile form
-  // (same results up to summation order inside a tile) has the shorter critical path.  GSR_BWD_FORM=quad|tile forces one.
-  const char* form = getenv("GSR_BWD_FORM");          // (read per call: the tests switch forms inside one process)
-  const char* mk = getenv("GSR_BWD_MASK");
-  const bool quad = form ? !strcmp(form, "quad") : tiles < 6000;
-  // (the walk order pays where a launch runs in several rounds of resident workgroups; a grid that is resident at once - 256 CUs x 5
-  // four-wave workgroups - has no late starters to reorder: 256 tiles 0.054 -> 0.056 ms with it, 3600 tiles 0.166 -> 0.150)
-  // ... nor does a launch of many rounds gain what its record gathers lose in locality (4K, 32 400 tiles = 6.3 rounds of one-wave
-  // workgroups: 1.381 -> 1.407 ms with the walk order); GSR_BWD_LPT=1 forces the order for any grid
-  if (tiles <= 1280 || tiles > 24000) {
-    const char* lp = getenv("GSR_BWD_LPT");
-    if (!(lp && lp[0] == '1')) walk_cnt = nullptr;
-  }
-  const bool mask = !(mk && !strcmp(mk, "0"));
-  // issue priority for long walks: thresholds from the frame itself (default), GSR_BWD_PRIO="t1,t2,t3" fixes them, "0" = none
-  int p1 = -1, p2 = -1, p3 = -1;
-  if (const char* pr = getenv("GSR_BWD_PRIO")) {
-    if (sscanf(pr, "%d,%d,%d", &p1, &p2, &p3) != 3) p1 = p2 = p3 = -2;
-  }
-  // GSR_BWD_REDUCE=mfma (opt-in, measured SLOWER: 0.52 against 0.42 ms at C3, profiles/r04_bwd_mx_ab.txt) takes the sums with
-  // v_mfma_f32_16x16x4_f32 (k_render_bwd_tile_mx); the default is the v_permlane / DPP halving tree
-  const char* red = getenv("GSR_BWD_REDUCE");
-  const bool mx = mask && red && !strcmp(red, "mfma");
-  // dL_dalpha (gsr_render_extras): the ALPHA instantiations; without it every launch below is the one it was
-#define GSR_BWD_BY_DA(LAUNCH, ...) do { if (dL_dalpha) LAUNCH(__VA_ARGS__, true); else LAUNCH(__VA_ARGS__, false); } while (0)
-  if ((!quad || (form && !strcmp(form, "tile"))) && mx) {
-#define GSR_BWD_MX_LAUNCH(D, A)                                                                                                   \
-  GSR_LAUNCH("render_bwd", (k_render_bwd_tile_mx<D, A>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x, \
-             ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, \
-             g_gsr_flags_min_r, dL_dalpha)
-    if (dL_dinvdepth) GSR_BWD_BY_DA(GSR_BWD_MX_LAUNCH, true); else GSR_BWD_BY_DA(GSR_BWD_MX_LAUNCH, false);
-#undef GSR_BWD_MX_LAUNCH
-    return;
-  }
-  if (!quad || (form && !strcmp(form, "tile"))) {
-#define GSR_BWD_TILE_LAUNCH(D, M, A)                                                                                       \
-  GSR_LAUNCH("render_bwd", (k_render_bwd_tile<D, M, A>), dim3(tiles), dim3(64), 0, st, s->image_width, s->image_height, grid_x, \
-             ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap, p1, p2, p3, \
-             walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r, dL_dalpha)
-    if (dL_dinvdepth) {
-      if (mask) GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, true, true); else GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, true, false);
-    } else {
-      if (mask) GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, false, true); else GSR_BWD_BY_DA(GSR_BWD_TILE_LAUNCH, false, false);
-    }
-#undef GSR_BWD_TILE_LAUNCH
-    return;
-  }
-#define GSR_BWD_QUAD_LAUNCH(D, A)                                                                                    \
-  GSR_LAUNCH("render_bwd", (k_render_bwd<D, A>), dim3(tiles), dim3(256), 0, st, s->image_width, s->image_height, grid_x, \
-             ranges, point_list, rec, s->bg, final_T, n_contrib, dL_dpix, dL_dinvdepth, slot_of_pos, igrad, n_dev, cap,    \
-             walk_cnt, walk_list, walk_of_tile, g_gsr_flags_min_r, dL_dalpha)
-  if (dL_dinvdepth) GSR_BWD_BY_DA(GSR_BWD_QUAD_LAUNCH, true); else GSR_BWD_BY_DA(GSR_BWD_QUAD_LAUNCH, false);
-#undef GSR_BWD_QUAD_LAUNCH
-#undef GSR_BWD_BY_DA
 }

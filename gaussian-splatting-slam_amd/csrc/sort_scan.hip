@@ -464,8 +464,7 @@ int gsr_radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1,
                          int bits, uint32_t* tmp, hipStream_t st, uint32_t* w0, uint32_t* w1, const uint32_t* n_dev,
                          bool head_zeroed, uint32_t* fail_flags, bool hist_counted, uint2* ranges_enc) {
   if (n == 0 || bits <= 0) return 0;
-  const char* force_env = getenv("GSR_TEST_FORCE_LOOKBACK_TIMEOUT");      // (read per call: a test switches it inside one process)
-  const uint32_t force = (force_env && force_env[0] == '1') ? 1u : 0u;
+  const uint32_t force = gsr_read_switches(GSR_SW_SORT).force_lookback_timeout ? 1u : 0u;   // (per call: a test switches it inside one process)
   const uint32_t nblk = (uint32_t)gsr_radix_blocks(n);
   const int subtiles = gsr_radix_subtiles(n);
   const int passes = gsr_radix_passes(bits);

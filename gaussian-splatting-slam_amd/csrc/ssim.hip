@@ -87,9 +87,8 @@ static inline unsigned ssim_grid(int gx, int gy, int planes, int tpw) {
 }
 // tiles per workgroup of the forward: the pipeline pays once the launch runs in several rounds of resident workgroups
 static inline int ssim_fwd_tpw(int gx, int gy, int planes) {
-  static const int forced = getenv("GSR_SSIM_TPW") ? atoi(getenv("GSR_SSIM_TPW")) : 0;
-  if (forced > 0) return forced;
-  return (long long)gx * gy * planes >= 4096 ? 2 : 1;
+  static const GsrSwitches sw = gsr_read_switches(GSR_SW_SSIM);      // (once per process)
+  return gsr_plan_ssim_tpw(sw, gx, gy, planes);
 }
 
 // `partials` != NULL: the kernel also reduces sum(ssim) and sum(|img1-img2|) over its tile into partials[2*block .. +1]
