@@ -329,6 +329,19 @@ EXPORTS = {
     "gsr_ransac_feature_matching": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                               C.c_int32, C.c_float, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.POINTER(gsr_ransac_debug), C.c_void_p]),
+    # w, h, image, channels, u8_out, box_out, stream
+    "gsr_orb_prepare": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_orb_cells": (C.c_int64, [C.c_int32, C.c_int32]),
+    # w, h, u8, mask, threshold, per_cell, slots, stream
+    "gsr_orb_detect": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # w, h, u8, box, M, keypoints, angle_bin, moments, descriptors, stream
+    "gsr_orb_describe": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gsr_orb_pattern": (C.c_int, [C.c_void_p]),      # out: HOST int8 [30720]
+    # Q, query, N, db, idx_out, best_out, second_out, stream
+    "gsr_hamming_match": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    # Q, query, N, db, K, segments, max_distance, ratio, votes, stream
+    "gsr_hamming_vote": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float,
+                                   C.c_void_p, C.c_void_p]),
     # layout (host), data + bytes, T_dev, min_y, max_range2, skip_nans, out_points, out_colors, out_index, cap, count_dev,
     # workspace + bytes, stream
     "gsr_pc2_decode_workspace_bytes": (C.c_size_t, [C.c_int64]),

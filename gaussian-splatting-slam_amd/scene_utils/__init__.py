@@ -28,3 +28,5 @@ from .odometry import OdometryLevel, OdometryResult, prepare_odometry_level, odo
     camera_after_odometry
 from .posegraph import PoseGraph, PoseGraphResult, information_from_point_clouds
 from .tsdf import TSDFVolume, fuse_views, weld_triangles
+from .features2d import OrbFeatures, PlaceEntry, PlaceDatabase, detect_orb, match_descriptors, hamming_match, keypoint_points, \
+    relative_pose_from_features, loop_closure_edge, orb_prepare, orb_detect, orb_describe

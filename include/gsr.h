@@ -69,6 +69,8 @@ extern "C" {
  *    gsr_debug_slot_views: the emission slot of every list position, for tests that read the backward's gradient records;
  *    gsr_tsdf_volume, gsr_tsdf_frame, gsr_tsdf_touch, gsr_tsdf_integrate, gsr_tsdf_extract_workspace_bytes, gsr_tsdf_extract_points,
  *    gsr_tsdf_extract_triangles: depth frames fused into a block-sparse TSDF volume, out as a cloud and a mesh (additions only);
+ *    gsr_orb_cells, gsr_orb_prepare, gsr_orb_detect, gsr_orb_describe, gsr_orb_pattern, gsr_hamming_match, gsr_hamming_vote: FAST
+ *    corners, steered BRIEF descriptors and Hamming matching for place recognition (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -1075,6 +1077,85 @@ int gsr_ransac_feature_matching(int64_t Ps, const float* source /*[Ps,3]*/, int6
                                 const int32_t* pairs /*[M,2]*/, float max_distance, int32_t ransac_n, float edge_length_threshold,
                                 uint64_t seed, int64_t t0, int64_t n, gsr_ransac_best* best /*device, in/out*/, void* workspace,
                                 size_t workspace_bytes, const gsr_ransac_debug* debug /*HOST struct or NULL*/, void* stream);
+
+/* ---- sparse image features for place recognition (csrc/orb.hip): FAST-9 corners, a 256-bit BRIEF
+ * descriptor steered by the intensity centroid, brute-force Hamming matching.  After the quantisation every step is integer
+ * arithmetic (one float64 atan2 of two integers aside): every output is a function of the input alone - no global atomics in the
+ * image kernels, no float atomics anywhere, the same bits on every run.  This is not OpenCV's ORB: the sampling pattern is the
+ * library's own (tools/make_orb_pattern.py), so the descriptors are not interchangeable with OpenCV's. ---- */
+#define GSR_ORB_CELL 32          /* a workgroup of the detector owns one 32 x 32 cell of pixels */
+#define GSR_ORB_BORDER 17        /* a keypoint has 17 <= x < w - 17, 17 <= y < h - 17: disc 15 + box 2 */
+#define GSR_ORB_BINS 30          /* orientation bins of 12 degrees */
+#define GSR_ORB_PER_CELL_MAX 16
+#define GSR_HAMMING_NONE 257     /* "no such row": larger than any distance of 256-bit words */
+
+/* Quantised planes of an image.  image: [3,h,w] planar with channels = 3 - the intensity is the odometry's I = ((r + g) + b) / 3,
+ * each step rounded to float32 - or [h,w] with channels = 1 (I as given).
+ *   u8[y][x]  = clamp(floor(fmaf(255, I, 0.5)), 0, 255): ONE fused multiply-add in float32 (a float64 evaluation of 255 I + 0.5
+ *               rounded once to float32 gives the same value), a NaN counts as 0, +inf as 255, -inf as 0;
+ *   box[y][x] = the sum of u8 over the 5 x 5 window centred on (x, y), coordinates clamped to the image (replicated border);
+ *               uint16, at most 6375.
+ * Errors before any launch: a side < 1 or w h > 2^30 - 1, a NULL pointer, channels not 1 or 3: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_orb_prepare(int32_t w, int32_t h, const float* image, int32_t channels, uint8_t* u8_out /*[h,w]*/,
+                    uint16_t* box_out /*[h,w]*/, void* stream);
+
+/* ceil(w / 32) ceil(h / 32): the cells of gsr_orb_detect, row-major (cell = cy * ceil(w / 32) + cx); 0 for a bad size. */
+int64_t gsr_orb_cells(int32_t w, int32_t h);
+
+/* FAST-9 corners of the u8 plane.  Circle of pixel p = (x, y), clockwise from the top with y down: c[0 .. 15] at the offsets
+ * (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).
+ *   score(p) = max over s = 0 .. 15 of max( min_{k<9} (c[(s+k) % 16] - p), min_{k<9} (p - c[(s+k) % 16]) )   (integers);
+ *   p qualifies iff 17 <= x < w - 17 and 17 <= y < h - 17 and (mask == NULL or mask[y][x] > 0);
+ *   p is a corner iff it qualifies and score(p) > threshold; S(p) = score(p) for a corner, 0 for every other pixel;
+ *   3 x 3 non-maximum suppression: a corner p survives iff for each of its 8 neighbours q: S(p) > S(q), or S(p) == S(q) and p
+ *   comes before q in raster order (y, then x).
+ * Every cell keeps its per_cell best survivors, ordered by score descending, then raster order ascending, in its own slots:
+ * slots[cell][r] = (x, y, score) int32, r = 0 .. per_cell - 1; an empty slot is (0, 0, 0).  Every slot is written.  An image with
+ * a side < 35 has no pixel that qualifies: all slots empty.
+ * Errors before the launch: a bad size, NULL u8 / slots, threshold outside 0 .. 254, per_cell outside 1 .. 16, more than 65535
+ * rows of cells: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_orb_detect(int32_t w, int32_t h, const uint8_t* u8 /*[h,w]*/, const float* mask /*[h,w] or NULL*/, int32_t threshold,
+                   int32_t per_cell, int32_t* slots /*[cells,per_cell,3]*/, void* stream);
+
+/* Orientation and descriptor of M keypoints (x, y, score), e.g. the slots of gsr_orb_detect as they are.  A row with score <= 0 or
+ * outside the border of 17 is skipped: angle_bin -1, moments 0, descriptor 0 - nothing is read out of bounds.  Otherwise
+ *   m10 = sum dx u8[y+dy][x+dx],  m01 = sum dy u8[y+dy][x+dx]  over the disc dx^2 + dy^2 <= 15^2   (int32, exact);
+ *   angle_bin = floor(atan2(m01, m10) / (2 pi / 30) + 0.5) mod 30 in float64 (m10 = m01 = 0: bin 0);
+ *   bit b of the descriptor = box[y + y1][x + x1] < box[y + y2][x + x2] with (x1, y1, x2, y2) = pattern[angle_bin][b];
+ *   descriptors[k][b / 32] holds bit b at position b % 32.
+ * moments: [M,2] = (m10, m01), or NULL.  M = 0 is legal.
+ * Errors before the launch: a bad size, NULL u8 / box, M outside [0, 2^30 - 1], with M > 0 a NULL keypoints / angle_bin /
+ * descriptors: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_orb_describe(int32_t w, int32_t h, const uint8_t* u8, const uint16_t* box, int64_t M, const int32_t* keypoints /*[M,3]*/,
+                     int32_t* angle_bin /*[M]*/, int32_t* moments /*[M,2] or NULL*/, int32_t* descriptors /*[M,8]*/, void* stream);
+
+/* The sampling pattern the library was built with, int8 [30][256][4] = (x1, y1, x2, y2) per bin and bit, into HOST memory `out`
+ * (30720 bytes).  256 pairs drawn iid from a Gaussian (sigma = 31 / 5) by a counter-based generator with a fixed seed, a draw
+ * rejected outside the disc of radius 15; each pair rotated by the bin angles 2 pi k / 30 as (x cos - y sin, x sin + y cos) and
+ * rounded to nearest; a pair is accepted only if all its rounded points stay within radius 15, otherwise it is drawn again
+ * (tools/make_orb_pattern.py writes csrc/orb_pattern.inc).  Needs no device. */
+int gsr_orb_pattern(int8_t* out /*HOST [30720]*/);
+
+/* Brute-force Hamming matching of 256-bit rows (8 x int32, 16-byte aligned).  For every query row i over the database rows j in
+ * ascending order: d = popcount(q_i xor t_j); idx_out[i] = the row of the smallest d, among equal distances the lowest row;
+ * best_out[i] = that d; second_out[i] = the second smallest d of the multiset (a duplicate of the best row: second == best).
+ * Where there is no such row (N = 0, or N = 1 for the second): idx -1, distance GSR_HAMMING_NONE.  Q = 0 or N = 0 is legal.
+ * The database passes through LDS in tiles; distances use the hardware popcount.
+ * Errors before the launch: Q or N outside [0, 2^30 - 1], a NULL or misaligned query (Q > 0) / db (N > 0), with Q > 0 a NULL
+ * output: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_hamming_match(int64_t Q, const int32_t* query /*[Q,8]*/, int64_t N, const int32_t* db /*[N,8]*/, int32_t* idx_out /*[Q]*/,
+                      int32_t* best_out /*[Q]*/, int32_t* second_out /*[Q]*/, void* stream);
+
+/* The keyframe-database query: db holds the descriptors of K frames one behind the other, frame k = rows [segments[k],
+ * segments[k+1]) (device int32 [K+1], ascending; a value outside 0 .. N is clamped, so nothing is read past the database).
+ * votes[k] = the number of query rows whose match INSIDE frame k (best, second as gsr_hamming_match defines them over the
+ * segment alone) has best <= max_distance and (float)best < ratio * (float)second, the product rounded to float32 - with a
+ * segment of one row second is GSR_HAMMING_NONE, an empty segment gets no vote.  One grid row per frame; the counts are int32
+ * sums (cleared by the call), the same on every run.  Q = 0, N = 0 or K = 0 is legal.
+ * Errors before any launch: sizes as gsr_hamming_match, K outside [0, 65535], with K > 0 a NULL segments / votes, max_distance
+ * < 0, ratio negative or NaN: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_hamming_vote(int64_t Q, const int32_t* query /*[Q,8]*/, int64_t N, const int32_t* db /*[N,8]*/, int64_t K,
+                     const int32_t* segments /*[K+1]*/, int32_t max_distance, float ratio, int32_t* votes /*[K]*/, void* stream);
 
 /* ---- sensor_msgs/PointCloud2 on the device (csrc/pointcloud2.hip): what the reference's
  * process_pointcloud / read_pointcloud do point by point with `struct` in Python before a cloud reaches Open3D ---- */
