@@ -429,7 +429,34 @@ int gsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, u
 /* Introspection for tests / bench: DEVICE pointers into the opaque state buffers (valid while the buffer lives). */
 /* rec48: the packed 48-B splat records, 12 floats per Gaussian = (mean2D.xy, conic A' B') (conic C', opacity, cut-off, r)
  * (g, b, 1/depth - or depth with GSR_DEPTH_Z -, depth); clamped: one byte per Gaussian, bit c set = colour channel c was clamped at 0 (any out pointer may
- * be NULL) */
+ * be NULL)
+ *
+ * Projection rules (what fills these views; SURVEY.md Appendix A plus the guards and margins stated only here; float32 throughout,
+ * no fused multiply-add; tests/projection_reference.py restates them in numpy and tests/test_projection_replay_gpu.py holds the
+ * kernels to that):
+ *   t = V^T (p, 1); visible needs t.z > 0.2f, det != 0 and a non-empty 3-sigma rectangle.  hom = PV^T (p, 1),
+ *   pw = 1 / (hom.w + 1e-7f), ndc = hom.xy pw, mean2D = ((ndc + 1) (W, H) - 1) / 2.
+ *   Sigma = R diag(scale_modifier s)^2 R^T (q used as given; raw_activations: s = exp, q = q / max(|q|, 1e-12f), opacity = sigmoid).
+ *   t.x / t.z and t.y / t.z are clamped to +-1.3f tanfov (then multiplied by t.z again); J = (fx / t.z, 0, -fx t.x / t.z^2;
+ *   0, fy / t.z, -fy t.y / t.z^2), fx = W / (2 tanfovx); cov2D = (J W) Sigma (J W)^T; (a, b, c) = (cov.xx + 0.3f, cov.xy, cov.yy + 0.3f);
+ *   det = a c - b^2; conic (A, B, C) = (c, -b, a) / det; antialiasing: opacity x sqrt(max(0.000025f, det0 / det)), det0 before the 0.3f.
+ *   radius = ceil(3 sqrt(max(mid + r, mid - r))), mid = (a + c) / 2, r = sqrt(max(0.1f, mid^2 - det)); 3-sigma rectangle =
+ *   clamp(trunc((mean2D -+ radius (+ 15)) / 16), 0, grid), the quotient clamped to +-1e9f before the conversion.
+ *   cut-off pmin = -ln(255 op) - 0.01f (op > 0; else 1): a pixel with power < pmin has alpha < 1 / 255.
+ *   first-stage box (what `rect` holds): q = -2 pmin; q <= 0 (255 op <= e^-0.01): empty; else half-widths
+ *   h = sqrt(q (a | c)) 1.0001f + 0.01f and tiles ceil((mean - h - 15) / 16) .. floor((mean + h) / 16) inside the 3-sigma rectangle;
+ *   the second stage keeps, per tile row ty of the box, the columns the ellipse d^T conic d <= q reaches: with (A, B, C, q) taken
+ *   back from the record words, half-height hy = sqrt(q A / det) 1.0001f + 0.01f; the row's band y in [16 ty - mean.y, + 15] cut to
+ *   [-hy, hy] (empty: no tile); at the band's y nearest to the extreme points -+B sqrt(q / (C det)) the column ends
+ *   x = (-B y +- sqrt(A qa - det y^2)) / A +- 0.01f with qa = 1.0002f q + 0.002f; tiles ceil((mean.x + xlo - 15) / 16) ..
+ *   floor((mean.x + xhi) / 16) inside the box (reciprocals and square roots to 1 ulp).  tiles_touched is their number and `rect`
+ *   is all zeros where it is 0.
+ *   record words 2, 3, 4, 6 are in base 2: A' = -(log2e / 2) A, B' = -log2e B, C' = -(log2e / 2) C, cut-off' = log2e pmin
+ *   (log2e = 1.4426950408889634f), so that log2(alpha / op) = (A' dx + B' dy) dx + C' dy dy.
+ *   colour = max(0, 0.5 + sum_k basis_k(dir) sh_k), dir = (p - campos) / |p - campos|; evaluated only where tiles_touched > 0
+ *   (zeros elsewhere); word 10 = 1 / t.z or t.z (GSR_DEPTH_Z); word 11 = t.z, whose bits are the depth key (0xFFFFFFFF: invisible).
+ *   backward only: d conic / d(a, b, c) carries 1 / (det^2 + 1e-7f); the clamped t.x (t.y) is a constant (zero dL/dt.x, and not
+ *   differentiated in J's dependence on t.z); dL/dscale keeps the scale_modifier factor. */
 int gsr_debug_geometry_views(const void* geometry_state, int32_t P, const float** rec48, const uint32_t** depth_keys_sorted,
                              const uint32_t** order, const uint32_t** tiles_touched, const uint16_t** rect,
                              const uint32_t** offsets, const uint8_t** clamped);

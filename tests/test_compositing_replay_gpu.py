@@ -18,22 +18,18 @@ scenes included.  The opt-in matrix-pipe form (`mfma`: k_render_bwd_tile_mx, GSR
 TILE CENTRE and mapped them to d = mean - pixel after the sum; for a splat a pixel or two wide the three terms of that map are a few
 hundred times the result.  It now forms each lane's terms about the mean, as the other forms do, and uses the matrix pipe for the
 sums over the wave only: 5.9e-6 on `needles`, 6.4e-7 on `sparse`."""
-import contextlib
 import ctypes as C
 import functools
-import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import compositing_reference as CR
+from frame_run import CAP, DEV, _env, _FrameRun, _Scene
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-CAP = 1 << 20
 BOUNDS = CR.bounds(CR.YARDSTICK)
 RANDOM_CASES = list(CR.CASES)
 STACK_CASES = [n for n in CR.all_case_names() if n not in CR.CASES]
@@ -51,121 +47,6 @@ def measure():
         worst = {k: max(worst.get(k, 0.0), v) for k, v in fig.items()}
     for k in CR.CLASSES:
         print(f"{k}: yardstick {worst[k]:.4e}, bound {max(CR.FLOOR, CR.FACTOR * worst[k]):.4e}")
-
-
-@contextlib.contextmanager
-def _env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    try:
-        for k, v in kw.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-
-
-class _Scene:
-    """Settings and Gaussians of one case as the C ABI takes them (the tensors are kept alive here)."""
-
-    def __init__(self, name):
-        from diff_gaussian_rasterization import GaussianRasterizationSettings, _settings_struct, _gauss_struct
-        from helpers import leaf_inputs
-        raw, cam, deg, W, H, bg = CR.case_scene(name)
-        self.W, self.H, self.bg = W, H, bg
-        inp = leaf_inputs(raw, torch.float32, DEV, "sh")
-        self.t = {k: v.detach().contiguous() for k, v in inp.items()}
-        self.P = int(self.t["means3D"].shape[0])
-        rs = GaussianRasterizationSettings(H, W, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), torch.from_numpy(bg).to(DEV),
-                                           1.0, cam.world_view_transform.to(DEV), cam.full_proj_transform.to(DEV), deg,
-                                           cam.camera_center.to(DEV), False, False, False)
-        self.s, self.keep = _settings_struct(rs, DEV)
-        t = self.t
-        self.g = _gauss_struct(self.P, t["means3D"], None, t["shs"], None, t["opacities"], t["scales"], t["rotations"], None)
-
-
-class _FrameRun:
-    """One forward (for_backward = 1) on fresh states; the states stay alive for the backward calls."""
-
-    def __init__(self, sc, tlo=1, depth_z=False):
-        from diff_gaussian_rasterization import _C, _stream
-        from helpers import _view
-        lib = _C.lib()
-        P, W, H = sc.P, sc.W, sc.H
-        self.sc, self.depth_kind = sc, 1 if depth_z else 0
-        self.geom = torch.zeros(max(4096, lib.gsr_geometry_state_bytes(P)), dtype=torch.uint8, device=DEV)
-        self.img = torch.zeros(lib.gsr_image_state_bytes(W, H), dtype=torch.uint8, device=DEV)
-        self.binning = torch.zeros(lib.gsr_binning_state_bytes(P, W, H, CAP), dtype=torch.uint8, device=DEV)
-        self.radii = torch.zeros(max(P, 1), dtype=torch.int32, device=DEV)
-        self.color = torch.full((3, H, W), 12345.0, device=DEV)
-        self.invd = torch.full((1, H, W), 12345.0, device=DEV)
-        self.alpha = torch.full((H, W), 12345.0, device=DEV)
-        status = torch.zeros(8, dtype=torch.int64).pin_memory()
-        ex = _C.gsr_render_extras(self.depth_kind, self.alpha.data_ptr(), None)
-        _C.check(lib.gsr_forward_async_ex(C.byref(sc.s), C.byref(sc.g), _C.ptr(self.geom), self.geom.numel(), _C.ptr(self.radii),
-                                          _C.ptr(self.binning), self.binning.numel(), CAP, _C.ptr(self.img), self.img.numel(),
-                                          _C.ptr(self.color), _C.ptr(self.invd), 1, 0, None, C.c_void_p(status.data_ptr()), tlo,
-                                          _stream(), None, C.byref(ex)))
-        torch.cuda.synchronize()
-        self.R = int(status[1])
-        assert 0 < self.R <= CAP and int(status[0]) & 1 == 0
-        tiles = math.prod(CR.R.tile_grid(W, H))
-        pi = [C.c_void_p() for _ in range(2)]
-        lib.gsr_debug_image_views(_C.ptr(self.img), W, H, C.byref(pi[0]), C.byref(pi[1]))
-        pv = [C.c_void_p() for _ in range(6)]
-        lib.gsr_debug_geometry_views(_C.ptr(self.geom), P, *[C.byref(p) for p in pv], None)
-        pb = [C.c_void_p() for _ in range(3)]
-        lib.gsr_debug_binning_views(_C.ptr(self.binning), W, H, CAP, C.byref(pb[0]), C.byref(pb[1]))
-        lib.gsr_debug_slot_views(_C.ptr(self.binning), W, H, CAP, C.byref(pb[2]))
-        self.out = dict(color=self.color.cpu().numpy().reshape(3, -1), depth=self.invd.cpu().numpy().reshape(-1),
-                        alpha=self.alpha.cpu().numpy().reshape(-1),
-                        fT=_view(self.img, pi[0].value, W * H, torch.float32).numpy(),
-                        nc=_view(self.img, pi[1].value, W * H, torch.int32).numpy().astype(np.int64))
-        self.rec = _view(self.geom, pv[0].value, P * 12, torch.float32).view(P, 12).numpy()
-        self.point_list = _view(self.binning, pb[0].value, self.R, torch.int32).numpy().view(np.uint32)
-        self.ranges = _view(self.binning, pb[1].value, tiles * 2, torch.int32).numpy().view(np.uint32).reshape(tiles, 2)
-        self.slot = _view(self.binning, pb[2].value, self.R, torch.int32).numpy().view(np.uint32).astype(np.int64)
-        self.frame = CR.Frame(self.rec, self.ranges, self.point_list, sc.bg, W, H)
-        # the lists are contiguous, in tile order, from position 0: list order = position order
-        lens = self.frame.ranges[:, 1] - self.frame.ranges[:, 0]
-        assert int(lens.sum()) == self.R
-        assert np.array_equal(self.frame.ranges[lens > 0, 0], (np.cumsum(lens) - lens)[lens > 0])
-        # the slots are a permutation, and the slots of one Gaussian are contiguous (k_preprocess_bwd streams them)
-        assert np.array_equal(np.sort(self.slot), np.arange(self.R))
-        gid_of_slot = np.empty(self.R, dtype=np.int64)
-        gid_of_slot[self.slot] = self.point_list
-        real = gid_of_slot[gid_of_slot != CR.NO_ID]
-        assert len(np.unique(real)) == 1 + int((np.diff(real) != 0).sum())
-
-    def backward(self, extras):
-        """gsr_backward (extras: gsr_backward_ex with dL/d(depth plane) and dL/d(alpha plane)) with a scratch buffer made here,
-        pre-filled with a pattern.  -> (records [R, 12] float32 by SLOT, validity flags [R] uint8, dL_dmeans2D [P, 3])"""
-        from diff_gaussian_rasterization import _C, _stream
-        lib = _C.lib()
-        sc = self.sc
-        P, W, H = sc.P, sc.W, sc.H
-        gp, gd, gA = (torch.from_numpy(x).to(DEV) for x in CR.upstream(W, H))
-        nbytes = lib.gsr_backward_scratch_bytes(P, CAP)
-        assert nbytes >= 48 * CAP + CAP
-        scratch = torch.full((nbytes,), 0x5A, dtype=torch.uint8, device=DEV)
-        d = {k: torch.zeros(*shape, device=DEV) for k, shape in
-             (("m3", (P, 3)), ("m2", (P, 3)), ("sh", tuple(sc.t["shs"].shape)), ("op", (P, 1)), ("sc", (P, 3)), ("ro", (P, 4)))}
-        gr = _C.gsr_grads(*[None if t is None else t.data_ptr() for t in
-                            (d["m3"], d["m2"], None, d["sh"], None, d["op"], d["sc"], d["ro"], None)])
-        args = (C.byref(sc.s), C.byref(sc.g), _C.ptr(self.radii), _C.ptr(self.geom), _C.ptr(self.binning), _C.ptr(self.img), CAP,
-                _C.ptr(gp), _C.ptr(gd) if extras else None, _C.ptr(scratch), scratch.numel(), C.byref(gr), _stream())
-        if extras:
-            ex = _C.gsr_render_extras(self.depth_kind, None, gA.data_ptr())
-            _C.check(lib.gsr_backward_ex(*args, C.byref(ex)))
-        elif self.depth_kind:
-            ex = _C.gsr_render_extras(self.depth_kind, None, None)
-            _C.check(lib.gsr_backward_ex(*args, C.byref(ex)))
-        else:
-            _C.check(lib.gsr_backward(*args))
-        torch.cuda.synchronize()
-        recs = scratch[:48 * self.R].clone().view(torch.float32).view(self.R, 12).cpu().numpy()
-        flags = scratch[48 * CAP:48 * CAP + self.R].cpu().numpy()
-        return recs, flags, d["m2"].cpu().numpy()
 
 
 @functools.lru_cache(maxsize=None)
@@ -275,8 +156,8 @@ def _backward_check(name, form, extras, flags_forced):
     prev = lib.gsr_debug_set_flags_min_r(0 if flags_forced else 0xFFFFFFFF)
     try:
         with _env(**{**_UNSET, **FORMS[form]}):
-            recs, flags, m2 = fr.backward(extras)
-            recs2, flags2, m2b = fr.backward(extras)
+            recs, flags, m2, _ = fr.backward(extras)
+            recs2, flags2, m2b, _ = fr.backward(extras)
     finally:
         lib.gsr_debug_set_flags_min_r(prev)
     # C: reproducible bit for bit (where the flags say "no record" the record bytes are not the kernel's)
