@@ -18,18 +18,19 @@
 
 #define GSR_GRADIENT_PIVOT_MIN 1e-12    // LDL^T: a pivot at or below this share of its diagonal entry is no pivot (registration.hip)
 
-struct GsrGradientLayout {
-  GsrNnLayout nn;
-  size_t masked;     // float[P][3]: the points, NaN NaN NaN where point, normal or colour is not finite - what the structure is built over
+struct GradientWs {
+  GsrNnWs nn;
+  float* masked;     // float[P][3]: the points, NaN NaN NaN where point, normal or colour is not finite - what the structure is built over
   size_t total;
 };
-static inline GsrGradientLayout gradient_layout(size_t P) {
-  GsrGradientLayout L;
+static GradientWs gradient_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  GradientWs w;
   if (P == 0) P = 1;
-  L.nn = nn_layout(P);
-  L.masked = L.nn.total;
-  L.total = L.masked + gsr_align(P * 12);
-  return L;
+  w.nn = nn_carve(c, P);
+  w.masked = c.take<float>(3 * P);
+  w.total = c.o;
+  return w;
 }
 
 __device__ __forceinline__ bool gradient_finite3(const float* __restrict__ a, size_t i) {
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void k_color_gradient(GsrKnnTree t, int k, flo
 
 extern "C" {
 
-size_t gsr_color_gradient_workspace_bytes(int64_t P) { return gradient_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_color_gradient_workspace_bytes(int64_t P) { return gradient_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_color_gradient(int64_t P, const float* points, const float* colors, const float* normals, float radius, int32_t max_nn,
                        float* gradient, int32_t* count_out, uint8_t* status_out, void* workspace, size_t workspace_bytes,
@@ -141,19 +142,13 @@ int gsr_color_gradient(int64_t P, const float* points, const float* colors, cons
                   (long long)P, (double)radius, (int)max_nn, GSR_KNN_K_MAX + 1);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrGradientLayout L = gradient_layout((size_t)P);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("color_gradient: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GradientWs w = gradient_ws(workspace, (size_t)P);
+  if (!gsr_workspace_fits("color_gradient", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const GsrKnnBuild b = nn_build_views(ws, L.nn);
-  const GsrKnnTree t = knn_tree(b, (size_t)P);
+  const GsrKnnTree t = knn_tree(w.nn, (size_t)P);
   const uint32_t nblk = (t.P + 255u) / 256u;
-  float* masked = (float*)(ws + L.masked);
-  GSR_LAUNCH("gradient_mask", k_gradient_mask, dim3(nblk), dim3(256), 0, st, t.P, points, colors, normals, masked);
-  gsr_knn_build(P, masked, b, st);
+  GSR_LAUNCH("gradient_mask", k_gradient_mask, dim3(nblk), dim3(256), 0, st, t.P, points, colors, normals, w.masked);
+  gsr_knn_build(P, w.masked, w.nn, st);
   const float r2 = radius * radius;      // the float32 square (+inf stays, and a large radius may become, +inf)
   const int k = (int)max_nn - 1;
 #define GRADIENT_K(K) \

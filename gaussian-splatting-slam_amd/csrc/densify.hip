@@ -182,10 +182,24 @@ int gsr_densification_stats(int64_t P, const float* grad_means2D, const int32_t*
   return gsr_launch_status("densification_stats launch");
 }
 
-size_t gsr_densify_workspace_bytes(int64_t P) {
-  const size_t p = (size_t)(P < 1 ? 1 : P);
-  return 6 * gsr_align(p * 4) + gsr_align(gsr_scan_tmp_elems(p) * 4) + 256;
+// the workspace gsr_densify_plan fills and gsr_densify_apply reads: the keep / clone / split flags of every row and their
+// exclusive scans; behind them the scans' scratch and one spare span
+struct DensifyWs {
+  uint32_t *f[3], *pfx[3];      // u32[P] each
+  uint32_t* scan_tmp;
+  size_t total;
+};
+static DensifyWs densify_ws(const void* base, size_t P) {
+  GsrCarve c(base);
+  DensifyWs w;
+  for (int k = 0; k < 3; k++) w.f[k] = c.take<uint32_t>(P);
+  for (int k = 0; k < 3; k++) w.pfx[k] = c.take<uint32_t>(P);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(P));
+  c.bytes(256);
+  w.total = c.o;
+  return w;
 }
+size_t gsr_densify_workspace_bytes(int64_t P) { return densify_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 // Plan + prefix sums.  Synchronises the stream once to return the three counts (host int64[3]: keep, clone, child pairs).
 int gsr_densify_plan(int64_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
@@ -198,20 +212,17 @@ int gsr_densify_plan(int64_t P, const float* xyz_gradient_accum, const float* de
   }
   counts_host[0] = counts_host[1] = counts_host[2] = 0;
   if (P == 0) return 0;
-  if (P > 0x7FFFFFFF || workspace_bytes < gsr_densify_workspace_bytes(P)) {
+  const DensifyWs w = densify_ws(workspace, (size_t)P);
+  if (P > 0x7FFFFFFF || workspace_bytes < w.total) {      // (its own wording, no sizes: not gsr_workspace_fits)
     gsr_set_error("densify_plan: workspace too small or P too large");
     return GSR_ERR_STATE_TOO_SMALL;
   }
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const size_t a = gsr_align((size_t)P * 4);
-  uint32_t* f[3] = {(uint32_t*)ws, (uint32_t*)(ws + a), (uint32_t*)(ws + 2 * a)};
-  uint32_t* pfx[3] = {(uint32_t*)(ws + 3 * a), (uint32_t*)(ws + 4 * a), (uint32_t*)(ws + 5 * a)};
-  uint32_t* scan_tmp = (uint32_t*)(ws + 6 * a);
+  uint32_t *const *f = w.f, *const *pfx = w.pfx;
   GSR_LAUNCH("densify_plan", k_densify_plan, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (int)P,
              xyz_gradient_accum, denom, scaling_raw, opacity_raw, max_grad, min_opacity, extent, percent_dense,
              (int)use_world_size_prune, f[0], f[1], f[2]);
-  for (int k = 0; k < 3; k++) gsr_scan_u32(f[k], nullptr, pfx[k], (size_t)P, 0, scan_tmp, st);
+  for (int k = 0; k < 3; k++) gsr_scan_u32(f[k], nullptr, pfx[k], (size_t)P, 0, w.scan_tmp, st);
   uint32_t last_f[3], last_p[3];
   for (int k = 0; k < 3; k++) {
     int rc;
@@ -258,13 +269,12 @@ int gsr_densify_apply(int64_t P, const void* workspace, const float* const* in_p
     gsr_set_error("densify_apply: xyz/scaling/rotation rows must be 3/3/4 floats");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const char* ws = (const char*)workspace;
-  const size_t a = gsr_align((size_t)P * 4);
+  const DensifyWs w = densify_ws(workspace, (size_t)P);
   hipStream_t st = (hipStream_t)stream;
   GSR_LAUNCH("densify_apply", k_densify_apply, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (int)P, t,
-             (const uint32_t*)ws, (const uint32_t*)(ws + a), (const uint32_t*)(ws + 2 * a), (const uint32_t*)(ws + 3 * a),
-             (const uint32_t*)(ws + 4 * a), (const uint32_t*)(ws + 5 * a), (uint32_t)n_keep, (uint32_t)n_clone,
-             (uint32_t)n_child, seed, source_of_row);
+             (const uint32_t*)w.f[0], (const uint32_t*)w.f[1], (const uint32_t*)w.f[2], (const uint32_t*)w.pfx[0],
+             (const uint32_t*)w.pfx[1], (const uint32_t*)w.pfx[2], (uint32_t)n_keep, (uint32_t)n_clone, (uint32_t)n_child, seed,
+             source_of_row);
   return gsr_launch_status("densify_apply launch");
 }
 

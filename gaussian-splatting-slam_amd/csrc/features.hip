@@ -38,27 +38,27 @@
 #define GSR_PI 3.14159265358979323846
 
 // ==== FPFH ==========================================================================================================================
-struct GsrFpfhLayout {
-  GsrNnLayout nn;
-  size_t masked;     // float[P][3]: the points, NaN NaN NaN where the point or the normal is not finite - what the structure is built over
-  size_t nrm;        // float4[P]: the normal of every sorted position
-  size_t bound;      // float[P]: min(r2, d_k) per sorted position (max_nn > 0)
-  size_t spfh;       // int32[P][33]: the SPFH counts per sorted position
-  size_t m;          // int32[P]: members besides the row itself
+struct FpfhWs {
+  GsrNnWs nn;
+  float* masked;     // float[P][3]: the points, NaN NaN NaN where the point or the normal is not finite - what the structure is built over
+  float4* nrm;       // float4[P]: the normal of every sorted position
+  float* bound;      // float[P]: min(r2, d_k) per sorted position (max_nn > 0)
+  int32_t* spfh;     // int32[P][33]: the SPFH counts per sorted position
+  int32_t* m;        // int32[P]: members besides the row itself
   size_t total;
 };
-static inline GsrFpfhLayout fpfh_layout(size_t P) {
-  GsrFpfhLayout L;
+static FpfhWs fpfh_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  FpfhWs w;
   if (P == 0) P = 1;
-  L.nn = nn_layout(P);
-  size_t o = L.nn.total;
-  L.masked = o; o += gsr_align(P * 12);
-  L.nrm = o;   o += gsr_align(P * 16);
-  L.bound = o; o += gsr_align(P * 4);
-  L.spfh = o;  o += gsr_align(P * GSR_FPFH_BINS * 4);
-  L.m = o;     o += gsr_align(P * 4);
-  L.total = o;
-  return L;
+  w.nn = nn_carve(c, P);
+  w.masked = c.take<float>(3 * P);
+  w.nrm = c.take<float4>(P);
+  w.bound = c.take<float>(P);
+  w.spfh = c.take<int32_t>(P * GSR_FPFH_BINS);
+  w.m = c.take<int32_t>(P);
+  w.total = c.o;
+  return w;
 }
 
 // the cloud the structure is built over: a row whose point or normal is not finite becomes NaN NaN NaN BEFORE the build, so it
@@ -294,34 +294,34 @@ __global__ __launch_bounds__(256) void k_feature_nn_finish(uint32_t Nq, const fl
 }
 
 // ==== RANSAC ============================================================================================================================
-struct GsrRansacLayout {
-  size_t meta;        // u32[64]: [0] = survivors of this call
-  size_t pairs;       // float4[2 M]: (s, valid), (t, 0)
-  size_t flag;        // u32[n]: 1 = the trial survived the checkers
-  size_t offset;      // u32[n]: exclusive scan of the flags
-  size_t list;        // u32[n]: the survivors, in trial order
-  size_t hyp;         // double[n][12]: rows 0 .. 2 of the trial's T
-  size_t count;       // int64[n]: per survivor
-  size_t sum;         // double[n]
-  size_t scan_tmp;
+struct RansacWs {
+  uint32_t* meta;       // u32[64]: [0] = survivors of this call
+  float4* pairs;        // float4[2 M]: (s, valid), (t, 0)
+  uint32_t* flag;       // u32[n]: 1 = the trial survived the checkers
+  uint32_t* offset;     // u32[n]: exclusive scan of the flags
+  uint32_t* list;       // u32[n]: the survivors, in trial order
+  double* hyp;          // double[n][12]: rows 0 .. 2 of the trial's T
+  long long* count;     // int64[n]: per survivor
+  double* sum;          // double[n]
+  uint32_t* scan_tmp;
   size_t total;
 };
-static inline GsrRansacLayout ransac_layout(size_t M, size_t n) {
-  GsrRansacLayout L;
+static RansacWs ransac_ws(void* base, size_t M, size_t n) {
+  GsrCarve c(base);
+  RansacWs w;
   if (M == 0) M = 1;
   if (n == 0) n = 1;
-  size_t o = 0;
-  L.meta = o;     o += 256;
-  L.pairs = o;    o += gsr_align(M * 32);
-  L.flag = o;     o += gsr_align(n * 4);
-  L.offset = o;   o += gsr_align(n * 4);
-  L.list = o;     o += gsr_align(n * 4);
-  L.hyp = o;      o += gsr_align(n * 96);
-  L.count = o;    o += gsr_align(n * 8);
-  L.sum = o;      o += gsr_align(n * 8);
-  L.scan_tmp = o; o += gsr_align(gsr_scan_tmp_elems(n) * 4);
-  L.total = o;
-  return L;
+  w.meta = c.take<uint32_t>(64);
+  w.pairs = c.take<float4>(2 * M);
+  w.flag = c.take<uint32_t>(n);
+  w.offset = c.take<uint32_t>(n);
+  w.list = c.take<uint32_t>(n);
+  w.hyp = c.take<double>(12 * n);
+  w.count = c.take<long long>(n);
+  w.sum = c.take<double>(n);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(n));
+  w.total = c.o;
+  return w;
 }
 
 // the points of every pair, once per call; a pair that names a row outside its cloud or a non-finite point: flag 0
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void k_ransac_best(uint64_t t0, const uint32_t
 
 extern "C" {
 
-size_t gsr_fpfh_workspace_bytes(int64_t P) { return fpfh_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_fpfh_workspace_bytes(int64_t P) { return fpfh_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float radius, int32_t max_nn, float* fpfh,
                      int32_t* spfh_counts, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -580,25 +580,16 @@ int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float
                   "finite radius)", (long long)P, (double)radius, (int)max_nn, GSR_KNN_K_MAX + 1);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrFpfhLayout L = fpfh_layout((size_t)P);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("compute_fpfh: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const FpfhWs w = fpfh_ws(workspace, (size_t)P);
+  if (!gsr_workspace_fits("compute_fpfh", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const GsrKnnBuild b = nn_build_views(ws, L.nn);
-  const GsrKnnTree t = knn_tree(b, (size_t)P);
+  const GsrKnnTree t = knn_tree(w.nn, (size_t)P);
   const uint32_t n = t.P, nblk = (n + 255u) / 256u;
-  float* masked = (float*)(ws + L.masked);
-  GSR_LAUNCH("fpfh_mask", k_fpfh_mask, dim3(nblk), dim3(256), 0, st, n, points, normals, masked);
-  gsr_knn_build(P, masked, b, st);
+  GSR_LAUNCH("fpfh_mask", k_fpfh_mask, dim3(nblk), dim3(256), 0, st, n, points, normals, w.masked);
+  gsr_knn_build(P, w.masked, w.nn, st);
   const uint32_t fblk = (n + GSR_FPFH_BLOCK - 1u) / GSR_FPFH_BLOCK;
-  float4* nrm = (float4*)(ws + L.nrm);
-  float* bound = radius_only ? nullptr : (float*)(ws + L.bound);
-  int32_t* spfh = (int32_t*)(ws + L.spfh);
-  int32_t* m_of = (int32_t*)(ws + L.m);
-  GSR_LAUNCH("fpfh_prepare", k_fpfh_prepare, dim3(nblk), dim3(256), 0, st, n, b.pts, normals, nrm);
+  float* bound = radius_only ? nullptr : w.bound;
+  GSR_LAUNCH("fpfh_prepare", k_fpfh_prepare, dim3(nblk), dim3(256), 0, st, n, w.nn.pts, normals, w.nrm);
   const float r2 = radius * radius;      // the float32 square (+inf stays, and a large radius may become, +inf)
   if (!radius_only) {
     const int k = (int)max_nn - 1;
@@ -607,13 +598,25 @@ int gsr_compute_fpfh(int64_t P, const float* points, const float* normals, float
 #undef FPFH_BOUND_K
   }
   GSR_LAUNCH("fpfh_spfh", k_fpfh_spfh, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, t.P, r2, (const float*)bound, t.pts,
-             (const float4*)nrm, t.box_lo, t.box_hi, t.nbox, t.sup_lo, t.sup_hi, t.nsuper, spfh, m_of, spfh_counts, count_out);
-  GSR_LAUNCH("fpfh_sum", k_fpfh_sum, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, t, r2, (const float*)bound, (const int32_t*)spfh,
-             (const int32_t*)m_of, fpfh);
+             (const float4*)w.nrm, t.box_lo, t.box_hi, t.nbox, t.sup_lo, t.sup_hi, t.nsuper, w.spfh, w.m, spfh_counts, count_out);
+  GSR_LAUNCH("fpfh_sum", k_fpfh_sum, dim3(fblk), dim3(GSR_FPFH_BLOCK), 0, st, t, r2, (const float*)bound, (const int32_t*)w.spfh,
+             (const int32_t*)w.m, fpfh);
   return gsr_launch_status("compute_fpfh launch");
 }
 
-size_t gsr_feature_nn_workspace_bytes(int64_t Nq) { return gsr_align((size_t)(Nq < 1 ? 1 : Nq) * 8); }
+// the workspace of gsr_feature_nn: one packed (distance bits, target row) key per query, reduced by atomicMin over the splits
+struct FeatureNnWs {
+  unsigned long long* keys;      // u64[Nq]
+  size_t total;
+};
+static FeatureNnWs feature_nn_ws(void* base, size_t Nq) {
+  GsrCarve c(base);
+  FeatureNnWs w;
+  w.keys = c.take<unsigned long long>(Nq);
+  w.total = c.o;
+  return w;
+}
+size_t gsr_feature_nn_workspace_bytes(int64_t Nq) { return feature_nn_ws(nullptr, (size_t)(Nq < 1 ? 1 : Nq)).total; }
 
 int32_t gsr_feature_nn_tiles_per_split(int64_t Nq, int64_t Nt) {
   if (gsr_bad_size(Nq) || gsr_bad_size(Nt)) return 0;
@@ -631,15 +634,13 @@ int gsr_feature_nn(int64_t Nq, const float* query, int64_t Nt, const float* targ
                   (int)width, GSR_FPFH_BINS);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (workspace_bytes < gsr_feature_nn_workspace_bytes(Nq)) {
-    gsr_set_error("feature_nn: workspace of %zu bytes, %zu needed", workspace_bytes, gsr_feature_nn_workspace_bytes(Nq));
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const FeatureNnWs w = feature_nn_ws(workspace, (size_t)Nq);
+  if (!gsr_workspace_fits("feature_nn", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t nq = (uint32_t)Nq, nt = (uint32_t)Nt, qblk = (nq + GSR_FEAT_BLOCK - 1u) / GSR_FEAT_BLOCK;
   const uint32_t ntiles = (nt + GSR_FEAT_TILE - 1u) / GSR_FEAT_TILE;
   const uint32_t tps = (uint32_t)gsr_feature_nn_tiles_per_split(Nq, Nt), splits = (ntiles + tps - 1u) / tps;
-  unsigned long long* keys = (unsigned long long*)workspace;
+  unsigned long long* keys = w.keys;
   {
     const int rc = gsr_check(hipMemsetAsync(keys, 0xFF, (size_t)nq * 8, st), "feature_nn: clearing the keys");
     if (rc < 0) return rc;
@@ -651,7 +652,7 @@ int gsr_feature_nn(int64_t Nq, const float* query, int64_t Nt, const float* targ
 }
 
 size_t gsr_ransac_workspace_bytes(int64_t M, int64_t n) {
-  return ransac_layout((size_t)(M < 1 ? 1 : M), (size_t)(n < 1 ? 1 : n)).total;
+  return ransac_ws(nullptr, (size_t)(M < 1 ? 1 : M), (size_t)(n < 1 ? 1 : n)).total;
 }
 
 int gsr_ransac_feature_matching(int64_t Ps, const float* source, int64_t Pt, const float* target, int64_t M, const int32_t* pairs,
@@ -668,32 +669,20 @@ int gsr_ransac_feature_matching(int64_t Ps, const float* source, int64_t Pt, con
                   GSR_RANSAC_N_MAX, (double)edge_length_threshold, (long long)t0, (long long)n, GSR_RANSAC_MAX_TRIALS);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrRansacLayout L = ransac_layout((size_t)M, (size_t)n);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("ransac_feature_matching: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const RansacWs w = ransac_ws(workspace, (size_t)M, (size_t)n);
+  if (!gsr_workspace_fits("ransac_feature_matching", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  uint32_t* meta = (uint32_t*)(ws + L.meta);
-  float4* pp = (float4*)(ws + L.pairs);
-  uint32_t* flag = (uint32_t*)(ws + L.flag);
-  uint32_t* offset = (uint32_t*)(ws + L.offset);
-  uint32_t* list = (uint32_t*)(ws + L.list);
-  double* hyp = (double*)(ws + L.hyp);
-  long long* count_of = (long long*)(ws + L.count);
-  double* sum_of = (double*)(ws + L.sum);
   const uint32_t m = (uint32_t)M, nn = (uint32_t)n, hblk = (nn + GSR_RANSAC_BLOCK - 1u) / GSR_RANSAC_BLOCK;
   const double md2 = (double)max_distance * (double)max_distance, theta = (double)edge_length_threshold;
   int32_t* ds = debug ? debug->samples : nullptr;
   int32_t* dst = debug ? debug->status : nullptr;
   double* dT = debug ? debug->T : nullptr;
   GSR_LAUNCH("ransac_gather", k_ransac_gather, dim3((m + 255u) / 256u), dim3(256), 0, st, m, pairs, (uint32_t)Ps, source,
-             (uint32_t)Pt, target, pp);
+             (uint32_t)Pt, target, w.pairs);
 #define RANSAC_HYP(N)                                                                                                     \
   case N:                                                                                                                 \
     GSR_LAUNCH("ransac_hyp_n" #N, k_ransac_hyp<N>, dim3(hblk), dim3(GSR_RANSAC_BLOCK), 0, st, nn, (uint64_t)t0, seed, m,   \
-               (const float4*)pp, md2, theta, flag, hyp, ds, dst, dT);                                                    \
+               (const float4*)w.pairs, md2, theta, w.flag, w.hyp, ds, dst, dT);                                           \
     break
   switch (ransac_n) {
     RANSAC_HYP(3);
@@ -704,13 +693,13 @@ int gsr_ransac_feature_matching(int64_t Ps, const float* source, int64_t Pt, con
     RANSAC_HYP(8);
   }
 #undef RANSAC_HYP
-  gsr_scan_u32(flag, nullptr, offset, (size_t)nn, 0, (uint32_t*)(ws + L.scan_tmp), st);
-  GSR_LAUNCH("ransac_compact", k_ransac_compact, dim3((nn + 255u) / 256u), dim3(256), 0, st, nn, (const uint32_t*)flag,
-             (const uint32_t*)offset, list, meta);
-  GSR_LAUNCH("ransac_score", k_ransac_score, dim3(hblk), dim3(GSR_RANSAC_BLOCK), 0, st, m, (const float4*)pp,
-             (const uint32_t*)meta, (const uint32_t*)list, (const double*)hyp, md2, count_of, sum_of);
-  GSR_LAUNCH("ransac_best", k_ransac_best, dim3(1), dim3(256), 0, st, (uint64_t)t0, (const uint32_t*)meta, (const uint32_t*)list,
-             (const double*)hyp, (const long long*)count_of, (const double*)sum_of, (double*)best);
+  gsr_scan_u32(w.flag, nullptr, w.offset, (size_t)nn, 0, w.scan_tmp, st);
+  GSR_LAUNCH("ransac_compact", k_ransac_compact, dim3((nn + 255u) / 256u), dim3(256), 0, st, nn, (const uint32_t*)w.flag,
+             (const uint32_t*)w.offset, w.list, w.meta);
+  GSR_LAUNCH("ransac_score", k_ransac_score, dim3(hblk), dim3(GSR_RANSAC_BLOCK), 0, st, m, (const float4*)w.pairs,
+             (const uint32_t*)w.meta, (const uint32_t*)w.list, (const double*)w.hyp, md2, w.count, w.sum);
+  GSR_LAUNCH("ransac_best", k_ransac_best, dim3(1), dim3(256), 0, st, (uint64_t)t0, (const uint32_t*)w.meta,
+             (const uint32_t*)w.list, (const double*)w.hyp, (const long long*)w.count, (const double*)w.sum, (double*)best);
   return gsr_launch_status("ransac_feature_matching launch");
 }
 

@@ -8,6 +8,7 @@
 
 #include "../../include/gsr.h"
 #include "launch_plan.h"
+#include "gsr_carve.h"
 
 #define GSR_TILE 16                 // 16x16 pixel tiles
 #define GSR_BLOCK_CULLED 0x80000000u  // top bit of a projection workgroup's instance total (tile-local form): a prefiltered point of it was culled
@@ -83,7 +84,7 @@ struct GsrImgLayout {
 // a row count the point-cloud entry points take: 1 .. 2^30 - 1
 static inline bool gsr_bad_size(int64_t P) { return P < 1 || P > 0x3FFFFFFF; }
 
-static inline __host__ __device__ size_t gsr_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// (gsr_align, the 256-byte rounding of every span: gsr_carve.h)
 static inline __host__ __device__ size_t gsr_igrad_bytes(size_t cap) { return gsr_align((cap < 1 ? 1 : cap) * 16 * 3); }
 // the validity flags of the gradient records (see GSR_IGRAD_F4): right behind the `cap` records
 template <typename T>
@@ -288,6 +289,13 @@ struct GsrFrame {
 // -------------------------------------------------------------------------------------------------
 void gsr_set_error(const char* fmt, ...);
 int gsr_check(hipError_t e, const char* what);
+// The size check of every entry point that takes a caller-owned blob (described with gsr_carve.h): false, with the error text
+// set, when `ws` is NULL or `have` is below `need`.  `what`: the blob's name in the message.  The return code is the caller's.
+static inline bool gsr_workspace_fits(const char* who, const void* ws, size_t have, size_t need, const char* what = "workspace") {
+  if (ws && have >= need) return true;
+  gsr_set_error("%s: %s of %zu bytes, %zu needed", who, what, have, need);
+  return false;
+}
 void gsr_prof_begin(const char* name, hipStream_t st);
 void gsr_prof_end(hipStream_t st);
 extern int g_gsr_profile_on;
@@ -393,9 +401,10 @@ int gsr_radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1,
 
 // knn.hip, for pointcloud.hip
 // Bounding box of the finite coordinates of P points -> bbox[6] = min xyz, max xyz (+inf / -inf where nothing is finite);
-// `part`: gsr_knn_bbox_part_bytes() of scratch.
+// `part`: float[GSR_KNN_BBOX_PART] of scratch, six per workgroup of the partial kernel.
+#define GSR_KNN_BBOX_BLOCKS 1024
+#define GSR_KNN_BBOX_PART (GSR_KNN_BBOX_BLOCKS * 6)
 void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipStream_t st);
-size_t gsr_knn_bbox_part_bytes();
 // The launches of gsr_knn_k on checked arguments; `workspace`: gsr_knn_k_workspace_bytes(P).
 void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st);
 

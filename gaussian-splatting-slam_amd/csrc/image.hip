@@ -381,9 +381,19 @@ int gsr_image_encode_rgb8(int32_t W, int32_t H, const float* image, void* out_by
   return gsr_launch_status("image_encode_rgb8 launch");
 }
 
-size_t gsr_depth_register_workspace_bytes(int32_t Wc, int32_t Hc) {
-  return gsr_align((size_t)(Wc < 1 ? 1 : Wc) * (size_t)(Hc < 1 ? 1 : Hc) * 4);
+// the workspace of gsr_depth_register: the z-buffer of the colour image, depth bits per pixel
+struct DregWs {
+  uint32_t* zbuf;      // u32[Wc Hc]
+  size_t total;
+};
+static DregWs dreg_ws(void* base, int32_t Wc, int32_t Hc) {
+  GsrCarve c(base);
+  DregWs w;
+  w.zbuf = c.take<uint32_t>((size_t)(Wc < 1 ? 1 : Wc) * (size_t)(Hc < 1 ? 1 : Hc));
+  w.total = c.o;
+  return w;
 }
+size_t gsr_depth_register_workspace_bytes(int32_t Wc, int32_t Hc) { return dreg_ws(nullptr, Wc, Hc).total; }
 
 int gsr_depth_register(int32_t Wd, int32_t Hd, const float* depth, const float* Kd, const float* Kc, const double* T_cd,
                        int32_t Wc, int32_t Hc, float* out, int32_t* status_dev, void* workspace, size_t workspace_bytes,
@@ -407,10 +417,8 @@ int gsr_depth_register(int32_t Wd, int32_t Hd, const float* depth, const float* 
       return GSR_ERR_INVALID_ARGUMENT;
     }
   }
-  if (workspace_bytes < gsr_depth_register_workspace_bytes(Wc, Hc)) {
-    gsr_set_error("depth_register: workspace of %zu bytes, %zu needed", workspace_bytes, gsr_depth_register_workspace_bytes(Wc, Hc));
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const DregWs w = dreg_ws(workspace, Wc, Hc);
+  if (!gsr_workspace_fits("depth_register", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   DregArgs A;
   A.Wd = Wd; A.Hd = Hd; A.Wc = Wc; A.Hc = Hc;
   A.fxd = Kd[0]; A.fyd = Kd[1]; A.cxd = Kd[2]; A.cyd = Kd[3];
@@ -418,7 +426,7 @@ int gsr_depth_register(int32_t Wd, int32_t Hd, const float* depth, const float* 
   for (int i = 0; i < 12; i++) A.T[i] = T_cd[i];
   hipStream_t st = (hipStream_t)stream;
   const uint32_t nd = (uint32_t)Wd * (uint32_t)Hd, nc = (uint32_t)Wc * (uint32_t)Hc;
-  uint32_t* buf = (uint32_t*)workspace;
+  uint32_t* buf = w.zbuf;
   GSR_LAUNCH("depth_register_clear", k_dreg_clear, dim3((nc + 255u) / 256u), dim3(256), 0, st, nc, buf, status_dev);
   GSR_LAUNCH("depth_register_splat", k_dreg_splat, dim3((nd + 255u) / 256u), dim3(256), 0, st, A, depth, buf, status_dev);
   GSR_LAUNCH("depth_register_finalize", k_dreg_finalize, dim3((nc + 255u) / 256u), dim3(256), 0, st, nc, (const uint32_t*)buf,

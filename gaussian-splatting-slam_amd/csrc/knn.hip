@@ -35,24 +35,23 @@
 #include "knn_common.h"
 
 // the workspace of gsr_knn_dist2 and gsr_knn_k: the structure's blob (knn_common.h), then what a subset of queries needs
-struct GsrKnnLayout {
-  GsrNnLayout nn;
-  size_t qflag, qpos, qlist;   // u32[P] each: first_query > 0 only - query flags in sorted order, their scan, the compacted list
-  size_t scan_tmp;
+struct KnnWs {
+  GsrNnWs nn;
+  uint32_t *qflag, *qpos, *qlist;   // u32[P] each: first_query > 0 only - query flags in sorted order, their scan, the compacted list
+  uint32_t* scan_tmp;
   size_t total;
 };
-
-static inline GsrKnnLayout knn_layout(size_t P) {
-  GsrKnnLayout L;
+static KnnWs knn_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  KnnWs w;
   if (P == 0) P = 1;
-  L.nn = nn_layout(P);
-  size_t o = L.nn.total;
-  L.qflag = o;     o += gsr_align(P * 4);
-  L.qpos = o;      o += gsr_align(P * 4);
-  L.qlist = o;     o += gsr_align(P * 4);
-  L.scan_tmp = o;  o += gsr_align(gsr_scan_tmp_elems(P) * 4);
-  L.total = o;
-  return L;
+  w.nn = nn_carve(c, P);
+  w.qflag = c.take<uint32_t>(P);
+  w.qpos = c.take<uint32_t>(P);
+  w.qlist = c.take<uint32_t>(P);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(P));
+  w.total = c.o;
+  return w;
 }
 
 // min / max of six per-thread values over a 256-thread workgroup -> out[6] (thread 0 writes)
@@ -305,9 +304,20 @@ __global__ __launch_bounds__(256) void k_unproject_write(GsrUnprojectArgs a, con
   for (int ch = 0; ch < 3; ch++) rgb[3 * (size_t)o + ch] = color[ch * plane + pix];
 }
 
-static size_t unproject_workspace_bytes(int32_t W, int32_t H) {
+// the workspace of gsr_unproject_rgbd, sized for every pixel of the image (stride 1)
+struct UnprojectWs {
+  uint32_t *flags, *offs, *scan_tmp;
+  size_t total;
+};
+static UnprojectWs unproject_ws(void* base, int32_t W, int32_t H) {
+  GsrCarve c(base);
+  UnprojectWs w;
   const size_t n = (size_t)(W < 1 ? 1 : W) * (size_t)(H < 1 ? 1 : H);
-  return 2 * gsr_align(n * 4) + gsr_align(gsr_scan_tmp_elems(n) * 4);
+  w.flags = c.take<uint32_t>(n);
+  w.offs = c.take<uint32_t>(n);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(n));
+  w.total = c.o;
+  return w;
 }
 
 // gsr_unproject_rgbd (ox = oy = 0) and gsr_unproject_rgbd_k: one flag pass, one scan, one write pass
@@ -320,29 +330,22 @@ static int unproject_rgbd(const gsr_unproject_params* p, float ox, float oy, con
     gsr_set_error("unproject_rgbd: bad arguments");
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (workspace_bytes < unproject_workspace_bytes(p->image_width, p->image_height)) {
-    gsr_set_error("unproject_rgbd: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  unproject_workspace_bytes(p->image_width, p->image_height));
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const UnprojectWs w = unproject_ws(workspace, p->image_width, p->image_height);
+  if (!gsr_workspace_fits("unproject_rgbd", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   GsrUnprojectArgs a;
   a.H = p->image_height; a.W = p->image_width; a.stride = p->stride;
   a.Hs = (a.H + a.stride - 1) / a.stride; a.Ws = (a.W + a.stride - 1) / a.stride;
   a.tanfovx = p->tanfovx; a.tanfovy = p->tanfovy; a.min_depth = p->min_depth; a.max_depth = p->max_depth;
   a.alpha_below = p->alpha_below; a.front_margin = p->front_margin;
   a.ox = ox; a.oy = oy;
-  const size_t full = (size_t)a.W * a.H, n = (size_t)a.Ws * a.Hs;
-  char* ws = (char*)workspace;
-  uint32_t* flags = (uint32_t*)ws;
-  uint32_t* offs = (uint32_t*)(ws + gsr_align(full * 4));
-  uint32_t* scan_tmp = (uint32_t*)(ws + 2 * gsr_align(full * 4));
+  const size_t n = (size_t)a.Ws * a.Hs;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)((n + 255) / 256);
-  GSR_LAUNCH("unproject_flag", k_unproject_flag, dim3(grid), dim3(256), 0, st, a, depth, alpha, rendered_z, flags);
-  gsr_scan_u32(flags, nullptr, offs, n, 0, scan_tmp, st);
+  GSR_LAUNCH("unproject_flag", k_unproject_flag, dim3(grid), dim3(256), 0, st, a, depth, alpha, rendered_z, w.flags);
+  gsr_scan_u32(w.flags, nullptr, w.offs, n, 0, w.scan_tmp, st);
   const uint32_t cap = (uint32_t)(capacity > 0x7FFFFFFF ? 0x7FFFFFFF : capacity);
   GSR_LAUNCH("unproject_write", k_unproject_write, dim3(grid), dim3(256), 0, st, a, depth, color, p->viewmatrix,
-             (const uint32_t*)flags, (const uint32_t*)offs, xyz, rgb, cap, count_dev);
+             (const uint32_t*)w.flags, (const uint32_t*)w.offs, xyz, rgb, cap, count_dev);
   return gsr_launch_status("unproject_rgbd launch");
 }
 
@@ -353,10 +356,9 @@ void gsr_knn_bbox(int64_t P, const float* points, float* part, float* bbox, hipS
   GSR_LAUNCH("knn_bbox_partial", k_knn_bbox_partial, dim3(bblk), dim3(256), 0, st, n, points, part);
   GSR_LAUNCH("knn_bbox_final", k_knn_bbox_final, dim3(1), dim3(256), 0, st, bblk, (const float*)part, bbox);
 }
-size_t gsr_knn_bbox_part_bytes() { return gsr_align((size_t)GSR_KNN_BBOX_BLOCKS * 6 * 4); }
 
 // the structure over a cloud (knn_common.h): what every search starts with
-void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st, uint32_t first_query, uint32_t* qflag) {
+void gsr_knn_build(int64_t P, const float* points, const GsrNnWs& b, hipStream_t st, uint32_t first_query, uint32_t* qflag) {
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u, nbox = (uint32_t)knn_nbox(n);
   gsr_knn_bbox(P, points, b.bbox_part, b.bbox, st);
   GSR_LAUNCH("knn_morton", k_knn_morton, dim3(nblk), dim3(256), 0, st, n, points, (const float*)b.bbox, b.key[0]);
@@ -369,7 +371,7 @@ void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStre
 
 // the launches of gsr_knn_k, arguments already checked (also the first stage of gsr_statistical_outliers, csrc/pointcloud.hip)
 void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float* mean, void* workspace, hipStream_t st) {
-  const GsrKnnBuild b = nn_build_views((char*)workspace, knn_layout((size_t)P).nn);
+  const GsrNnWs b = knn_ws(workspace, (size_t)P).nn;
   gsr_knn_build(P, points, b, st);
   const GsrKnnTree t = knn_tree(b, (size_t)P);
   const uint32_t nblk = (t.P + 255u) / 256u;
@@ -380,7 +382,7 @@ void gsr_knn_k_launch(int64_t P, const float* points, int k, float* dist2, float
 
 extern "C" {
 
-size_t gsr_knn_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_knn_workspace_bytes(int64_t P) { return knn_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* mean_dist2, void* workspace,
                   size_t workspace_bytes, void* stream) {
@@ -388,30 +390,25 @@ int gsr_knn_dist2(int64_t P, const float* points, int64_t first_query, float* me
     gsr_set_error("knn_dist2: bad arguments (P = %lld, first_query = %lld)", (long long)P, (long long)first_query);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrKnnLayout L = knn_layout((size_t)P);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("knn_dist2: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const KnnWs w = knn_ws(workspace, (size_t)P);
+  if (!gsr_workspace_fits("knn_dist2", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const GsrKnnBuild b = nn_build_views(ws, L.nn);
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  uint32_t *qflag = (uint32_t*)(ws + L.qflag), *qpos = (uint32_t*)(ws + L.qpos), *qlist = (uint32_t*)(ws + L.qlist);
   const bool subset = first_query > 0;
 
-  gsr_knn_build(P, points, b, st, (uint32_t)first_query, subset ? qflag : nullptr);
+  gsr_knn_build(P, points, w.nn, st, (uint32_t)first_query, subset ? w.qflag : nullptr);
   const uint32_t nq = (uint32_t)(P - first_query);
   if (subset) {
-    gsr_scan_u32(qflag, nullptr, qpos, (size_t)n, 0, (uint32_t*)(ws + L.scan_tmp), st);
-    GSR_LAUNCH("knn_compact", k_knn_compact, dim3(nblk), dim3(256), 0, st, n, (const uint32_t*)qflag, (const uint32_t*)qpos, qlist);
+    gsr_scan_u32(w.qflag, nullptr, w.qpos, (size_t)n, 0, w.scan_tmp, st);
+    GSR_LAUNCH("knn_compact", k_knn_compact, dim3(nblk), dim3(256), 0, st, n, (const uint32_t*)w.qflag, (const uint32_t*)w.qpos,
+               w.qlist);
   }
-  GSR_LAUNCH("knn_query", k_knn_query, dim3((nq + 255u) / 256u), dim3(256), 0, st, knn_tree(b, (size_t)P), nq,
-             subset ? (const uint32_t*)qlist : (const uint32_t*)nullptr, (uint32_t)first_query, mean_dist2);
+  GSR_LAUNCH("knn_query", k_knn_query, dim3((nq + 255u) / 256u), dim3(256), 0, st, knn_tree(w.nn, (size_t)P), nq,
+             subset ? (const uint32_t*)w.qlist : (const uint32_t*)nullptr, (uint32_t)first_query, mean_dist2);
   return gsr_launch_status("knn_dist2 launch");
 }
 
-size_t gsr_knn_k_workspace_bytes(int64_t P) { return knn_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_knn_k_workspace_bytes(int64_t P) { return knn_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_knn_k(int64_t P, const float* points, int32_t k, float* dist2_out, float* mean_dist_out, void* workspace,
               size_t workspace_bytes, void* stream) {
@@ -420,16 +417,12 @@ int gsr_knn_k(int64_t P, const float* points, int32_t k, float* dist2_out, float
                   GSR_KNN_K_MAX);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const size_t need = knn_layout((size_t)P).total;
-  if (workspace_bytes < need) {
-    gsr_set_error("knn_k: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  if (!gsr_workspace_fits("knn_k", workspace, workspace_bytes, knn_ws(nullptr, (size_t)P).total)) return GSR_ERR_STATE_TOO_SMALL;
   gsr_knn_k_launch(P, points, (int)k, dist2_out, mean_dist_out, workspace, (hipStream_t)stream);
   return gsr_launch_status("knn_k launch");
 }
 
-size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) { return unproject_workspace_bytes(W, H); }
+size_t gsr_unproject_workspace_bytes(int32_t W, int32_t H) { return unproject_ws(nullptr, W, H).total; }
 
 int gsr_unproject_rgbd(const gsr_unproject_params* p, const float* depth, const float* color, const float* alpha,
                        const float* rendered_z, float* xyz, float* rgb, int64_t capacity, int64_t* count_dev, void* workspace,

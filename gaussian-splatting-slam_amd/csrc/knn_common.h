@@ -8,27 +8,56 @@
 
 #define GSR_KNN_BOX 64
 #define GSR_KNN_SUPER 64
-#define GSR_KNN_BBOX_BLOCKS 1024
 #define GSR_NONE 0x7FFFFFFFu       // no row (yet): above every row (P <= 2^30 - 1)
 
 static inline size_t knn_nbox(size_t P) { return (P + GSR_KNN_BOX - 1) / GSR_KNN_BOX; }
 static inline size_t knn_nsuper(size_t P) { return (knn_nbox(P) + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER; }
 
-// The buffers of one structure: bounding box, Morton sort (ping-pong keys / values, the sort's scratch), the points in sorted order
-// (xyz, bits of the original row) and the AABBs of the 64-point boxes and the 64-box super-boxes.
-struct GsrKnnBuild {
-  float* bbox_part;      // gsr_knn_bbox_part_bytes()
-  float* bbox;           // float[8]: min xyz, max xyz
-  uint32_t* key[2];      // u32[P] each
-  uint32_t* val[2];      // u32[P] each
-  uint32_t* radix_tmp;   // gsr_radix_tmp_elems(P) words
-  float4* pts;           // float4[P]
-  float4 *box_lo, *box_hi;   // float4[knn_nbox(P)]
-  float4 *sup_lo, *sup_hi;   // float4[knn_nsuper(P)]
+// One structure in ONE caller-owned blob (registration.hip: the target's index; normals.hip: the workspace; the head of the
+// workspaces of knn.hip, colored.hip and features.hip), and the only description of that blob: what a search reads first - the
+// bounding box, the points in Morton order (xyz, bits of the original row), the AABBs of the 64-point boxes and the 64-box
+// super-boxes - then the build's scratch: the box partials, the Morton sort's ping-pong keys / values and its tables.
+struct GsrNnWs {
+  float* bbox;                  // float[8] min xyz, max xyz; double[3] centre at + 64 bytes
+  float4* pts;                  // float4[P]
+  float4 *box_lo, *box_hi;      // float4[knn_nbox(P)]
+  float4 *sup_lo, *sup_hi;      // float4[knn_nsuper(P)]
+  size_t keep;                  // bytes from the blob's start that a search reads; behind them the build's scratch
+  float* bbox_part;             // float[GSR_KNN_BBOX_PART]
+  uint32_t* key[2];             // u32[P] each
+  uint32_t* val[2];             // u32[P] each
+  uint32_t* radix_tmp;          // gsr_radix_tmp_elems(P) words
 };
+// carves the structure of P points at the carver's position (a workspace that holds more goes on carving behind it)
+static inline GsrNnWs nn_carve(GsrCarve& c, size_t P) {
+  GsrNnWs w;
+  if (P == 0) P = 1;
+  const size_t start = c.o;
+  w.bbox = c.take<float>(64);
+  w.pts = c.take<float4>(P);
+  w.box_lo = c.take<float4>(knn_nbox(P));
+  w.box_hi = c.take<float4>(knn_nbox(P));
+  w.sup_lo = c.take<float4>(knn_nsuper(P));
+  w.sup_hi = c.take<float4>(knn_nsuper(P));
+  w.keep = c.o - start;
+  w.bbox_part = c.take<float>(GSR_KNN_BBOX_PART);
+  for (int i = 0; i < 2; i++) w.key[i] = c.take<uint32_t>(P);
+  for (int i = 0; i < 2; i++) w.val[i] = c.take<uint32_t>(P);
+  w.radix_tmp = c.take<uint32_t>(gsr_radix_tmp_elems(P));
+  return w;
+}
+// a blob that holds the structure and nothing else
+struct GsrNnBlob { GsrNnWs nn; size_t total; };
+static inline GsrNnBlob nn_ws(const void* blob, size_t P) {
+  GsrCarve c(blob);
+  GsrNnBlob w;
+  w.nn = nn_carve(c, P);
+  w.total = c.o;
+  return w;
+}
 // knn.hip: bounding box, 30-bit Morton codes, the stable sort, boxes, super-boxes - the launches every search starts with.
 // qflag (or NULL): u32[P], 1 at the sorted positions whose original row is >= first_query
-void gsr_knn_build(int64_t P, const float* points, const GsrKnnBuild& b, hipStream_t st, uint32_t first_query = 0u,
+void gsr_knn_build(int64_t P, const float* points, const GsrNnWs& b, hipStream_t st, uint32_t first_query = 0u,
                    uint32_t* qflag = nullptr);
 
 // what a search kernel reads of a built structure, passed to it by value
@@ -36,7 +65,7 @@ struct GsrKnnTree {
   const float4 *pts, *box_lo, *box_hi, *sup_lo, *sup_hi;
   uint32_t P, nbox, nsuper;
 };
-static inline GsrKnnTree knn_tree(const GsrKnnBuild& b, size_t P) {
+static inline GsrKnnTree knn_tree(const GsrNnWs& b, size_t P) {
   return GsrKnnTree{b.pts, b.box_lo, b.box_hi, b.sup_lo, b.sup_hi, (uint32_t)P, (uint32_t)knn_nbox(P), (uint32_t)knn_nsuper(P)};
 }
 // the smallest compile-time list size K in {4, 8, 16, 32} that holds k (<= GSR_KNN_K_MAX) neighbours: runs LAUNCH(K)
@@ -47,59 +76,6 @@ static inline GsrKnnTree knn_tree(const GsrKnnBuild& b, size_t P) {
     else if ((k) <= 16) LAUNCH(16); \
     else LAUNCH(32);              \
   } while (0)
-
-// ---- a structure kept in ONE caller-owned blob (registration.hip: the target's index; normals.hip: the workspace): what a search
-// reads first, the build's scratch behind it ----
-struct GsrNnLayout {
-  size_t bbox;                  // float[8] min xyz, max xyz; double[3] centre at + 64
-  size_t pts;                   // float4[P]
-  size_t box_lo, box_hi;        // float4[nbox]
-  size_t sup_lo, sup_hi;        // float4[nsuper]
-  size_t keep;                  // what a search reads ends here; the rest is the build's scratch
-  size_t bbox_part, key_a, key_b, val_a, val_b, radix_tmp;
-  size_t total;
-};
-static inline GsrNnLayout nn_layout(size_t P) {
-  GsrNnLayout L;
-  size_t o = 0;
-  if (P == 0) P = 1;
-  L.bbox = o;      o += 256;
-  L.pts = o;       o += gsr_align(P * 16);
-  L.box_lo = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.box_hi = o;    o += gsr_align(knn_nbox(P) * 16);
-  L.sup_lo = o;    o += gsr_align(knn_nsuper(P) * 16);
-  L.sup_hi = o;    o += gsr_align(knn_nsuper(P) * 16);
-  L.keep = o;
-  L.bbox_part = o; o += gsr_knn_bbox_part_bytes();
-  L.key_a = o;     o += gsr_align(P * 4);
-  L.key_b = o;     o += gsr_align(P * 4);
-  L.val_a = o;     o += gsr_align(P * 4);
-  L.val_b = o;     o += gsr_align(P * 4);
-  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
-  L.total = o;
-  return L;
-}
-// the tree inside a built blob of that layout, for a search that only reads it
-static inline GsrKnnTree nn_tree(const void* blob, size_t P) {
-  const GsrNnLayout L = nn_layout(P);
-  const char* ix = (const char*)blob;
-  return GsrKnnTree{(const float4*)(ix + L.pts), (const float4*)(ix + L.box_lo), (const float4*)(ix + L.box_hi),
-                    (const float4*)(ix + L.sup_lo), (const float4*)(ix + L.sup_hi), (uint32_t)P, (uint32_t)knn_nbox(P),
-                    (uint32_t)knn_nsuper(P)};
-}
-// the buffers of gsr_knn_build inside a blob of that layout
-static inline GsrKnnBuild nn_build_views(char* blob, const GsrNnLayout& L) {
-  GsrKnnBuild b;
-  b.bbox_part = (float*)(blob + L.bbox_part);
-  b.bbox = (float*)(blob + L.bbox);
-  b.key[0] = (uint32_t*)(blob + L.key_a); b.key[1] = (uint32_t*)(blob + L.key_b);
-  b.val[0] = (uint32_t*)(blob + L.val_a); b.val[1] = (uint32_t*)(blob + L.val_b);
-  b.radix_tmp = (uint32_t*)(blob + L.radix_tmp);
-  b.pts = (float4*)(blob + L.pts);
-  b.box_lo = (float4*)(blob + L.box_lo); b.box_hi = (float4*)(blob + L.box_hi);
-  b.sup_lo = (float4*)(blob + L.sup_lo); b.sup_hi = (float4*)(blob + L.sup_hi);
-  return b;
-}
 
 #ifdef __HIPCC__
 // (KNN_INF, knn_finite: gsr_common.h)

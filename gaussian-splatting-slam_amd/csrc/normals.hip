@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void k_normals(GsrKnnTree t, int k, float r2, 
 
 extern "C" {
 
-size_t gsr_normals_workspace_bytes(int64_t P) { return nn_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_normals_workspace_bytes(int64_t P) { return nn_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t max_nn, const float* viewpoint, float* normals,
                          int32_t* count_out, float* eigenvalues_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -146,14 +146,10 @@ int gsr_estimate_normals(int64_t P, const float* points, float radius, int32_t m
                   "viewpoint or none)", (long long)P, (double)radius, (int)max_nn, GSR_KNN_K_MAX + 1);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrNnLayout L = nn_layout((size_t)P);      // (the layout of a target index: knn_common.h)
-  if (workspace_bytes < L.total) {
-    gsr_set_error("estimate_normals: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GsrNnBlob w = nn_ws(workspace, (size_t)P);      // (the blob of a target index: knn_common.h)
+  if (!gsr_workspace_fits("estimate_normals", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const GsrKnnBuild b = nn_build_views(ws, L);
+  const GsrNnWs& b = w.nn;
   gsr_knn_build(P, points, b, st);
   const GsrKnnTree t = knn_tree(b, (size_t)P);
   const uint32_t nblk = (t.P + 255u) / 256u;

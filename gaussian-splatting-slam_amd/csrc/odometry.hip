@@ -25,7 +25,7 @@
 #define GSR_ODO_TILE_H 8
 #define GSR_ODO_H 3                                // n, sum r_D^2, sum r_I^2 (both unweighted)
 #define GSR_ODO_SUMS (GSR_ODO_H + GSR_GN6_TERMS)   // ... J^T r [6], upper triangle of J^T J [21]
-// (the workspace: gn_layout(GSR_ODO_SUMS, false) of solve6_common.h - the rows of partial sums, no shift)
+// (the workspace: gn_ws(.., GSR_ODO_SUMS, false) of solve6_common.h - the rows of partial sums, no shift)
 
 namespace {
 
@@ -182,7 +182,7 @@ extern "C" int gsr_odometry_prepare(int32_t w, int32_t h, const float* color, co
 extern "C" size_t gsr_odometry_workspace_bytes(int32_t w, int32_t h) {
   (void)w;
   (void)h;      // (the partial sums of at most GSR_GN_BLOCKS workgroups: the size does not grow with the image)
-  return gn_layout(GSR_ODO_SUMS, false).total;
+  return gn_ws(nullptr, GSR_ODO_SUMS, false).total;
 }
 
 extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const float* src_intensity, const float* src_depth,
@@ -200,11 +200,8 @@ extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const 
                   "0 .. 1; depth_diff_max = %g: expected > 0)", K[0], K[1], K[2], K[3], lambda_geometric, depth_diff_max);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrGnLayout L = gn_layout(GSR_ODO_SUMS, false);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("odometry_update: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GsrGnWs ws = gn_ws(workspace, GSR_ODO_SUMS, false);
+  if (!gsr_workspace_fits("odometry_update", workspace, workspace_bytes, ws.total)) return GSR_ERR_STATE_TOO_SMALL;
   GsrOdoArgs A;
   A.w = w; A.h = h;
   A.fx = K[0]; A.fy = K[1]; A.cx = K[2]; A.cy = K[3];
@@ -212,7 +209,7 @@ extern "C" int gsr_odometry_update(int32_t w, int32_t h, const double* K, const 
   A.sqrt_i = sqrt(1.0 - lambda_geometric);
   A.depth_diff_max = depth_diff_max;
   hipStream_t st = (hipStream_t)stream;
-  double* part = (double*)((char*)workspace + L.part);
+  double* part = ws.part;
   const uint32_t N = (uint32_t)w * (uint32_t)h, sblk = gn_partial_blocks(N);
   GSR_LAUNCH("odometry_partial", k_odometry_partial, dim3(sblk), dim3(256), 0, st, A, src_intensity, src_depth, tgt_intensity,
              tgt_depth, tgt_grad, (const double*)T_dev, part);

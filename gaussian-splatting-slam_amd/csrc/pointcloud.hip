@@ -28,38 +28,35 @@
 #define GSR_VOXEL_LONG_BLOCKS 1024
 #define GSR_STAT_BLOCKS 256
 
-struct GsrVoxelLayout {
-  size_t bbox_part, bbox;
-  size_t cell;                          // u64[P]
-  size_t key_a, key_b, val_a, val_b;    // u32[P] each
-  size_t flag, offs;                    // u32[P] each
-  size_t start;                         // u32[P + 1]
-  size_t longlist;                      // u32[P / 64 + 1]
-  size_t meta;                          // u32[64]: [0] entries of longlist
-  size_t scan_tmp, radix_tmp;
+struct VoxelWs {
+  float *bbox_part, *bbox;           // gsr_knn_bbox's scratch and result
+  unsigned long long* cell;          // u64[P]
+  uint32_t *key[2], *val[2];         // u32[P] each
+  uint32_t *flag, *offs;             // u32[P] each
+  uint32_t* start;                   // u32[P + 1]
+  uint32_t* longlist;                // u32[P / 64 + 1]
+  uint32_t* meta;                    // u32[64]: [0] entries of longlist
+  uint32_t *scan_tmp, *radix_tmp;
   size_t total;
 };
-
-static inline GsrVoxelLayout voxel_layout(size_t P) {
-  GsrVoxelLayout L;
-  size_t o = 0;
+static VoxelWs voxel_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  VoxelWs w;
   if (P == 0) P = 1;
-  L.bbox_part = o; o += gsr_knn_bbox_part_bytes();
-  L.bbox = o;      o += 256;
-  L.cell = o;      o += gsr_align(P * 8);
-  L.key_a = o;     o += gsr_align(P * 4);
-  L.key_b = o;     o += gsr_align(P * 4);
-  L.val_a = o;     o += gsr_align(P * 4);
-  L.val_b = o;     o += gsr_align(P * 4);
-  L.flag = o;      o += gsr_align(P * 4);
-  L.offs = o;      o += gsr_align(P * 4);
-  L.start = o;     o += gsr_align((P + 1) * 4);
-  L.longlist = o;  o += gsr_align((P / GSR_VOXEL_SHORT + 1) * 4);
-  L.meta = o;      o += 256;
-  L.scan_tmp = o;  o += gsr_align(gsr_scan_tmp_elems(P) * 4);
-  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
-  L.total = o;
-  return L;
+  w.bbox_part = c.take<float>(GSR_KNN_BBOX_PART);
+  w.bbox = c.take<float>(64);
+  w.cell = c.take<unsigned long long>(P);
+  for (int i = 0; i < 2; i++) w.key[i] = c.take<uint32_t>(P);
+  for (int i = 0; i < 2; i++) w.val[i] = c.take<uint32_t>(P);
+  w.flag = c.take<uint32_t>(P);
+  w.offs = c.take<uint32_t>(P);
+  w.start = c.take<uint32_t>(P + 1);
+  w.longlist = c.take<uint32_t>(P / GSR_VOXEL_SHORT + 1);
+  w.meta = c.take<uint32_t>(64);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(P));
+  w.radix_tmp = c.take<uint32_t>(gsr_radix_tmp_elems(P));
+  w.total = c.o;
+  return w;
 }
 
 struct GsrVoxelGrid {
@@ -194,23 +191,23 @@ __global__ __launch_bounds__(256) void k_voxel_reduce_long(const uint32_t* __res
 }
 
 // ---- statistical outlier filter -----------------------------------------------------------------------------------------------
-struct GsrOutlierLayout {
-  size_t knn;        // gsr_knn_k's workspace
-  size_t dbar;       // float[P] (mean_dist == NULL)
-  size_t part;       // double[GSR_STAT_BLOCKS][2]
-  size_t stats;      // double[4] (stats_dev == NULL)
+struct OutlierWs {
+  void* knn;         // gsr_knn_k's workspace
+  float* dbar;       // float[P] (mean_dist == NULL)
+  double* part;      // double[GSR_STAT_BLOCKS][2]
+  double* stats;     // double[4] (stats_dev == NULL)
   size_t total;
 };
-static inline GsrOutlierLayout outlier_layout(size_t P) {
-  GsrOutlierLayout L;
-  size_t o = 0;
+static OutlierWs outlier_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  OutlierWs w;
   if (P == 0) P = 1;
-  L.knn = o;   o += gsr_align(gsr_knn_k_workspace_bytes((int64_t)P));
-  L.dbar = o;  o += gsr_align(P * 4);
-  L.part = o;  o += gsr_align((size_t)GSR_STAT_BLOCKS * 2 * 8);
-  L.stats = o; o += 256;
-  L.total = o;
-  return L;
+  w.knn = c.bytes(gsr_knn_k_workspace_bytes((int64_t)P));
+  w.dbar = c.take<float>(P);
+  w.part = c.take<double>((size_t)GSR_STAT_BLOCKS * 2);
+  w.stats = c.take<double>(32);
+  w.total = c.o;
+  return w;
 }
 
 // MODE 0: (sum of dbar, number of finite dbar) of this workgroup's rows; MODE 1: (sum of (dbar - mu)^2, 0)
@@ -262,7 +259,7 @@ __global__ __launch_bounds__(256) void k_outlier_keep(uint32_t P, const float* _
 
 extern "C" {
 
-size_t gsr_voxel_workspace_bytes(int64_t P) { return voxel_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_voxel_workspace_bytes(int64_t P) { return voxel_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_voxel_down_sample(int64_t P, const float* points, const float* colors, float voxel_size, const float* origin,
                           float* out_points, float* out_colors, int32_t* out_npts, int64_t capacity, int64_t* count_dev,
@@ -274,61 +271,51 @@ int gsr_voxel_down_sample(int64_t P, const float* points, const float* colors, f
                   (double)voxel_size, (long long)capacity);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrVoxelLayout L = voxel_layout((size_t)P);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("voxel_down_sample: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const VoxelWs w = voxel_ws(workspace, (size_t)P);
+  if (!gsr_workspace_fits("voxel_down_sample", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  float* bbox = (float*)(ws + L.bbox);
-  unsigned long long* cell = (unsigned long long*)(ws + L.cell);
-  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
-  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
-  uint32_t *flag = (uint32_t*)(ws + L.flag), *offs = (uint32_t*)(ws + L.offs), *start = (uint32_t*)(ws + L.start);
-  uint32_t *longlist = (uint32_t*)(ws + L.longlist), *meta = (uint32_t*)(ws + L.meta);
-  uint32_t* radix_tmp = (uint32_t*)(ws + L.radix_tmp);
 
   GsrVoxelGrid g;
   g.voxel = voxel_size;
   g.has_origin = origin ? 1 : 0;
   for (int a = 0; a < 3; a++) g.origin[a] = origin ? origin[a] : 0.f;
   (void)hipMemsetAsync(count_dev, 0, 2 * sizeof(int64_t), st);
-  (void)hipMemsetAsync(meta, 0, 256, st);
-  if (!origin) gsr_knn_bbox(P, points, (float*)(ws + L.bbox_part), bbox, st);
-  GSR_LAUNCH("voxel_cell", k_voxel_cell, dim3(nblk), dim3(256), 0, st, n, points, (const float*)bbox, g, cell, key[0], count_dev);
-  // LSD over the axes: x, y, z; `w` = the buffer pair that holds the permutation so far
-  int w = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 21, radix_tmp, st);
+  (void)hipMemsetAsync(w.meta, 0, 256, st);
+  if (!origin) gsr_knn_bbox(P, points, w.bbox_part, w.bbox, st);
+  GSR_LAUNCH("voxel_cell", k_voxel_cell, dim3(nblk), dim3(256), 0, st, n, points, (const float*)w.bbox, g, w.cell, w.key[0],
+             count_dev);
+  // LSD over the axes: x, y, z; `at` = the buffer pair that holds the permutation so far
+  int at = gsr_radix_sort_pairs(w.key[0], w.val[0], w.key[1], w.val[1], true, (size_t)n, 21, w.radix_tmp, st);
   for (int axis = 1; axis < 3; axis++) {
     const int bits = axis == 2 ? 22 : 21;      // (bit 21 of the z key: a dropped row)
-    GSR_LAUNCH("voxel_key", k_voxel_key, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)cell,
-               (const uint32_t*)val[w], 21 * axis, (1u << bits) - 1u, key[w]);
-    const int r = gsr_radix_sort_pairs(key[w], val[w], key[w ^ 1], val[w ^ 1], false, (size_t)n, bits, radix_tmp, st);
-    w ^= r;
+    GSR_LAUNCH("voxel_key", k_voxel_key, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)w.cell,
+               (const uint32_t*)w.val[at], 21 * axis, (1u << bits) - 1u, w.key[at]);
+    const int r = gsr_radix_sort_pairs(w.key[at], w.val[at], w.key[at ^ 1], w.val[at ^ 1], false, (size_t)n, bits, w.radix_tmp, st);
+    at ^= r;
   }
-  const uint32_t* perm = val[w];
-  GSR_LAUNCH("voxel_flag", k_voxel_flag, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)cell, perm, flag);
-  gsr_scan_u32(flag, nullptr, offs, (size_t)n, 0, (uint32_t*)(ws + L.scan_tmp), st);
-  GSR_LAUNCH("voxel_starts", k_voxel_starts, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)cell, perm,
-             (const uint32_t*)flag, (const uint32_t*)offs, start, count_dev);
+  const uint32_t* perm = w.val[at];
+  GSR_LAUNCH("voxel_flag", k_voxel_flag, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)w.cell, perm, w.flag);
+  gsr_scan_u32(w.flag, nullptr, w.offs, (size_t)n, 0, w.scan_tmp, st);
+  GSR_LAUNCH("voxel_starts", k_voxel_starts, dim3(nblk), dim3(256), 0, st, n, (const unsigned long long*)w.cell, perm,
+             (const uint32_t*)w.flag, (const uint32_t*)w.offs, w.start, count_dev);
   GsrVoxelOut out;
   out.points = out_points;
   out.colors = (colors && out_colors) ? out_colors : nullptr;
   out.npts = out_npts;
   out.capacity = (uint32_t)(capacity > 0x7FFFFFFF ? 0x7FFFFFFF : capacity);
   GSR_LAUNCH("voxel_reduce_short", k_voxel_reduce_short, dim3(nblk), dim3(256), 0, st, n, (const int64_t*)count_dev,
-             (const uint32_t*)start, perm, points, colors, out, longlist, meta);
+             (const uint32_t*)w.start, perm, points, colors, out, w.longlist, w.meta);
   const uint32_t max_long = n / (uint32_t)(GSR_VOXEL_SHORT + 1);
   if (max_long > 0u) {
     const uint32_t lblk = max_long < (uint32_t)GSR_VOXEL_LONG_BLOCKS ? max_long : (uint32_t)GSR_VOXEL_LONG_BLOCKS;
-    GSR_LAUNCH("voxel_reduce_long", k_voxel_reduce_long, dim3(lblk), dim3(256), 0, st, (const uint32_t*)meta,
-               (const uint32_t*)longlist, (const uint32_t*)start, perm, points, colors, out);
+    GSR_LAUNCH("voxel_reduce_long", k_voxel_reduce_long, dim3(lblk), dim3(256), 0, st, (const uint32_t*)w.meta,
+               (const uint32_t*)w.longlist, (const uint32_t*)w.start, perm, points, colors, out);
   }
   return gsr_launch_status("voxel_down_sample launch");
 }
 
-size_t gsr_outlier_workspace_bytes(int64_t P) { return outlier_layout((size_t)(P < 1 ? 1 : P)).total; }
+size_t gsr_outlier_workspace_bytes(int64_t P) { return outlier_ws(nullptr, (size_t)(P < 1 ? 1 : P)).total; }
 
 int gsr_statistical_outliers(int64_t P, const float* points, int32_t nb_neighbors, double std_ratio, uint8_t* keep,
                              float* mean_dist, double* stats_dev, void* workspace, size_t workspace_bytes, void* stream) {
@@ -338,18 +325,14 @@ int gsr_statistical_outliers(int64_t P, const float* points, int32_t nb_neighbor
                   (long long)P, (int)nb_neighbors, GSR_KNN_K_MAX + 1, std_ratio);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrOutlierLayout L = outlier_layout((size_t)P);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("statistical_outliers: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const OutlierWs w = outlier_ws(workspace, (size_t)P);
+  if (!gsr_workspace_fits("statistical_outliers", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   const uint32_t n = (uint32_t)P, nblk = (n + 255u) / 256u;
-  float* dbar = mean_dist ? mean_dist : (float*)(ws + L.dbar);
-  double* part = (double*)(ws + L.part);
-  double* stats = stats_dev ? stats_dev : (double*)(ws + L.stats);
-  gsr_knn_k_launch(P, points, (int)nb_neighbors - 1, nullptr, dbar, ws + L.knn, st);
+  float* dbar = mean_dist ? mean_dist : w.dbar;
+  double* part = w.part;
+  double* stats = stats_dev ? stats_dev : w.stats;
+  gsr_knn_k_launch(P, points, (int)nb_neighbors - 1, nullptr, dbar, w.knn, st);
   const uint32_t sblk = nblk < (uint32_t)GSR_STAT_BLOCKS ? nblk : (uint32_t)GSR_STAT_BLOCKS;
   GSR_LAUNCH("outlier_sum", k_outlier_partial<0>, dim3(sblk), dim3(256), 0, st, n, (const float*)dbar, (const double*)stats, part);
   GSR_LAUNCH("outlier_mean", k_outlier_final<0>, dim3(1), dim3(256), 0, st, sblk, (const double*)part, std_ratio, stats);

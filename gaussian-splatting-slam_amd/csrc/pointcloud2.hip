@@ -45,17 +45,19 @@ struct Pc2Args {
   int64_t* count_dev;
 };
 
-struct Pc2Layout {
-  size_t cnt, offs, scan_tmp, total;
+// the workspace of gsr_pc2_decode over N points: per chunk of PC2_CHUNK its count of kept points, their exclusive scan, the scan's scratch
+struct Pc2Ws {
+  uint32_t *cnt, *offs, *scan_tmp;
+  size_t total;
 };
-static inline Pc2Layout pc2_layout(size_t N) {
-  Pc2Layout W;
+static Pc2Ws pc2_ws(void* base, size_t N) {
+  GsrCarve c(base);
+  Pc2Ws W;
   const size_t nb = (N + PC2_CHUNK - 1) / PC2_CHUNK;
-  size_t o = 0;
-  W.cnt = o;      o += gsr_align(nb * 4);
-  W.offs = o;     o += gsr_align(nb * 4);
-  W.scan_tmp = o; o += gsr_align(gsr_scan_tmp_elems(nb) * 4);
-  W.total = o;
+  W.cnt = c.take<uint32_t>(nb);
+  W.offs = c.take<uint32_t>(nb);
+  W.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(nb));
+  W.total = c.o;
   return W;
 }
 
@@ -273,7 +275,7 @@ static bool pc2_field_ok(int32_t off, int32_t dt, uint32_t point_step) {
 
 extern "C" {
 
-size_t gsr_pc2_decode_workspace_bytes(int64_t N) { return pc2_layout((size_t)(N < 1 ? 1 : N)).total; }
+size_t gsr_pc2_decode_workspace_bytes(int64_t N) { return pc2_ws(nullptr, (size_t)(N < 1 ? 1 : N)).total; }
 
 int32_t gsr_debug_pc2_force_direct(int32_t on) {
   const int32_t prev = g_pc2_force_direct;
@@ -321,13 +323,9 @@ int gsr_pc2_decode(const gsr_pc2_layout* layout, const void* data, size_t data_b
                   row_bytes, (unsigned long long)data_bytes);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const Pc2Layout W = pc2_layout((size_t)n64);
-  if (workspace_bytes < W.total) {
-    gsr_set_error("pc2_decode: workspace of %zu bytes, %zu needed", workspace_bytes, W.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const Pc2Ws W = pc2_ws(workspace, (size_t)n64);
+  if (!gsr_workspace_fits("pc2_decode", workspace, workspace_bytes, W.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   Pc2Args A;
   A.L = L;
   A.data = (const uint8_t*)data;
@@ -345,10 +343,9 @@ int gsr_pc2_decode(const gsr_pc2_layout* layout, const void* data, size_t data_b
   A.cap = (uint32_t)(cap > 0x3FFFFFFF ? 0x3FFFFFFF : cap);
   A.count_dev = count_dev;
   const uint32_t nb = (A.N + (uint32_t)PC2_CHUNK - 1u) / (uint32_t)PC2_CHUNK;
-  uint32_t *cnt = (uint32_t*)(ws + W.cnt), *offs = (uint32_t*)(ws + W.offs);
-  GSR_LAUNCH("pc2_count", k_pc2<false>, dim3(nb), dim3(PC2_CHUNK), 0, st, A, cnt, (const uint32_t*)offs);
-  gsr_scan_u32(cnt, nullptr, offs, (size_t)nb, 0, (uint32_t*)(ws + W.scan_tmp), st);
-  GSR_LAUNCH("pc2_scatter", k_pc2<true>, dim3(nb), dim3(PC2_CHUNK), 0, st, A, cnt, (const uint32_t*)offs);
+  GSR_LAUNCH("pc2_count", k_pc2<false>, dim3(nb), dim3(PC2_CHUNK), 0, st, A, W.cnt, (const uint32_t*)W.offs);
+  gsr_scan_u32(W.cnt, nullptr, W.offs, (size_t)nb, 0, W.scan_tmp, st);
+  GSR_LAUNCH("pc2_scatter", k_pc2<true>, dim3(nb), dim3(PC2_CHUNK), 0, st, A, W.cnt, (const uint32_t*)W.offs);
   return gsr_launch_status("pc2_decode launch");
 }
 

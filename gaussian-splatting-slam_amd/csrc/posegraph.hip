@@ -25,33 +25,44 @@
 
 namespace {
 
-struct PgTopoLayout { size_t s, t, ptr, adj, fixed, total; };
-inline PgTopoLayout pg_topo_layout(size_t N, size_t E) {
-  PgTopoLayout L;
-  size_t o = 0;
-  L.s = o;     o += gsr_align((E ? E : 1) * 4);
-  L.t = o;     o += gsr_align((E ? E : 1) * 4);
-  L.ptr = o;   o += gsr_align((N + 1) * 4);
-  L.adj = o;   o += gsr_align((E ? 2 * E : 1) * 4);
-  L.fixed = o; o += gsr_align(N * 4);
-  L.total = o;
-  return L;
+// the topology blob (built on the host, read on the device): edge ends, the CSR of every node's incident edges, the fixed flags
+struct PgTopo {
+  int32_t *s, *t;      // int32[E] each (one element when E = 0)
+  int32_t* ptr;        // int32[N + 1]
+  int32_t* adj;        // int32[2 E]
+  int32_t* fixed;      // int32[N]
+  size_t total;
+};
+inline PgTopo pg_topo(const void* base, size_t N, size_t E) {
+  GsrCarve c(base);
+  PgTopo w;
+  w.s = c.take<int32_t>(E ? E : 1);
+  w.t = c.take<int32_t>(E ? E : 1);
+  w.ptr = c.take<int32_t>(N + 1);
+  w.adj = c.take<int32_t>(E ? 2 * E : 1);
+  w.fixed = c.take<int32_t>(N);
+  w.total = c.o;
+  return w;
 }
-struct PgWsLayout { size_t Xn, erec, nrec, fac, x, r, z, p, Ap, total; };
-inline PgWsLayout pg_ws_layout(size_t N, size_t E) {
-  PgWsLayout L;
-  size_t o = 0;
-  L.Xn = o;   o += gsr_align(N * 16 * 8);
-  L.erec = o; o += gsr_align((E ? E : 1) * PG_EDGE * 8);
-  L.nrec = o; o += gsr_align(N * PG_NODE * 8);
-  L.fac = o;  o += gsr_align(N * 21 * 8);
-  L.x = o;    o += gsr_align(N * 6 * 8);
-  L.r = o;    o += gsr_align(N * 6 * 8);
-  L.z = o;    o += gsr_align(N * 6 * 8);
-  L.p = o;    o += gsr_align(N * 6 * 8);
-  L.Ap = o;   o += gsr_align(N * 6 * 8);
-  L.total = o;
-  return L;
+// the workspace of a solve or an optimisation: the trial poses, the edge and node records, the factors, the PCG's iterates
+struct PgWs {
+  double *Xn, *erec, *nrec, *fac, *x, *r, *z, *p, *Ap;
+  size_t total;
+};
+inline PgWs pg_ws(void* base, size_t N, size_t E) {
+  GsrCarve c(base);
+  PgWs w;
+  w.Xn = c.take<double>(N * 16);
+  w.erec = c.take<double>((E ? E : 1) * PG_EDGE);
+  w.nrec = c.take<double>(N * PG_NODE);
+  w.fac = c.take<double>(N * 21);
+  w.x = c.take<double>(N * 6);
+  w.r = c.take<double>(N * 6);
+  w.z = c.take<double>(N * 6);
+  w.p = c.take<double>(N * 6);
+  w.Ap = c.take<double>(N * 6);
+  w.total = c.o;
+  return w;
 }
 inline bool pg_bad_sizes(int64_t N, int64_t E) { return N < 1 || N > 0x3FFFFFFF || E < 0 || E > 0x3FFFFFFF; }
 
@@ -650,22 +661,15 @@ __global__ __launch_bounds__(256) void k_info_final(uint32_t nblk, const double*
 
 PgCtx pg_ctx(int64_t N, int64_t E, const void* topo, const double* eT, const double* eL, const uint8_t* unc, double mu,
              double* erec, double* nrec, void* workspace) {
-  const PgTopoLayout TL = pg_topo_layout((size_t)N, (size_t)E);
-  const PgWsLayout WL = pg_ws_layout((size_t)N, (size_t)E);
-  const char* tp = (const char*)topo;
-  char* ws = (char*)workspace;
+  const PgTopo t = pg_topo(topo, (size_t)N, (size_t)E);
+  const PgWs w = pg_ws(workspace, (size_t)N, (size_t)E);      // (no workspace: every span NULL)
   PgCtx C;
   C.N = (int)N; C.E = (int)E;
-  C.es = (const int32_t*)(tp + TL.s); C.et = (const int32_t*)(tp + TL.t); C.ptr = (const int32_t*)(tp + TL.ptr);
-  C.adj = (const int32_t*)(tp + TL.adj); C.fixed = (const int32_t*)(tp + TL.fixed);
+  C.es = t.s; C.et = t.t; C.ptr = t.ptr; C.adj = t.adj; C.fixed = t.fixed;
   C.eT = eT; C.eL = eL; C.unc = unc; C.mu = mu;
-  C.erec = erec ? erec : (ws ? (double*)(ws + WL.erec) : nullptr);
-  C.nrec = nrec ? nrec : (ws ? (double*)(ws + WL.nrec) : nullptr);
-  C.fac = C.x = C.r = C.z = C.p = C.Ap = C.Xn = nullptr;
-  if (ws) {
-    C.fac = (double*)(ws + WL.fac); C.x = (double*)(ws + WL.x); C.r = (double*)(ws + WL.r); C.z = (double*)(ws + WL.z);
-    C.p = (double*)(ws + WL.p); C.Ap = (double*)(ws + WL.Ap); C.Xn = (double*)(ws + WL.Xn);
-  }
+  C.erec = erec ? erec : w.erec;
+  C.nrec = nrec ? nrec : w.nrec;
+  C.fac = w.fac; C.x = w.x; C.r = w.r; C.z = w.z; C.p = w.p; C.Ap = w.Ap; C.Xn = w.Xn;
   return C;
 }
 
@@ -673,7 +677,7 @@ PgCtx pg_ctx(int64_t N, int64_t E, const void* topo, const double* eT, const dou
 
 extern "C" size_t gsr_information_workspace_bytes(int64_t Ps) {
   (void)Ps;      // (the partial sums of at most GSR_GN_BLOCKS workgroups: the size does not grow with the cloud)
-  return gsr_align((size_t)GSR_GN_BLOCKS * PG_INFO_SUMS * 8);
+  return gn_ws(nullptr, PG_INFO_SUMS, false).total;
 }
 
 extern "C" int gsr_registration_information(int64_t Pt, const float* target, int64_t Ps, const int32_t* idx, double* info_out,
@@ -682,22 +686,19 @@ extern "C" int gsr_registration_information(int64_t Pt, const float* target, int
     gsr_set_error("registration_information: bad arguments (Pt = %lld, Ps = %lld, or a NULL pointer)", (long long)Pt, (long long)Ps);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (workspace_bytes < gsr_information_workspace_bytes(Ps)) {
-    gsr_set_error("registration_information: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  gsr_information_workspace_bytes(Ps));
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GsrGnWs w = gn_ws(workspace, PG_INFO_SUMS, false);      // (the rows of partial sums of solve6_common.h, no shift)
+  if (!gsr_workspace_fits("registration_information", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t nblk = gn_partial_blocks((uint32_t)Ps);
   GSR_LAUNCH("information_partial", k_info_partial, dim3(nblk), dim3(256), 0, st, (uint32_t)Ps, (uint32_t)Pt, target, idx,
-             (double*)workspace);
-  GSR_LAUNCH("information_final", k_info_final, dim3(1), dim3(256), 0, st, nblk, (const double*)workspace, info_out, stats_dev);
+             w.part);
+  GSR_LAUNCH("information_final", k_info_final, dim3(1), dim3(256), 0, st, nblk, (const double*)w.part, info_out, stats_dev);
   return gsr_launch_status("registration_information launch");
 }
 
 extern "C" size_t gsr_posegraph_topology_bytes(int64_t N, int64_t E) {
   if (pg_bad_sizes(N, E)) return 0;
-  return pg_topo_layout((size_t)N, (size_t)E).total;
+  return pg_topo(nullptr, (size_t)N, (size_t)E).total;
 }
 
 extern "C" int gsr_posegraph_topology(int64_t N, int64_t E, const int32_t* edges_host, const uint8_t* fixed_host,
@@ -714,15 +715,11 @@ extern "C" int gsr_posegraph_topology(int64_t N, int64_t E, const int32_t* edges
       return GSR_ERR_INVALID_ARGUMENT;
     }
   }
-  const PgTopoLayout L = pg_topo_layout((size_t)N, (size_t)E);
-  if (topology_bytes < L.total) {
-    gsr_set_error("posegraph_topology: topology of %zu bytes, %zu needed", topology_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const PgTopo L = pg_topo(host_scratch, (size_t)N, (size_t)E);      // (filled on the host, copied whole)
+  if (!gsr_workspace_fits("posegraph_topology", topology, topology_bytes, L.total, "topology")) return GSR_ERR_STATE_TOO_SMALL;
   // the CSR, built once in the caller's host scratch: node_ptr[N + 1], node_edge[2E] = 2 k + (1 where the node is edge k's
   // target), k ascending.  node_ptr[i] serves as node i's fill cursor and is shifted back afterwards: no second array.
-  int32_t* host = (int32_t*)host_scratch;
-  int32_t *hs = host + L.s / 4, *ht = host + L.t / 4, *hp = host + L.ptr / 4, *ha = host + L.adj / 4, *hf = host + L.fixed / 4;
+  int32_t *hs = L.s, *ht = L.t, *hp = L.ptr, *ha = L.adj, *hf = L.fixed;
   for (int64_t i = 0; i <= N; i++) hp[i] = 0;
   for (int64_t k = 0; k < E; k++) {
     hs[k] = edges_host[2 * k];
@@ -740,12 +737,12 @@ extern "C" int gsr_posegraph_topology(int64_t N, int64_t E, const int32_t* edges
   }
   for (int64_t i = N; i > 0; i--) hp[i] = hp[i - 1];      // (every cursor ended at its node's end = the next node's start)
   hp[0] = 0;
-  return gsr_check(hipMemcpyAsync(topology, host, L.total, hipMemcpyHostToDevice, (hipStream_t)stream), "posegraph_topology copy");
+  return gsr_check(hipMemcpyAsync(topology, host_scratch, L.total, hipMemcpyHostToDevice, (hipStream_t)stream), "posegraph_topology copy");
 }
 
 extern "C" size_t gsr_posegraph_workspace_bytes(int64_t N, int64_t E) {
   if (pg_bad_sizes(N, E)) return 0;
-  return pg_ws_layout((size_t)N, (size_t)E).total;
+  return pg_ws(nullptr, (size_t)N, (size_t)E).total;
 }
 
 extern "C" int gsr_posegraph_linearize(int64_t N, int64_t E, const void* topology, const double* poses, const double* edge_T,
@@ -772,10 +769,8 @@ extern "C" int gsr_posegraph_solve(int64_t N, int64_t E, const void* topology, c
                   (int)cg_max_iteration);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (workspace_bytes < gsr_posegraph_workspace_bytes(N, E)) {
-    gsr_set_error("posegraph_solve: workspace of %zu bytes, %zu needed", workspace_bytes, gsr_posegraph_workspace_bytes(N, E));
+  if (!gsr_workspace_fits("posegraph_solve", workspace, workspace_bytes, gsr_posegraph_workspace_bytes(N, E)))
     return GSR_ERR_STATE_TOO_SMALL;
-  }
   PgCtx C = pg_ctx(N, E, topology, nullptr, nullptr, nullptr, 1.0, const_cast<double*>(edge_rec), const_cast<double*>(node_rec),
                    workspace);
   C.x = delta_out;
@@ -801,10 +796,8 @@ extern "C" int gsr_posegraph_optimize(int64_t N, int64_t E, const void* topology
                   min_relative_increment, min_relative_residual_increment, cg_rtol, (int)cg_max_iteration);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (workspace_bytes < gsr_posegraph_workspace_bytes(N, E)) {
-    gsr_set_error("posegraph_optimize: workspace of %zu bytes, %zu needed", workspace_bytes, gsr_posegraph_workspace_bytes(N, E));
+  if (!gsr_workspace_fits("posegraph_optimize", workspace, workspace_bytes, gsr_posegraph_workspace_bytes(N, E)))
     return GSR_ERR_STATE_TOO_SMALL;
-  }
   const PgCtx C = pg_ctx(N, E, topology, edge_T, edge_info, edge_uncertain, mu, nullptr, nullptr, workspace);
   PgOpt O;
   O.max_iteration = max_iteration; O.cg_max_iteration = cg_max_iteration;

@@ -40,27 +40,26 @@
 #define GSR_ICP_PLANE_SUMS (GSR_ICP_PLANE_H + GSR_GN6_TERMS)          // ... J^T r [6], upper triangle of J^T J [21]
 #define GSR_ICP_COLORED_SUMS (GSR_ICP_COLORED_H + GSR_GN6_TERMS)
 
-// (the index blob: GsrNnLayout / nn_layout / nn_build_views of knn_common.h - normals.hip's workspace has the same layout)
+// (the index blob: GsrNnWs / nn_ws of knn_common.h - normals.hip's workspace is the same blob)
 
 // workspace of gsr_nn_query_order: codes / rows ping-pong and the sort's scratch
-struct GsrNnOrderLayout {
-  size_t key_a, key_b, val_a, val_b, radix_tmp, total;
+struct NnOrderWs {
+  uint32_t *key[2], *val[2], *radix_tmp;
+  size_t total;
 };
-static inline GsrNnOrderLayout nn_order_layout(size_t P) {
-  GsrNnOrderLayout L;
-  size_t o = 0;
+static NnOrderWs nn_order_ws(void* base, size_t P) {
+  GsrCarve c(base);
+  NnOrderWs w;
   if (P == 0) P = 1;
-  L.key_a = o;     o += gsr_align(P * 4);
-  L.key_b = o;     o += gsr_align(P * 4);
-  L.val_a = o;     o += gsr_align(P * 4);
-  L.val_b = o;     o += gsr_align(P * 4);
-  L.radix_tmp = o; o += gsr_align(gsr_radix_tmp_elems(P) * 4);
-  L.total = o;
-  return L;
+  for (int i = 0; i < 2; i++) w.key[i] = c.take<uint32_t>(P);
+  for (int i = 0; i < 2; i++) w.val[i] = c.take<uint32_t>(P);
+  w.radix_tmp = c.take<uint32_t>(gsr_radix_tmp_elems(P));
+  w.total = c.o;
+  return w;
 }
 
-// workspace of gsr_icp_update and gsr_icp_update_plane: gn_layout(GSR_ICP_PLANE_SUMS, true) (solve6_common.h; the point-to-point
-// update uses GSR_ICP_SUMS of each row's); of gsr_icp_update_colored: gn_layout(GSR_ICP_COLORED_SUMS, true), a size of its own
+// workspace of gsr_icp_update and gsr_icp_update_plane: gn_ws(.., GSR_ICP_PLANE_SUMS, true) (solve6_common.h; the point-to-point
+// update uses GSR_ICP_SUMS of each row's); of gsr_icp_update_colored: gn_ws(.., GSR_ICP_COLORED_SUMS, true), a size of its own
 
 // ---- q = (float)(R s + t): RegT, reg_load, reg_apply (rigid_common.h, shared with pointcloud2.hip) -----------------------------
 
@@ -368,14 +367,11 @@ struct IcpRun {
 // partial kernel, and the shift launch.  GSR_OK, or the error to return
 static int icp_begin(const char* entry, int sums, int64_t Ps, const float* source, int64_t Pt, const float* target,
                      const int32_t* idx, const double* T_dev, void* workspace, size_t workspace_bytes, void* stream, IcpRun& r) {
-  const GsrGnLayout L = gn_layout(sums, true);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("%s: workspace of %zu bytes, %zu needed", entry, workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GsrGnWs w = gn_ws(workspace, sums, true);
+  if (!gsr_workspace_fits(entry, workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   r.st = (hipStream_t)stream;
-  r.shift = (double*)((char*)workspace + L.shift);
-  r.part = (double*)((char*)workspace + L.part);
+  r.shift = w.shift;
+  r.part = w.part;
   r.ns = (uint32_t)Ps;
   r.nt = (uint32_t)Pt;
   r.sblk = gn_partial_blocks(r.ns);
@@ -385,28 +381,24 @@ static int icp_begin(const char* entry, int sums, int64_t Ps, const float* sourc
 
 extern "C" {
 
-size_t gsr_nn_index_bytes(int64_t Pt) { return nn_layout((size_t)(Pt < 1 ? 1 : Pt)).total; }
+size_t gsr_nn_index_bytes(int64_t Pt) { return nn_ws(nullptr, (size_t)(Pt < 1 ? 1 : Pt)).total; }
 
 int gsr_nn_index_build(int64_t Pt, const float* target, void* index, size_t index_bytes, void* stream) {
   if (gsr_bad_size(Pt) || !target || !index) {
     gsr_set_error("nn_index_build: bad arguments (Pt = %lld)", (long long)Pt);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrNnLayout L = nn_layout((size_t)Pt);
-  if (index_bytes < L.total) {
-    gsr_set_error("nn_index_build: index of %zu bytes, %zu needed", index_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const GsrNnBlob w = nn_ws(index, (size_t)Pt);
+  if (!gsr_workspace_fits("nn_index_build", index, index_bytes, w.total, "index")) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ix = (char*)index;
-  const GsrKnnBuild b = nn_build_views(ix, L);
+  const GsrNnWs& b = w.nn;
   gsr_knn_build(Pt, target, b, st);
   const uint32_t n = (uint32_t)Pt;
   GSR_LAUNCH("nn_finish_index", k_nn_finish_index, dim3((n + 255u) / 256u), dim3(256), 0, st, n, b.pts, b.bbox);
   return gsr_launch_status("nn_index_build launch");
 }
 
-size_t gsr_nn_order_workspace_bytes(int64_t Ps) { return nn_order_layout((size_t)(Ps < 1 ? 1 : Ps)).total; }
+size_t gsr_nn_order_workspace_bytes(int64_t Ps) { return nn_order_ws(nullptr, (size_t)(Ps < 1 ? 1 : Ps)).total; }
 
 int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* source, const double* T_dev, int32_t* order_out,
                        void* workspace, size_t workspace_bytes, void* stream) {
@@ -414,20 +406,14 @@ int gsr_nn_query_order(int64_t Pt, const void* index, int64_t Ps, const float* s
     gsr_set_error("nn_query_order: bad arguments (Pt = %lld, Ps = %lld)", (long long)Pt, (long long)Ps);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrNnOrderLayout L = nn_order_layout((size_t)Ps);
-  if (workspace_bytes < L.total) {
-    gsr_set_error("nn_query_order: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-    return GSR_ERR_STATE_TOO_SMALL;
-  }
+  const NnOrderWs w = nn_order_ws(workspace, (size_t)Ps);
+  if (!gsr_workspace_fits("nn_query_order", workspace, workspace_bytes, w.total)) return GSR_ERR_STATE_TOO_SMALL;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   const uint32_t n = (uint32_t)Ps;
-  uint32_t* key[2] = {(uint32_t*)(ws + L.key_a), (uint32_t*)(ws + L.key_b)};
-  uint32_t* val[2] = {(uint32_t*)(ws + L.val_a), (uint32_t*)(ws + L.val_b)};
-  const float* bbox = (const float*)((const char*)index + nn_layout((size_t)Pt).bbox);
-  GSR_LAUNCH("nn_query_codes", k_nn_query_codes, dim3((n + 255u) / 256u), dim3(256), 0, st, n, source, T_dev, bbox, key[0]);
-  const int where = gsr_radix_sort_pairs(key[0], val[0], key[1], val[1], true, (size_t)n, 30, (uint32_t*)(ws + L.radix_tmp), st);
-  (void)hipMemcpyAsync(order_out, val[where], (size_t)n * 4, hipMemcpyDeviceToDevice, st);
+  const float* bbox = nn_ws(index, (size_t)Pt).nn.bbox;
+  GSR_LAUNCH("nn_query_codes", k_nn_query_codes, dim3((n + 255u) / 256u), dim3(256), 0, st, n, source, T_dev, bbox, w.key[0]);
+  const int where = gsr_radix_sort_pairs(w.key[0], w.val[0], w.key[1], w.val[1], true, (size_t)n, 30, w.radix_tmp, st);
+  (void)hipMemcpyAsync(order_out, w.val[where], (size_t)n * 4, hipMemcpyDeviceToDevice, st);
   return gsr_launch_status("nn_query_order launch");
 }
 
@@ -438,7 +424,7 @@ int gsr_nn_search(int64_t Pt, const void* index, int64_t Ps, const float* source
                   (double)max_dist2);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  const GsrKnnTree t = nn_tree(index, (size_t)Pt);
+  const GsrKnnTree t = knn_tree(nn_ws(index, (size_t)Pt).nn, (size_t)Pt);
   const uint32_t ns = (uint32_t)Ps;
   GSR_LAUNCH("nn_search", k_nn_search, dim3((ns + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, t, ns, source,
              (const uint32_t*)order, T_dev, max_dist2, idx_out, dist2_out);
@@ -457,7 +443,7 @@ int gsr_transform_points(int64_t P, const float* points, const double* T_dev, fl
 
 size_t gsr_icp_workspace_bytes(int64_t Ps) {
   (void)Ps;      // (the partial sums of at most GSR_GN_BLOCKS workgroups: the size does not grow with the cloud)
-  return gn_layout(GSR_ICP_PLANE_SUMS, true).total;
+  return gn_ws(nullptr, GSR_ICP_PLANE_SUMS, true).total;
 }
 
 int gsr_icp_update(int64_t Ps, const float* source, int64_t Pt, const float* target, const int32_t* idx, double* T_dev,
@@ -498,7 +484,7 @@ int gsr_icp_update_plane(int64_t Ps, const float* source, int64_t Pt, const floa
 
 size_t gsr_icp_colored_workspace_bytes(int64_t Ps) {
   (void)Ps;      // (as gsr_icp_workspace_bytes: at most GSR_GN_BLOCKS rows of partial sums)
-  return gn_layout(GSR_ICP_COLORED_SUMS, true).total;
+  return gn_ws(nullptr, GSR_ICP_COLORED_SUMS, true).total;
 }
 
 int gsr_icp_update_colored(int64_t Ps, const float* source, const float* source_colors, int64_t Pt, const float* target,

@@ -1,5 +1,5 @@
 // solve6_common.h - the 6-unknown Gauss-Newton step of include/gsr.h, shared by registration.hip (gsr_icp_update_plane,
-// gsr_icp_update_colored) and odometry.hip (gsr_odometry_update): ONE workspace layout, ONE final kernel (the rows of partial sums,
+// gsr_icp_update_colored) and odometry.hip (gsr_odometry_update): ONE workspace description, ONE final kernel (the rows of partial sums,
 // the stats header, the n < 6 rule, the unpacking of the triangle) and ONE body for the LDL^T solve, the vector-to-matrix
 // composition and T <- dT T (posegraph.hip takes the same three for its 6 x 6 node blocks and its pose update), so the
 // thresholds, the stats layout, the pivot rule and the order of operations agree by construction.  What differs between the updates stays in their files: the partial kernel that forms a workgroup's row
@@ -13,17 +13,18 @@
 #define GSR_GN6_TERMS 27          // J^T r [6], upper triangle of J^T J [21]: what follows the H header sums of a row
 
 // workspace of an update: the rows of partial sums do not grow with the cloud or the image
-struct GsrGnLayout {
-  size_t shift;      // double[4]: the shift, [3] = 1 when a valid row exists (with_shift only)
-  size_t part;       // double[GSR_GN_BLOCKS][sums]
+struct GsrGnWs {
+  double* shift;     // double[4]: the shift, [3] = 1 when a valid row exists (with_shift only, else NULL)
+  double* part;      // double[GSR_GN_BLOCKS][sums]
   size_t total;
 };
-static inline GsrGnLayout gn_layout(int sums, bool with_shift) {
-  GsrGnLayout L;
-  L.shift = 0;
-  L.part = with_shift ? 256 : 0;
-  L.total = L.part + gsr_align((size_t)GSR_GN_BLOCKS * sums * 8);
-  return L;
+static inline GsrGnWs gn_ws(void* base, int sums, bool with_shift) {
+  GsrCarve c(base);
+  GsrGnWs w;
+  w.shift = with_shift ? c.take<double>(4) : nullptr;
+  w.part = c.take<double>((size_t)GSR_GN_BLOCKS * sums);
+  w.total = c.o;
+  return w;
 }
 // workgroups of a partial kernel over n rows or pixels: 256 each, the rest by the grid-stride loop
 static inline uint32_t gn_partial_blocks(uint32_t n) {

@@ -321,9 +321,20 @@ void launch_rows(bool uniform, dim3 grid, hipStream_t st, int P, const int32_t* 
 
 }  // namespace
 
-extern "C" size_t gsr_transform_workspace_bytes(int32_t K) {
-  return gsr_align((size_t)(K < 1 ? 1 : K) * sizeof(XfEntry));
+// the workspace of gsr_transform_gaussians: the table of K prepared transforms
+struct XfWs {
+  XfEntry* table;      // XfEntry[K]
+  size_t total;
+};
+static XfWs xf_ws(void* base, int32_t K) {
+  GsrCarve c(base);
+  XfWs w;
+  w.table = c.take<XfEntry>((size_t)(K < 1 ? 1 : K));
+  w.total = c.o;
+  return w;
 }
+
+extern "C" size_t gsr_transform_workspace_bytes(int32_t K) { return xf_ws(nullptr, K).total; }
 
 extern "C" int gsr_transform_gaussians(int64_t P, const int32_t* anchor, int32_t K, const double* transforms, void* workspace,
                                        size_t workspace_bytes, float* xyz, float* rotation, float* scaling_raw,
@@ -336,10 +347,8 @@ extern "C" int gsr_transform_gaussians(int64_t P, const int32_t* anchor, int32_t
     gsr_set_error("transform_gaussians: P = %lld, K = %d out of range", (long long)P, (int)K);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (K > 0 && (!workspace || workspace_bytes < gsr_transform_workspace_bytes(K))) {
-    gsr_set_error("transform_gaussians: workspace of %zu bytes, %zu needed", workspace_bytes, gsr_transform_workspace_bytes(K));
-    return GSR_ERR_INVALID_ARGUMENT;
-  }
+  const XfWs w = xf_ws(workspace, K);
+  if (K > 0 && !gsr_workspace_fits("transform_gaussians", workspace, workspace_bytes, w.total)) return GSR_ERR_INVALID_ARGUMENT;
   if (P > 0 && !xyz) {
     gsr_set_error("transform_gaussians: xyz is NULL");
     return GSR_ERR_INVALID_ARGUMENT;
@@ -360,7 +369,7 @@ extern "C" int gsr_transform_gaussians(int64_t P, const int32_t* anchor, int32_t
     return GSR_ERR_INVALID_ARGUMENT;
   }
   hipStream_t st = (hipStream_t)stream;
-  XfEntry* table = (XfEntry*)workspace;
+  XfEntry* table = w.table;
   GSR_LAUNCH("transform_table", k_transform_table, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, (int)K, transforms, table);
   const dim3 grid((unsigned)((P + XF_BT - 1) / XF_BT));
   const bool uniform = anchor == nullptr;

@@ -496,15 +496,19 @@ TsdfCam make_cam(const gsr_tsdf_frame* f) {
   return C;
 }
 
-struct TsdfExtractLayout { size_t count, offs, scan_tmp, total; };
-TsdfExtractLayout extract_layout(size_t B) {
-  TsdfExtractLayout L;
-  size_t o = 0;
-  L.count = o;    o += gsr_align(B * 4);
-  L.offs = o;     o += gsr_align(B * 4);
-  L.scan_tmp = o; o += gsr_align(gsr_scan_tmp_elems(B) * 4);
-  L.total = o;
-  return L;
+// the workspace of the two extract calls: per block its count of outputs, their exclusive scan, the scan's scratch
+struct TsdfExtractWs {
+  uint32_t *count, *offs, *scan_tmp;      // u32[B], u32[B], gsr_scan_tmp_elems(B) words
+  size_t total;
+};
+TsdfExtractWs extract_ws(void* base, size_t B) {
+  GsrCarve c(base);
+  TsdfExtractWs w;
+  w.count = c.take<uint32_t>(B);
+  w.offs = c.take<uint32_t>(B);
+  w.scan_tmp = c.take<uint32_t>(gsr_scan_tmp_elems(B));
+  w.total = c.o;
+  return w;
 }
 
 // the checks the two extract calls share; -> 0, or the error code
@@ -518,10 +522,8 @@ int extract_check(const char* who, const gsr_tsdf_volume* vol, int64_t B, const 
                   GSR_TSDF_MAX_BLOCKS, (long long)capacity, (double)min_weight);
     return GSR_ERR_INVALID_ARGUMENT;
   }
-  if (B > 0 && workspace_bytes < extract_layout((size_t)B).total) {
-    gsr_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, extract_layout((size_t)B).total);
+  if (B > 0 && !gsr_workspace_fits(who, workspace, workspace_bytes, extract_ws(nullptr, (size_t)B).total))
     return GSR_ERR_STATE_TOO_SMALL;
-  }
   return 0;
 }
 
@@ -559,7 +561,7 @@ int gsr_tsdf_integrate(const gsr_tsdf_volume* vol, const gsr_tsdf_frame* frame, 
 }
 
 size_t gsr_tsdf_extract_workspace_bytes(int64_t B) {
-  return extract_layout((size_t)(B < 1 ? 1 : (B > GSR_TSDF_MAX_BLOCKS ? GSR_TSDF_MAX_BLOCKS : B))).total;
+  return extract_ws(nullptr, (size_t)(B < 1 ? 1 : (B > GSR_TSDF_MAX_BLOCKS ? GSR_TSDF_MAX_BLOCKS : B))).total;
 }
 
 int gsr_tsdf_extract_points(const gsr_tsdf_volume* vol, int64_t B, const int64_t* keys_sorted, const int32_t* row_of_sorted,
@@ -571,18 +573,16 @@ int gsr_tsdf_extract_points(const gsr_tsdf_volume* vol, int64_t B, const int64_t
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (B == 0) return gsr_check(hipMemsetAsync(count_dev, 0, sizeof(int64_t), st), "tsdf_extract_points memset");
-  const TsdfExtractLayout L = extract_layout((size_t)B);
-  char* ws = (char*)workspace;
-  uint32_t *count = (uint32_t*)(ws + L.count), *offs = (uint32_t*)(ws + L.offs);
+  const TsdfExtractWs w = extract_ws(workspace, (size_t)B);
   const TsdfVol V = make_vol(vol);
   const TsdfStore S = {(const long long*)keys_sorted, (const int*)row_of_sorted, tsdf, weight, color, (int)B, min_weight};
-  GSR_LAUNCH("tsdf_points_count", k_tsdf_points<false>, dim3((unsigned)B), dim3(256), 0, st, V, S, count, (const uint32_t*)offs,
+  GSR_LAUNCH("tsdf_points_count", k_tsdf_points<false>, dim3((unsigned)B), dim3(256), 0, st, V, S, w.count, (const uint32_t*)w.offs,
              (long long)0, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  gsr_scan_u32(count, nullptr, offs, (size_t)B, 0, (uint32_t*)(ws + L.scan_tmp), st);
-  GSR_LAUNCH("tsdf_total", k_tsdf_total, dim3(1), dim3(64), 0, st, (const uint32_t*)count, (const uint32_t*)offs, (int)B,
+  gsr_scan_u32(w.count, nullptr, w.offs, (size_t)B, 0, w.scan_tmp, st);
+  GSR_LAUNCH("tsdf_total", k_tsdf_total, dim3(1), dim3(64), 0, st, (const uint32_t*)w.count, (const uint32_t*)w.offs, (int)B,
              (long long*)count_dev);
   if (capacity > 0)
-    GSR_LAUNCH("tsdf_points_emit", k_tsdf_points<true>, dim3((unsigned)B), dim3(256), 0, st, V, S, count, (const uint32_t*)offs,
+    GSR_LAUNCH("tsdf_points_emit", k_tsdf_points<true>, dim3((unsigned)B), dim3(256), 0, st, V, S, w.count, (const uint32_t*)w.offs,
                (long long)capacity, points, normals, colors);
   return gsr_launch_status("tsdf_extract_points launch");
 }
@@ -596,19 +596,17 @@ int gsr_tsdf_extract_triangles(const gsr_tsdf_volume* vol, int64_t B, const int6
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (B == 0) return gsr_check(hipMemsetAsync(count_dev, 0, sizeof(int64_t), st), "tsdf_extract_triangles memset");
-  const TsdfExtractLayout L = extract_layout((size_t)B);
-  char* ws = (char*)workspace;
-  uint32_t *count = (uint32_t*)(ws + L.count), *offs = (uint32_t*)(ws + L.offs);
+  const TsdfExtractWs w = extract_ws(workspace, (size_t)B);
   const TsdfVol V = make_vol(vol);
   const TsdfStore S = {(const long long*)keys_sorted, (const int*)row_of_sorted, tsdf, weight, color, (int)B, min_weight};
-  GSR_LAUNCH("tsdf_triangles_count", k_tsdf_triangles<false>, dim3((unsigned)B), dim3(256), 0, st, V, S, count,
-             (const uint32_t*)offs, (long long)0, (float*)nullptr, (float*)nullptr);
-  gsr_scan_u32(count, nullptr, offs, (size_t)B, 0, (uint32_t*)(ws + L.scan_tmp), st);
-  GSR_LAUNCH("tsdf_total", k_tsdf_total, dim3(1), dim3(64), 0, st, (const uint32_t*)count, (const uint32_t*)offs, (int)B,
+  GSR_LAUNCH("tsdf_triangles_count", k_tsdf_triangles<false>, dim3((unsigned)B), dim3(256), 0, st, V, S, w.count,
+             (const uint32_t*)w.offs, (long long)0, (float*)nullptr, (float*)nullptr);
+  gsr_scan_u32(w.count, nullptr, w.offs, (size_t)B, 0, w.scan_tmp, st);
+  GSR_LAUNCH("tsdf_total", k_tsdf_total, dim3(1), dim3(64), 0, st, (const uint32_t*)w.count, (const uint32_t*)w.offs, (int)B,
              (long long*)count_dev);
   if (capacity > 0)
-    GSR_LAUNCH("tsdf_triangles_emit", k_tsdf_triangles<true>, dim3((unsigned)B), dim3(256), 0, st, V, S, count,
-               (const uint32_t*)offs, (long long)capacity, positions, colors);
+    GSR_LAUNCH("tsdf_triangles_emit", k_tsdf_triangles<true>, dim3((unsigned)B), dim3(256), 0, st, V, S, w.count,
+               (const uint32_t*)w.offs, (long long)capacity, positions, colors);
   return gsr_launch_status("tsdf_extract_triangles launch");
 }
 
