@@ -128,6 +128,18 @@ IMG_TILE_W = 256             # GSR_IMG_TILE_W: pixels of one row per workgroup o
 IMG_TILE_H = 1               # rows per workgroup: rows are not tiled (Bayer stages the rows above and below as halo)
 DEPTH_REGISTER_CAP = 8       # columns / rows of a footprint of gsr_depth_register before it is cut
 
+
+class gsr_cloud_camera(C.Structure):
+    # HOST struct: the camera a cloud is projected into (csrc/cloud_image.hip); w2c = rows 0 .. 2 of cloud frame -> camera
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("K", C.c_float * 4), ("w2c", C.c_double * 12),
+                ("z_near", C.c_float), ("z_far", C.c_float), ("footprint", C.c_int32), ("occlusion_scale", C.c_float)]
+
+
+CLOUD_MAX_FOOTPRINT = 4      # GSR_CLOUD_MAX_FOOTPRINT
+DENSIFY_MAX_RADIUS = 8       # GSR_DENSIFY_MAX_RADIUS
+DENSIFY_TILE_W = 32          # pixels per workgroup of gsr_depth_densify: 32 x 8
+DENSIFY_TILE_H = 8
+
 class gsr_tsdf_volume(C.Structure):
     # HOST struct: the lattice of a TSDF volume (csrc/tsdf.hip)
     _fields_ = [("origin", C.c_double * 3), ("voxel_size", C.c_double), ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float),
@@ -360,8 +372,14 @@ EXPORTS = {
     "gsr_depth_register": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "gsr_cloud_project_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    # camera (host), N, points, image, mask, depth, index, pixel, z, visible, colors, count_dev, workspace + bytes, stream
+    "gsr_cloud_project": (C.c_int, [C.POINTER(gsr_cloud_camera), C.c_int64] + [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
+    # W, H, depth, radius, band_scale, min_neighbors, dense, valid, stream
+    "gsr_depth_densify": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "gsr_unproject_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "gsr_unproject_rgbd": (C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
+    "gsr_unproject_rgbd":(C.c_int, [C.POINTER(gsr_unproject_params)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                            C.c_size_t, C.c_void_p]),
     "gsr_unproject_rgbd_k": (C.c_int, [C.POINTER(gsr_unproject_params_k)] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p,
                                                                                                C.c_size_t, C.c_void_p]),

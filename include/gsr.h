@@ -71,6 +71,8 @@ extern "C" {
  *    gsr_tsdf_extract_triangles: depth frames fused into a block-sparse TSDF volume, out as a cloud and a mesh (additions only);
  *    gsr_orb_cells, gsr_orb_prepare, gsr_orb_detect, gsr_orb_describe, gsr_orb_pattern, gsr_hamming_match, gsr_hamming_vote: FAST
  *    corners, steered BRIEF descriptors and Hamming matching for place recognition (additions only);
+ *    gsr_cloud_camera, gsr_cloud_project_workspace_bytes, gsr_cloud_project, gsr_depth_densify: a LiDAR cloud projected into the
+ *    colour camera - sparse depth, winner rows, visibility, image colours - and the sparse depth filled (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -1332,6 +1334,69 @@ size_t gsr_depth_register_workspace_bytes(int32_t Wc, int32_t Hc);
 int gsr_depth_register(int32_t Wd, int32_t Hd, const float* depth /*[Hd,Wd]*/, const float* Kd /*HOST [4]*/,
                        const float* Kc /*HOST [4]*/, const double* T_cd /*HOST [12]*/, int32_t Wc, int32_t Hc, float* out /*[Hc,Wc]*/,
                        int32_t* status_dev /*[1]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- a LiDAR cloud in the colour camera (csrc/cloud_image.hip): the fourth member of a
+ * /Visual_Merged message, Local_Map, joined with the first.  The reference carries the field and has no code for this step: the
+ * rules below are this library's own.  Occlusion by a square footprint is the crude, standard form; hidden-point removal by
+ * convex hull and per-beam ray tests are not attempted.  Every step is one correctly rounded float32 operation unless stated.
+ *
+ * PROJECT, per row i of points [N,3] (cloud frame):
+ *   q = w2c p as "q = T s" above: per component (float)(((T[k,0] x + T[k,1] y) + T[k,2] z) + T[k,3]), the three products and
+ *   three sums each rounded to float64, then one rounding to float32.
+ *   The row TAKES PART iff q.x, q.y, q.z are finite and z_near <= q.z <= z_far.
+ *   px = fx * (q.x / q.z) + cx, py = fy * (q.y / q.z) + cy;  (u, v) = (floorf(px + 0.5f), floorf(py + 0.5f)), clamped IN FLOAT to
+ *   [-(r + 1), W + r] / [-(r + 1), H + r] before the conversion to int (r = footprint).
+ *   Every row that takes part OCCLUDES: each pixel of [u - r, u + r] x [v - r, v + r] inside the image takes the minimum of its
+ *   word of zocc and the bits of q.z (32-bit integer atomicMin: positive floats order as their bits).
+ *   A CANDIDATE is a row that takes part whose (u, v) is inside the image and, with a mask, has mask[v W + u] != 0.  It competes
+ *   for its pixel with the 64-bit key (bits(q.z) << 32) | i by integer atomicMin: the nearest wins, on equal z the lowest row.
+ *   z[i] = q.z, or 0 for a row that does not take part;  pixel[i] = v W + u for a candidate, else -1.
+ * RESOLVE:
+ *   a candidate is VISIBLE iff z[i] <= zocc[pixel[i]] * occlusion_scale (one product).  visible[i] = 1 / 0 (0 for every other row).
+ *   Per pixel p with winner (z_w, i_w): visible -> depth[p] = z_w, index[p] = i_w;  not visible, or no candidate -> depth[p] = 0,
+ *   index[p] = -1.  The winner has the smallest z of its pixel's candidates and the test is monotone in z, so where the winner
+ *   is not visible no candidate of that pixel is: index[p] >= 0 exactly where some visible row has pixel == p.
+ *   count_dev[0] = visible rows, count_dev[1] = candidates (device int64, cleared by the call; integer atomics).
+ *   With image and colors: a visible row gets, per channel plane I, the bilinear sample at (px, py): x0 = floorf(px), tx = px - x0,
+ *   likewise y0, ty; the taps x0, x0 + 1, y0, y0 + 1 clamped to the image; top = a + tx * (b - a) on row y0, bot likewise on row
+ *   y0 + 1, colour = top + ty * (bot - top).  Rows that are not visible are NOT WRITTEN: one colour array can be painted over
+ *   many frames.  image without colors is ignored.
+ * The result does not depend on the order of arrival; depth is unchanged under a permutation of the rows.  The workspace (a
+ * uint32 and a uint64 per pixel) is initialised by the call.  No float atomics, no allocation.  N == 0: depth = 0, index = -1,
+ * counts 0, no per-row launch (points, pixel, z, visible may then be NULL).
+ * Errors before any launch: NULL cam / depth / index / count_dev / workspace, NULL points / pixel / z / visible with N > 0, N < 0 or
+ * above 2^30 - 1, colors without image, a side < 1 or W H above 2^30 - 1, K or w2c not finite, fx or fy <= 0, not 0 < z_near <
+ * z_far < inf, footprint outside 0 .. GSR_CLOUD_MAX_FOOTPRINT, occlusion_scale not a finite value >= 1: GSR_ERR_INVALID_ARGUMENT;
+ * workspace below gsr_cloud_project_workspace_bytes(W, H): GSR_ERR_STATE_TOO_SMALL.
+ *
+ * DENSIFY, per pixel of depth [H,W] (0 = no reading):
+ *   depth > 0: dense = depth, valid = 1.  Otherwise, over the (2 radius + 1)^2 window around it (outside the image: no reading):
+ *   zn = the smallest reading > 0; none: dense = 0, valid = 0.  The IN-BAND readings are those with 0 < z <= zn * band_scale.
+ *   Fewer than min_neighbors of them: dense = 0, valid = 0.  Else dense = (sum w z) / (sum w), valid = 1, with w = 1.0f /
+ *   (float)(dx^2 + dy^2) and both sums accumulated in float32 from 0 in row-major window order (s = s + w; t = t + w * z).
+ *   The rule prefers the foreground, as gsr_frame_pyramid's depth_band does: a hole beside a depth edge takes the near
+ *   surface's depth, never a mix of the two.  valid is float32 1 / 0, what a Frame's mask is.  No atomics, no workspace.
+ * Errors before the launch: NULL depth / dense / valid, a side < 1, W H above 2^30 - 1, radius outside 1 ..
+ * GSR_DENSIFY_MAX_RADIUS, band_scale not a finite value >= 1, min_neighbors < 1: GSR_ERR_INVALID_ARGUMENT. */
+#define GSR_CLOUD_MAX_FOOTPRINT 4
+#define GSR_DENSIFY_MAX_RADIUS 8
+
+typedef struct gsr_cloud_camera {   /* HOST struct */
+  int32_t width, height;
+  float K[4];                       /* fx, fy, cx, cy; centre of pixel (0,0) at (0,0) */
+  double w2c[12];                   /* rows 0..2 of the rigid cloud-frame -> camera matrix */
+  float z_near, z_far;              /* 0 < z_near < z_far, finite */
+  int32_t footprint;                /* r, 0 .. GSR_CLOUD_MAX_FOOTPRINT: a point occludes (2r+1)^2 pixels */
+  float occlusion_scale;            /* >= 1, finite: float32(1 + relative margin), formed by the host */
+} gsr_cloud_camera;
+size_t gsr_cloud_project_workspace_bytes(int32_t W, int32_t H);
+int gsr_cloud_project(const gsr_cloud_camera* cam, int64_t N, const float* points /*[N,3]*/,
+                      const float* image /*[3,H,W] or NULL*/, const float* mask /*[H,W] or NULL*/, float* depth /*[H,W]*/,
+                      int32_t* index /*[H,W]*/, int32_t* pixel /*[N]*/, float* z /*[N]*/, uint8_t* visible /*[N]*/,
+                      float* colors /*[N,3] or NULL*/, int64_t* count_dev /*[2]*/, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int gsr_depth_densify(int32_t W, int32_t H, const float* depth /*[H,W]*/, int32_t radius, float band_scale,
+                      int32_t min_neighbors, float* dense /*[H,W]*/, float* valid /*[H,W]*/, void* stream);
 
 /* Back-projection and selection of an RGB-D keyframe.  Pixel centres sit at integer coordinates, as everywhere in this library:
  * ndc = (2 px + 1) / S - 1, p_view = (ndc_x tanfovx d, ndc_y tanfovy d, d), p_world = C2W p_view with C2W the rigid inverse of
