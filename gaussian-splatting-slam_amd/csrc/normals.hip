@@ -19,34 +19,13 @@
 //   NaN normal and eigenvalues, count 0.
 //   The top-K registers of sweep 1 are dead in sweep 2, where the nine float64 sums live: one launch holds both.
 #include "knn_common.h"
-
-#define GSR_NORMALS_SWEEPS 8      // cyclic Jacobi on a 3 x 3 symmetric matrix: quadratic once the off-diagonal is small; 5 - 6 reach 1e-16
+#include "jacobi3_common.h"      // normals_rotate, GSR_NORMALS_SWEEPS (shared with gicp.hip)
 
 // rows with a non-finite coordinate become NaN NaN NaN (.w, the original row, stays)
 __global__ __launch_bounds__(256) void k_normals_mask(uint32_t P, float4* __restrict__ pts) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= P) return;
   pts[j] = knn_mask_non_finite(pts[j]);
-}
-
-// one Jacobi rotation in the (p, q) plane of a symmetric 3 x 3: app, aqq, apq the plane's entries, akp / akq the two entries that
-// couple the third index k to it, (v0p, v0q) .. (v2p, v2q) the rows of the eigenvector matrix's columns p and q
-__device__ __forceinline__ void normals_rotate(double& app, double& aqq, double& apq, double& akp, double& akq, double& v0p,
-                                               double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  const double kp = akp, kq = akq;
-  akp = c * kp - s * kq;
-  akq = s * kp + c * kq;
-  double a, b;
-  a = v0p; b = v0q; v0p = c * a - s * b; v0q = s * a + c * b;
-  a = v1p; b = v1q; v1p = c * a - s * b; v1q = s * a + c * b;
-  a = v2p; b = v2q; v2p = c * a - s * b; v2q = s * a + c * b;
 }
 
 struct GsrNormalsView {

@@ -299,6 +299,16 @@ EXPORTS = {
     "gsr_icp_update_colored": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
+    # P, points, radius, max_nn, epsilon, cov_out, count_out, workspace + bytes, stream
+    "gsr_covariance_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_estimate_covariances": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    # P, cov_in, epsilon, cov_out, stream
+    "gsr_regularize_covariances": (C.c_int, [C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    # Ps, source, source_cov, Pt, target, target_cov, idx, T_dev, stats_dev, workspace + bytes, stream
+    "gsr_icp_generalized_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_icp_update_generalized": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # w, h, color, depth, mask, depth_min, depth_max, intensity_out, depth_out, grad_out, stream
     "gsr_odometry_prepare": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -21,6 +21,7 @@ from .registration import NeighborIndex, RegistrationResult, nn_search, transfor
     registration_icp, register_and_merge, align_map, compute_fpfh_feature, feature_nn, match_features, \
     registration_ransac_based_on_feature_matching, global_registration, ransac_trials, registration_colored_icp, \
     registration_multiscale
+from .gicp import estimate_covariances, regularize_covariances, gicp_update, registration_generalized_icp, register_scan_to_map
 from .messages import PointField, PointCloud2, decode_pointcloud2, pose_matrix, process_pointcloud, accumulate_pointclouds, \
     encode_pointcloud2, Image, CameraInfo, decode_image, encode_image, camera_info_intrinsics, pose_from_transform, register_depth, \
     frame_from_messages, frame_from_visual_merged

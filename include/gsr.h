@@ -73,6 +73,8 @@ extern "C" {
  *    corners, steered BRIEF descriptors and Hamming matching for place recognition (additions only);
  *    gsr_cloud_camera, gsr_cloud_project_workspace_bytes, gsr_cloud_project, gsr_depth_densify: a LiDAR cloud projected into the
  *    colour camera - sparse depth, winner rows, visibility, image colours - and the sparse depth filled (additions only);
+ *    gsr_covariance_workspace_bytes, gsr_estimate_covariances, gsr_regularize_covariances, gsr_icp_generalized_workspace_bytes,
+ *    gsr_icp_update_generalized: generalized ICP - a covariance per point and the plane-to-plane update (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -799,6 +801,73 @@ int gsr_estimate_normals(int64_t P, const float* points /*[P,3]*/, float radius,
                          const float* viewpoint /*HOST [3] or NULL*/, float* normals /*[P,3]*/, int32_t* count_out /*[P] or NULL*/,
                          float* eigenvalues_out /*[P,3] ascending, or NULL*/, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ---- generalized ICP (csrc/gicp.hip) - Segal, Haehnel, Thrun 2009 as Open3D's
+ * registration_generalized_icp states it: a covariance per point on BOTH clouds, and updates that weigh every pair by the inverse of
+ * the combined covariance.  A covariance is six float32 per row: xx, xy, xz, yy, yz, zz (the layout of cov3D_precomp).  Every
+ * result is a function of the input only, never of traversal, scheduling or launch shape; no float atomics, no allocation. ---- */
+
+/* The regularised covariance of a symmetric 3 x 3 matrix A (float64) with epsilon in (0, 1] - R(A, epsilon) below:
+ * cyclic Jacobi on A in float64, the rotations and the fixed number of sweeps of gsr_estimate_normals, in its order (0,1), (0,2),
+ * (1,2).  With a00, a11, a22 the diagonal after the sweeps: if a00 == a11 && a11 == a22 (float64 equality; a multiple of the
+ * identity meets it exactly, since a zero off-diagonal entry is never rotated) the result is I.  Otherwise w = the column of the
+ * eigenvector matrix that belongs to the smallest of the three (the first on ties), divided by sqrt((wx wx + wy wy) + wz wz), k = 1
+ * - epsilon, and
+ *   xx = 1 - (k wx) wx,  xy = 0 - (k wx) wy,  xz = 0 - (k wx) wz,  yy = 1 - (k wy) wy,  yz = 0 - (k wy) wz,  zz = 1 - (k wz) wz
+ * - every product and difference one float64 operation, in this order, no fused multiply-add, each entry rounded to float32 once.
+ * That is I - (1 - epsilon) w w^T = V diag(epsilon, 1, 1) V^T, Open3D's regularisation (the surface is flat along its normal and
+ * of unit extent across it); w enters as a square, so no sign rule is needed. */
+
+/* Covariance of every row from its hybrid neighbourhood.  Neighbourhood: N_i of gsr_estimate_normals exactly (float32 d2, k =
+ * max_nn - 1, bound = min(r2, d_k), rows tied at the bound all belong - the departure from Open3D's hybrid search inherited from
+ * there - duplicates are members; a row with a non-finite coordinate is masked and is nobody's neighbour), max_nn in [3,
+ * GSR_KNN_K_MAX + 1].  S1, S2 and C = S2 / n - (S1 / n)(S1 / n)^T as gsr_estimate_normals forms them (float64, the order of the
+ * sorted structure: two runs give identical bits).  cov_out[i] = R(C, epsilon); count_i < 3: I (that row then pulls as a
+ * point-to-point pair does); a non-finite row: six NaN and count 0.  count_out = |N_i|.  One launch after the index build.
+ * Errors before any launch: P outside [1, 2^30 - 1], NULL points / cov_out / workspace, radius <= 0 or NaN, max_nn outside [3, 33],
+ * epsilon outside (0, 1] or NaN: GSR_ERR_INVALID_ARGUMENT; workspace below gsr_covariance_workspace_bytes(P):
+ * GSR_ERR_STATE_TOO_SMALL. */
+size_t gsr_covariance_workspace_bytes(int64_t P);
+int gsr_estimate_covariances(int64_t P, const float* points /*[P,3]*/, float radius, int32_t max_nn, double epsilon,
+                             float* cov_out /*[P,6]*/, int32_t* count_out /*[P] or NULL*/, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* cov_out[i] = R(A_i, epsilon) of covariances that are GIVEN (a Gaussian map's own), A_i the float32 entries of cov_in[i] promoted:
+ * their shape is kept - the direction of least extent - and their size replaced by (epsilon, 1, 1).  A row with a non-finite entry:
+ * six NaN.  One thread per row, no workspace; cov_out may be cov_in.  Errors before the launch: P outside [1, 2^30 - 1], NULL
+ * cov_in / cov_out, epsilon outside (0, 1] or NaN: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_regularize_covariances(int64_t P, const float* cov_in /*[P,6]*/, double epsilon, float* cov_out /*[P,6]*/, void* stream);
+
+/* One generalized ICP update on the device: gsr_icp_update_plane with the residual d_i = q_i - p_i (three components) weighted by
+ * W_i = M_i^-1.  With k = idx[i] and R the rotation block of the INCOMING T: row i takes part iff 0 <= k < Pt, q = T s_i and p =
+ * target[k] are finite, the six entries of source_cov[i] and of target_cov[k] are finite, and det M (below) is finite and > 0.
+ * Everything is formed about the shift c of gsr_icp_update (the target point of the first row whose q and p are finite - the
+ * covariances play no part in it), q' = q - c, all in float64, every operation rounded on its own (no fused multiply-add), sums
+ * of three terms as (a + b) + c:
+ *   A = R Sigma_s:   A[a][b] = (R[a][0] S[0][b] + R[a][1] S[1][b]) + R[a][2] S[2][b]
+ *   M = Sigma_t + A R^T, the upper triangle (the lower one is its mirror image):
+ *                    M[a][b] = Sigma_t[a][b] + ((A[a][0] R[b][0] + A[a][1] R[b][1]) + A[a][2] R[b][2]),  a <= b
+ *   adjugate, M = [m0 m1 m2; m1 m3 m4; m2 m4 m5]:
+ *                    k00 = m3 m5 - m4 m4,  k01 = m2 m4 - m1 m5,  k02 = m1 m4 - m2 m3,
+ *                    k11 = m0 m5 - m2 m2,  k12 = m1 m2 - m0 m4,  k22 = m0 m3 - m1 m1,   det = (m0 k00 + m1 k01) + m2 k02
+ *   W[a][b] = k_ab / det (symmetric);  d = q - p (float32 values promoted, so d = q' - p');
+ *   J = [-[q']x, I] (3 x 6: the derivative of dR q' + t - p' at 0):  rows (0, q'z, -q'y, 1, 0, 0), (-q'z, 0, q'x, 0, 1, 0),
+ *   (q'y, -q'x, 0, 0, 0, 1).
+ * Over the n rows, with the summation structure of gsr_icp_update (at most 256 workgroups over fixed slices, a fixed butterfly, no
+ * float atomics: deterministic), 30 sums per workgroup: the 21 entries of the upper triangle of J^T W J, the 6 of J^T W d, n,
+ * sum |d|^2 and sum d^T W d.  Solve and composition are the plane update's: J^T W J x = -J^T W d by LDL^T with its pivot rule, x =
+ * (alpha, beta, gamma, t), dR = Rz(gamma) Ry(beta) Rx(alpha), dT = Tr(c) [dR, t] Tr(-c), T <- dT T (row 3 = 0 0 0 1).
+ * stats_dev[8] = n, fitness = n / Ps, inlier_rmse = sqrt(sum |d|^2 / n) (Euclidean; 0 with n = 0), status, sum |d|^2, sum d^T W d,
+ * 0, 0 - all of the INCOMING T.  status: 0 = T updated; 1 = n < 6, T unchanged; 2 = a rejected pivot (gsr_icp_update_plane's rule),
+ * T unchanged - with isotropic covariances on one side M is positive definite in every direction and a single plane is solved,
+ * where the plane update returns 2.  Covariances are used as given: nothing here regularises them.
+ * Errors before any launch: sizes outside [1, 2^30 - 1], a NULL pointer: GSR_ERR_INVALID_ARGUMENT; workspace below
+ * gsr_icp_generalized_workspace_bytes(Ps): GSR_ERR_STATE_TOO_SMALL.  No allocation. */
+size_t gsr_icp_generalized_workspace_bytes(int64_t Ps);
+int gsr_icp_update_generalized(int64_t Ps, const float* source /*[Ps,3]*/, const float* source_cov /*[Ps,6]*/, int64_t Pt,
+                               const float* target /*[Pt,3]*/, const float* target_cov /*[Pt,6]*/, const int32_t* idx /*[Ps]*/,
+                               double* T_dev /*[16] in/out*/, double* stats_dev /*[8] out*/, void* workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* ---- coloured ICP (csrc/colored.hip, csrc/registration.hip) - Park, Zhou, Koltun 2017 as Open3D's
  * registration_colored_icp states it: a colour gradient per target point, then updates that join the point-to-plane residual
