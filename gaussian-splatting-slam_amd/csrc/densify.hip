@@ -38,10 +38,12 @@ __global__ __launch_bounds__(256) void k_densify_plan(int P, const float* __rest
   float g = grad_accum[i] / denom[i];
   if (g != g) g = 0.f;                                             // grads[grads.isnan()] = 0.0
   const float s0 = expf(scaling[3 * (size_t)i]), s1 = expf(scaling[3 * (size_t)i + 1]), s2 = expf(scaling[3 * (size_t)i + 2]);
-  const float smax = fmaxf(s0, fmaxf(s1, s2));
+  // torch.max propagates NaN where fmaxf drops it: a NaN axis makes smax NaN, every comparison with it false, and the row is
+  // neither split (smax > ...) nor cloned (smax <= ..., a comparison of its own at :392) nor pruned by size
+  const float smax = (s0 != s0 || s1 != s1 || s2 != s2) ? s0 + s1 + s2 : fmaxf(s0, fmaxf(s1, s2));
   const bool big = smax > percent_dense * extent;
   const bool sel = g >= max_grad;
-  const bool clone = sel && !big;
+  const bool clone = sel && smax <= percent_dense * extent;
   const bool split = sel && big;
   const float op = 1.0f / (1.0f + expf(-opacity[i]));
   const bool low = op < min_opacity;
