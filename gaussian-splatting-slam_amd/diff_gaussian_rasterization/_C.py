@@ -139,6 +139,9 @@ CLOUD_MAX_FOOTPRINT = 4      # GSR_CLOUD_MAX_FOOTPRINT
 DENSIFY_MAX_RADIUS = 8       # GSR_DENSIFY_MAX_RADIUS
 DENSIFY_TILE_W = 32          # pixels per workgroup of gsr_depth_densify: 32 x 8
 DENSIFY_TILE_H = 8
+SCAN_CONTEXT_MAX_RINGS = 40       # GSR_SCAN_CONTEXT_MAX_RINGS
+SCAN_CONTEXT_MAX_SECTORS = 120    # GSR_SCAN_CONTEXT_MAX_SECTORS
+SCAN_CONTEXT_MAX_ORIGINS = 16     # GSR_SCAN_CONTEXT_MAX_ORIGINS
 
 class gsr_tsdf_volume(C.Structure):
     # HOST struct: the lattice of a TSDF volume (csrc/tsdf.hip)
@@ -364,6 +367,13 @@ EXPORTS = {
     # Q, query, N, db, K, segments, max_distance, ratio, votes, stream
     "gsr_hamming_vote": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float,
                                    C.c_void_p, C.c_void_p]),
+    # N, points, frame (host [12] or NULL), B, origins (host [B,3] or NULL), rings, sectors, max_range, height_offset,
+    # descriptors, norms, stream
+    "gsr_scan_context": (C.c_int, [C.c_int64, C.c_void_p, c_float_p, C.c_int32, c_float_p, C.c_int32, C.c_int32, C.c_float,
+                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # rings, sectors, B, query, query_norms, K, db, db_norms, dist, shift, variant, stream
+    "gsr_scan_context_distance": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] +
+                                  [C.c_void_p] * 6),
     # layout (host), data + bytes, T_dev, min_y, max_range2, skip_nans, out_points, out_colors, out_index, cap, count_dev,
     # workspace + bytes, stream
     "gsr_pc2_decode_workspace_bytes": (C.c_size_t, [C.c_int64]),

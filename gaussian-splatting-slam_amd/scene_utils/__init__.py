@@ -32,3 +32,4 @@ from .tsdf import TSDFVolume, fuse_views, weld_triangles
 from .features2d import OrbFeatures, PlaceEntry, PlaceDatabase, detect_orb, match_descriptors, hamming_match, keypoint_points, \
     relative_pose_from_features, loop_closure_edge, orb_prepare, orb_detect, orb_describe
 from .lidar import CloudProjection, project_cloud, densify_depth, colorize_cloud, lidar_frame, frame_from_visual_merged_map
+from .scancontext import ScanContext, ScanEntry, ScanDatabase, scan_context, scan_context_distance, scan_loop_closure_edge

@@ -75,6 +75,8 @@ extern "C" {
  *    colour camera - sparse depth, winner rows, visibility, image colours - and the sparse depth filled (additions only);
  *    gsr_covariance_workspace_bytes, gsr_estimate_covariances, gsr_regularize_covariances, gsr_icp_generalized_workspace_bytes,
  *    gsr_icp_update_generalized: generalized ICP - a covariance per point and the plane-to-plane update (additions only);
+ *    gsr_scan_context, gsr_scan_context_distance: the polar descriptor of a LiDAR scan and the search over all column shifts -
+ *    place recognition with a yaw estimate (additions only);
  * 6: host_status word 0 bit 0 = radix-sort look-back time-out (was reserved; debug = 1 fails the call), gsr_debug_wave_reduce_pk,
  *    gsr_forward_async_culled (host_status word 0 bit 1 / word 6 = a truncated tile list was too short);
  * 5: gsr_fused_adam.dynamic + gsr_adam_set_dynamic (optimizer factors in device memory, for HIP-graph replay), gsr_l1_mean_*;
@@ -1254,6 +1256,51 @@ int gsr_hamming_match(int64_t Q, const int32_t* query /*[Q,8]*/, int64_t N, cons
  * < 0, ratio negative or NaN: GSR_ERR_INVALID_ARGUMENT. */
 int gsr_hamming_vote(int64_t Q, const int32_t* query /*[Q,8]*/, int64_t N, const int32_t* db /*[N,8]*/, int64_t K,
                      const int32_t* segments /*[K+1]*/, int32_t max_distance, float ratio, int32_t* votes /*[K]*/, void* stream);
+
+/* ---- LiDAR scans for place recognition (csrc/scancontext.hip): the polar "scan context" descriptor
+ * of Kim & Kim (IROS 2018) - rings x sectors around the sensor, the largest height per cell - and the exhaustive search over all
+ * column shifts.  A rotation of the sensor about its vertical axis is a cyclic shift of the descriptor's columns, so the search
+ * gives a distance and a yaw together.  Integer atomic max only (a height >= +0 orders by its float bits), every sum in one
+ * fixed order: the same bits on every run, whatever the order of the points.  No workspace. ---- */
+#define GSR_SCAN_CONTEXT_MAX_RINGS 40
+#define GSR_SCAN_CONTEXT_MAX_SECTORS 120
+#define GSR_SCAN_CONTEXT_MAX_ORIGINS 16
+
+/* B descriptors of one cloud, one per origin.  frame: HOST, row-major 3 x 4, cloud -> levelled sensor frame with z up (NULL: the
+ * identity, no arithmetic at all); origins: HOST [B,3] in the levelled frame (NULL: B = 1, the origin 0 0 0).  Per point and
+ * origin, every operation rounded to float32 on its own (no fused multiply-add):
+ *   q_i = ((F[i][0] x + F[i][1] y) + F[i][2] z) + F[i][3]  (q = the point itself without a frame);  p = q - origin;
+ *   the point is skipped if a component of p is not finite;
+ *   rho2 = p.x p.x + p.y p.y; skipped unless 0 < rho2 < max_range max_range;
+ *   ring = min(R - 1, floor(sqrt(rho2) R / max_range));
+ *   theta = atan2f(p.y, p.x), + float32(2 pi) where negative;  sector = min(S - 1, floor(theta S / float32(2 pi)));
+ *   h = p.z + height_offset where that is > 0, else +0;   descriptors[b][ring][sector] = max over the points; an empty cell is 0.
+ * (atan2f is the device library's: a point within a few ulp of a sector boundary may fall on either side.)
+ * norms[b][c] = sqrt(s_R) with s_0 = 0, s_{r+1} = s_r + d d, d = descriptors[b][r][c]: rings in ascending order.
+ * N = 0 is legal: all zeros.
+ * Errors before any launch: rings outside 1 .. 40, sectors outside 1 .. 120, B outside 1 .. 16, NULL origins with B > 1, N
+ * outside [0, 2^30 - 1], NULL descriptors / norms, NULL points with N > 0, max_range not finite or <= 0, height_offset, a frame
+ * or an origin entry not finite: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_scan_context(int64_t N, const float* points /*[N,3]*/, const float* frame /*HOST [12] or NULL*/, int32_t B,
+                     const float* origins /*HOST [B,3] or NULL*/, int32_t rings, int32_t sectors, float max_range,
+                     float height_offset, float* descriptors /*[B,rings,sectors]*/, float* norms /*[B,sectors]*/, void* stream);
+
+/* B query descriptors (the variants: one scan seen from B origins) against K database descriptors, with their norms.  For variant b
+ * and shift s, in float32, every operation rounded on its own:
+ *   d(b, s) = 1 - (sum over c of dot(c) / (nq[b][(c + s) mod S] nd[k][c])) / n,
+ *   dot(c) = sum over r ascending of q[b][r][(c + s) mod S] d[k][r][c], starting from 0;
+ * the outer sum runs, c ascending from 0, over the n columns where both norms are non-zero; n = 0: d = 1.
+ * dist[k] = the minimum over b and s, variant[k] and shift[k] where it is reached: among equal distances the smallest b, then the
+ * smallest s.  A shift s says: the query's points are about Rz(s 2 pi / S) times the database scan's points.
+ * Descriptors and norms are expected finite, as gsr_scan_context writes them: a d(b, s) that comes out NaN (an inf or NaN in a
+ * grid supplied by the caller) never wins, and a row where no d(b, s) is comparable gets dist +inf, shift = variant = INT32_MAX.
+ * One workgroup per database row, both grids in LDS, one lane per shift.  K = 0 is legal.
+ * Errors before the launch: sizes as gsr_scan_context, K outside [0, 2^30 - 1], NULL query / query_norms, with K > 0 a NULL db /
+ * db_norms / output: GSR_ERR_INVALID_ARGUMENT. */
+int gsr_scan_context_distance(int32_t rings, int32_t sectors, int32_t B, const float* query /*[B,rings,sectors]*/,
+                              const float* query_norms /*[B,sectors]*/, int64_t K, const float* db /*[K,rings,sectors]*/,
+                              const float* db_norms /*[K,sectors]*/, float* dist /*[K]*/, int32_t* shift /*[K]*/,
+                              int32_t* variant /*[K]*/, void* stream);
 
 /* ---- sensor_msgs/PointCloud2 on the device (csrc/pointcloud2.hip): what the reference's
  * process_pointcloud / read_pointcloud do point by point with `struct` in Python before a cloud reaches Open3D ---- */
